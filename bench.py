@@ -6,9 +6,11 @@ GPU, CFA already resident in HBM, result left resident in HBM (SURVEY.md section
 Frames are independent, so N GPUs process N frames per step with no data-path collective
 (weak scaling); the only collective is the completion barrier / max-over-ranks of the time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: metric, value (MP/s), unit, higher_is_better, dtype and ms_per_step
+(wall time of one timed step).  A plain run does only that; --full adds, among others,
   roofline     : dominant kernel's algorithmic bytes / its average launch time vs 8 TB/s HBM
   cpu_baseline : the CPU oracle (port of the reference's x86-64 path) timed on this host.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 from __future__ import annotations
 
@@ -64,6 +66,29 @@ def failure_line(records, failed, elapsed, mp, args, world, dry=False):
             "higher_is_better": True, "scaling": "weak", "data": "synthetic",
             "config": {"workload": "INCOMPLETE: a rank's step failed; value counts the frames of the ranks that succeeded", "workload_flag": args.workload,
                        "completion_records": len(records), "records": records}}
+
+
+DUMP_BYTES = 64 << 20          # all .npy files of one --dump-outputs run together
+
+
+def dump_outputs(dirname, planes, world):
+    """--dump-outputs: each device plane the last timed step left (name -> 2-D float32 tensor) as DIR/<name>.npy, float32.  A plane of at
+    most `per` values is written whole; a larger one as its values at `per` flat indices drawn with seed 0 and sorted -- the same positions
+    for every plane of that shape in every run, so that two builds compare value for value.  `per` keeps the run under DUMP_BYTES."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    per = min(1 << 20, (DUMP_BYTES // world - 4096 * len(planes)) // (4 * len(planes)))
+    idx = {}
+    for name, t in planes.items():
+        n = t.numel()
+        if n <= per:
+            a = t.cpu().numpy()
+        else:
+            if n not in idx:
+                idx[n] = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, per, replace=False))).to(t.device)
+            a = t.reshape(-1)[idx[n]].cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32, copy=False))
 
 
 def dry_main(args, rank, world, dist, torch, synth) -> None:
@@ -136,8 +161,14 @@ def main() -> None:
                          "denoise + exposure + tone curve (BASELINE configs[2], the configuration the metric is quoted on); "
                          "c4: c3 + guided chroma smoothing + NL-means (the per-frame pipe of BASELINE configs[3]); "
                          "c5: X-Trans 3-pass (Markesteijn, CIELab) + the c3 stages on a 100 MP 11648x8736 frame (BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-stage and dominant-kernel times, the roofline block, the sustained run, "
+                         "the NEUTRAL / separate-stage / one-pass / two-frames / host-buffer legs and the CPU baseline.  Without it a run sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps: what the last one computed, as DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="only the timed steps (no NEUTRAL / separate-stage / two-frames legs behind them): kernel traces and counter passes")
+                    help="--full: no NEUTRAL / separate-stage / one-pass legs behind the timed steps")
     ap.add_argument("--separate-stages", action="store_true",
                     help="one library call per stage of the reference's order (getImage, denoise, exposure) instead of the fused tool "
                          "artgpu_improc_denoise_fused; same result, the image written and read again between the stages")
@@ -155,11 +186,15 @@ def main() -> None:
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="artgpu_set_option on every context of the run (A/B switches, e.g. dn_streams=0)")
     ap.add_argument("--sustained-seconds", type=float, default=5.0,
-                    help="after the timed K steps: back-to-back steps for at least this long (the batch queue of simpleprocess.cc:591-611 runs "
+                    help="--full, after the timed K steps: back-to-back steps for at least this long (the batch queue of simpleprocess.cc:591-611 runs "
                          "for minutes, the contract region for a fraction of a second at boost clocks); reported as `sustained`.  0: off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-repeats", type=int, default=3)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry and args.dump_outputs:
+        ap.error("--dump-outputs needs device work (not --dry)")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, the same command the driver
     # uses: torch.distributed.run on 127.0.0.1) and hand over to them.  Under a launcher WORLD_SIZE is set and we are one rank.
@@ -242,7 +277,8 @@ def main() -> None:
         stage_names = ["demosaic", "get_image+matrix+denoise+exposure", "tone_curve"] if fused_tool else ["demosaic", "get_image+matrix", "denoise", "exposure", "tone_curve"]
     else:
         stage_names = ["demosaic"]
-    stage_ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(stage_names) + 1)] for _ in range(args.steps)]
+    # (per-stage events in the timed steps: --full only)
+    stage_ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(stage_names) + 1)] for _ in range(args.steps)] if args.full else None
     cur = {"ev": None}
 
     def mark(k):
@@ -381,7 +417,7 @@ def main() -> None:
     # stream could not take: none at this frame size), no border_interpolate2 -- so the stage events recorded around the call bracket
     # that kernel (+0.5 %) and are read after the timed region; the other demosaicers use the library's own event pair, which the host
     # has to wait for once per step.
-    lib_timing = xtrans or method != capi.BAYER_AMAZE or border < 4
+    lib_timing = args.full and (xtrans or method != capi.BAYER_AMAZE or border < 4)
     if lib_timing:
         ctx.enable_timing(True)
     kernel_ms = []
@@ -390,7 +426,7 @@ def main() -> None:
     t0 = time.perf_counter()
     evs[0].record(stream)
     def timed_step(k):
-        cur["ev"] = stage_ev[k]
+        cur["ev"] = stage_ev[k] if args.full else None
         step()
         if lib_timing:
             kernel_ms.append(ctx.timings().demosaic_ms)
@@ -402,7 +438,7 @@ def main() -> None:
     t1 = time.perf_counter()
     if lib_timing:
         ctx.enable_timing(False)
-    elif not guard.status:
+    elif args.full and not guard.status:
         kernel_ms = [ev[0].elapsed_time(ev[1]) for ev in stage_ev]
     # completion step: all-gather of the 64-byte per-rank records (the batch's only collective),
     # elapsed = MAX over ranks
@@ -439,8 +475,60 @@ def main() -> None:
             print(json.dumps(failure_line(records, failed, elapsed, mp, args, world)), flush=True)
         sys.stdout.flush(); sys.stderr.flush()
         os._exit(3)
-    stage_ms = {nm: round(statistics.mean(ev[i].elapsed_time(ev[i + 1]) for ev in stage_ev), 4) for i, nm in enumerate(stage_names)}
     value = world * args.lanes * args.steps * mp / elapsed
+    if args.dump_outputs:
+        # what a caller receives: the finished image of a pipeline workload, the demosaiced planes otherwise; one frame per lane
+        kind = "image" if pipeline else "demosaic"
+        planes = {}
+        for k, frame in enumerate([d_img if pipeline else d_out] + [ln["img"] for ln in extra]):
+            pre = (f"rank{rank}_" if world > 1 else "") + (f"lane{k}_" if k else "")
+            planes.update({f"{pre}{kind}_{c}": t for c, t in zip("rgb", frame)})
+        dump_outputs(args.dump_outputs, planes, world)
+    result = {
+        "metric": ("megapixels/sec end-to-end (X-Trans+FTblockDN+tone), 100 MP X-Trans" if xtrans else
+                   "megapixels/sec end-to-end (AMaZE+FTblockDN+tone), 45 MP Bayer"),
+        "value": round(value, 2),
+        "unit": "MP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": ((("X-Trans 3-pass Markesteijn (CIELab)" if xt_passes == 3 else "X-Trans 1-pass Markesteijn (YPbPr)") if xtrans else "AMaZE") + f" + getImage/matrix + ImProcFunctions::denoise (chroma noise-curve map, FTblockDN wavelet shrinkage luma 40 / "
+                         f"chroma 15 / gamma 1.7 + DCT detail recovery 50"
+                         + (", guided chroma smoothing r=3, NL-means 50/80" if smoothing else "")
+                         + f") + exposure 0.3 EV + tone curve {args.tone.upper()}, {W}x{H} " + ("X-Trans" if xtrans else "Bayer RGGB") + f" fp32, {args.lanes} frame{'s' if args.lanes > 1 else ''} per GPU per step "
+                         + ("(BASELINE configs[4])" if xtrans else "(per-frame pipe of BASELINE configs[3])" if smoothing else "(BASELINE configs[2])"))
+                        if pipeline else f"{args.workload.upper()} demosaic only, {W}x{H} Bayer RGGB fp32 (BASELINE configs[1])",
+            "stage_calls": ("fused tool: artgpu_improc_denoise_fused (getImage + matrix in front of ImProcFunctions::denoise, exposure behind it, inside its pixel passes)"
+                            if pipeline and fused_tool else "one call per stage"),
+            "frame": f"{W}x{H}", "frames_per_step": world * args.lanes, "lanes_per_gpu": args.lanes,
+            "parallelism": f"frame-per-gpu x{world}" + (f", {args.lanes} frames in flight per GPU" if args.lanes > 1 else ""),
+            "completion_records": len(records), "completion_via": gather_via,
+        },
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if hard_exit:               # a thread is still blocked inside RCCL: do not wait for it
+            sys.stdout.flush()
+            os._exit(0)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # --full: everything below measures beside the headline line
+    stage_ms = {nm: round(statistics.mean(ev[i].elapsed_time(ev[i + 1]) for ev in stage_ev), 4) for i, nm in enumerate(stage_names)}
     kern_ms = statistics.mean(kernel_ms)
     achieved = (W * H * ALGO_BYTES_PER_PX / 1e9) / (kern_ms / 1e3)
 
@@ -497,52 +585,23 @@ def main() -> None:
 
     if issue is not None:
         issue["frac_of_kernel_ms"] = round(issue["issue_time_ms"] / kern_ms, 3)
-    result = {
-        "metric": ("megapixels/sec end-to-end (X-Trans+FTblockDN+tone), 100 MP X-Trans" if xtrans else
-                   "megapixels/sec end-to-end (AMaZE+FTblockDN+tone), 45 MP Bayer"),
-        "value": round(value, 2),
-        "unit": "MP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": ((("X-Trans 3-pass Markesteijn (CIELab)" if xt_passes == 3 else "X-Trans 1-pass Markesteijn (YPbPr)") if xtrans else "AMaZE") + f" + getImage/matrix + ImProcFunctions::denoise (chroma noise-curve map, FTblockDN wavelet shrinkage luma 40 / "
-                         f"chroma 15 / gamma 1.7 + DCT detail recovery 50"
-                         + (", guided chroma smoothing r=3, NL-means 50/80" if smoothing else "")
-                         + f") + exposure 0.3 EV + tone curve {args.tone.upper()}, {W}x{H} " + ("X-Trans" if xtrans else "Bayer RGGB") + f" fp32, {args.lanes} frame{'s' if args.lanes > 1 else ''} per GPU per step "
-                         + ("(BASELINE configs[4])" if xtrans else "(per-frame pipe of BASELINE configs[3])" if smoothing else "(BASELINE configs[2])"))
-                        if pipeline else f"{args.workload.upper()} demosaic only, {W}x{H} Bayer RGGB fp32 (BASELINE configs[1])",
-            "stage_ms": stage_ms,
-            "stage_ms_schema": 2 if (pipeline and fused_tool) else 1,     # 1: one key per reference stage; 2: the fused tool's three stages as one key
-            "stage_calls": ("fused tool: artgpu_improc_denoise_fused (getImage + matrix in front of ImProcFunctions::denoise, exposure behind it, inside its pixel passes)"
-                            if pipeline and fused_tool else "one call per stage"),
-            "frame": f"{W}x{H}", "frames_per_step": world * args.lanes, "lanes_per_gpu": args.lanes,
-            "parallelism": f"frame-per-gpu x{world}" + (f", {args.lanes} frames in flight per GPU" if args.lanes > 1 else ""),
-            "completion_records": len(records), "completion_via": gather_via,
-        },
-        "roofline": {
-            "bound": "hbm", "kernel": kname,
-            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale, "traffic_raw_counters": traffic_raw,
-            # the whole step against the same contract (MP/s x 16 B / 8 TB/s), next to the dominant kernel's fraction
-            "end_to_end_frac": round(value * 1e6 * ALGO_BYTES_PER_PX / 1e9 / HBM_PEAK_GBS / max(world, 1), 5),
-            # the survey's diagnostic ceiling: traffic no fusion can remove because of global dependencies -- MAD medians need whole
-            # subbands before shrinking, separable recurrences a transpose point: FTblockDN ~760 B/px on top of the 16 B/px contract (config 4: + NL-means
-            # 12 B/px + guided filter ~40 B/px) => ~10 300 MP/s per GPU for config 3.  Not the contract figure; it says how far the chain is from what
-            # its barriers allow.
-            "barrier_aware": {"bytes_per_px": BARRIER_AWARE_B_PER_PX[args.workload], "ceiling_mps": round(HBM_PEAK_GBS * 1e9 / BARRIER_AWARE_B_PER_PX[args.workload] / 1e6, 1),
-                              "end_to_end_frac": round(value / max(world, 1) / (HBM_PEAK_GBS * 1e9 / BARRIER_AWARE_B_PER_PX[args.workload] / 1e6), 4)},
-            "kernel_ms": round(kern_ms, 4), "algorithmic_bytes": W * H * ALGO_BYTES_PER_PX,
-            "device_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
-            "traffic_rate_frac_of_copy": None if (copy_gbs is None or traffic is None) else round(traffic / 1e9 / (kern_ms / 1e3) / copy_gbs, 4),
-            "instruction_issue": issue,
-        },
+    result["config"].update(stage_ms=stage_ms, stage_ms_schema=2 if (pipeline and fused_tool) else 1)     # schema 1: one key per reference stage; 2: the fused tool's three stages as one key
+    result["roofline"] = {
+        "bound": "hbm", "kernel": kname,
+        "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale, "traffic_raw_counters": traffic_raw,
+        # the whole step against the same contract (MP/s x 16 B / 8 TB/s), next to the dominant kernel's fraction
+        "end_to_end_frac": round(value * 1e6 * ALGO_BYTES_PER_PX / 1e9 / HBM_PEAK_GBS / max(world, 1), 5),
+        # the survey's diagnostic ceiling: traffic no fusion can remove because of global dependencies -- MAD medians need whole
+        # subbands before shrinking, separable recurrences a transpose point: FTblockDN ~760 B/px on top of the 16 B/px contract (config 4: + NL-means
+        # 12 B/px + guided filter ~40 B/px) => ~10 300 MP/s per GPU for config 3.  Not the contract figure; it says how far the chain is from what
+        # its barriers allow.
+        "barrier_aware": {"bytes_per_px": BARRIER_AWARE_B_PER_PX[args.workload], "ceiling_mps": round(HBM_PEAK_GBS * 1e9 / BARRIER_AWARE_B_PER_PX[args.workload] / 1e6, 1),
+                          "end_to_end_frac": round(value / max(world, 1) / (HBM_PEAK_GBS * 1e9 / BARRIER_AWARE_B_PER_PX[args.workload] / 1e6), 4)},
+        "kernel_ms": round(kern_ms, 4), "algorithmic_bytes": W * H * ALGO_BYTES_PER_PX,
+        "device_copy_gbs": None if copy_gbs is None else round(copy_gbs, 1),
+        "traffic_rate_frac_of_copy": None if (copy_gbs is None or traffic is None) else round(traffic / 1e9 / (kern_ms / 1e3) / copy_gbs, 4),
+        "instruction_issue": issue,
     }
 
     # the same step back to back for several seconds (no per-step barrier: the host runs ahead of the device, as a batch would)
@@ -769,14 +828,7 @@ def main() -> None:
         result["cpu_baseline"]["note"] = ("a CPU restatement of the reference's algorithm, not the reference (it cannot be built here: glibmm, lcms2, fftw3 are absent); "
                                           "SURVEY probe for scale: the reference's AMaZE alone runs 38.9 MP/s on 8 vCPU.  The GPU/CPU ratio is not a quality measure; "
                                           "roofline.frac and roofline.end_to_end_frac are.")
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if hard_exit:               # a thread is still blocked inside RCCL: do not wait for it
-        sys.stdout.flush()
-        os._exit(0)
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

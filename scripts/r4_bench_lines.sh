@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r4; mkdir -p $O
-B="timeout 300 python $R/bench.py"
+B="timeout 300 python $R/bench.py --full"
 Q="--no-cpu-baseline --sustained-seconds 0"
 $B > $O/bench_c3_n1.json 2> $O/err.txt
 $B --workload amaze $Q > $O/bench_amaze_n1.json 2>> $O/err.txt
