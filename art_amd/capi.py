@@ -56,6 +56,12 @@ class NeutralState(C.Structure):
     _fields_ = [("ws", C.c_double * 9), ("iws", C.c_double * 9), ("to_out", C.c_float * 9), ("to_work", C.c_float * 9)]
 
 
+class CaParams(C.Structure):
+    """artgpu_ca_params: RAWParams' CA correction fields"""
+    _fields_ = [("autocorrect", C.c_int32), ("iterations", C.c_int32), ("red", C.c_double), ("blue", C.c_double),
+                ("avoid_colour_shift", C.c_int32)]
+
+
 class PipelineParams(C.Structure):
     pass
 
@@ -77,7 +83,7 @@ PipelineParams._fields_ = [
     ("ws", C.c_double * 9), ("iws", C.c_double * 9), ("denoise_enabled", C.c_int32), ("denoise", DenoiseToolParams),
     ("exposure_enabled", C.c_int32), ("expcomp", C.c_double), ("black", C.c_double), ("tone_enabled", C.c_int32),
     ("tone_mode", C.c_int32), ("tone_lut", C.POINTER(C.c_float)), ("white_point", C.c_float), ("to_out", C.c_float * 9),
-    ("to_work", C.c_float * 9), ("scale", C.c_double), ("chrominance_auto_factor", C.c_double)]
+    ("to_work", C.c_float * 9), ("scale", C.c_double), ("chrominance_auto_factor", C.c_double), ("ca_enabled", C.c_int32), ("ca", CaParams)]
 
 
 
@@ -165,6 +171,7 @@ def _load():
                                           C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_uint32]
     lib.artgpu_improc_denoise_fused.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(DenoiseFusion), C.POINTER(DenoiseToolParams), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_uint32]
+    lib.artgpu_raw_ca_correct.argtypes = [C.c_void_p, C.POINTER(Plane), C.c_uint32, C.POINTER(CaParams), C.POINTER(C.c_double)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
     lib.artgpu_denoise_compute_params.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_double),
@@ -241,7 +248,7 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_convert_color_space", "artgpu_exposure", "artgpu_tone_curve",
            "artgpu_wavelet_decompose", "artgpu_wavelet_mad", "artgpu_wavelet_info", "artgpu_wavelet_get_band", "artgpu_wavelet_set_band",
            "artgpu_wavelet_reconstruct", "artgpu_wavelet_free", "artgpu_rgb_denoise", "artgpu_denoise_guided_smoothing",
-           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer"]
+           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -398,6 +405,13 @@ class Context:
         self._chk(LIB.artgpu_scale_colors(self._h, src.ctypes.data, w, h, src.strides[0], 1 if src.dtype == np.uint16 else 0, 0, filters, xt,
                                           cb, sm, C.byref(dst), mx))
         return [float(v) for v in mx]
+
+    def raw_ca_correct(self, raw: Plane, filters: int, params: "CaParams", want_fit: bool = False):
+        """RawImageSource::CA_correct_RT in place on a scaled CFA plane; returns fitparams as a (2, 2, 16) array when want_fit"""
+        fit = np.zeros(64, np.float64) if want_fit else None
+        self._chk(LIB.artgpu_raw_ca_correct(self._h, C.byref(raw), filters, C.byref(params),
+                                            fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fit else None))
+        return fit.reshape(2, 2, 16) if want_fit else None
 
     def denoise_compute_params(self, planes: RGB, border: int, mul, do_clip: bool, cam_to_work, ws, dn: DenoiseParams,
                                auto_factor: float = 1.0, store: "DenoiseInfoStore" = None) -> "DenoiseInfoStore":

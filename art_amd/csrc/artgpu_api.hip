@@ -1121,6 +1121,7 @@ namespace {
 
 enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1, P_SF, P_TMP, P_HISTO, P_MAD, P_GAM, P_CCALC, P_LIN, P_BLOCKS, P_DTAB, P_CCMAP, P_CACHEF, P_PQ, P_XCBRT, P_GAUSS64, P_DMASK, P_LABTABS, P_PIPE_R, P_PIPE_G, P_PIPE_B, P_DNINFO, P_BATCH, P_DCTTAB, P_CBANDS2, P_CLOW0_2, P_CLOW1_2, P_SF_A, P_SF_B, P_HISTO_A, P_HISTO_B, P_RGBCURVES, P_FUSED, P_LBANDS2,
        P_IO_IN0, P_IO_IN1, P_IO_CFA, P_IO_IMG0, P_IO_IMG1, P_IO_IMG2, P_IO_IMG3, P_IO_IMG4, P_IO_IMG5, P_IO_OUT0, P_IO_OUT1, P_IO_FLAGS,      // artgpu_batch_run_io: staging slots, the CFA plane, the working image, the frames' flag words
+       P_CA_HALF, P_CA_BLK, P_CA_GUARD, P_CA_RAW,                                                                       // artgpu_raw_ca_correct
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 
@@ -2960,19 +2961,141 @@ int artgpu_scale_colors(artgpu_ctx *ctx, const void *src, int32_t w, int32_t h, 
     return ARTGPU_OK;
 }
 
+namespace {
+// Bayer 2x2 colour map of `filters` for the CA correction: FC packed as CaArgs::cfa; false for X-Trans, a fourth colour or a
+// pattern without one green per row and column
+static bool ca_cfa(uint32_t filters, unsigned *cfa)
+{
+    if (filters == 9) return false;
+    unsigned f[2][2], packed = 0;
+    for (int r = 0; r < 2; ++r)
+        for (int c = 0; c < 2; ++c) {
+            f[r][c] = (filters >> ((((r << 1) & 14) + (c & 1)) << 1)) & 3;
+            if (f[r][c] == 3) return false;
+            packed |= f[r][c] << ((r * 2 + c) * 2);
+        }
+    for (int k = 0; k < 2; ++k)
+        if ((f[k][0] == 1) == (f[k][1] == 1) || (f[0][k] == 1) == (f[1][k] == 1)) return false;
+    *cfa = packed;
+    return true;
+}
+
+// CA_correct_RT on a contiguous-or-strided device CFA plane, enqueued on ctx->stream (no synchronisation unless fit_out)
+static int ca_correct_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, unsigned cfa, const artgpu_ca_params *p, double *fit_out)
+{
+    constexpr int ts = 128, border2 = 16, cb = 2;
+    CaArgs a = {};
+    a.raw = raw; a.stride = stride; a.W = W; a.H = H; a.width = W + (W & 1); a.cfa = cfa;
+    const int vz1 = (H + border2) % (ts - border2) == 0 ? 1 : 0;
+    const int hz1 = (a.width + border2) % (ts - border2) == 0 ? 1 : 0;
+    a.vblsz = (int)ceil((float)(H + border2) / (ts - border2) + 2 + vz1);
+    a.hblsz = (int)ceil((float)(a.width + border2) / (ts - border2) + 2 + hz1);
+    a.ntv = (H + 8 + (ts - border2) - 1) / (ts - border2);
+    a.nth = (W + 8 + (ts - border2) - 1) / (ts - border2);
+    a.fw = (W + 1 - 2 * cb) / 2; a.fh = (H + 1 - 2 * cb) / 2;
+    a.autoCA = p->autocorrect ? 1 : 0;
+    a.cared = p->red; a.cablue = p->blue;
+    const int iterations = a.autoCA ? (p->iterations > 1 ? p->iterations : 1) : 1;
+    const bool guard = p->avoid_colour_shift != 0;
+    const size_t half = (size_t)H * a.width / 2, nb = (size_t)a.vblsz * a.hblsz, ninner = (size_t)(a.vblsz - 2) * (a.hblsz - 2);
+    const size_t fplane = (size_t)a.fw * a.fh;
+    float *halfp, *blk, *grd = nullptr;
+    int rc;
+    if ((rc = pool_get(ctx, P_CA_HALF, 2 * half * 4, &halfp)) || (rc = pool_get(ctx, P_CA_BLK, (144 + nb * 5 + ninner * 8 + 4) * 4, &blk)))
+        return rc;
+    if (guard && (rc = pool_get(ctx, P_CA_GUARD, ((size_t)a.fw * (H - 2 * cb) + 3 * fplane) * 4, &grd))) return rc;
+    a.Gtmp = halfp; a.RawDataTmp = halfp + half;
+    a.fit = reinterpret_cast<double *>(blk);                       // 64 doubles first: 8-byte aligned
+    a.words = reinterpret_cast<int *>(blk + 128);
+    a.blockwt = blk + 144; a.blockshifts = a.blockwt + ((nb + 3) & ~(size_t)3); a.blockfit = a.blockshifts + 4 * nb;
+    if (guard) { a.oldraw = grd; a.red = grd + (size_t)a.fw * (H - 2 * cb); a.blue = a.red + fplane; }
+    // the reference zeroes blockwt / blockshifts once per call (L208); Gtmp (never written in manual mode) and fitparams (only
+    // partly written by a linear fit) are zeroed here so that every value the device reads is defined
+    HIPCHK(ctx, hipMemsetAsync(halfp, 0, half * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(blk, 0, (144 + ((nb + 3) & ~(size_t)3) + 4 * nb) * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.words), 1, 2, ctx->stream));       // run, processpasstwo
+    HIPCHK(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.words + 2), 4, 1, ctx->stream));   // polyord
+    if (guard) HIPCHK(ctx, launch_ca_capture(a, ctx->stream));
+    for (int it = 0; it < iterations; ++it) {
+        HIPCHK(ctx, launch_ca_iteration(a, ctx->stream));
+        if (guard) {
+            HIPCHK(ctx, launch_ca_factors(a, ctx->stream));
+            if ((rc = gaussian_dev(ctx, a.red, a.blue + fplane, a.fw, a.fh, 30.0)) || (rc = gaussian_dev(ctx, a.blue, a.blue + fplane, a.fw, a.fh, 30.0)))
+                return rc;
+            HIPCHK(ctx, launch_ca_apply(a, ctx->stream));
+        }
+        HIPCHK(ctx, launch_ca_step(a, ctx->stream));
+    }
+    if (fit_out) {
+        HIPCHK(ctx, hipMemcpyAsync(fit_out, a.fit, 64 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return ARTGPU_OK;
+}
+} // namespace
+
+int artgpu_raw_ca_correct(artgpu_ctx *ctx, artgpu_plane *raw, uint32_t filters, const artgpu_ca_params *p, double fit_out[64])
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!plane_ok(raw) || !p) return fail(ctx, ARTGPU_EINVAL, "raw_ca_correct: bad argument");
+    unsigned cfa;
+    if (!ca_cfa(filters, &cfa)) return fail(ctx, ARTGPU_EUNSUPPORTED, "raw_ca_correct: RGB Bayer patterns only (filters 0x%08x)", filters);
+    if (raw->w < 64 || raw->h < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "raw_ca_correct: frame smaller than 64x64");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if (raw->on_device) return ca_correct_dev(ctx, raw->p, (size_t)(raw->row_stride_bytes / 4), raw->w, raw->h, cfa, p, fit_out);
+    float *work;
+    if ((rc = pool_get(ctx, P_CA_RAW, (size_t)raw->w * raw->h * 4, &work))) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(work, (size_t)raw->w * 4, raw->p, (size_t)raw->row_stride_bytes, (size_t)raw->w * 4, raw->h, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ca_correct_dev(ctx, work, raw->w, raw->w, raw->h, cfa, p, fit_out))) return rc;
+    return pool_to_plane(ctx, work, raw);
+}
+
 // ---------------------------------------------------------------------------------------------
 // one frame / one batch share through the whole path
 // ---------------------------------------------------------------------------------------------
+namespace {
+// the call site's condition (rawimagesource.cc:1827): CA correction enabled, auto or a manual shift, Bayer only (X-Trans skips it)
+static bool pipeline_ca(const artgpu_pipeline_params *p)
+{
+    return p->ca_enabled && (p->ca.autocorrect || fabs(p->ca.red) > 0.001 || fabs(p->ca.blue) > 0.001) && p->sensor == 0;
+}
+// CA correction of the CFA plane `raw` (device, rows of `stride` floats) in place, ahead of the demosaic
+static int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, const artgpu_pipeline_params *p)
+{
+    unsigned cfa;
+    if (!ca_cfa(p->filters, &cfa)) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on RGB Bayer patterns only (filters 0x%08x)", p->filters);
+    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on a frame smaller than 64x64");
+    return ca_correct_dev(ctx, raw, stride, W, H, cfa, &p->ca, nullptr);
+}
+static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca);
+} // namespace
+
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *p, artgpu_rgb *out)
+{
+    return pipeline_run_impl(ctx, raw, p, out, true);
+}
+
+namespace {
+static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca)
 {
     StageScope scope_(ctx, "ImageProcessor (stage_init .. stage_finish)");
     if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(raw) || !p || !out) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: null/bad argument");
-    const int W = raw->w, H = raw->h, b = p->border;
+    if (!plane_ok(raw_in) || !p || !out) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: null/bad argument");
+    const int W = raw_in->w, H = raw_in->h, b = p->border;
     if (b < 0 || W - 2 * b < 8 || H - 2 * b < 8) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: border %d leaves no image", b);
     if (out->r.w != W - 2 * b || out->r.h != H - 2 * b) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", W - 2 * b, H - 2 * b);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
+    // RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy: the caller's raw is never written
+    artgpu_plane rawc = *raw_in;
+    const artgpu_plane *raw = raw_in;
+    if (do_ca && pipeline_ca(p)) {
+        float *cp;
+        if ((rc = plane_to_pool(ctx, raw_in, P_CA_RAW, &cp)) || (rc = pipeline_ca_dev(ctx, cp, W, W, H, p))) return rc;
+        rawc.p = cp; rawc.row_stride_bytes = (int64_t)W * 4; rawc.on_device = 1;
+        raw = &rawc;
+    }
     // demosaiced planes live in the context pool (never leave the device)
     float *pl[3];
     for (int k = 0; k < 3; ++k)
@@ -3031,6 +3154,7 @@ int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_p
     }
     return unbind_rgb(ctx, out, &d);
 }
+} // namespace
 
 int artgpu_set_batch_lanes(artgpu_ctx *ctx, int lanes)
 {
@@ -3248,10 +3372,12 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
 
     // ---- the path
     artgpu_plane raw = {cfa, W, H, (int64_t)W * 4, 1};
+    // CA_correct_RT on the staged CFA plane itself, after scaleColors and before the demosaic (rawimagesource.cc:1666,1827)
+    if (pipeline_ca(p) && (rc = pipeline_ca_dev(c, cfa, W, W, H, p))) return rc;
     artgpu_rgb image;
     artgpu_plane *ip[3] = {&image.r, &image.g, &image.b};
     for (int k = 0; k < 3; ++k) { ip[k]->p = img[k]; ip[k]->w = iw; ip[k]->h = ih; ip[k]->row_stride_bytes = (int64_t)iw * 4; ip[k]->on_device = 1; }
-    if ((rc = artgpu_pipeline_run(c, &raw, p, &image))) return rc;
+    if ((rc = pipeline_run_impl(c, &raw, p, &image, false))) return rc;
 
     // ---- rgb2out (matrix + TRC, in place) and the writers' scanlines
     OutArgs o = {};

@@ -551,4 +551,26 @@ hipError_t launch_nlm(const NlmArgs &a, hipStream_t s);
 bool nlm_group_supported(const NlmArgs &a);
 hipError_t launch_nlm_group(const NlmArgs &a, hipStream_t s);   // nlm_sweep.hip: workgroup per tile, a search row of offsets in flight
 
+// raw CA correction (cacorrect.hip, RawImageSource::CA_correct_RT): one frame, Bayer, in place on a scaled CFA plane
+struct CaArgs {
+    float *raw; size_t stride;             // W x H CFA plane, row stride in floats
+    int W, H, width;                       // width = W + (W & 1)
+    unsigned cfa;                          // FC(r, c) for r, c in {0, 1} at bits ((r * 2 + c) * 2)
+    int vblsz, hblsz, ntv, nth;            // block grid (tiles are blocks 1..ntv x 1..nth) and tile counts
+    int fw, fh;                            // colour-shift factor planes (and oldraw's row length fw)
+    float *Gtmp, *RawDataTmp;              // H x width / 2 half planes
+    float *blockwt, *blockshifts;          // vblsz * hblsz floats, vblsz * hblsz float4 ([c][dir])
+    float *blockfit;                       // (vblsz - 2) * (hblsz - 2) * 8: medians, acceptance, weight of the inner blocks
+    float *oldraw, *red, *blue;            // colour-shift guard: (H - 4) x fw, fh x fw, fh x fw
+    double *fit;                           // fitparams[2][2][16]
+    int *words;                            // [0] the iteration runs, [1] processpasstwo, [2] polyord
+    int autoCA;
+    double cared, cablue;
+};
+hipError_t launch_ca_capture(const CaArgs &a, hipStream_t s);
+hipError_t launch_ca_iteration(const CaArgs &a, hipStream_t s);   // pass 1 + fit (auto), pass 2, copy back
+hipError_t launch_ca_factors(const CaArgs &a, hipStream_t s);     // factor planes + odd-size fills (before the blur)
+hipError_t launch_ca_apply(const CaArgs &a, hipStream_t s);       // raw *= blurred factors
+hipError_t launch_ca_step(const CaArgs &a, hipStream_t s);        // end of an iteration: the next one runs if this one ran pass 2
+
 } // namespace artgpu

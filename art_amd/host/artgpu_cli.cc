@@ -7,7 +7,8 @@
 //   artgpu-cli --in frame.f32 --width 4000 --height 3000 [--u16] [--filters 0x94949494]
 //              [--method amaze|rcd] [--border 4] [--denoise L,C] [--chroma-auto] [--expcomp 0.3] [--out out.ppm]
 //              [--dual bilinear|vng4] [--dual-contrast C] [--logenc REG] [--saturation S,V] [--labchroma C]   (SURVEY 8f N4 tools)
-//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--out prefix]
+//              [--ca auto[,N] | --ca manual,R,B] [--ca-keep-colourshift]   (RawImageSource::CA_correct_RT after the load, before the demosaic)
+//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <chrono>
@@ -48,6 +49,9 @@ int main(int argc, char **argv)
     int gradius = 3, nlstrength = 0, nldetail = 80;
     bool dual = false, dual_auto = true, logenc = false, labcurve = false;
     int dual_second = ARTGPU_DUAL_BILINEAR, logenc_reg = 60, sat = 0, vib = 0, labchroma = 0;
+    bool ca_enable = false, ca_auto = true, ca_avoid = true;       // RAWParams: enable_ca, ca_autocorrect, ca_avoidcolourshift
+    int ca_iter = 2;                                               // caautoiterations
+    double ca_red = 0.0, ca_blue = 0.0;                            // cared, cablue
     double dual_contrast = 20;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -74,6 +78,14 @@ int main(int argc, char **argv)
         else if (a == "--logenc") { logenc = true; logenc_reg = std::atoi(next()); }
         else if (a == "--saturation") { if (std::sscanf(next(), "%d,%d", &sat, &vib) != 2) { std::fprintf(stderr, "--saturation S,V\n"); return 2; } }
         else if (a == "--labchroma") { labchroma = std::atoi(next()); labcurve = true; }
+        else if (a == "--ca") {
+            const std::string m = next();
+            ca_enable = true;
+            if (m == "auto" || m.rfind("auto,", 0) == 0) { ca_auto = true; if (m.size() > 5) ca_iter = std::atoi(m.c_str() + 5); }
+            else if (std::sscanf(m.c_str(), "manual,%lf,%lf", &ca_red, &ca_blue) == 2) ca_auto = false;
+            else { std::fprintf(stderr, "--ca auto[,N] | --ca manual,R,B\n"); return 2; }
+        }
+        else if (a == "--ca-keep-colourshift") ca_avoid = false;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
@@ -85,6 +97,8 @@ int main(int argc, char **argv)
             params.denoise.enabled = dn; params.denoise.luminance = lum; params.denoise.chrominance = chroma; params.denoise.luminanceDetail = 50;
             params.exposure.expcomp = expcomp;
             params.toneCurve.lut = default_tone_lut(); params.toneCurve.curveMode = tone_mode;
+            params.raw.enable_ca = ca_enable; params.raw.ca_autocorrect = ca_auto; params.raw.caautoiterations = ca_iter;
+            params.raw.cared = ca_red; params.raw.cablue = ca_blue; params.raw.ca_avoidcolourshift = ca_avoid;
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -169,6 +183,9 @@ int main(int argc, char **argv)
         params.xtranssensor.method = xtrans_passes == 1 ? ProcParams::ONE_PASS : ProcParams::THREE_PASS;
         imgsrc.setBorder(border);
         imgsrc.load(cfa.data());
+        params.raw.enable_ca = ca_enable; params.raw.ca_autocorrect = ca_auto; params.raw.caautoiterations = ca_iter;
+        params.raw.cared = ca_red; params.raw.cablue = ca_blue; params.raw.ca_avoidcolourshift = ca_avoid;
+        imgsrc.preprocessCA(params);            // rawimagesource.cc:1827-1840 (the input stands for the scaled CFA)
         imgsrc.demosaic(params);
         int fw, fh;
         imgsrc.getFullSize(fw, fh);

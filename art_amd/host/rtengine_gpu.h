@@ -81,6 +81,14 @@ struct ProcParams {
     struct { int method = ARTGPU_BAYER_AMAZE; int border = 4; bool dual = false; int dualSecond = ARTGPU_DUAL_BILINEAR; double dualDemosaicContrast = 20; bool dualDemosaicAutoContrast = true; } bayersensor;
     enum XTransMethod { ONE_PASS = 1, THREE_PASS = 3 };
     struct { int method = THREE_PASS; int border = 7; } xtranssensor;          // raw.xtranssensor.{method,border} (procparams.cc:3064)
+    // RAWParams' CA correction fields (procparams.cc:3122-3133; the Dynamic profile's Auto-Matched Curve.arp sets enable_ca and ca_autocorrect)
+    struct { bool enable_ca = false; bool ca_autocorrect = false; int caautoiterations = 2; double cared = 0, cablue = 0; bool ca_avoidcolourshift = true; } raw;
+    // the call site's condition (rawimagesource.cc:1827): Bayer only, auto or a manual shift
+    bool caApplies() const { return raw.enable_ca && (raw.ca_autocorrect || std::fabs(raw.cared) > 0.001 || std::fabs(raw.cablue) > 0.001); }
+    artgpu_ca_params caParams() const
+    {
+        return artgpu_ca_params{raw.ca_autocorrect ? 1 : 0, raw.caautoiterations, raw.cared, raw.cablue, raw.ca_avoidcolourshift ? 1 : 0};
+    }
     struct { bool enabled = false; double luminance = 0, luminanceDetail = 0; int luminanceDetailThreshold = 0; double chrominance = 15,
              chrominanceRedGreen = 0, chrominanceBlueYellow = 0, gamma = 1.7, chrominanceAutoFactor = 1; bool aggressive = false; int colorSpace = 0, chrominanceMethod = 0;
              bool smoothingEnabled = false; int guidedChromaRadius = 3, nlDetail = 80, nlStrength = 0; } denoise;   // procparams.cc:1900-1918 (chrominanceMethod: 0 MANUAL, 1 AUTOMATIC)
@@ -118,6 +126,19 @@ public:
     }
     void setBorder(int b) { border = b; }                                   // rawimagesource.h (simpleprocess.cc:138-146)
     void load(const float *cfa_host) { rawData.upload(cfa_host); }          // stands in for load()/preprocess(): CFA 0..65535
+    // RawImageSource::CA_correct_RT on rawData (CA_correct_RT.cc:122-1384, one frame), called from preprocess after scaleColors
+    // (rawimagesource.cc:1827-1840) when ProcParams::caApplies(); X-Trans frames never get here (the reference skips them)
+    void CA_correct_RT(bool autoCA, size_t autoIterations, double cared, double cablue, bool avoidColourshift)
+    {
+        artgpu_plane raw = rawData.view();
+        const artgpu_ca_params cp{autoCA ? 1 : 0, (int32_t)autoIterations, cared, cablue, avoidColourshift ? 1 : 0};
+        ctx.check(artgpu_raw_ca_correct(ctx.get(), &raw, filters, &cp, nullptr));
+    }
+    void preprocessCA(const ProcParams &p)
+    {
+        if (!isXtrans && p.caApplies())
+            CA_correct_RT(p.raw.ca_autocorrect, (size_t)p.raw.caautoiterations, p.raw.cared, p.raw.cablue, p.raw.ca_avoidcolourshift);
+    }
     // RawImageSource::demosaic (rawimagesource.cc:1854-1962)
     void demosaic(const ProcParams &p)
     {
@@ -361,6 +382,7 @@ public:
         pp.exposure_enabled = p.exposure.enabled ? 1 : 0; pp.expcomp = p.exposure.expcomp; pp.black = p.exposure.black;
         pp.tone_enabled = p.toneCurve.enabled ? 1 : 0; pp.tone_mode = p.toneCurve.curveMode; pp.tone_lut = p.toneCurve.lut.data(); pp.white_point = p.toneCurve.whitePoint;
         pp.scale = 1.0; pp.chrominance_auto_factor = d.chrominanceAutoFactor;
+        pp.ca_enabled = p.raw.enable_ca ? 1 : 0; pp.ca = p.caParams();    // the library applies the call site's condition per frame
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {

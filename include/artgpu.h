@@ -495,6 +495,27 @@ int artgpu_rgb_curves(artgpu_ctx *ctx, artgpu_rgb *img, const float *rcurve, con
  * (integers; both 0 = nothing to do), ws = working-space matrix (row 1 is the luminance). */
 int artgpu_saturation_vibrance(artgpu_ctx *ctx, artgpu_rgb *img, int saturation, int vibrance, const double ws[9]);
 
+/* RawImageSource::CA_correct_RT (rtengine/CA_correct_RT.cc:122-1384) for one frame (numFrames == 1, no fitParamsTransfer), called
+ * after scaleColors and before the demosaic (rawimagesource.cc:1827-1840).  In place on the scaled CFA plane `raw` (host or device;
+ * a host plane is staged and written back).  Auto mode: caautoiterations passes of detection (tiles of 128, step 112), 4th-order
+ * (linear under 32 blocks) fit and correction; fewer than 10 usable blocks or a vanishing block denominator end the iterations
+ * without pass 2, which is not an error.  Manual mode: one pass with shifts from red / blue (L1040-1046).  avoid_colour_shift:
+ * the factors oldraw / raw at R and B sites, blurred by gaussianBlur(sigma 30), multiplied back after every iteration
+ * (L168-181,1276-1352).  Block sums are taken in tile raster order (the reference leaves that order to its thread schedule).
+ * fit_out (may be NULL): fitparams[2][2][16] ([colour][dir][coefficient]) of the last fit that ran, zeros where none did; a non-NULL
+ * fit_out makes the call wait for the stream.  ARTGPU_EUNSUPPORTED, plane untouched: X-Trans (filters == 9), a fourth colour,
+ * a frame under 64x64.  Manual shifts are not limited, as in the reference (ART's sliders reach 8, i.e. 8 * H / W px); past
+ * 60 px, where the reference's reads would leave its tile's colour planes, they are held at 60.  Manual mode reads the G
+ * half plane where its own interpolation does not reach (tile borders); the reference leaves that plane unwritten in manual mode,
+ * the device zeroes it. */
+typedef struct {
+    int32_t autocorrect;          /* RAWParams::ca_autocorrect */
+    int32_t iterations;           /* caautoiterations (auto only; < 1 means 1, as the reference) */
+    double  red, blue;            /* cared, cablue (manual only) */
+    int32_t avoid_colour_shift;   /* ca_avoidcolourshift */
+} artgpu_ca_params;
+int artgpu_raw_ca_correct(artgpu_ctx *ctx, artgpu_plane *raw, uint32_t filters, const artgpu_ca_params *p, double fit_out[64]);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -527,6 +548,10 @@ typedef struct {
     double scale;
     double chrominance_auto_factor; /* DenoiseParams::chrominanceAutoFactor; 0 means 1 (only read when denoise.dn.chrominance_method is AUTOMATIC:
                                      * artgpu_denoise_compute_params then runs on the demosaiced planes, as simpleprocess.cc:254-256 does) */
+    int32_t ca_enabled;             /* RAWParams::enable_ca: artgpu_raw_ca_correct ahead of the demosaic when
+                                     * ca_enabled && (ca.autocorrect || |ca.red| > 0.001 || |ca.blue| > 0.001) && sensor == Bayer
+                                     * (rawimagesource.cc:1827); on a device copy of `raw` (artgpu_batch_run_io: on its staged plane) */
+    artgpu_ca_params ca;
 } artgpu_pipeline_params;
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *params, artgpu_rgb *out);
 
