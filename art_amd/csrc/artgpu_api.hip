@@ -34,6 +34,8 @@ struct artgpu_ctx {
     int ccalc_nonneg = 0;          // set by artgpu_improc_denoise around RGB_denoise: the chroma noise map is the one chroma_map_kernel has just written (squares: no negative value)
     int opt_dn_fused = 1;          // ShrinkAllL / ShrinkAllAB -- 0: three kernels per channel (factors, row sums, column sums + update); 2: one kernel per
                                    // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
+    int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
+                                   // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
     int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
@@ -489,6 +491,7 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
     else if (n == "roctx") ctx->opt_roctx = value != 0;
     else if (n == "dn_streams") ctx->opt_dn_streams = value != 0;
     else if (n == "dn_fused") ctx->opt_dn_fused = (int)value;
+    else if (n == "dn_detail_plain") { if (value < 0 || value > 3) return fail(ctx, ARTGPU_EINVAL, "dn_detail_plain: 0 .. 3"); ctx->opt_dn_detail_plain = (int)value; }
     else if (n == "dn_debug_stall") ctx->opt_dn_debug_stall = (int)value;
     else if (n == "dn_wait_ms") ctx->opt_dn_wait_ms = value < 0 ? 0 : value;
     else if (n == "lut_lds") ctx->opt_lut_lds = value != 0;
@@ -1597,6 +1600,7 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
             }
             da.tm_in = dtab; da.tm_out = dtab + 4096; da.costab = dtab + 2 * 4096; da.costab_t = dtab + 3 * 4096;
             da.L = Lout; da.Lin = Lin;
+            da.plain = ctx->opt_dn_detail_plain == 1 ? 3 : ctx->opt_dn_detail_plain == 2 ? 1 : ctx->opt_dn_detail_plain == 3 ? 2 : 0;
             if (p->luminance_detail_threshold > 0) {
                 // detail_mask(LL, mask, 65535, 25, 10000, amount, GAUSS, 25 / scale) on the denoised L (FTblockDN.cc:1502-1507)
                 float *dmask;
@@ -3205,7 +3209,7 @@ int batch_prepare_lanes(artgpu_ctx *ctx, int L)
         peer->curve_tail_kind = ctx->curve_tail_kind; peer->curve_tail_y = ctx->curve_tail_y; peer->curve_tail_pc = ctx->curve_tail_pc;
         peer->opt_amaze_path = ctx->opt_amaze_path; peer->opt_amaze_split = ctx->opt_amaze_split; peer->opt_amaze_overlap = ctx->opt_amaze_overlap; peer->opt_amaze_grid = ctx->opt_amaze_grid;
         peer->opt_amaze_zero_mask = ctx->opt_amaze_zero_mask; peer->opt_amaze_zero_frame = ctx->opt_amaze_zero_frame; peer->opt_amaze_poison = ctx->opt_amaze_poison;
-        peer->opt_rcd_rows = ctx->opt_rcd_rows; peer->opt_roctx = ctx->opt_roctx; peer->opt_lut_lds = ctx->opt_lut_lds; peer->opt_dn_streams = ctx->opt_dn_streams; peer->opt_dn_fused = ctx->opt_dn_fused;
+        peer->opt_rcd_rows = ctx->opt_rcd_rows; peer->opt_roctx = ctx->opt_roctx; peer->opt_lut_lds = ctx->opt_lut_lds; peer->opt_dn_streams = ctx->opt_dn_streams; peer->opt_dn_fused = ctx->opt_dn_fused; peer->opt_dn_detail_plain = ctx->opt_dn_detail_plain;
         peer->opt_dn_wait_ms = ctx->opt_dn_wait_ms; peer->opt_dn_debug_stall = ctx->opt_dn_debug_stall; peer->opt_io_direct = ctx->opt_io_direct;
         peer->progress_fn = ctx->progress_fn; peer->progress_user = ctx->progress_user;
         peer->frames_in_flight = L;

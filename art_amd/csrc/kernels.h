@@ -495,6 +495,8 @@ struct DetailArgs {
     int blur_rad;
     const float *mask;      // luminanceDetailThreshold > 0: detail mask (w x h), else nullptr
     float params_Ldetail;
+    int plain;              // bit 0: detail_blocks_kernel, bit 1: detail_gather_kernel as they were before the trimmed forms (same bits; tests, timing)
+    int inside32;           // set by launch_detail_blocks: the planes are small enough for 32-bit byte offsets inside a block
 };
 hipError_t launch_detail_blocks(const DetailArgs &a, hipStream_t s);
 hipError_t launch_detail_gather(const DetailArgs &a, hipStream_t s);

@@ -87,6 +87,9 @@ int artgpu_synchronize(artgpu_ctx *ctx);
  *                       frames in flight (the other frames' memory-bound passes get the rest)
  *   "dn_fused"          1 (default): ShrinkAllL / ShrinkAllAB as one pass over the coefficients, one launch for the three channels where nothing has
  *                       to happen between them; 2: one launch per channel; 0: the three-kernel form (factors, row sums, column sums + update)
+ *   "dn_detail_plain"   0 (default): the DCT detail recovery's trimmed kernels (blocks inside the image on a path of their own, the gather by rows);
+ *                       1: the kernels before them, same bits (what tests/test_gpu_detail_paths.py compares against); 2 / 3: only the block kernel /
+ *                       only the gather kernel plain
  *   "dn_streams"        0 (default since round 5): RGB_denoise's kernels one after the other on the context's stream; 1: the DCT detail recovery of L on a
  *                       side stream beside the reconstructions of a and b (the default of rounds 3 and 4); "lut_lds" 0: never the LUT-in-LDS shape
  *                       of the pixel passes; "rcd_rows" 4 | 8; "roctx" 1: roctx ranges named after the reference functions
