@@ -5,6 +5,7 @@
 // reference's bits (rtengine is built with -ffp-contract=off, CMakeLists.txt:35-38).
 //
 //   sse_min/sse_max : _mm_min_ps/_mm_max_ps operand order (rtengine/helpersse2.h:168-179)
+//   sse_cvt_rn/_trunc : cvtps2dq / cvttss2si, which return 0x80000000 for what an int cannot hold
 //   intp            : a*b + (1-a)*c (rtengine/rt_math.h:109-118, sleefsseavx.h:1435-1442)
 //   median3         : rtengine/median.h:52-64
 //   xdiv2f/xdivf    : exponent-field arithmetic (rtengine/sleef.h:1267-1301)
@@ -22,6 +23,10 @@ __device__ __forceinline__ unsigned fc(unsigned filters, unsigned row, unsigned 
 }
 __device__ __forceinline__ float sse_min(float x, float y) { return x < y ? x : y; }
 __device__ __forceinline__ float sse_max(float x, float y) { return x > y ? x : y; }
+// float -> int as SSE2 converts: a value an int cannot hold gives the "integer indefinite" 0x80000000, where v_cvt_i32_f32 saturates.  The two
+// only part above INT_MAX (below INT_MIN both give INT_MIN; NaN gives 0 here and INT_MIN there, which every user clamps to the same index 0).
+__device__ __forceinline__ int sse_cvt_rn(float x) { return x >= 2147483648.f ? (int)0x80000000 : __float2int_rn(x); }
+__device__ __forceinline__ int sse_cvt_trunc(float x) { return x >= 2147483648.f ? (int)0x80000000 : (int)x; }
 __device__ __forceinline__ float std_min(float a, float b) { return b < a ? b : a; }
 __device__ __forceinline__ float std_max(float a, float b) { return a < b ? b : a; }
 __device__ __forceinline__ float sqr(float x) { return x * x; }

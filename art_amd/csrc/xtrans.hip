@@ -240,7 +240,7 @@ __global__ void __launch_bounds__(XTRANS_THREADS, XTRANS_MIN_WAVES) xtrans_tiles
                         const float x0 = p0 * a.xyz_cam[0] + p1 * a.xyz_cam[1] + p2 * a.xyz_cam[2];
                         const float x1 = p0 * a.xyz_cam[3] + p1 * a.xyz_cam[4] + p2 * a.xyz_cam[5];
                         const float x2 = p0 * a.xyz_cam[6] + p1 * a.xyz_cam[7] + p2 * a.xyz_cam[8];
-                        ix[u][0] = __float2int_rn(x0); ix[u][1] = __float2int_rn(x1); ix[u][2] = __float2int_rn(x2);
+                        ix[u][0] = sse_cvt_rn(x0); ix[u][1] = sse_cvt_rn(x1); ix[u][2] = sse_cvt_rn(x2);      // (far above the table: index 0, not the last)
                         // ... the scalar tail (the row's last two columns) rounds by adding 0.5 and truncating: only the waves that hold such a pixel
                         const bool vec = j < ((LW - 3 + 3) / 4) * 4;
                         if (__builtin_amdgcn_ballot_w64(!vec) != 0) {
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(XTRANS_THREADS, XTRANS_MIN_WAVES) xtrans_tiles
                             y0 += a.xyz_cam[0] * p0; y1 += a.xyz_cam[3] * p0; y2 += a.xyz_cam[6] * p0;
                             y0 += a.xyz_cam[1] * p1; y1 += a.xyz_cam[4] * p1; y2 += a.xyz_cam[7] * p1;
                             y0 += a.xyz_cam[2] * p2; y1 += a.xyz_cam[5] * p2; y2 += a.xyz_cam[8] * p2;
-                            if (!vec) { ix[u][0] = (int)y0; ix[u][1] = (int)y1; ix[u][2] = (int)y2; }
+                            if (!vec) { ix[u][0] = sse_cvt_trunc(y0); ix[u][1] = sse_cvt_trunc(y1); ix[u][2] = sse_cvt_trunc(y2); }
                         }
                     }
                     float cv[U][3];

@@ -9,6 +9,8 @@ Scene = smooth gradient (integer sine table) + 64-px checker + a patch of 1-px
 (Nyquist) stripes (exercises amaze_demosaic_RT.cc:846-954) + a clipped patch at 65535
 (exercises the clip_pt paths, L417-425,565) + hash noise, multiplied by per-colour
 gains R 0.6 / G 1.0 / B 0.7 through the CFA.
+
+Everything outside that domain -- negatives, fractions, runs of zeros, -0.0, subnormals, values above 65535 -- is in tests/value_domains.py.
 """
 from __future__ import annotations
 

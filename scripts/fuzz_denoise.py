@@ -1,11 +1,13 @@
 """Random sizes and parameters through RGB_denoise (gamma / YUV, MadRgb, the shrinkage passes with their box blurs, reconstruction; the DCT
-stage off, so bit for bit) on ONE context: GPU vs oracle.  Not a test; run on an MI355X box: `python scripts/fuzz_denoise.py` (env SEED, N)."""
-import os, sys
+stage off, so bit for bit) on ONE context: GPU vs oracle.  Not a test; run on an MI355X box: `python scripts/fuzz_denoise.py [--family NAME]` (env SEED, N; --family: the demosaiced frame comes from that
+value domain of tests/value_domains.py instead of synth's own)."""
+import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import oracle_lib as O
 from art_amd import capi, synth
+import value_domains as VD
 
 
 def cases(seed, n):
@@ -19,8 +21,11 @@ def cases(seed, n):
                    aggressive=int(rng.integers(0, 2)), scale=float(rng.choice([1.0, 1.0, 2.0])))
 
 
-def run(ctx, c):
-    raw = synth.bayer_frame(c["w"] // 2 * 2, c["h"] // 2 * 2, synth.FILTERS_RGGB, seed=c["seed"], noise=c["noise"])
+def run(ctx, c, family=None):
+    if family:          # one base frame per size (seed 3, noise 1500): the case's seed and noise are not used
+        raw = VD.family(family, c["w"] // 2 * 2, c["h"] // 2 * 2, synth.FILTERS_RGGB)
+    else:
+        raw = synth.bayer_frame(c["w"] // 2 * 2, c["h"] // 2 * 2, synth.FILTERS_RGGB, seed=c["seed"], noise=c["noise"])
     img = [np.ascontiguousarray(p[:c["h"], :c["w"]]) for p in O.amaze(raw, synth.FILTERS_RGGB, 1.0, 4)]
     got = [p.copy() for p in img]
     p = capi.DenoiseParams(c["luminance"], 50.0, 0, c["chrominance"], c["rg"], c["by"], c["gamma"], c["aggressive"], 0, 0)
@@ -31,10 +36,14 @@ def run(ctx, c):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--family", choices=VD.NAMES, default=None,
+                    help="frames of this value domain; only the size varies then, the cases' seed and noise settings are ignored")
+    family = ap.parse_args().family
     ctx = capi.Context(0)
     bad = 0
     for c in cases(int(os.environ.get("SEED", "1")), int(os.environ.get("N", "30"))):
-        d = run(ctx, c)
+        d = run(ctx, c, family)
         bad += d != 0
         print(c, "ok" if d == 0 else f"DIFF {d}", flush=True)
     print("failures:", bad)
