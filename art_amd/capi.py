@@ -62,6 +62,16 @@ class CaParams(C.Structure):
                 ("avoid_colour_shift", C.c_int32)]
 
 
+class LocalContrastRegion(C.Structure):
+    """artgpu_local_contrast_region: one LocalContrastParams::Region, its curve as the 501-entry LUT, its blend mask"""
+    _fields_ = [("contrast", C.c_double), ("curve", C.POINTER(C.c_float)), ("mask", C.POINTER(Plane))]
+
+
+class LocalContrastInfo(C.Structure):
+    _fields_ = [("nlevels", C.c_int32), ("ave", C.c_float), ("min0", C.c_float), ("max0", C.c_float),
+                ("mean", C.c_float * 10), ("sigma", C.c_float * 10), ("maxp", C.c_float * 10)]
+
+
 class PipelineParams(C.Structure):
     pass
 
@@ -83,7 +93,8 @@ PipelineParams._fields_ = [
     ("ws", C.c_double * 9), ("iws", C.c_double * 9), ("denoise_enabled", C.c_int32), ("denoise", DenoiseToolParams),
     ("exposure_enabled", C.c_int32), ("expcomp", C.c_double), ("black", C.c_double), ("tone_enabled", C.c_int32),
     ("tone_mode", C.c_int32), ("tone_lut", C.POINTER(C.c_float)), ("white_point", C.c_float), ("to_out", C.c_float * 9),
-    ("to_work", C.c_float * 9), ("scale", C.c_double), ("chrominance_auto_factor", C.c_double), ("ca_enabled", C.c_int32), ("ca", CaParams)]
+    ("to_work", C.c_float * 9), ("scale", C.c_double), ("chrominance_auto_factor", C.c_double), ("ca_enabled", C.c_int32), ("ca", CaParams),
+    ("local_contrast_enabled", C.c_int32), ("local_contrast_nregions", C.c_int32), ("local_contrast_regions", C.POINTER(LocalContrastRegion))]
 
 
 
@@ -101,6 +112,9 @@ class ScanlineFrame(C.Structure):
 
 
 DN_SKIP_DETAIL_RECOVERY = 1
+LOCAL_CONTRAST_MIN_SIZE = 8
+# LocalContrastParams::Region's default curve (procparams.cc:1700-1714)
+DEFAULT_LOCAL_CONTRAST_CURVE_POINTS = (1.0, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0)
 # the chroma noise curve ImProcFunctions::denoise always installs (ipdenoise.cc:1139-1149)
 DEFAULT_NOISE_C_CURVE_POINTS = (1.0, 0.05, 0.50, 0.35, 0.35, 0.35, 0.05, 0.35, 0.35)
 
@@ -115,6 +129,33 @@ def noise_curve_lut(points=DEFAULT_NOISE_C_CURVE_POINTS):
         raise ArtGpuError(f"artgpu_noise_curve_lut: error {rc}")
     return lut, float(s.value)
 
+
+def local_contrast_curve_lut(points=DEFAULT_LOCAL_CONTRAST_CURVE_POINTS):
+    """WavOpacityCurveWL::Set -> (501-entry float32 LUT, is_set); an unset LUT (identity, empty or linear curve) comes back zeroed."""
+    pts = (C.c_double * max(len(points), 1))(*[float(p) for p in points])
+    lut = np.zeros(501, np.float32)
+    is_set = C.c_int(0)
+    rc = LIB.artgpu_local_contrast_curve_lut(pts, len(points), lut.ctypes.data_as(C.POINTER(C.c_float)), C.byref(is_set))
+    if rc:
+        raise ArtGpuError(f"artgpu_local_contrast_curve_lut: error {rc}")
+    return lut, bool(is_set.value)
+
+
+def local_contrast_regions(regions):
+    """[(contrast, curve LUT or None, mask Plane or None), ...] -> (LocalContrastRegion array, objects to keep alive with it)"""
+    arr = (LocalContrastRegion * max(len(regions), 1))()
+    keep = []
+    for k, (contrast, curve, mask) in enumerate(regions):
+        arr[k].contrast = float(contrast)
+        if curve is not None:
+            cv = np.ascontiguousarray(curve, dtype=np.float32)
+            assert cv.shape == (501,)
+            keep.append(cv)
+            arr[k].curve = cv.ctypes.data_as(C.POINTER(C.c_float))
+        if mask is not None:
+            keep.append(mask)
+            arr[k].mask = C.pointer(mask)
+    return arr, keep
 
 
 class ArtGpuError(RuntimeError):
@@ -172,6 +213,8 @@ def _load():
     lib.artgpu_improc_denoise_fused.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(DenoiseFusion), C.POINTER(DenoiseToolParams), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_uint32]
     lib.artgpu_raw_ca_correct.argtypes = [C.c_void_p, C.POINTER(Plane), C.c_uint32, C.POINTER(CaParams), C.POINTER(C.c_double)]
+    lib.artgpu_local_contrast_curve_lut.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
     lib.artgpu_denoise_compute_params.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_double),
@@ -248,7 +291,7 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_convert_color_space", "artgpu_exposure", "artgpu_tone_curve",
            "artgpu_wavelet_decompose", "artgpu_wavelet_mad", "artgpu_wavelet_info", "artgpu_wavelet_get_band", "artgpu_wavelet_set_band",
            "artgpu_wavelet_reconstruct", "artgpu_wavelet_free", "artgpu_rgb_denoise", "artgpu_denoise_guided_smoothing",
-           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct"]
+           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -412,6 +455,17 @@ class Context:
         self._chk(LIB.artgpu_raw_ca_correct(self._h, C.byref(raw), filters, C.byref(params),
                                             fit.ctypes.data_as(C.POINTER(C.c_double)) if want_fit else None))
         return fit.reshape(2, 2, 16) if want_fit else None
+
+    def local_contrast(self, L: Plane, regions, scale: float = 1.0, want_info: bool = False):
+        """ImProcFunctions::localContrast in place on an L plane; `regions`: [(contrast, curve LUT or None, mask Plane or None), ...].
+        Returns the LocalContrastInfo of the last region when want_info."""
+        arr, keep = local_contrast_regions(regions)
+        info = LocalContrastInfo() if want_info else None
+        self._chk(LIB.artgpu_local_contrast(self._h, C.byref(L), arr, len(regions), float(scale), C.byref(info) if want_info else None))
+        del keep
+        return info
+
+    local_contrast_curve_lut = staticmethod(local_contrast_curve_lut)
 
     def denoise_compute_params(self, planes: RGB, border: int, mul, do_clip: bool, cam_to_work, ws, dn: DenoiseParams,
                                auto_factor: float = 1.0, store: "DenoiseInfoStore" = None) -> "DenoiseInfoStore":

@@ -50,7 +50,7 @@ struct artgpu_ctx {
     float *stage[NSTAGE] = {};
     size_t stage_bytes[NSTAGE] = {};
     // grow-only scratch pool for the denoise path (planes, decompositions, shrink buffers)
-    static constexpr int NPOOL = 64;
+    static constexpr int NPOOL = 72;
     float *pool[NPOOL] = {};
     size_t pool_bytes[NPOOL] = {};
     // artgpu_batch_run lanes: sibling contexts (own stream, arena, pools) that take every lanes-th frame on their own host thread
@@ -1125,6 +1125,7 @@ namespace {
 enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1, P_SF, P_TMP, P_HISTO, P_MAD, P_GAM, P_CCALC, P_LIN, P_BLOCKS, P_DTAB, P_CCMAP, P_CACHEF, P_PQ, P_XCBRT, P_GAUSS64, P_DMASK, P_LABTABS, P_PIPE_R, P_PIPE_G, P_PIPE_B, P_DNINFO, P_BATCH, P_DCTTAB, P_CBANDS2, P_CLOW0_2, P_CLOW1_2, P_SF_A, P_SF_B, P_HISTO_A, P_HISTO_B, P_RGBCURVES, P_FUSED, P_LBANDS2,
        P_IO_IN0, P_IO_IN1, P_IO_CFA, P_IO_IMG0, P_IO_IMG1, P_IO_IMG2, P_IO_IMG3, P_IO_IMG4, P_IO_IMG5, P_IO_OUT0, P_IO_OUT1, P_IO_FLAGS,      // artgpu_batch_run_io: staging slots, the CFA plane, the working image, the frames' flag words
        P_CA_HALF, P_CA_BLK, P_CA_GUARD, P_CA_RAW,                                                                       // artgpu_raw_ca_correct
+       P_LC_BANDS, P_LC_LOW0, P_LC_LOW1, P_LC_NEW, P_LC_STATS, P_LC_MASK, P_LC_L,                                       // artgpu_local_contrast
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 
@@ -1135,7 +1136,7 @@ struct DevDecomp {
     float *band(int l, int dir) const { return bands + ((size_t)l * 3 + (dir - 1)) * n; }
 };
 
-int decompose_dev(artgpu_ctx *ctx, DevDecomp &d, const float *src, hipStream_t st = nullptr)
+int decompose_dev(artgpu_ctx *ctx, DevDecomp &d, const float *src, hipStream_t st = nullptr, size_t src_stride = 0)
 {
     if (!st) st = ctx->stream;
     WaveArgs a = {};
@@ -1143,7 +1144,7 @@ int decompose_dev(artgpu_ctx *ctx, DevDecomp &d, const float *src, hipStream_t s
     for (int l = 0; l < d.nlevels; ++l) {
         a.b1 = d.band(l, 1); a.b2 = d.band(l, 2); a.b3 = d.band(l, 3);
         if (l == 0) {
-            a.src = src; a.src_stride = d.w; a.lo = d.low[0]; d.cur = 0;
+            a.src = src; a.src_stride = src_stride ? src_stride : (size_t)d.w; a.lo = d.low[0]; d.cur = 0;
             HIPCHK(ctx, launch_wavelet_analysis0(a, st));
         } else {
             a.src = d.low[d.cur]; a.lo = d.low[d.cur ^ 1]; a.skip = wavelet_skip(l);
@@ -3056,6 +3057,116 @@ int artgpu_raw_ca_correct(artgpu_ctx *ctx, artgpu_plane *raw, uint32_t filters, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// ImProcFunctions::localContrast
+// ---------------------------------------------------------------------------------------------
+int artgpu_local_contrast_curve_lut(const double *points, int npoints, float lut[501], int *is_set)
+{
+    if (!lut || !is_set || npoints < 0 || (npoints > 0 && !points)) return ARTGPU_EINVAL;
+    *is_set = lc_curve_lut(points, npoints, lut) ? 1 : 0;
+    return ARTGPU_OK;
+}
+
+namespace {
+// what the call cannot do, before anything is touched: 0, or the code with the message set
+static int local_contrast_check(artgpu_ctx *ctx, int w, int h, const artgpu_local_contrast_region *regions, int nregions, double scale, const char *who)
+{
+    if (nregions < 0 || (nregions > 0 && !regions)) return fail(ctx, ARTGPU_EINVAL, "%s: bad region list", who);
+    for (int r = 0; r < nregions; ++r) {
+        const artgpu_plane *m = regions[r].mask;
+        if (m && (!plane_ok(m) || m->w != w || m->h != h)) return fail(ctx, ARTGPU_EINVAL, "%s: the mask of region %d must be a %dx%d plane", who, r, w, h);
+    }
+    if (scale != 1.0) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: scale %g (the skip form of the wavelet is not on the device path)", who, scale);
+    if (w < ARTGPU_LOCAL_CONTRAST_MIN_SIZE || h < ARTGPU_LOCAL_CONTRAST_MIN_SIZE)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %dx%d is below %dx%d", who, w, h, ARTGPU_LOCAL_CONTRAST_MIN_SIZE, ARTGPU_LOCAL_CONTRAST_MIN_SIZE);
+    const int nl = lc_wavelet_levels(w, h), w2 = (w + 1) / 2, h2 = (h + 1) / 2;
+    if ((w2 < h2 ? w2 : h2) < 2 * wavelet_skip(nl - 1))       // the wavelet kernels' own limit: never reached by the level rule from 8x8 up
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %dx%d too small for %d wavelet levels on the device path", who, w, h, nl);
+    return ARTGPU_OK;
+}
+
+// the regions of ImProcFunctions::localContrast (L463-481) on a device L plane (rows of `stride` floats), enqueued on ctx->stream; per
+// region the host waits once, for the statistics block it computes the constants of L372-380 from
+static int local_contrast_dev(artgpu_ctx *ctx, float *L, size_t stride, int w, int h, const artgpu_local_contrast_region *regions, int nregions,
+                              artgpu_local_contrast_info *info)
+{
+    DevDecomp d = {};
+    d.w = w; d.h = h; d.w2 = (w + 1) / 2; d.h2 = (h + 1) / 2; d.nlevels = lc_wavelet_levels(w, h);
+    d.n = (size_t)d.w2 * d.h2;
+    if (d.n > 0x7fffffff) return fail(ctx, ARTGPU_EUNSUPPORTED, "local_contrast: band larger than an int holds (the reference's W_L * H_L is an int)");
+    const int nbands = 3 * d.nlevels, nchunk = (int)((d.n + LC_CHUNK - 1) / LC_CHUNK);
+    // statistics block: results | curve | partial sums | counts | maxima | minima
+    const size_t res_bytes = 32 * sizeof(LcSegStats), curve_bytes = 512 * 4, np = (size_t)(nbands + 1) * nchunk;
+    float *Lnew, *stats;
+    int rc;
+    if ((rc = pool_get(ctx, P_LC_BANDS, (size_t)nbands * d.n * 4, &d.bands)) || (rc = pool_get(ctx, P_LC_LOW0, d.n * 4, &d.low[0])) ||
+        (rc = pool_get(ctx, P_LC_LOW1, d.n * 4, &d.low[1])) || (rc = pool_get(ctx, P_LC_NEW, (size_t)w * h * 4, &Lnew)) ||
+        (rc = pool_get(ctx, P_LC_STATS, res_bytes + curve_bytes + np * (8 + 4 + 4 + 4), &stats)))
+        return rc;
+    char *sb = reinterpret_cast<char *>(stats);
+    LcStatArgs sa = {};
+    sa.bands = d.bands; sa.n = d.n; sa.nbands = nbands; sa.nchunk = nchunk;
+    sa.res = reinterpret_cast<LcSegStats *>(sb);
+    float *curve_dev = reinterpret_cast<float *>(sb + res_bytes);
+    sa.psum = reinterpret_cast<double *>(sb + res_bytes + curve_bytes);
+    sa.pcnt = reinterpret_cast<int *>(sa.psum + np);
+    sa.pmax = reinterpret_cast<float *>(sa.pcnt + np);
+    sa.pmin = sa.pmax + np;
+    for (int r = 0; r < nregions; ++r) {
+        const artgpu_local_contrast_region &reg = regions[r];
+        const bool contrast_on = (float)reg.contrast != 0;
+        if ((rc = decompose_dev(ctx, d, L, nullptr, stride))) return rc;
+        if (reg.curve && (rc = h2d_table(ctx, curve_dev, reg.curve, 501 * 4))) return rc;
+        sa.coeff0 = contrast_on ? d.low[d.cur] : nullptr;
+        HIPCHK(ctx, launch_lc_stats(sa, ctx->stream));
+        LcSegStats res[32];
+        const int nseg = nbands + (contrast_on ? 1 : 0);
+        HIPCHK(ctx, hipMemcpyAsync(res, sa.res, (size_t)nseg * sizeof(LcSegStats), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));             // the region's one host wait
+        LcRemapArgs ra = {};
+        LcHostInfo hi;
+        lc_host_constants(res, d.nlevels, d.n, reg.contrast, &ra, &hi);
+        ra.bands = d.bands; ra.coeff0 = d.low[d.cur]; ra.n = d.n; ra.nlevels = d.nlevels; ra.curve = reg.curve ? curve_dev : nullptr;
+        HIPCHK(ctx, launch_lc_remap(ra, ctx->stream));
+        if ((rc = reconstruct_dev(ctx, d, Lnew))) return rc;
+        LcBlendArgs ba = {};
+        ba.L = L; ba.l_stride = stride; ba.Lnew = Lnew; ba.w = w; ba.h = h;
+        if (reg.mask) {
+            if (reg.mask->on_device) { ba.mask = reg.mask->p; ba.m_stride = (size_t)(reg.mask->row_stride_bytes / 4); }
+            else {
+                float *m;
+                if ((rc = plane_to_pool(ctx, reg.mask, P_LC_MASK, &m))) return rc;
+                ba.mask = m; ba.m_stride = w;
+            }
+        }
+        HIPCHK(ctx, launch_lc_blend(ba, ctx->stream));
+        if (info && r == nregions - 1) {
+            info->nlevels = d.nlevels;
+            info->ave = hi.ave; info->min0 = hi.min0; info->max0 = hi.max0;
+            for (int k = 0; k < 10; ++k) { info->mean[k] = hi.mean[k]; info->sigma[k] = hi.sigma[k]; info->maxp[k] = hi.maxp[k]; }
+        }
+    }
+    return ARTGPU_OK;
+}
+} // namespace
+
+int artgpu_local_contrast(artgpu_ctx *ctx, artgpu_plane *L, const artgpu_local_contrast_region *regions, int nregions, double scale,
+                          artgpu_local_contrast_info *info)
+{
+    StageScope scope_(ctx, "ImProcFunctions::localContrast");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!plane_ok(L)) return fail(ctx, ARTGPU_EINVAL, "local_contrast: bad plane");
+    int rc;
+    if ((rc = local_contrast_check(ctx, L->w, L->h, regions, nregions, scale, "local_contrast"))) return rc;
+    if (info) *info = artgpu_local_contrast_info{};
+    if (nregions == 0) return ARTGPU_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (L->on_device) return local_contrast_dev(ctx, L->p, (size_t)(L->row_stride_bytes / 4), L->w, L->h, regions, nregions, info);
+    float *work;
+    if ((rc = plane_to_pool(ctx, L, P_LC_L, &work)) || (rc = local_contrast_dev(ctx, work, L->w, L->w, L->h, regions, nregions, info))) return rc;
+    return pool_to_plane(ctx, work, L);
+}
+
+// ---------------------------------------------------------------------------------------------
 // one frame / one batch share through the whole path
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -3091,6 +3202,9 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
     if (out->r.w != W - 2 * b || out->r.h != H - 2 * b) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", W - 2 * b, H - 2 * b);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
+    if (p->local_contrast_enabled && p->local_contrast_nregions > 0 &&
+        (rc = local_contrast_check(ctx, W - 2 * b, H - 2 * b, p->local_contrast_regions, p->local_contrast_nregions, p->scale > 0 ? p->scale : 1.0, "pipeline_run(local contrast)")))
+        return rc;
     // RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy: the caller's raw is never written
     artgpu_plane rawc = *raw_in;
     const artgpu_plane *raw = raw_in;
@@ -3155,6 +3269,13 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
             rc = artgpu_tone_curve(ctx, &img, p->tone_mode, p->tone_lut, p->white_point, 1);
         }
         if (rc) return rc;
+    }
+    if (p->local_contrast_enabled && p->local_contrast_nregions > 0) {
+        // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), the regions on the L plane (Imagefloat::g), back to RGB
+        if ((rc = artgpu_rgb_to_lab(ctx, &img, p->ws)) ||
+            (rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, p->local_contrast_regions, p->local_contrast_nregions, nullptr)) ||
+            (rc = artgpu_lab_to_rgb(ctx, &img, p->iws)))
+            return rc;
     }
     return unbind_rgb(ctx, out, &d);
 }

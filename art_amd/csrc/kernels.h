@@ -575,4 +575,50 @@ hipError_t launch_ca_factors(const CaArgs &a, hipStream_t s);     // factor plan
 hipError_t launch_ca_apply(const CaArgs &a, hipStream_t s);       // raw *= blurred factors
 hipError_t launch_ca_step(const CaArgs &a, hipStream_t s);        // end of an iteration: the next one runs if this one ran pass 2
 
+// local contrast (localcontrast.hip, rtengine/iplocalcontrast.cc:97-420): statistics of the detail bands and of coeff0, the two
+// coefficient remaps, the mask blend.  A "segment" is one array of n = w2 * h2 coefficients: segment 3 * level + dir - 1 is
+// level_coeffs(level)[dir], segment `nbands` is coeff0.
+constexpr int LC_CHUNK = 4096;             // coefficients behind one partial: the unit of the reductions' fixed order
+struct LcSegStats {                        // one segment's sums, as the host reads them back (32 bytes)
+    double sum;                            // bands: sum of the values >= 5 (eval_avg's averaP); coeff0: sum of all values (avedbl)
+    double vari;                           // bands: sum of the float SQR(x - avg) over the values >= 5 (eval_sigma's variP)
+    int cnt;                               // bands: countP
+    float maxv, minv;                      // bands: max of the counted values (from 0); coeff0: max from 0, min from FLT_MAX
+    float avg;                             // bands: averagePlus = (float)(sum / cnt), 0 without a counted value
+};
+struct LcStatArgs {
+    const float *bands;                    // nbands segments of n floats
+    const float *coeff0;                   // n floats; nullptr: no coeff0 statistics (contrast == 0)
+    size_t n;
+    int nbands, nchunk;                    // nchunk = ceil(n / LC_CHUNK)
+    double *psum; int *pcnt; float *pmax, *pmin;   // partials, [segment][chunk]
+    LcSegStats *res;                       // [nbands + 1]
+};
+struct LcLevelConst { int on; float mean, thr, logmax, rap, asig, bsig, amean; };   // L371-380; thr = mean + sigma
+struct LcRemapArgs {
+    float *bands, *coeff0;
+    size_t n;
+    int nlevels;
+    const float *curve;                    // 501 entries on the device; nullptr: unset curve, operator[] returns 0 (L53-56)
+    LcLevelConst lv[10];
+    int c0_on;                             // contrast != 0 && max0 > 0 (L271, L324)
+    float ave, ah, bh, al, bl;             // L317-322
+};
+struct LcBlendArgs {
+    float *L; size_t l_stride;             // rgb->g: the plane before the region on entry, the blend on return
+    const float *Lnew;                     // the reconstruction, rows of w floats
+    const float *mask; size_t m_stride;    // nullptr: all ones
+    int w, h;
+};
+// averages (partials, then their combination and averagePlus), then the variances the same way: four launches, no host step between them
+hipError_t launch_lc_stats(const LcStatArgs &a, hipStream_t s);
+hipError_t launch_lc_remap(const LcRemapArgs &a, hipStream_t s);
+hipError_t launch_lc_blend(const LcBlendArgs &a, hipStream_t s);
+// host side: the level rule (L256-260), WavOpacityCurveWL::Set (L85-94) and everything between the statistics and the
+// coefficient loops (eval_level's averages L204-231, L278-279 + L315-324, L371-380)
+int lc_wavelet_levels(int w, int h);
+bool lc_curve_lut(const double *pts, int npts, float lut[501]);
+struct LcHostInfo { float ave, min0, max0, mean[10], sigma[10], maxp[10]; };
+void lc_host_constants(const LcSegStats *res, int nlevels, size_t n, double contrast, LcRemapArgs *ra, LcHostInfo *info);
+
 } // namespace artgpu

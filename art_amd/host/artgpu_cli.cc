@@ -8,6 +8,8 @@
 //              [--method amaze|rcd] [--border 4] [--denoise L,C] [--chroma-auto] [--expcomp 0.3] [--out out.ppm]
 //              [--dual bilinear|vng4] [--dual-contrast C] [--logenc REG] [--saturation S,V] [--labchroma C]   (SURVEY 8f N4 tools)
 //              [--ca auto[,N] | --ca manual,R,B] [--ca-keep-colourshift]   (RawImageSource::CA_correct_RT after the load, before the demosaic)
+//              [--local-contrast C[,curve-points]]   (ImProcFunctions::localContrast: one region, contrast C, the default region's curve unless FlatCurve
+//                                                      control points follow: kind,x,y,left,right,...)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
@@ -53,6 +55,9 @@ int main(int argc, char **argv)
     int ca_iter = 2;                                               // caautoiterations
     double ca_red = 0.0, ca_blue = 0.0;                            // cared, cablue
     double dual_contrast = 20;
+    bool lc_enable = false;                                        // LocalContrastParams::enabled, one region
+    double lc_contrast = 0;
+    std::vector<double> lc_curve;                                  // empty: the default region's curve
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -86,6 +91,19 @@ int main(int argc, char **argv)
             else { std::fprintf(stderr, "--ca auto[,N] | --ca manual,R,B\n"); return 2; }
         }
         else if (a == "--ca-keep-colourshift") ca_avoid = false;
+        else if (a == "--local-contrast") {
+            const char *v = next();
+            char *end = nullptr;
+            lc_contrast = std::strtod(v, &end);
+            if (end == v) { std::fprintf(stderr, "--local-contrast C[,curve-points]\n"); return 2; }
+            lc_enable = true;
+            while (*end == ',') {
+                const char *q = end + 1;
+                const double x = std::strtod(q, &end);
+                if (end == q) { std::fprintf(stderr, "--local-contrast C[,curve-points]\n"); return 2; }
+                lc_curve.push_back(x);
+            }
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
@@ -168,6 +186,13 @@ int main(int argc, char **argv)
         params.logenc.enabled = logenc; params.logenc.regularization = logenc_reg;
         params.saturation.enabled = sat != 0 || vib != 0; params.saturation.saturation = sat; params.saturation.vibrance = vib;
         params.labCurve.enabled = labcurve; params.labCurve.chromaticity = labchroma;
+        params.localContrast.enabled = lc_enable;
+        if (lc_enable) {
+            ProcParams::LocalContrastRegion region;
+            region.contrast = lc_contrast;
+            if (!lc_curve.empty()) region.curve = lc_curve;
+            params.localContrast.regions.push_back(region);
+        }
         params.labCurve.curves = [](const uint32_t *, std::vector<float> &lc, std::vector<float> &ac, std::vector<float> &bc) {
             // stands in for get_L_curve / get_ab_curves (DiagonalCurve, host code of the application): identity curves, so only chromaticity acts
             lc.resize(32770); ac.resize(65536); bc.resize(65536);

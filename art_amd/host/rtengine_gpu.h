@@ -102,6 +102,11 @@ struct ProcParams {
     struct { bool enabled = false; int chromaticity = 0, contrast = 0;
              std::function<void(const uint32_t *hist16, std::vector<float> &lcurve, std::vector<float> &acurve, std::vector<float> &bcurve)> curves; } labCurve;
     struct { bool enabled = false; int saturation = 0, vibrance = 0; } saturation;                                               // SaturationParams
+    // LocalContrastParams (procparams.cc:1700-1760): regions {contrast, curve as FlatCurve control points}; masks[i].enabled and the blend
+    // plane generateMasks makes of masks[i] (host code of the application; nullptr = all ones), one per region
+    struct LocalContrastRegion { double contrast = 0; std::vector<double> curve = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0}; };
+    struct LocalContrastMask { bool enabled = true; const DevicePlane *blend = nullptr; };
+    struct { bool enabled = false; std::vector<LocalContrastRegion> regions; std::vector<LocalContrastMask> masks; } localContrast;
     struct { bool enabled = false; std::vector<float> rlut, glut, blut; } rgbCurves;                                             // RGBCurvesParams, as outCurve LUTs
     struct { bool enabled = true; int curveMode = ARTGPU_TONE_STD; std::vector<float> lut; float whitePoint = 1.f; bool basecurveLinear = true; } toneCurve;
     // toneCurve.curveMode: ARTGPU_TONE_STD or ARTGPU_TONE_NEUTRAL (ART's default, procparams.cc:1585)
@@ -207,7 +212,7 @@ public:
         case Stage::STAGE_0: break;
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
         case Stage::STAGE_2: break;
-        case Stage::STAGE_3: logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); break;  // improcfun.cc:607-623 (the steps this library has)
+        case Stage::STAGE_3: logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:607-625 (the steps this library has)
         }
         return false;
     }
@@ -256,6 +261,33 @@ public:
         if (lc.size() != 32770 || ac.size() != 65536 || bc.size() != 65536) throw std::runtime_error("labAdjustments: curve LUT sizes");
         ctx.check(artgpu_lab_adjustments(ctx.get(), &i, lc.data(), ac.data(), bc.data(), (p.chromaticity + 100.0f) / 100.0f));
         ctx.check(artgpu_lab_to_rgb(ctx.get(), &i, params->workingSpaceInverse));
+    }
+    // ImProcFunctions::localContrast (iplocalcontrast.cc:425-487): setMode(LAB), every enabled region through local_contrast_wavelets and the
+    // mask blend on the L plane (Imagefloat::g); like labAdjustments this mirror converts back at once.  An empty or FCT_Linear curve takes
+    // the default region's (L358-363); a curve whose LUT stays unset (identity) reads as 0 (L53-56)
+    bool localContrast(Imagefloat *img)
+    {
+        const auto &p = params->localContrast;
+        if (!p.enabled) return false;
+        std::vector<std::vector<float>> luts(p.regions.size(), std::vector<float>(501));
+        std::vector<artgpu_plane> blends(p.regions.size());
+        std::vector<artgpu_local_contrast_region> regions;
+        for (size_t k = 0; k < p.regions.size(); ++k) {
+            if (k < p.masks.size() && !p.masks[k].enabled) continue;
+            const ProcParams::LocalContrastRegion dflt;
+            const auto &r = p.regions[k];
+            const std::vector<double> &curve = (r.curve.empty() || r.curve[0] == 0 /*FCT_Linear*/) ? dflt.curve : r.curve;
+            int is_set = 0;
+            ctx.check(artgpu_local_contrast_curve_lut(curve.data(), (int)curve.size(), luts[k].data(), &is_set));
+            artgpu_local_contrast_region reg{r.contrast, is_set ? luts[k].data() : nullptr, nullptr};
+            if (k < p.masks.size() && p.masks[k].blend) { blends[k] = p.masks[k].blend->view(); reg.mask = &blends[k]; }
+            regions.push_back(reg);
+        }
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_rgb_to_lab(ctx.get(), &i, params->workingSpace));
+        ctx.check(artgpu_local_contrast(ctx.get(), &i.g, regions.data(), (int)regions.size(), scale, nullptr));
+        ctx.check(artgpu_lab_to_rgb(ctx.get(), &i, params->workingSpaceInverse));
+        return false;
     }
     // ImProcFunctions::saturationVibrance (ipsaturation.cc:43-83)
     void saturationVibrance(Imagefloat *img)

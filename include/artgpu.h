@@ -519,10 +519,42 @@ typedef struct {
 } artgpu_ca_params;
 int artgpu_raw_ca_correct(artgpu_ctx *ctx, artgpu_plane *raw, uint32_t filters, const artgpu_ca_params *p, double fit_out[64]);
 
+/* ImProcFunctions::localContrast (rtengine/iplocalcontrast.cc:425-487; called at improcfun.cc:625) on the L plane of an image in LAB mode
+ * (artgpu_rgb_to_lab: Imagefloat::g), in place; the plane may be on the host or on the device, with any row stride.  For every region, in
+ * order: local_contrast_wavelets (L251-420) -- wavelet_decomposition(L, level, subsamp 1) with the level rule of L256-260, the contrast
+ * remap of coeff0 (L271-347), evaluate_params (L97-248: double sums in a fixed order on the device, no atomics), the curve remap of the
+ * detail bands (L365-417), reconstruct(L, 1.f) -- then rgb->g = intp(mask, L_new, l) (L474-480; a NULL mask does the same arithmetic with
+ * 1.f), and L carries on into the next region.  The caller keeps what is host code in the reference: generateMasks' blend planes and
+ * the `masks[i].enabled` test (a disabled region is simply not passed).
+ * The constants of L372-380 go through the C library's log, so they are computed on the host: per region the call waits once for the
+ * stream, for the statistics block.  A non-NULL `info` receives what the last region computed.
+ * ARTGPU_EUNSUPPORTED, plane untouched: scale != 1 (wavelet_decomposition's skip form is not on the device path); a plane narrower or
+ * lower than ARTGPU_LOCAL_CONTRAST_MIN_SIZE, the smallest size at which the wavelet kernels take the level count the reference chooses
+ * (artgpu_wavelet_decompose: w, h >= 8 and min(w2, h2) >= 2^(levels - 1), which the level rule satisfies from 8 up).
+ * Device scratch (context pool, artgpu_trim_scratch returns it): 3 * levels + 2 quarter-size band planes and one full-size plane. */
+#define ARTGPU_LOCAL_CONTRAST_MIN_SIZE 8
+typedef struct {
+    double contrast;              /* LocalContrastParams::Region::contrast */
+    const float *curve;           /* 501 entries (host), WavOpacityCurveWL's LUT; NULL = unset curve (operator[] returns 0, L53-56) */
+    const artgpu_plane *mask;     /* generateMasks' blend plane for this region (host or device); NULL = all ones */
+} artgpu_local_contrast_region;
+typedef struct {                  /* what the last region computed; filled only when asked for */
+    int32_t nlevels;
+    float ave, min0, max0;        /* coeff0 statistics (ave as the float of L317; min0 / max0 before the / 327.68); 0 when contrast == 0 */
+    float mean[10], sigma[10], maxp[10];   /* evaluate_params' mean, sigma, MaxP per level */
+} artgpu_local_contrast_info;
+/* WavOpacityCurveWL::Set(const std::vector<double>&) (L85-94): the 501-entry LUT of a FlatCurve {FCT_MinMaxCPoints, x, y, left tangent,
+ * right tangent, ...} with identity value 0, on the host (no context needed).  *is_set = 0 (lut zeroed) for an empty, FCT_Linear or identity
+ * curve, whose LUT the reference leaves unset; in the empty / FCT_Linear case the caller passes the default region's curve
+ * {1, 0, 0.5, 0, 0, 1, 0.5, 0, 0} instead, as L358-363 do. */
+int artgpu_local_contrast_curve_lut(const double *points, int npoints, float lut[501], int *is_set);
+int artgpu_local_contrast(artgpu_ctx *ctx, artgpu_plane *L, const artgpu_local_contrast_region *regions, int nregions,
+                          double scale, artgpu_local_contrast_info *info /* may be NULL */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
- *   ImProcFunctions::exposure -> ImProcFunctions::toneCurve.
+ *   ImProcFunctions::exposure -> ImProcFunctions::toneCurve [-> ImProcFunctions::localContrast].
  * raw: CFA plane (host or device).  out: (W - 2*border) x (H - 2*border) planes (host or device; the frame stays on the device
  * between the stages either way).  Disabled stages are skipped exactly like their `enabled == false` early-outs. */
 typedef struct {
@@ -555,6 +587,11 @@ typedef struct {
                                      * ca_enabled && (ca.autocorrect || |ca.red| > 0.001 || |ca.blue| > 0.001) && sensor == Bayer
                                      * (rawimagesource.cc:1827); on a device copy of `raw` (artgpu_batch_run_io: on its staged plane) */
     artgpu_ca_params ca;
+    int32_t local_contrast_enabled; /* LocalContrastParams::enabled: after the tone curve (improcfun.cc:617-625 with the steps in between off) the image goes
+                                     * through artgpu_rgb_to_lab(ws), artgpu_local_contrast on its L plane with these regions and `scale`, artgpu_lab_to_rgb(iws);
+                                     * what artgpu_local_contrast does not support fails the frame before any stage has run.  0 = off */
+    int32_t local_contrast_nregions;
+    const artgpu_local_contrast_region *local_contrast_regions;   /* masks: planes of the output size */
 } artgpu_pipeline_params;
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *params, artgpu_rgb *out);
 
