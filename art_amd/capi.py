@@ -72,6 +72,17 @@ class LocalContrastInfo(C.Structure):
                 ("mean", C.c_float * 10), ("sigma", C.c_float * 10), ("maxp", C.c_float * 10)]
 
 
+class DehazeParams(C.Structure):
+    """artgpu_dehaze_params: DehazeParams, the strength curve as FlatCurve points"""
+    _fields_ = [("enabled", C.c_int32), ("strength", C.POINTER(C.c_double)), ("nstrength", C.c_int32), ("show_depth_map", C.c_int32),
+                ("depth", C.c_int32), ("luminance", C.c_int32), ("blackpoint", C.c_int32)]
+
+
+class DehazeInfo(C.Structure):
+    _fields_ = [("haze_detected", C.c_int32), ("patchsize", C.c_int32), ("small_w", C.c_int32), ("small_h", C.c_int32),
+                ("maxval", C.c_float), ("black", C.c_float * 3), ("ambient", C.c_float * 3), ("max_t", C.c_float), ("t0", C.c_float)]
+
+
 class PipelineParams(C.Structure):
     pass
 
@@ -94,7 +105,8 @@ PipelineParams._fields_ = [
     ("exposure_enabled", C.c_int32), ("expcomp", C.c_double), ("black", C.c_double), ("tone_enabled", C.c_int32),
     ("tone_mode", C.c_int32), ("tone_lut", C.POINTER(C.c_float)), ("white_point", C.c_float), ("to_out", C.c_float * 9),
     ("to_work", C.c_float * 9), ("scale", C.c_double), ("chrominance_auto_factor", C.c_double), ("ca_enabled", C.c_int32), ("ca", CaParams),
-    ("local_contrast_enabled", C.c_int32), ("local_contrast_nregions", C.c_int32), ("local_contrast_regions", C.POINTER(LocalContrastRegion))]
+    ("local_contrast_enabled", C.c_int32), ("local_contrast_nregions", C.c_int32), ("local_contrast_regions", C.POINTER(LocalContrastRegion)),
+    ("dehaze_enabled", C.c_int32), ("dehaze", DehazeParams)]
 
 
 
@@ -139,6 +151,41 @@ def local_contrast_curve_lut(points=DEFAULT_LOCAL_CONTRAST_CURVE_POINTS):
     if rc:
         raise ArtGpuError(f"artgpu_local_contrast_curve_lut: error {rc}")
     return lut, bool(is_set.value)
+
+
+# DehazeParams::strength's default (procparams.cc:2694-2711)
+DEFAULT_DEHAZE_STRENGTH_POINTS = (1.0, 0.0, 0.75, 0.0, 0.0, 1.0, 0.75, 0.0, 0.0)
+
+
+def dehaze_strength_lut(points=DEFAULT_DEHAZE_STRENGTH_POINTS):
+    """ipdehaze.cc:419-424 -> the 65536-entry float32 strength table"""
+    pts = (C.c_double * max(len(points), 1))(*[float(p) for p in points])
+    lut = np.zeros(65536, np.float32)
+    rc = LIB.artgpu_dehaze_strength_lut(pts, len(points), lut.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise ArtGpuError(f"artgpu_dehaze_strength_lut: error {rc}")
+    return lut
+
+
+def dehaze_estimate_ambient(R, G, B):
+    """get_dark_channel(.., 2, nullptr, false) + estimate_ambient_light on three hh x ww planes -> (ambient float32[3], max_t)"""
+    planes = [np.ascontiguousarray(a, dtype=np.float32) for a in (R, G, B)]
+    hh, ww = planes[0].shape
+    ambient = (C.c_float * 3)()
+    max_t = C.c_float(0)
+    fp = C.POINTER(C.c_float)
+    rc = LIB.artgpu_dehaze_estimate_ambient(*[a.ctypes.data_as(fp) for a in planes], ww, hh, ambient, C.byref(max_t))
+    if rc:
+        raise ArtGpuError(f"artgpu_dehaze_estimate_ambient: error {rc}")
+    return np.array(ambient[:], np.float32), np.float32(max_t.value)
+
+
+def dehaze_params(strength=DEFAULT_DEHAZE_STRENGTH_POINTS, depth=25, show_depth_map=False, luminance=False, blackpoint=0, enabled=True):
+    """-> (DehazeParams, the object to keep alive with it)"""
+    pts = (C.c_double * max(len(strength), 1))(*[float(v) for v in strength])
+    p = DehazeParams(1 if enabled else 0, C.cast(pts, C.POINTER(C.c_double)), len(strength), 1 if show_depth_map else 0, int(depth),
+                     1 if luminance else 0, int(blackpoint))
+    return p, pts
 
 
 def local_contrast_regions(regions):
@@ -214,6 +261,10 @@ def _load():
                                                 C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_uint32]
     lib.artgpu_raw_ca_correct.argtypes = [C.c_void_p, C.POINTER(Plane), C.c_uint32, C.POINTER(CaParams), C.POINTER(C.c_double)]
     lib.artgpu_local_contrast_curve_lut.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+    lib.artgpu_dehaze.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(DehazeParams), C.POINTER(C.c_double), C.c_double, C.POINTER(DehazeInfo)]
+    lib.artgpu_dehaze_strength_lut.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float)]
+    lib.artgpu_dehaze_estimate_ambient.argtypes = [C.POINTER(C.c_float)] * 3 + [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.artgpu_dehaze_dark_channel.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(Plane)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -291,7 +342,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_convert_color_space", "artgpu_exposure", "artgpu_tone_curve",
            "artgpu_wavelet_decompose", "artgpu_wavelet_mad", "artgpu_wavelet_info", "artgpu_wavelet_get_band", "artgpu_wavelet_set_band",
            "artgpu_wavelet_reconstruct", "artgpu_wavelet_free", "artgpu_rgb_denoise", "artgpu_denoise_guided_smoothing",
-           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast"]
+           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
+           "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -466,6 +518,20 @@ class Context:
         return info
 
     local_contrast_curve_lut = staticmethod(local_contrast_curve_lut)
+
+    def dehaze(self, image: RGB, params: "DehazeParams", ws, scale: float = 1.0, want_info: bool = False):
+        """ImProcFunctions::dehaze in place (params from dehaze_params()); returns the DehazeInfo when want_info."""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        info = DehazeInfo() if want_info else None
+        self._chk(LIB.artgpu_dehaze(self._h, C.byref(image), C.byref(params), wsd, float(scale), C.byref(info) if want_info else None))
+        return info
+
+    def dehaze_dark_channel(self, rgb: RGB, patchsize: int, ambient, clip: bool, dst: Plane):
+        amb = None if ambient is None else (C.c_float * 3)(*[float(v) for v in ambient])
+        self._chk(LIB.artgpu_dehaze_dark_channel(self._h, C.byref(rgb), int(patchsize), amb, 1 if clip else 0, C.byref(dst)))
+
+    dehaze_strength_lut = staticmethod(dehaze_strength_lut)
+    dehaze_estimate_ambient = staticmethod(dehaze_estimate_ambient)
 
     def denoise_compute_params(self, planes: RGB, border: int, mul, do_clip: bool, cam_to_work, ws, dn: DenoiseParams,
                                auto_factor: float = 1.0, store: "DenoiseInfoStore" = None) -> "DenoiseInfoStore":

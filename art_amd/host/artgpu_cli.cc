@@ -10,7 +10,9 @@
 //              [--ca auto[,N] | --ca manual,R,B] [--ca-keep-colourshift]   (RawImageSource::CA_correct_RT after the load, before the demosaic)
 //              [--local-contrast C[,curve-points]]   (ImProcFunctions::localContrast: one region, contrast C, the default region's curve unless FlatCurve
 //                                                      control points follow: kind,x,y,left,right,...)
-//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--out prefix]
+//              [--dehaze depth[,strength_y[,blackpoint[,luminance]]]]   (ImProcFunctions::dehaze in STAGE_0: strength_y = the y of a flat two-point
+//                                                      strength curve, default 0.75)
+//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <chrono>
@@ -58,6 +60,9 @@ int main(int argc, char **argv)
     bool lc_enable = false;                                        // LocalContrastParams::enabled, one region
     double lc_contrast = 0;
     std::vector<double> lc_curve;                                  // empty: the default region's curve
+    bool dh_enable = false;                                        // DehazeParams::enabled
+    int dh_depth = 25, dh_black = 0, dh_lum = 0;
+    double dh_y = 0.75;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -104,6 +109,10 @@ int main(int argc, char **argv)
                 lc_curve.push_back(x);
             }
         }
+        else if (a == "--dehaze") {
+            if (std::sscanf(next(), "%d,%lf,%d,%d", &dh_depth, &dh_y, &dh_black, &dh_lum) < 1) { std::fprintf(stderr, "--dehaze depth[,strength_y[,blackpoint[,luminance]]]\n"); return 2; }
+            dh_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
@@ -117,6 +126,8 @@ int main(int argc, char **argv)
             params.toneCurve.lut = default_tone_lut(); params.toneCurve.curveMode = tone_mode;
             params.raw.enable_ca = ca_enable; params.raw.ca_autocorrect = ca_auto; params.raw.caautoiterations = ca_iter;
             params.raw.cared = ca_red; params.raw.cablue = ca_blue; params.raw.ca_avoidcolourshift = ca_avoid;
+            params.dehaze.enabled = dh_enable; params.dehaze.depth = dh_depth; params.dehaze.blackpoint = dh_black; params.dehaze.luminance = dh_lum != 0;
+            params.dehaze.strength = {1, 0.0, dh_y, 0.0, 0.0, 1.0, dh_y, 0.0, 0.0};
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -186,6 +197,8 @@ int main(int argc, char **argv)
         params.logenc.enabled = logenc; params.logenc.regularization = logenc_reg;
         params.saturation.enabled = sat != 0 || vib != 0; params.saturation.saturation = sat; params.saturation.vibrance = vib;
         params.labCurve.enabled = labcurve; params.labCurve.chromaticity = labchroma;
+        params.dehaze.enabled = dh_enable; params.dehaze.depth = dh_depth; params.dehaze.blackpoint = dh_black; params.dehaze.luminance = dh_lum != 0;
+        params.dehaze.strength = {1, 0.0, dh_y, 0.0, 0.0, 1.0, dh_y, 0.0, 0.0};
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;
@@ -230,6 +243,7 @@ int main(int argc, char **argv)
         // stage_denoise (simpleprocess.cc:311-315)
         imgsrc.convertColorSpace(&img, mat);
         ipf.denoise(&imgsrc, &img);
+        ipf.process(ImProcFunctions::Pipeline::OUTPUT, ImProcFunctions::Stage::STAGE_0, &img);       // simpleprocess.cc:329
         // stage_finish (simpleprocess.cc:389-396)
         ipf.process(ImProcFunctions::Pipeline::OUTPUT, ImProcFunctions::Stage::STAGE_1, &img);
         ipf.process(ImProcFunctions::Pipeline::OUTPUT, ImProcFunctions::Stage::STAGE_2, &img);

@@ -102,6 +102,14 @@ struct ProcParams {
     struct { bool enabled = false; int chromaticity = 0, contrast = 0;
              std::function<void(const uint32_t *hist16, std::vector<float> &lcurve, std::vector<float> &acurve, std::vector<float> &bcurve)> curves; } labCurve;
     struct { bool enabled = false; int saturation = 0, vibrance = 0; } saturation;                                               // SaturationParams
+    // DehazeParams (procparams.cc:2694-2711); strength = FlatCurve control points
+    struct { bool enabled = false; std::vector<double> strength = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.75, 0.0, 0.0, 1.0, 0.75, 0.0, 0.0}; bool showDepthMap = false;
+             int depth = 25; bool luminance = false; int blackpoint = 0; } dehaze;
+    artgpu_dehaze_params dehazeParams() const
+    {
+        return artgpu_dehaze_params{dehaze.enabled ? 1 : 0, dehaze.strength.data(), (int32_t)dehaze.strength.size(), dehaze.showDepthMap ? 1 : 0, dehaze.depth,
+                                    dehaze.luminance ? 1 : 0, dehaze.blackpoint};
+    }
     // LocalContrastParams (procparams.cc:1700-1760): regions {contrast, curve as FlatCurve control points}; masks[i].enabled and the blend
     // plane generateMasks makes of masks[i] (host code of the application; nullptr = all ones), one per region
     struct LocalContrastRegion { double contrast = 0; std::vector<double> curve = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0}; };
@@ -204,17 +212,25 @@ public:
     ImProcFunctions(Context &c, const ProcParams *p, double scale = 1.0) : ctx(c), params(p), scale(scale) {}
 
     // ImProcFunctions::process (improcfun.cc:567-641): same step order; steps that are disabled / identity in the
-    // default ProcParams (dehaze, DRC, channelMixer, hslEqualizer, toneEqualizer, sharpening, ... blackAndWhite) are
-    // not on the device path and are skipped here exactly as their `enabled == false` early-outs skip them.
+    // default ProcParams and not on the device path (DRC, toneEqualizer, sharpening, ... blackAndWhite) are skipped
+    // here exactly as their `enabled == false` early-outs skip them.
     bool process(Pipeline, Stage stage, Imagefloat *img)
     {
         switch (stage) {
-        case Stage::STAGE_0: break;
+        case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
         case Stage::STAGE_2: break;
         case Stage::STAGE_3: logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:607-625 (the steps this library has)
         }
         return false;
+    }
+    // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
+    void dehaze(Imagefloat *img)
+    {
+        if (!params->dehaze.enabled) return;
+        const artgpu_dehaze_params dp = params->dehazeParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_dehaze(ctx.get(), &i, &dp, params->workingSpace, scale, nullptr));
     }
     // ImProcFunctions::channelMixer (ipchmixer.cc:152-234), RGB_MATRIX mode: the nine percentages / 1000 (L185-199)
     void channelMixer(Imagefloat *img)
@@ -415,6 +431,7 @@ public:
         pp.tone_enabled = p.toneCurve.enabled ? 1 : 0; pp.tone_mode = p.toneCurve.curveMode; pp.tone_lut = p.toneCurve.lut.data(); pp.white_point = p.toneCurve.whitePoint;
         pp.scale = 1.0; pp.chrominance_auto_factor = d.chrominanceAutoFactor;
         pp.ca_enabled = p.raw.enable_ca ? 1 : 0; pp.ca = p.caParams();    // the library applies the call site's condition per frame
+        pp.dehaze_enabled = p.dehaze.enabled ? 1 : 0; pp.dehaze = p.dehazeParams();
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {

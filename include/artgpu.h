@@ -551,10 +551,59 @@ int artgpu_local_contrast_curve_lut(const double *points, int npoints, float lut
 int artgpu_local_contrast(artgpu_ctx *ctx, artgpu_plane *L, const artgpu_local_contrast_region *regions, int nregions,
                           double scale, artgpu_local_contrast_info *info /* may be NULL */);
 
+/* ImProcFunctions::dehaze (rtengine/ipdehaze.cc:306-512; the first step of ImProcFunctions::process, improcfun.cc:577, STAGE_0): haze
+ * removal by the dark channel prior, in place on an RGB image whose planes are on the host or on the device, with any row stride.
+ * The call follows the reference step by step: normalize (L64-80: maxval = max(2 * max(r, g, b), 65535), the image times
+ * 1.f / maxval -- a multiplication by a reciprocal, which the final * maxval does not undo in bits), subtract_black when
+ * blackpoint != 0 (L249-301), extract_channels (L233-246: three self-guided filters, r = max(int(5 / scale), 2), epsilon 0.1f),
+ * rescaleNearest to the ww x hh thumbnail (L372-381; for portrait frames ww = 200 / (W / H) is larger than 200 and hh = 200),
+ * the ambient light (L385-386), the dark channel with patchsize = max(max(W, H) / 600, 2), the ambient light and the clip (L396-404),
+ * t~ = 1 - |s| * dark with s = strength[rgbLuminance(r, g, b, ws) * maxval] (L419-436), guidedFilter(B, t~, t, 4 * patchsize, 1e-5f)
+ * (L438-445), the recovery loop with all of its branches (L453-509) and restore (L511).  When the ambient estimate finds no haze
+ * (max_t < 0, L387-393) the image returned is restore() of the normalised, black-subtracted image, not the input, and
+ * info->haze_detected = 0.  ws = the working-space matrix (row 1 is the luminance), scale = ImProcFunctions::scale.
+ * Every reduction of the tool is a maximum or a minimum, so the result does not depend on the order the device takes them in; the
+ * few log / exp (float overloads) and double sums work on the thumbnail and run on the host: the call waits once for the stream, for
+ * the three thumbnail planes.  Contract: NaN-free input (normalize's max depends on the order for NaN).
+ * ARTGPU_EUNSUPPORTED, image untouched, where the reference itself reads out of bounds or the kernels have a limit:
+ *   - blackpoint != 0 with min(ww, hh) < 2 * (max(ww, hh) / 20) + 1: the thumbnail is narrower than the box blur's window
+ *     (boxblur.h:318 needs W, H >= 2 * radius + 1), an aspect ratio above about 9.5;
+ *   - a side shorter than the guided filters' subsampling (W / s or H / s == 0: rescaleBilinear to an empty grid);
+ *   - max(W, H) >= 600 * 257 (a patch wider than the dark-channel kernel's workgroup).
+ * Device scratch (context pool, artgpu_trim_scratch returns it): one full-size plane, the guided filters' statistics grids (six planes
+ * of W / s x H / s twice), the patch grid, the thumbnails and the strength table. */
+typedef struct artgpu_dehaze_params {
+    int32_t enabled;                  /* DehazeParams::enabled; 0: the call returns at once (L315-320) */
+    const double *strength;           /* DehazeParams::strength, FlatCurve points {FCT_MinMaxCPoints, x, y, lt, rt, ...}; */
+    int32_t nstrength;                /*   default procparams.cc:2694-2711: {1, 0, 0.75, 0, 0, 1, 0.75, 0, 0} */
+    int32_t show_depth_map, depth, luminance, blackpoint;
+} artgpu_dehaze_params;
+typedef struct artgpu_dehaze_info {   /* what the call derived; for callers and for locating a mismatch */
+    int32_t haze_detected;            /* 0: the "no haze" return; ambient and t0 are then 0 */
+    int32_t patchsize;                /* max(max(W, H) / 600, 2) */
+    int32_t small_w, small_h;         /* the thumbnail, ww x hh */
+    float maxval, black[3], ambient[3], max_t, t0;
+} artgpu_dehaze_info;
+int artgpu_dehaze(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_dehaze_params *params, const double ws[9], double scale,
+                  artgpu_dehaze_info *info /* may be NULL */);
+/* L419-424 on the host (no context needed): lut[i] = (FlatCurve(points, false).getVal(Color::gamma2curve[i] / 65535.f) - 0.5f) * 1.3f
+ * with identity value 0.5; Color::gamma2curve as color.cc:241-244 build it (gamma2 in double, stored as float, *= 65535.f).  An empty,
+ * FCT_Linear or identity curve gives all zeros. */
+int artgpu_dehaze_strength_lut(const double *points, int npoints, float lut[65536]);
+/* get_dark_channel(RR, GG, BB, D, 2, nullptr, false) and estimate_ambient_light (L128-230, L385-386) on the host, on three contiguous
+ * ww x hh planes: the ambient light and max_t; *max_t < 0 (ambient zeroed) when no dark-channel value lies in [0, 1 - 1e-5]. */
+int artgpu_dehaze_estimate_ambient(const float *R, const float *G, const float *B, int ww, int hh, float ambient[3], float *max_t);
+/* get_dark_channel (L89-125) on the device: dst = per patchsize x patchsize patch (edge patches are partial) the minimum of r, g, b, each
+ * divided by its ambient component when `ambient` is not NULL, LIM01 of it when clip != 0.  With positive ambient components the
+ * division is taken once per channel and patch (x / a is monotonic in x, the bits are the same); otherwise per pixel, as written.
+ * The sign of a zero result is not defined (the minimum of zeros of opposite sign depends on the order).  patchsize 1 .. 256. */
+int artgpu_dehaze_dark_channel(artgpu_ctx *ctx, const artgpu_rgb *rgb, int patchsize, const float *ambient /* [3] or NULL */, int clip,
+                               artgpu_plane *dst);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
- *   ImProcFunctions::exposure -> ImProcFunctions::toneCurve [-> ImProcFunctions::localContrast].
+ *   [ImProcFunctions::dehaze ->] ImProcFunctions::exposure -> ImProcFunctions::toneCurve [-> ImProcFunctions::localContrast].
  * raw: CFA plane (host or device).  out: (W - 2*border) x (H - 2*border) planes (host or device; the frame stays on the device
  * between the stages either way).  Disabled stages are skipped exactly like their `enabled == false` early-outs. */
 typedef struct {
@@ -592,6 +641,11 @@ typedef struct {
                                      * what artgpu_local_contrast does not support fails the frame before any stage has run.  0 = off */
     int32_t local_contrast_nregions;
     const artgpu_local_contrast_region *local_contrast_regions;   /* masks: planes of the output size */
+    int32_t dehaze_enabled;         /* DehazeParams::enabled: artgpu_dehaze with `dehaze`, ws and `scale` between the denoise tool and the exposure
+                                     * (simpleprocess.cc:329 before :389; the exposure then runs as its own artgpu_exposure call instead of inside the
+                                     * tool's last pass, the tool's ecomp is unchanged); what artgpu_dehaze does not support fails the frame before
+                                     * any stage has run.  0 = off (dehaze.enabled is not looked at) */
+    artgpu_dehaze_params dehaze;
 } artgpu_pipeline_params;
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *params, artgpu_rgb *out);
 
