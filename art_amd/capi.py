@@ -83,6 +83,31 @@ class DehazeInfo(C.Structure):
                 ("maxval", C.c_float), ("black", C.c_float * 3), ("ambient", C.c_float * 3), ("max_t", C.c_float), ("t0", C.c_float)]
 
 
+SHARPEN_RLD, SHARPEN_USM, SHARPEN_PSF = 0, 1, 2
+SHARPEN_REGIME_COPY, SHARPEN_REGIME_3X3, SHARPEN_REGIME_5X5, SHARPEN_REGIME_7X7, SHARPEN_REGIME_YVV = 0, 1, 2, 3, 4
+GAUSS_STANDARD, GAUSS_MULT, GAUSS_DIV = 0, 1, 2
+
+
+class SharpeningParams(C.Structure):
+    """artgpu_sharpening_params: SharpeningParams' fields of the rld method + ImProcFunctions' crop geometry"""
+    _fields_ = [("enabled", C.c_int32), ("method", C.c_int32), ("amount", C.c_int32), ("deconvamount", C.c_int32),
+                ("contrast", C.c_double), ("deconvradius", C.c_double), ("deconvCornerBoost", C.c_double),
+                ("deconvCornerLatitude", C.c_int32), ("offset_x", C.c_int32), ("offset_y", C.c_int32),
+                ("full_width", C.c_int32), ("full_height", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SharpeningInfo(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("regime", C.c_int32), ("early_out", C.c_int32), ("contrast_threshold", C.c_float),
+                ("pad_", C.c_int32), ("impulse_pixels", C.c_int64), ("frozen_pixels", C.c_int64)]
+
+
+def sharpening_params(enabled=True, method=SHARPEN_RLD, amount=200, contrast=20.0, deconvradius=0.75, deconvamount=100, corner_boost=0.0,
+                      corner_latitude=25, offset_x=0, offset_y=0, full_width=0, full_height=0):
+    """SharpeningParams' defaults (procparams.cc:1756-1775); Sharpening.arp sets Enabled, Method=rld, Contrast=20, DeconvAmount=100"""
+    return SharpeningParams(1 if enabled else 0, int(method), int(amount), int(deconvamount), float(contrast), float(deconvradius),
+                            float(corner_boost), int(corner_latitude), int(offset_x), int(offset_y), int(full_width), int(full_height), 0)
+
+
 class PipelineParams(C.Structure):
     pass
 
@@ -106,7 +131,9 @@ PipelineParams._fields_ = [
     ("tone_mode", C.c_int32), ("tone_lut", C.POINTER(C.c_float)), ("white_point", C.c_float), ("to_out", C.c_float * 9),
     ("to_work", C.c_float * 9), ("scale", C.c_double), ("chrominance_auto_factor", C.c_double), ("ca_enabled", C.c_int32), ("ca", CaParams),
     ("local_contrast_enabled", C.c_int32), ("local_contrast_nregions", C.c_int32), ("local_contrast_regions", C.POINTER(LocalContrastRegion)),
-    ("dehaze_enabled", C.c_int32), ("dehaze", DehazeParams)]
+    ("dehaze_enabled", C.c_int32), ("dehaze", DehazeParams),
+    ("sharpening_enabled", C.c_int32), ("sharpening_auto_radius", C.c_int32), ("sharpening_clip_val", C.c_float), ("pad_sharpening_", C.c_int32),
+    ("sharpening", SharpeningParams)]
 
 
 
@@ -265,6 +292,10 @@ def _load():
     lib.artgpu_dehaze_strength_lut.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float)]
     lib.artgpu_dehaze_estimate_ambient.argtypes = [C.POINTER(C.c_float)] * 3 + [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.artgpu_dehaze_dark_channel.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(Plane)]
+    lib.artgpu_sharpening.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(SharpeningParams), C.POINTER(C.c_double), C.c_double, C.POINTER(SharpeningInfo)]
+    lib.artgpu_rl_deconvolution.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(Plane), C.c_void_p, C.c_double, C.c_float, C.POINTER(SharpeningInfo)]
+    lib.artgpu_gaussian_blur_ex.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(Plane), C.POINTER(Plane), C.c_double, C.c_int]
+    lib.artgpu_deconv_auto_radius.argtypes = [C.c_void_p, C.POINTER(Plane), C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -343,7 +374,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_wavelet_decompose", "artgpu_wavelet_mad", "artgpu_wavelet_info", "artgpu_wavelet_get_band", "artgpu_wavelet_set_band",
            "artgpu_wavelet_reconstruct", "artgpu_wavelet_free", "artgpu_rgb_denoise", "artgpu_denoise_guided_smoothing",
            "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
-           "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel"]
+           "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
+           "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -532,6 +564,30 @@ class Context:
 
     dehaze_strength_lut = staticmethod(dehaze_strength_lut)
     dehaze_estimate_ambient = staticmethod(dehaze_estimate_ambient)
+
+    def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
+        """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        info = SharpeningInfo() if want_info else None
+        self._chk(LIB.artgpu_sharpening(self._h, C.byref(image), C.byref(params), wsd, float(scale), C.byref(info) if want_info else None))
+        return info
+
+    def rl_deconvolution(self, luminance: Plane, blend: Plane, impulse, sigma: float, amount: float, want_info: bool = False):
+        """deconvsharpening in place on `luminance`; impulse: the address of W * H bytes where the luminance plane lives (host or device)"""
+        info = SharpeningInfo() if want_info else None
+        self._chk(LIB.artgpu_rl_deconvolution(self._h, C.byref(luminance), C.byref(blend), C.c_void_p(int(impulse)), float(sigma), float(amount),
+                                              C.byref(info) if want_info else None))
+        return info
+
+    def gaussian_blur_ex(self, src: Plane, dst: Plane, div, sigma: float, gausstype: int):
+        """gaussianBlur(src, dst, .., gausstype, div) for src != dst, GAUSS_DIV / GAUSS_MULT; above sigma 1.15 GAUSS_MULT overwrites src"""
+        self._chk(LIB.artgpu_gaussian_blur_ex(self._h, C.byref(src), C.byref(dst), None if div is None else C.byref(div), float(sigma), int(gausstype)))
+
+    def deconv_auto_radius(self, raw: Plane, filters: int, lower_limit: float = 1000.0, clip_val: float = 65535.0):
+        """RawImageSource::getDeconvAutoRadius (Bayer / monochrome) -> (radius, max_ratio) as float32"""
+        r, m = C.c_float(0), C.c_float(0)
+        self._chk(LIB.artgpu_deconv_auto_radius(self._h, C.byref(raw), int(filters), float(lower_limit), float(clip_val), C.byref(r), C.byref(m)))
+        return np.float32(r.value), np.float32(m.value)
 
     def denoise_compute_params(self, planes: RGB, border: int, mul, do_clip: bool, cam_to_work, ws, dn: DenoiseParams,
                                auto_factor: float = 1.0, store: "DenoiseInfoStore" = None) -> "DenoiseInfoStore":

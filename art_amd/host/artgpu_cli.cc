@@ -12,7 +12,9 @@
 //                                                      control points follow: kind,x,y,left,right,...)
 //              [--dehaze depth[,strength_y[,blackpoint[,luminance]]]]   (ImProcFunctions::dehaze in STAGE_0: strength_y = the y of a flat two-point
 //                                                      strength curve, default 0.75)
-//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--out prefix]
+//              [--sharpen contrast[,radius|auto[,amount[,cornerboost[,latitude]]]]]   (ImProcFunctions::sharpening in STAGE_2, method rld; `auto`
+//                                                      (the default) takes the radius from RawImageSource::getDeconvAutoRadius as simpleprocess.cc:274-278 does)
+//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <chrono>
@@ -63,6 +65,9 @@ int main(int argc, char **argv)
     bool dh_enable = false;                                        // DehazeParams::enabled
     int dh_depth = 25, dh_black = 0, dh_lum = 0;
     double dh_y = 0.75;
+    bool sh_enable = false, sh_auto = true;                        // SharpeningParams::enabled, deconvAutoRadius
+    double sh_contrast = 20.0, sh_radius = 0.75, sh_boost = 0.0;
+    int sh_amount = 100, sh_latitude = 25;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -113,6 +118,20 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%d,%lf,%d,%d", &dh_depth, &dh_y, &dh_black, &dh_lum) < 1) { std::fprintf(stderr, "--dehaze depth[,strength_y[,blackpoint[,luminance]]]\n"); return 2; }
             dh_enable = true;
         }
+        else if (a == "--sharpen") {
+            // contrast[,radius|auto[,amount[,cornerboost[,latitude]]]]
+            std::vector<std::string> f;
+            const std::string v = next();
+            for (size_t pos = 0;;) { const size_t e = v.find(',', pos); f.push_back(v.substr(pos, e == std::string::npos ? std::string::npos : e - pos)); if (e == std::string::npos) break; pos = e + 1; }
+            char *end = nullptr;
+            sh_contrast = std::strtod(f[0].c_str(), &end);
+            if (end == f[0].c_str() || f.size() > 5) { std::fprintf(stderr, "--sharpen contrast[,radius|auto[,amount[,cornerboost[,latitude]]]]\n"); return 2; }
+            if (f.size() > 1 && f[1] != "auto") { sh_auto = false; sh_radius = std::atof(f[1].c_str()); }
+            if (f.size() > 2) sh_amount = std::atoi(f[2].c_str());
+            if (f.size() > 3) sh_boost = std::atof(f[3].c_str());
+            if (f.size() > 4) sh_latitude = std::atoi(f[4].c_str());
+            sh_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
@@ -128,6 +147,8 @@ int main(int argc, char **argv)
             params.raw.cared = ca_red; params.raw.cablue = ca_blue; params.raw.ca_avoidcolourshift = ca_avoid;
             params.dehaze.enabled = dh_enable; params.dehaze.depth = dh_depth; params.dehaze.blackpoint = dh_black; params.dehaze.luminance = dh_lum != 0;
             params.dehaze.strength = {1, 0.0, dh_y, 0.0, 0.0, 1.0, dh_y, 0.0, 0.0};
+            params.sharpening.enabled = sh_enable; params.sharpening.contrast = sh_contrast; params.sharpening.deconvradius = sh_radius; params.sharpening.deconvAutoRadius = sh_auto;
+            params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -199,6 +220,8 @@ int main(int argc, char **argv)
         params.labCurve.enabled = labcurve; params.labCurve.chromaticity = labchroma;
         params.dehaze.enabled = dh_enable; params.dehaze.depth = dh_depth; params.dehaze.blackpoint = dh_black; params.dehaze.luminance = dh_lum != 0;
         params.dehaze.strength = {1, 0.0, dh_y, 0.0, 0.0, 1.0, dh_y, 0.0, 0.0};
+        params.sharpening.enabled = sh_enable; params.sharpening.contrast = sh_contrast; params.sharpening.deconvradius = sh_radius; params.sharpening.deconvAutoRadius = sh_auto;
+        params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;
@@ -238,6 +261,13 @@ int main(int argc, char **argv)
             ipf.denoiseComputeParams(&imgsrc, mul, true, dnstore, params.denoise);
             std::fprintf(stderr, "auto chrominance: %.6f  red-green %.6f  blue-yellow %.6f\n", params.denoise.chrominance,
                          params.denoise.chrominanceRedGreen, params.denoise.chrominanceBlueYellow);
+        }
+        if (params.sharpening.enabled && params.sharpening.deconvAutoRadius) {      // simpleprocess.cc:274-278
+            float r = 0.f;
+            if (imgsrc.getDeconvAutoRadius(&r)) {
+                params.sharpening.deconvradius = r;
+                std::fprintf(stderr, "auto deconvolution radius: %.6f\n", r);
+            }
         }
         imgsrc.getImage(mul, true, &img);
         // stage_denoise (simpleprocess.cc:311-315)

@@ -110,6 +110,17 @@ struct ProcParams {
         return artgpu_dehaze_params{dehaze.enabled ? 1 : 0, dehaze.strength.data(), (int32_t)dehaze.strength.size(), dehaze.showDepthMap ? 1 : 0, dehaze.depth,
                                     dehaze.luminance ? 1 : 0, dehaze.blackpoint};
     }
+    // SharpeningParams (procparams.cc:1756-1775), the fields the rld method reads; the Dynamic profile's Sharpening.arp sets enabled, method rld,
+    // contrast 20, deconvamount 100 and deconvAutoRadius below ISO 640
+    struct { bool enabled = false; double contrast = 20.0; int amount = 200; int method = ARTGPU_SHARPEN_RLD; int deconvamount = 100; double deconvradius = 0.75;
+             bool deconvAutoRadius = true; double deconvCornerBoost = 0.0; int deconvCornerLatitude = 25; } sharpening;
+    // offset_x / offset_y / full_width / full_height: ImProcFunctions' crop geometry (improcfun.h), 0 = the image itself
+    artgpu_sharpening_params sharpeningParams(int offset_x = 0, int offset_y = 0, int full_width = 0, int full_height = 0) const
+    {
+        return artgpu_sharpening_params{sharpening.enabled ? 1 : 0, sharpening.method, sharpening.amount, sharpening.deconvamount, sharpening.contrast,
+                                        sharpening.deconvradius, sharpening.deconvCornerBoost, sharpening.deconvCornerLatitude, offset_x, offset_y,
+                                        full_width, full_height, 0};
+    }
     // LocalContrastParams (procparams.cc:1700-1760): regions {contrast, curve as FlatCurve control points}; masks[i].enabled and the blend
     // plane generateMasks makes of masks[i] (host code of the application; nullptr = all ones), one per region
     struct LocalContrastRegion { double contrast = 0; std::vector<double> curve = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0}; };
@@ -171,6 +182,17 @@ public:
         ctx.check(artgpu_demosaic_bayer(ctx.get(), p.bayersensor.method, &raw, filters, initialGain, border, &out));
     }
     double dualDemosaicContrastUsed = 0;
+    // RawImageSource::getDeconvAutoRadius (deconvautoradius.cc:200-245) on rawData as preprocess left it: Bayer and monochrome (filters 0)
+    // sensors; out == nullptr only asks whether the sensor is supported.  clipVal = (ri->get_white(1) - ri->get_cblack(1)) * scale_mul[1].
+    bool getDeconvAutoRadius(float *out = nullptr)
+    {
+        if (isXtrans) return false;                                       // calcRadiusXtrans is not on the device path
+        if (!out) return true;
+        artgpu_plane raw = rawData.view();
+        ctx.check(artgpu_deconv_auto_radius(ctx.get(), &raw, filters, 1000.f, deconvClipVal, out, nullptr));
+        return true;
+    }
+    float deconvClipVal = 65535.f;
     void getFullSize(int &w, int &h) const { w = W - 2 * border; h = H - 2 * border; }   // computeFullSize (L1163-1193), tran = 0
     // RawImageSource::getImage (rawimagesource.cc:781-1104): tran = 0, skip = 1; rm/gm/bm as the caller computed them
     void getImage(const float mul[3], bool doClip, Imagefloat *image, int x = 0, int y = 0, int skip = 1)
@@ -212,14 +234,14 @@ public:
     ImProcFunctions(Context &c, const ProcParams *p, double scale = 1.0) : ctx(c), params(p), scale(scale) {}
 
     // ImProcFunctions::process (improcfun.cc:567-641): same step order; steps that are disabled / identity in the
-    // default ProcParams and not on the device path (DRC, toneEqualizer, sharpening, ... blackAndWhite) are skipped
-    // here exactly as their `enabled == false` early-outs skip them.
+    // default ProcParams and not on the device path (DRC, toneEqualizer, impulse denoise, defringe, ... blackAndWhite) are
+    // skipped here exactly as their `enabled == false` early-outs skip them.  STAGE_2 holds capture sharpening, its first step.
     bool process(Pipeline, Stage stage, Imagefloat *img)
     {
         switch (stage) {
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
-        case Stage::STAGE_2: break;
+        case Stage::STAGE_2: sharpening(img); break;                                          // improcfun.cc:595
         case Stage::STAGE_3: logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:607-625 (the steps this library has)
         }
         return false;
@@ -232,6 +254,17 @@ public:
         artgpu_rgb i = img->view();
         ctx.check(artgpu_dehaze(ctx.get(), &i, &dp, params->workingSpace, scale, nullptr));
     }
+    // ImProcFunctions::sharpening (ipsharpen.cc:791-794 -> doSharpening L712-788), method rld; the radius is params->sharpening.deconvradius, which
+    // the caller replaces by RawImageSource::getDeconvAutoRadius's when deconvAutoRadius is set (simpleprocess.cc:274-278)
+    bool sharpening(Imagefloat *img)
+    {
+        if (!params->sharpening.enabled) return false;
+        const artgpu_sharpening_params sp = params->sharpeningParams(offset_x, offset_y, full_width, full_height);
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_sharpening(ctx.get(), &i, &sp, params->workingSpace, scale, nullptr));
+        return false;
+    }
+    int offset_x = 0, offset_y = 0;    // with full_width / full_height (logEncoding): where the image lies in the full frame (improcfun.h setViewport)
     // ImProcFunctions::channelMixer (ipchmixer.cc:152-234), RGB_MATRIX mode: the nine percentages / 1000 (L185-199)
     void channelMixer(Imagefloat *img)
     {
@@ -432,6 +465,8 @@ public:
         pp.scale = 1.0; pp.chrominance_auto_factor = d.chrominanceAutoFactor;
         pp.ca_enabled = p.raw.enable_ca ? 1 : 0; pp.ca = p.caParams();    // the library applies the call site's condition per frame
         pp.dehaze_enabled = p.dehaze.enabled ? 1 : 0; pp.dehaze = p.dehazeParams();
+        pp.sharpening_enabled = p.sharpening.enabled ? 1 : 0; pp.sharpening = p.sharpeningParams();
+        pp.sharpening_auto_radius = p.sharpening.deconvAutoRadius ? 1 : 0; pp.sharpening_clip_val = (65535.f - cblacksom[1]) * scale_mul[1];
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {

@@ -600,6 +600,88 @@ int artgpu_dehaze_estimate_ambient(const float *R, const float *G, const float *
 int artgpu_dehaze_dark_channel(artgpu_ctx *ctx, const artgpu_rgb *rgb, int patchsize, const float *ambient /* [3] or NULL */, int clip,
                                artgpu_plane *dst);
 
+/* Capture sharpening: ImProcFunctions::doSharpening(img, params->sharpening, false) for method "rld" (rtengine/ipsharpen.cc:712-788; the
+ * first step of STAGE_2, improcfun.cc:595), in place on an RGB image whose planes are on the host or on the device, with any row stride.
+ *   early-outs (L717: !enabled, amount < 1, W < 8, H < 8): the image is untouched, the call succeeds;
+ *   Y = r * ws[1][0] + g * ws[1][1] + b * ws[1][2] in float (rt_algo.cc:942-956; TMatrix is float here: row 1 of `ws` is rounded once);
+ *   the blend mask: buildBlendMask(Y, blend, W, H, pow_F(contrast / 100.f, 1.2f) * sqrt(scale), 1.f, false, 2.f / sqrt(scale)) (L726-729);
+ *   markImpulse(W, H, Y, impulse, 2.f) (rt_algo.cc:497-596): gaussian sigma 2, the 25-term sum of |src - lpf| in row-major order, the
+ *   sign-bit test in the columns of the reference's 4-wide loop and `>` elsewhere;
+ *   deconvsharpening (L144-229) with sigma = deconvradius / scale, amount = deconvamount / 100.f: twenty Richardson-Lucy iterations of
+ *   gaussianBlur(GAUSS_DIV) and gaussianBlur(GAUSS_MULT) with check_stop, see artgpu_rl_deconvolution;
+ *   the corner boost when deconvCornerBoost / scale > 0.01f: a second run at sigma + delta, blended by CornerBoostMask (L315-340, L758-774);
+ *   multiply (rt_algo.cc:958-976): the three planes times YY / Y where Y > 0.
+ * Where deconvsharpening returns early (amount <= 0, sigma < 0.2f) the planes are still multiplied by Y / Y, as in the reference.
+ * ARTGPU_EUNSUPPORTED, image untouched: another method (usm, psf); a sigma (after the corner-boost delta as well) that is not finite or
+ * is >= 25 (the reference's behaviour there is an accident of NaN comparisons); 2 / sqrt(scale) < 0.6 (the mask blur leaves the shared
+ * gaussian's range).  Not built: show_sharpening_mask, prsharpening.
+ * Device scratch (context pool, artgpu_trim_scratch returns it): eight full-size planes and a byte plane, one plane more with corner boost. */
+#define ARTGPU_SHARPEN_RLD 0
+#define ARTGPU_SHARPEN_USM 1
+#define ARTGPU_SHARPEN_PSF 2
+#define ARTGPU_SHARPEN_REGIME_COPY 0   /* sigma in [0.2, 0.25): gaussianBlur copies */
+#define ARTGPU_SHARPEN_REGIME_3X3  1   /* [0.25, 0.6) */
+#define ARTGPU_SHARPEN_REGIME_5X5  2   /* [0.6, 0.84] */
+#define ARTGPU_SHARPEN_REGIME_7X7  3   /* (0.84, 1.15] */
+#define ARTGPU_SHARPEN_REGIME_YVV  4   /* (1.15, 25): the recursive gaussian */
+typedef struct artgpu_sharpening_params {   /* SharpeningParams (procparams.h:669-693; defaults procparams.cc:1756-1775) */
+    int32_t enabled;
+    int32_t method;                   /* ARTGPU_SHARPEN_* */
+    int32_t amount;                   /* only its `< 1` early-out is read on this path (L717) */
+    int32_t deconvamount;
+    double contrast;
+    double deconvradius;
+    double deconvCornerBoost;
+    int32_t deconvCornerLatitude;
+    int32_t offset_x, offset_y;       /* ImProcFunctions::offset_x / offset_y / full_width / full_height: where the image lies in the */
+    int32_t full_width, full_height;  /*   full frame (corner boost only); 0 = W / H (L763-764) */
+    int32_t pad_;
+} artgpu_sharpening_params;
+typedef struct artgpu_sharpening_info {     /* what the call derived; filling it costs a host wait, so it is filled only when asked for */
+    double sigma;                     /* of the (first) deconvolution */
+    int32_t regime;                   /* ARTGPU_SHARPEN_REGIME_*; -1: no iteration ran */
+    int32_t early_out;                /* 0 none; 1 !enabled, 2 amount < 1, 3 W or H < 8 (doSharpening); 4 amount <= 0, 5 sigma < 0.2f (deconvsharpening) */
+    float contrast_threshold;         /* pow_F(contrast / 100.f, 1.2f) * sqrt(scale); 0 from artgpu_rl_deconvolution */
+    int32_t pad_;
+    int64_t impulse_pixels;           /* non-zero bytes of the impulse map */
+    int64_t frozen_pixels;            /* pixels check_stop froze before the last iteration (iterations 1 .. 19 of 20) */
+} artgpu_sharpening_info;
+int artgpu_sharpening(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_sharpening_params *params, const double ws[9], double scale,
+                      artgpu_sharpening_info *info /* may be NULL */);
+/* deconvsharpening(luminance, blend, impulse, W, H, sigma, amount) (ipsharpen.cc:144-229) in place on `luminance`: + 1000, the estimate
+ * max(l, 0), twenty times  tmp = l / blur(estimate) (GAUSS_DIV), estimate *= blur(tmp) (GAUSS_MULT), check_stop (a pixel whose estimate
+ * leaves l +- 0.2 l is frozen at get_output the first time that happens and goes on iterating for its neighbours), then get_output and
+ * max(l - 1000, 0).  For the stencil regimes an iteration is ONE kernel (the estimate ping-pongs between two planes); above 1.15 the
+ * recurrences are the shared recursive gaussian and the DIV / MULT / check_stop steps run behind it.  amount <= 0 or sigma < 0.2f: nothing
+ * happens (L146-156).  sigma not finite or >= 25: ARTGPU_EUNSUPPORTED.  W, H >= 8.  impulse: W * H bytes, rows of W, on the host or on
+ * the device like `luminance`; blend: a plane of the same size, either residency. */
+int artgpu_rl_deconvolution(artgpu_ctx *ctx, artgpu_plane *luminance, const artgpu_plane *blend, const uint8_t *impulse,
+                            double sigma, float amount, artgpu_sharpening_info *info /* may be NULL */);
+/* gaussianBlur(src, dst, W, H, sigma, nullptr, gausstype, div) for src != dst and the GAUSS_DIV / GAUSS_MULT types (gauss.cc:1437-1523):
+ *   sigma < 0.25 a copy (whatever the type); [0.25, 0.6) gauss3x3div / gauss3x3mult with their edge formulas; [0.6, 0.84] and (0.84, 1.15]
+ *   the 5x5 / 7x7 forms (DIV writes 1.f into a ring of width 2 / 3 and divides by max(val, 0.00001f); MULT leaves the ring of dst alone;
+ *   the 7x7 forms multiply one term of the c21 group by c21 twice, L302 / L404); (1.15, 25) gaussHorizontalSse + gaussVerticalSsediv /
+ *   gaussVerticalSsemult (the 8-column groups' last three rows carry no max(.., 0)).
+ * DIV: dst = div / blur(src) in the form's rule.  MULT: dst is read and written, dst *= blur(src).  Above 1.15 the reference filters src in
+ * place for MULT: `src` IS OVERWRITTEN there (with the blurred plane; its content is not part of the contract).  Planes on the host or on the
+ * device, any row stride, W, H >= 8; sigma not finite or >= 25 and GAUSS_STANDARD (artgpu_gaussian_blur): ARTGPU_EUNSUPPORTED. */
+#define ARTGPU_GAUSS_STANDARD 0
+#define ARTGPU_GAUSS_MULT 1
+#define ARTGPU_GAUSS_DIV 2
+int artgpu_gaussian_blur_ex(artgpu_ctx *ctx, artgpu_plane *src, artgpu_plane *dst, const artgpu_plane *div /* DIV only */, double sigma,
+                            int gausstype);
+/* RawImageSource::getDeconvAutoRadius for Bayer and monochrome sensors = calcRadiusBayer(rawData, W, H, lower_limit, clip_val, fc)
+ * (deconvautoradius.cc:39-96, 200-245): one pass over the green sites of rows 4 .. H - 5 (columns 5 + (FC(row, 0) & 1), step 2, below
+ * W - 4) and their two lower diagonal neighbours.  The reference adopts a pair only if maxVal > maxRatio * minVal, under an OpenMP
+ * max-reduction, so its own result depends on the thread schedule in the last place; the contract here is
+ *   *max_ratio = max(1, fl(maxVal / minVal)) over ALL eligible pairs (both values positive, maxVal > lower_limit, neither clipped rule
+ *   fires), a tree of maxima: deterministic;  *radius = sqrt((1 / (log(1 / max_ratio) / 2)) / -2) in the float overloads, on the host.
+ * filters: the Bayer pattern; 0 = monochrome (fc = {0, 0}).  max_ratio == 1 (no eligible pair) makes the radius NaN as in the reference:
+ * it is returned and the caller decides (artgpu_sharpening rejects it).  The call waits for the stream.  X-Trans (filters == 9,
+ * calcRadiusXtrans): ARTGPU_EUNSUPPORTED. */
+int artgpu_deconv_auto_radius(artgpu_ctx *ctx, const artgpu_plane *raw, uint32_t filters, float lower_limit, float clip_val,
+                              float *radius, float *max_ratio /* may be NULL */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -646,6 +728,16 @@ typedef struct {
                                      * tool's last pass, the tool's ecomp is unchanged); what artgpu_dehaze does not support fails the frame before
                                      * any stage has run.  0 = off (dehaze.enabled is not looked at) */
     artgpu_dehaze_params dehaze;
+    int32_t sharpening_enabled;     /* artgpu_sharpening with `sharpening`, ws and `scale` after the exposure and before the tone curve (the first step of
+                                     * STAGE_2: simpleprocess.cc:395 between :389 and :396); method, scale and an X-Trans frame with the automatic radius
+                                     * fail the frame before any stage has run.  0 = off (nothing below is looked at) */
+    int32_t sharpening_auto_radius; /* SharpeningParams::deconvAutoRadius: when sharpening.enabled, artgpu_deconv_auto_radius(raw as the demosaic reads it,
+                                     * after CA correction; filters; 1000.f; sharpening_clip_val) replaces sharpening.deconvradius (simpleprocess.cc:274-278).
+                                     * The pass is launched ahead of the demosaic; the host waits for its number where the sharpening starts.  A frame
+                                     * without an eligible pair (radius NaN) fails there with ARTGPU_EUNSUPPORTED */
+    float sharpening_clip_val;      /* (ri->get_white(1) - ri->get_cblack(1)) * scale_mul[1] (deconvautoradius.cc:202) */
+    int32_t pad_sharpening_;
+    artgpu_sharpening_params sharpening;
 } artgpu_pipeline_params;
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *params, artgpu_rgb *out);
 
