@@ -83,6 +83,16 @@ class DehazeInfo(C.Structure):
                 ("maxval", C.c_float), ("black", C.c_float * 3), ("ambient", C.c_float * 3), ("max_t", C.c_float), ("t0", C.c_float)]
 
 
+class TextureBoostRegion(C.Structure):
+    """artgpu_texture_boost_region: one TextureBoostParams::Region and its blend mask"""
+    _fields_ = [("strength", C.c_double), ("detail_threshold", C.c_double), ("iterations", C.c_int32), ("mask", C.POINTER(Plane))]
+
+
+class TextureBoostInfo(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("isguided", C.c_int32), ("rescaled", C.c_int32), ("work_w", C.c_int32), ("work_h", C.c_int32),
+                ("kernel_size", C.c_int32), ("minval", C.c_float), ("strength", C.c_float), ("strength2", C.c_float)]
+
+
 SHARPEN_RLD, SHARPEN_USM, SHARPEN_PSF = 0, 1, 2
 SHARPEN_REGIME_COPY, SHARPEN_REGIME_3X3, SHARPEN_REGIME_5X5, SHARPEN_REGIME_7X7, SHARPEN_REGIME_YVV = 0, 1, 2, 3, 4
 GAUSS_STANDARD, GAUSS_MULT, GAUSS_DIV = 0, 1, 2
@@ -133,7 +143,8 @@ PipelineParams._fields_ = [
     ("local_contrast_enabled", C.c_int32), ("local_contrast_nregions", C.c_int32), ("local_contrast_regions", C.POINTER(LocalContrastRegion)),
     ("dehaze_enabled", C.c_int32), ("dehaze", DehazeParams),
     ("sharpening_enabled", C.c_int32), ("sharpening_auto_radius", C.c_int32), ("sharpening_clip_val", C.c_float), ("pad_sharpening_", C.c_int32),
-    ("sharpening", SharpeningParams)]
+    ("sharpening", SharpeningParams),
+    ("texture_boost_enabled", C.c_int32), ("texture_boost_nregions", C.c_int32), ("texture_boost_regions", C.POINTER(TextureBoostRegion))]
 
 
 
@@ -152,6 +163,7 @@ class ScanlineFrame(C.Structure):
 
 DN_SKIP_DETAIL_RECOVERY = 1
 LOCAL_CONTRAST_MIN_SIZE = 8
+TEXTURE_BOOST_MIN_SIZE = 5
 # LocalContrastParams::Region's default curve (procparams.cc:1700-1714)
 DEFAULT_LOCAL_CONTRAST_CURVE_POINTS = (1.0, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0)
 # the chroma noise curve ImProcFunctions::denoise always installs (ipdenoise.cc:1139-1149)
@@ -213,6 +225,20 @@ def dehaze_params(strength=DEFAULT_DEHAZE_STRENGTH_POINTS, depth=25, show_depth_
     p = DehazeParams(1 if enabled else 0, C.cast(pts, C.POINTER(C.c_double)), len(strength), 1 if show_depth_map else 0, int(depth),
                      1 if luminance else 0, int(blackpoint))
     return p, pts
+
+
+def texture_boost_regions(regions):
+    """[(strength, detail threshold, iterations, mask Plane or None), ...] -> (TextureBoostRegion array, objects to keep alive with it)"""
+    arr = (TextureBoostRegion * max(len(regions), 1))()
+    keep = []
+    for k, (strength, threshold, iterations, mask) in enumerate(regions):
+        arr[k].strength = float(strength)
+        arr[k].detail_threshold = float(threshold)
+        arr[k].iterations = int(iterations)
+        if mask is not None:
+            keep.append(mask)
+            arr[k].mask = C.pointer(mask)
+    return arr, keep
 
 
 def local_contrast_regions(regions):
@@ -296,6 +322,9 @@ def _load():
     lib.artgpu_rl_deconvolution.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(Plane), C.c_void_p, C.c_double, C.c_float, C.POINTER(SharpeningInfo)]
     lib.artgpu_gaussian_blur_ex.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(Plane), C.POINTER(Plane), C.c_double, C.c_int]
     lib.artgpu_deconv_auto_radius.argtypes = [C.c_void_p, C.POINTER(Plane), C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.artgpu_texture_boost_plane.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(TextureBoostRegion), C.c_double, C.c_int, C.POINTER(TextureBoostInfo)]
+    lib.artgpu_texture_boost.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(TextureBoostRegion), C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int,
+                                         C.POINTER(TextureBoostInfo)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -375,7 +404,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_wavelet_reconstruct", "artgpu_wavelet_free", "artgpu_rgb_denoise", "artgpu_denoise_guided_smoothing",
            "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
            "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
-           "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius"]
+           "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
+           "artgpu_texture_boost_plane", "artgpu_texture_boost"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -564,6 +594,25 @@ class Context:
 
     dehaze_strength_lut = staticmethod(dehaze_strength_lut)
     dehaze_estimate_ambient = staticmethod(dehaze_estimate_ambient)
+
+    def texture_boost_plane(self, Y: Plane, strength: float, detail_threshold: float = 0.2, iterations: int = 1, scale: float = 1.0,
+                            high_detail: bool = True, want_info: bool = False):
+        """one texture_boost call (iptextureboost.cc:37-178) in place on a Y plane; returns the TextureBoostInfo when want_info."""
+        arr, _ = texture_boost_regions([(strength, detail_threshold, iterations, None)])
+        info = TextureBoostInfo() if want_info else None
+        self._chk(LIB.artgpu_texture_boost_plane(self._h, C.byref(Y), arr, float(scale), 1 if high_detail else 0, C.byref(info) if want_info else None))
+        return info
+
+    def texture_boost(self, image: RGB, regions, ws, scale: float = 1.0, high_detail: bool = True, to_rgb: bool = True, want_info: bool = False):
+        """ImProcFunctions::textureBoost in place on an RGB image.  regions: [(strength, detail threshold, iterations, mask Plane or None), ...];
+        returns the TextureBoostInfo of the last region that ran when want_info."""
+        arr, keep = texture_boost_regions(regions)
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        info = TextureBoostInfo() if want_info else None
+        self._chk(LIB.artgpu_texture_boost(self._h, C.byref(image), arr, len(regions), wsd, float(scale), 1 if high_detail else 0, 1 if to_rgb else 0,
+                                           C.byref(info) if want_info else None))
+        del keep
+        return info
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""

@@ -45,6 +45,27 @@ struct DhRecoverArgs {
     int show_depth_map, luminance;
 };
 
+// (shared with textureboost.hip, whose guided filters end the same way)
+// getBilinearValue (rescale.h:27-50) on a plane with rows of `stride` floats
+__device__ __forceinline__ float dh_bilinear(const float *__restrict__ src, size_t stride, int W, int H, float x, float y)
+{
+    const int xi = min((int)x, W - 1), yi = min((int)y, H - 1);
+    const float xf = x - xi, yf = y - yi;
+    const int xi1 = min(xi + 1, W - 1), yi1 = min(yi + 1, H - 1);
+    const float bl = src[(size_t)yi * stride + xi], br = src[(size_t)yi * stride + xi1];
+    const float tl = src[(size_t)yi1 * stride + xi], tr = src[(size_t)yi1 * stride + xi1];
+    const float b = xf * br + (1.f - xf) * bl;
+    const float t = xf * tr + (1.f - xf) * tl;
+    return yf * t + (1.f - yf) * b;
+}
+
+// q = rescaleBilinear(mean a) * I + rescaleBilinear(mean b) at (y, x) (guidedfilter.cc:225-240)
+__device__ __forceinline__ float dh_q(const float *__restrict__ ma, const float *__restrict__ mb, int w, int h, float col_scale, float ymrs, int x, float I)
+{
+    const float fx = x * col_scale;
+    return dh_bilinear(ma, w, w, h, fx, ymrs) * I + dh_bilinear(mb, w, w, h, fx, ymrs);
+}
+
 hipError_t launch_dh_max(const DhImage &im, float *partial, int npartial, DhState *st, hipStream_t s);
 hipError_t launch_dh_thumb(const DhThumbArgs &a, hipStream_t s);
 hipError_t launch_dh_black(const float *thumb, int n, float scaling, DhState *st, hipStream_t s);

@@ -14,7 +14,9 @@
 //                                                      strength curve, default 0.75)
 //              [--sharpen contrast[,radius|auto[,amount[,cornerboost[,latitude]]]]]   (ImProcFunctions::sharpening in STAGE_2, method rld; `auto`
 //                                                      (the default) takes the radius from RawImageSource::getDeconvAutoRadius as simpleprocess.cc:274-278 does)
-//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..] [--out prefix]
+//              [--texture-boost strength,threshold,iterations]   (ImProcFunctions::textureBoost, the first step of STAGE_3: one region, no mask)
+//   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
+//              [--texture-boost ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <chrono>
@@ -68,6 +70,9 @@ int main(int argc, char **argv)
     bool sh_enable = false, sh_auto = true;                        // SharpeningParams::enabled, deconvAutoRadius
     double sh_contrast = 20.0, sh_radius = 0.75, sh_boost = 0.0;
     int sh_amount = 100, sh_latitude = 25;
+    bool tb_enable = false;                                        // TextureBoostParams::enabled, one region
+    double tb_strength = 0.0, tb_threshold = 0.2;
+    int tb_iterations = 1;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -132,6 +137,10 @@ int main(int argc, char **argv)
             if (f.size() > 4) sh_latitude = std::atoi(f[4].c_str());
             sh_enable = true;
         }
+        else if (a == "--texture-boost") {
+            if (std::sscanf(next(), "%lf,%lf,%d", &tb_strength, &tb_threshold, &tb_iterations) != 3) { std::fprintf(stderr, "--texture-boost strength,threshold,iterations\n"); return 2; }
+            tb_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
@@ -149,6 +158,7 @@ int main(int argc, char **argv)
             params.dehaze.strength = {1, 0.0, dh_y, 0.0, 0.0, 1.0, dh_y, 0.0, 0.0};
             params.sharpening.enabled = sh_enable; params.sharpening.contrast = sh_contrast; params.sharpening.deconvradius = sh_radius; params.sharpening.deconvAutoRadius = sh_auto;
             params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
+            params.textureBoost.enabled = tb_enable; params.textureBoost.regions = {{tb_strength, tb_threshold, tb_iterations}};
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -222,6 +232,7 @@ int main(int argc, char **argv)
         params.dehaze.strength = {1, 0.0, dh_y, 0.0, 0.0, 1.0, dh_y, 0.0, 0.0};
         params.sharpening.enabled = sh_enable; params.sharpening.contrast = sh_contrast; params.sharpening.deconvradius = sh_radius; params.sharpening.deconvAutoRadius = sh_auto;
         params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
+        params.textureBoost.enabled = tb_enable; params.textureBoost.regions = {{tb_strength, tb_threshold, tb_iterations}};
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;

@@ -126,6 +126,25 @@ struct ProcParams {
     struct LocalContrastRegion { double contrast = 0; std::vector<double> curve = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0}; };
     struct LocalContrastMask { bool enabled = true; const DevicePlane *blend = nullptr; };
     struct { bool enabled = false; std::vector<LocalContrastRegion> regions; std::vector<LocalContrastMask> masks; } localContrast;
+    // TextureBoostParams (procparams.cc:1950-2022): regions {strength, detailThreshold, iterations}; masks[i].enabled and the blend plane
+    // generateMasks makes of masks[i] (host code of the application; nullptr = all ones), one per region
+    struct TextureBoostRegion { double strength = 0; double detailThreshold = 0.2; int iterations = 1; };
+    struct TextureBoostMask { bool enabled = true; const DevicePlane *blend = nullptr; };
+    struct { bool enabled = false; std::vector<TextureBoostRegion> regions = {TextureBoostRegion()}; std::vector<TextureBoostMask> masks; } textureBoost;
+    // the enabled regions as the library takes them; `blends` keeps the mask views the regions point to
+    std::vector<artgpu_texture_boost_region> textureBoostRegions(std::vector<artgpu_plane> &blends) const
+    {
+        const auto &p = textureBoost;
+        blends.assign(p.regions.size(), artgpu_plane{});
+        std::vector<artgpu_texture_boost_region> regions;
+        for (size_t k = 0; k < p.regions.size(); ++k) {
+            if (k < p.masks.size() && !p.masks[k].enabled) continue;
+            artgpu_texture_boost_region reg{p.regions[k].strength, p.regions[k].detailThreshold, p.regions[k].iterations, nullptr};
+            if (k < p.masks.size() && p.masks[k].blend) { blends[k] = p.masks[k].blend->view(); reg.mask = &blends[k]; }
+            regions.push_back(reg);
+        }
+        return regions;
+    }
     struct { bool enabled = false; std::vector<float> rlut, glut, blut; } rgbCurves;                                             // RGBCurvesParams, as outCurve LUTs
     struct { bool enabled = true; int curveMode = ARTGPU_TONE_STD; std::vector<float> lut; float whitePoint = 1.f; bool basecurveLinear = true; } toneCurve;
     // toneCurve.curveMode: ARTGPU_TONE_STD or ARTGPU_TONE_NEUTRAL (ART's default, procparams.cc:1585)
@@ -236,14 +255,28 @@ public:
     // ImProcFunctions::process (improcfun.cc:567-641): same step order; steps that are disabled / identity in the
     // default ProcParams and not on the device path (DRC, toneEqualizer, impulse denoise, defringe, ... blackAndWhite) are
     // skipped here exactly as their `enabled == false` early-outs skip them.  STAGE_2 holds capture sharpening, its first step.
-    bool process(Pipeline, Stage stage, Imagefloat *img)
+    bool process(Pipeline pipeline, Stage stage, Imagefloat *img)
     {
+        cur_pipeline = pipeline;
         switch (stage) {
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
         case Stage::STAGE_2: sharpening(img); break;                                          // improcfun.cc:595
-        case Stage::STAGE_3: logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:607-625 (the steps this library has)
+        case Stage::STAGE_3: textureBoost(img); logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:606-625 (the steps this library has)
         }
+        return false;
+    }
+    Pipeline cur_pipeline = Pipeline::OUTPUT;
+    // ImProcFunctions::textureBoost (iptextureboost.cc:183-248): setMode(YUV), every enabled region with strength != 0 through texture_boost and
+    // the mask blend on the Y plane; this mirror has no mode tracking and converts back at once (Imagefloat::yuv_to_rgb)
+    bool textureBoost(Imagefloat *img)
+    {
+        if (!params->textureBoost.enabled) return false;
+        std::vector<artgpu_plane> blends;
+        const std::vector<artgpu_texture_boost_region> regions = params->textureBoostRegions(blends);
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_texture_boost(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, scale,
+                                       (scale == 1 || cur_pipeline == Pipeline::OUTPUT) ? 1 : 0, 1, nullptr));
         return false;
     }
     // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
@@ -467,6 +500,9 @@ public:
         pp.dehaze_enabled = p.dehaze.enabled ? 1 : 0; pp.dehaze = p.dehazeParams();
         pp.sharpening_enabled = p.sharpening.enabled ? 1 : 0; pp.sharpening = p.sharpeningParams();
         pp.sharpening_auto_radius = p.sharpening.deconvAutoRadius ? 1 : 0; pp.sharpening_clip_val = (65535.f - cblacksom[1]) * scale_mul[1];
+        std::vector<artgpu_plane> tb_blends;
+        const std::vector<artgpu_texture_boost_region> tb_regions = p.textureBoostRegions(tb_blends);
+        pp.texture_boost_enabled = p.textureBoost.enabled ? 1 : 0; pp.texture_boost_nregions = (int32_t)tb_regions.size(); pp.texture_boost_regions = tb_regions.data();
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {

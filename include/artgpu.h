@@ -682,10 +682,63 @@ int artgpu_gaussian_blur_ex(artgpu_ctx *ctx, artgpu_plane *src, artgpu_plane *ds
 int artgpu_deconv_auto_radius(artgpu_ctx *ctx, const artgpu_plane *raw, uint32_t filters, float lower_limit, float clip_val,
                               float *radius, float *max_ratio /* may be NULL */);
 
+/* Texture boost: ImProcFunctions::textureBoost (rtengine/iptextureboost.cc:183-248; the first arithmetic step of STAGE_3, improcfun.cc:606),
+ * ART's detail tool.  artgpu_texture_boost_plane is one texture_boost call (L37-178) in place on a Y plane (host or device, any row stride),
+ * without a mask blend:
+ *   the scalars of L39-50 on the host exactly as written (pow_F in the sleef form): full_radius = detail_threshold * 3.5f, fradius =
+ *   full_radius / scale, radius = max(int(fradius + 0.5f), 1), delta = radius / fradius, s, strength, strength2, isguided = full_radius >= 1;
+ *   the rescale of L57-63 when fradius > 1 && delta > 1.01: the work happens on rescaleBilinear(Y) at int(W * delta + 0.5f) x
+ *   int(H * delta + 0.5f) (up to 1.33x per axis) and L175-177 rescale src * 65535.f back;
+ *   L85-101: v = src / 65535.f, mid = clamp(v, 1e-5f, 32.f), minval = min(v); columns below 4 * (w / 4) clamp as the reference's vector body
+ *   does (vmaxf(vminf(v, hi), lo)), the others as LIM does, likewise the max of L145 / L154: a NaN pixel lands where the reference puts it;
+ *   per iteration i (L114-157): mid = guidedFilter(mid, mid, mid, radius, 0.001f) when isguided, else Convolution(build_gaussian_kernel(
+ *   fradius))(mid, mid); base = guidedFilter(mid, mid, ., radius * 4, 0.0001f); src = intp(2^-i, max(base + (src - mid) * strength +
+ *   (mid - base) * strength2, minval), src); then src * 65535.f.
+ * Convolution (rt_algo.cc:733-899) is an FFTW product in the reference.  Its index arithmetic makes it
+ *   dst[y][x] = sum over ky, kx of kernel[ky][kx] * src[clamp(y + K / 2 - ky)][clamp(x + K / 2 - kx)]  (clamp to edge, K = 3, 5, 7 or 9 for
+ *   a sigma below 1), and that sum is what runs here: fp32, ky-major, unfused, from 0.f, with build_gaussian_kernel (L902-939) restated on the
+ *   host.  This stage is exact against that definition; the reference's own output differs from it by the FFT's rounding (the direct sum is
+ *   within (K * K + 1) * 2^-24 relative of the exact convolution of positive input).
+ * artgpu_texture_boost is the whole tool on an image in RGB mode: setMode(YUV) (always, also when no region runs: the YUV round trip is not
+ * the identity in bits), for every region with strength != 0 in order texture_boost(Y) and Y = intp(mask, Y_new, Y) (L221-241; a NULL mask
+ * does the same arithmetic with 1.f), and setMode(RGB) on top when to_rgb != 0 (the reference leaves the image in YUV mode, as
+ * artgpu_hsl_equalizer's to_rgb).  The caller keeps what is host code in the reference: generateMasks' blend planes and the
+ * `masks[i].enabled` test (a disabled region is simply not passed).  high_detail = (scale == 1 || pipeline == OUTPUT) (L228).
+ * A non-NULL `info` receives what the last region that ran derived (zeros when none ran); filling it costs the call's one host wait.
+ * Contract: NaN-free input for minval (a minimum's result depends on the order for NaN), and the sign of a zero minval is not defined.
+ * ARTGPU_EUNSUPPORTED, image untouched, decided before any kernel runs:
+ *   - !isguided && !high_detail (the preview's gaussianBlur at a sub-pixel sigma);
+ *   - !isguided with a gaussian larger than 9 x 9 (fradius >= 1 while full_radius < 1: scale < 1);
+ *   - iterations < 1;
+ *   - a working plane with a side shorter than the guided filters' subsampling (w / s or h / s == 0 at radius or radius * 4, s <= 5 and
+ *     s == 1 while max(w, h) <= 600): every plane with both sides >= ARTGPU_TEXTURE_BOOST_MIN_SIZE is accepted;
+ *   - a box radius above 900 (detail_threshold above about 320).
+ * Device scratch (context pool, artgpu_trim_scratch returns it): two planes of the working size (three on the convolution path), the
+ * guided filters' statistics grid twice (two planes of w / s x h / s each), 64 K floats of partial minima; a host mask or Y plane is staged
+ * in one plane more each. */
+#define ARTGPU_TEXTURE_BOOST_MIN_SIZE 5
+typedef struct artgpu_texture_boost_region {
+    double strength;                  /* TextureBoostParams::Region::strength (procparams.h:789-793; defaults 0, 0.2, 1) */
+    double detail_threshold;          /* ::detailThreshold */
+    int32_t iterations;               /* ::iterations */
+    const artgpu_plane *mask;         /* generateMasks' blend plane for this region (host or device); NULL = all ones; artgpu_texture_boost only */
+} artgpu_texture_boost_region;
+typedef struct artgpu_texture_boost_info {
+    int32_t radius, isguided, rescaled;
+    int32_t work_w, work_h;           /* the size the region worked at */
+    int32_t kernel_size;              /* K of the gaussian; 0 when isguided */
+    float minval, strength, strength2;
+} artgpu_texture_boost_info;
+int artgpu_texture_boost_plane(artgpu_ctx *ctx, artgpu_plane *Y, const artgpu_texture_boost_region *region, double scale, int high_detail,
+                               artgpu_texture_boost_info *info /* may be NULL */);
+int artgpu_texture_boost(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_texture_boost_region *regions, int nregions, const double ws[9],
+                         double scale, int high_detail, int to_rgb, artgpu_texture_boost_info *info /* may be NULL */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
- *   [ImProcFunctions::dehaze ->] ImProcFunctions::exposure -> ImProcFunctions::toneCurve [-> ImProcFunctions::localContrast].
+ *   [ImProcFunctions::dehaze ->] ImProcFunctions::exposure [-> ImProcFunctions::sharpening] [-> ImProcFunctions::textureBoost] ->
+ *   ImProcFunctions::toneCurve [-> ImProcFunctions::localContrast].
  * raw: CFA plane (host or device).  out: (W - 2*border) x (H - 2*border) planes (host or device; the frame stays on the device
  * between the stages either way).  Disabled stages are skipped exactly like their `enabled == false` early-outs. */
 typedef struct {
@@ -738,6 +791,11 @@ typedef struct {
     float sharpening_clip_val;      /* (ri->get_white(1) - ri->get_cblack(1)) * scale_mul[1] (deconvautoradius.cc:202) */
     int32_t pad_sharpening_;
     artgpu_sharpening_params sharpening;
+    int32_t texture_boost_enabled;  /* TextureBoostParams::enabled: artgpu_texture_boost with these regions, ws, `scale`, high_detail = 1 (the batch pipe is the
+                                     * OUTPUT pipeline) and to_rgb = 1 after the sharpening and before the tone curve (the first arithmetic step of STAGE_3,
+                                     * improcfun.cc:606); what artgpu_texture_boost does not support fails the frame before any stage has run.  0 = off */
+    int32_t texture_boost_nregions;
+    const artgpu_texture_boost_region *texture_boost_regions;   /* masks: planes of the output size */
 } artgpu_pipeline_params;
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *params, artgpu_rgb *out);
 
