@@ -93,6 +93,63 @@ class TextureBoostInfo(C.Structure):
                 ("kernel_size", C.c_int32), ("minval", C.c_float), ("strength", C.c_float), ("strength2", C.c_float)]
 
 
+class MaskParams(C.Structure):
+    """artgpu_mask_params: one rtengine::procparams::Mask as the parametric path of generateMasks reads it"""
+    _fields_ = [("parametric_enabled", C.c_int32), ("lightness_detail", C.c_int32), ("hue", C.POINTER(C.c_double)),
+                ("chromaticity", C.POINTER(C.c_double)), ("lightness", C.POINTER(C.c_double)), ("nhue", C.c_int32), ("nchromaticity", C.c_int32),
+                ("nlightness", C.c_int32), ("contrast_threshold", C.c_int32), ("blur", C.c_double), ("area", C.POINTER(Plane)),
+                ("posterization", C.c_int32), ("smoothing", C.c_int32), ("inverted", C.c_int32), ("opacity", C.c_int32),
+                ("deltae_enabled", C.c_int32), ("drawn_enabled", C.c_int32), ("external_enabled", C.c_int32), ("linked_enabled", C.c_int32),
+                ("curve_is_identity", C.c_int32), ("show_mask", C.c_int32)]
+
+
+class MasksInfo(C.Structure):
+    """artgpu_masks_info, one per region"""
+    _fields_ = [("has_mask", C.c_int32), ("has_lmask", C.c_int32), ("ll_radius_small", C.c_int32), ("ll_radius", C.c_int32),
+                ("blurred", C.c_int32), ("r1", C.c_int32), ("r2", C.c_int32), ("cthr_w", C.c_int32), ("cthr_h", C.c_int32),
+                ("smoothing_radius", C.c_int32)]
+
+
+MASKS_MIN_SIZE = 8
+MASKS_MODE_RGB, MASKS_MODE_LAB, MASKS_MODE_YUV, MASKS_MODE_XYZ = 0, 1, 2, 3
+# ParametricMask's default curves (procparams.cc:1014-1053)
+DEFAULT_MASK_HUE_POINTS = (1.0, 0.166666667, 1.0, 0.35, 0.35, 0.8287775246, 1.0, 0.35, 0.35)
+DEFAULT_MASK_CL_POINTS = (1.0, 0.0, 1.0, 0.35, 0.35, 1.0, 1.0, 0.35, 0.35)
+
+
+def mask_params(masks):
+    """[dict, ...] -> (MaskParams array, objects to keep alive with it).  A dict holds Mask's fields under the names of MaskParams with
+    Mask's defaults for what it leaves out (parametric_enabled False, the default curves, blur 0, opacity 100, curve_is_identity True);
+    curves are sequences of FlatCurve points, `area` a Plane."""
+    arr = (MaskParams * max(len(masks), 1))()
+    keep = []
+    for k, m in enumerate(masks):
+        m = dict(m)
+        a = arr[k]
+        a.parametric_enabled = 1 if m.pop("parametric_enabled", False) else 0
+        for name, dflt in (("hue", DEFAULT_MASK_HUE_POINTS), ("chromaticity", DEFAULT_MASK_CL_POINTS), ("lightness", DEFAULT_MASK_CL_POINTS)):
+            pts = m.pop(name, dflt)
+            buf = (C.c_double * max(len(pts), 1))(*[float(v) for v in pts])
+            keep.append(buf)
+            setattr(a, name, C.cast(buf, C.POINTER(C.c_double)))
+            setattr(a, "n" + name, len(pts))
+        a.lightness_detail = int(m.pop("lightness_detail", 0))
+        a.contrast_threshold = int(m.pop("contrast_threshold", 0))
+        a.blur = float(m.pop("blur", 0.0))
+        area = m.pop("area", None)
+        if area is not None:
+            keep.append(area)
+            a.area = C.pointer(area)
+        a.posterization = int(m.pop("posterization", 0)); a.smoothing = int(m.pop("smoothing", 0))
+        a.inverted = 1 if m.pop("inverted", False) else 0
+        a.opacity = int(m.pop("opacity", 100))
+        for name in ("deltae_enabled", "drawn_enabled", "external_enabled", "linked_enabled", "show_mask"):
+            setattr(a, name, 1 if m.pop(name, False) else 0)
+        a.curve_is_identity = 1 if m.pop("curve_is_identity", True) else 0
+        assert not m, sorted(m)
+    return arr, keep
+
+
 SHARPEN_RLD, SHARPEN_USM, SHARPEN_PSF = 0, 1, 2
 SHARPEN_REGIME_COPY, SHARPEN_REGIME_3X3, SHARPEN_REGIME_5X5, SHARPEN_REGIME_7X7, SHARPEN_REGIME_YVV = 0, 1, 2, 3, 4
 GAUSS_STANDARD, GAUSS_MULT, GAUSS_DIV = 0, 1, 2
@@ -325,6 +382,9 @@ def _load():
     lib.artgpu_texture_boost_plane.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(TextureBoostRegion), C.c_double, C.c_int, C.POINTER(TextureBoostInfo)]
     lib.artgpu_texture_boost.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(TextureBoostRegion), C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int,
                                          C.POINTER(TextureBoostInfo)]
+    lib.artgpu_generate_masks.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.POINTER(C.c_double), C.POINTER(MaskParams), C.c_int, C.c_int, C.c_int,
+                                          C.c_double, C.POINTER(Plane), C.POINTER(Plane), C.POINTER(MasksInfo)]
+    lib.artgpu_set_pipeline_masks.argtypes = [C.c_void_p, C.POINTER(MaskParams), C.c_int, C.POINTER(MaskParams), C.c_int]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -405,7 +465,7 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
            "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
            "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
-           "artgpu_texture_boost_plane", "artgpu_texture_boost"]
+           "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -613,6 +673,31 @@ class Context:
                                            C.byref(info) if want_info else None))
         del keep
         return info
+
+    def generate_masks(self, image: RGB, mode: int, ws, masks, full_w: int = -1, full_h: int = -1, scale: float = 1.0, Lmask=None, abmask=None,
+                       want_info: bool = False):
+        """rtengine::generateMasks' parametric path.  masks: what mask_params() takes; Lmask / abmask: a list of len(masks) Planes each, or
+        None.  Returns the list of MasksInfo (one per region) when want_info."""
+        arr, keep = mask_params(masks)
+        n = len(masks)
+        wsd = None if ws is None else (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        sets = []
+        for planes in (Lmask, abmask):
+            assert planes is None or len(planes) == n
+            sets.append(None if planes is None else (Plane * max(n, 1))(*planes))
+        info = (MasksInfo * max(n, 1))() if want_info else None
+        self._chk(LIB.artgpu_generate_masks(self._h, C.byref(image), int(mode), wsd, arr, n, int(full_w), int(full_h), float(scale), sets[0], sets[1], info))
+        del keep
+        return list(info)[:n] if want_info else None
+
+    def set_pipeline_masks(self, local_contrast_masks=None, texture_boost_masks=None):
+        """the region masks pipeline_run / batch_run / batch_run_io generate themselves (what mask_params() takes, one per region of the tool;
+        None: that tool's regions use their own planes).  The library copies them."""
+        lc, k1 = mask_params(local_contrast_masks or [])
+        tb, k2 = mask_params(texture_boost_masks or [])
+        self._chk(LIB.artgpu_set_pipeline_masks(self._h, lc if local_contrast_masks else None, len(local_contrast_masks or []),
+                                                tb if texture_boost_masks else None, len(texture_boost_masks or [])))
+        del k1, k2
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "dehaze.h"
 #include "textureboost.h"
+#include "masks.h"
 #include "sharpen.h"
 
 using namespace artgpu;
@@ -42,6 +43,10 @@ struct artgpu_ctx {
                                    // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
+    // artgpu_set_pipeline_masks: deep copies (entries, curves, area descriptors); batch lanes point at their parent's
+    struct PipeMasks { std::vector<artgpu_mask_params> m; std::vector<std::vector<double>> curves; std::vector<artgpu_plane> areas; } pipe_lc_own, pipe_tb_own;
+    const artgpu_mask_params *pipe_lc = nullptr, *pipe_tb = nullptr;
+    int pipe_nlc = 0, pipe_ntb = 0;
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
     int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
@@ -56,7 +61,7 @@ struct artgpu_ctx {
     float *stage[NSTAGE] = {};
     size_t stage_bytes[NSTAGE] = {};
     // grow-only scratch pool for the denoise path (planes, decompositions, shrink buffers)
-    static constexpr int NPOOL = 80;
+    static constexpr int NPOOL = 96;
     float *pool[NPOOL] = {};
     size_t pool_bytes[NPOOL] = {};
     // artgpu_batch_run lanes: sibling contexts (own stream, arena, pools) that take every lanes-th frame on their own host thread
@@ -1138,6 +1143,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_DH_STATE, P_DH_THUMB, P_DH_LOW, P_DH_TMP, P_DH_T, P_DH_DARK,                                                   // artgpu_dehaze
        P_SH_PLANES, P_SH_BYTES, P_SH_STATE,                                                                             // artgpu_sharpening
        P_TB_PLANES, P_TB_LOW, P_TB_TMP, P_TB_STATE, P_TB_MASK, P_TB_Y,                                                  // artgpu_texture_boost
+       P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 
@@ -1747,31 +1753,26 @@ int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const doub
     return unbind_rgb(ctx, img, &d);
 }
 
-int artgpu_guided_filter(artgpu_ctx *ctx, const artgpu_plane *guide, const artgpu_plane *src, artgpu_plane *dst, int r, float epsilon, int subsampling)
+// rtengine::guidedFilter (guidedfilter.cc:80-241) on contiguous device planes (rows of W floats), q with rows of q_stride floats; q may be
+// `guide` or `src` (the last pass is pointwise).  Enqueued on ctx->stream; scratch: the statistics grid in P_TMP / P_LIN
+static int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
+                             const char *who)
 {
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!guide || !src || !dst || !plane_ok(guide) || !plane_ok(src) || !plane_ok(dst)) return fail(ctx, ARTGPU_EINVAL, "guided_filter: bad plane");
-    const int W = src->w, H = src->h;
-    if (guide->w != W || guide->h != H || dst->w != W || dst->h != H || r < 0) return fail(ctx, ARTGPU_EINVAL, "guided_filter: size mismatch / negative radius");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     const int sub = subsampling > 0 ? subsampling : gf_subsampling(W, H, r);
     GuidedArgs g = {};
     g.W = W; g.H = H; g.w = W / sub; g.h = H / sub; g.epsilon = epsilon; g.nch = 1;
-    if (g.w < 1 || g.h < 1) return fail(ctx, ARTGPU_EINVAL, "guided_filter: subsampling %d leaves no pixels", sub);
-    const size_t n = (size_t)W * H, nl = (size_t)g.w * g.h;
-    float *big, *low, *tmp;
+    if (g.w < 1 || g.h < 1) return fail(ctx, ARTGPU_EINVAL, "%s: subsampling %d leaves no pixels", who, sub);
+    const size_t nl = (size_t)g.w * g.h;
+    float *low, *tmp;
     int rc;
-    if ((rc = pool_get(ctx, P_SF, 3 * n * 4, &big)) || (rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
-    g.guide = big; g.chan[0] = big + n; g.q = big + 2 * n; g.q_stride = W;
-    const size_t rowb = (size_t)W * 4;
-    HIPCHK(ctx, hipMemcpy2DAsync(g.guide, rowb, guide->p, (size_t)guide->row_stride_bytes, rowb, H, guide->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpy2DAsync(g.chan[0], rowb, src->p, (size_t)src->row_stride_bytes, rowb, H, src->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
+    g.guide = const_cast<float *>(guide); g.chan[0] = const_cast<float *>(src); g.q = q; g.q_stride = q_stride;
     for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
-    HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
     const float r1 = float(r) / sub;
     int rad = (int)r1;
     { const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }     // f_mean's LIM (L160-164)
-    if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "guided_filter: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", rad, HBLUR_MAX_RADIUS);
+    if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, rad, HBLUR_MAX_RADIUS);
+    HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
     BlurArgs bl = {};
     bl.n = nl; bl.w = g.w; bl.h = g.h; bl.steady_div = 1; bl.plain = 1;
     for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
@@ -1788,7 +1789,25 @@ int artgpu_guided_filter(artgpu_ctx *ctx, const artgpu_plane *guide, const artgp
     HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
     if ((rc = blur_plane(g.low[2])) || (rc = blur_plane(g.low[5]))) return rc;       // mean a, mean b
     HIPCHK(ctx, launch_gf_finish_plain(g, ctx->stream));
-    HIPCHK(ctx, hipMemcpy2DAsync(dst->p, (size_t)dst->row_stride_bytes, g.q, rowb, rowb, H, dst->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    return ARTGPU_OK;
+}
+
+int artgpu_guided_filter(artgpu_ctx *ctx, const artgpu_plane *guide, const artgpu_plane *src, artgpu_plane *dst, int r, float epsilon, int subsampling)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!guide || !src || !dst || !plane_ok(guide) || !plane_ok(src) || !plane_ok(dst)) return fail(ctx, ARTGPU_EINVAL, "guided_filter: bad plane");
+    const int W = src->w, H = src->h;
+    if (guide->w != W || guide->h != H || dst->w != W || dst->h != H || r < 0) return fail(ctx, ARTGPU_EINVAL, "guided_filter: size mismatch / negative radius");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H;
+    float *big;
+    int rc;
+    if ((rc = pool_get(ctx, P_SF, 3 * n * 4, &big))) return rc;
+    const size_t rowb = (size_t)W * 4;
+    HIPCHK(ctx, hipMemcpy2DAsync(big, rowb, guide->p, (size_t)guide->row_stride_bytes, rowb, H, guide->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpy2DAsync(big + n, rowb, src->p, (size_t)src->row_stride_bytes, rowb, H, src->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = guided_filter_dev(ctx, big, big + n, big + 2 * n, (size_t)W, W, H, r, epsilon, subsampling, "guided_filter"))) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(dst->p, (size_t)dst->row_stride_bytes, big + 2 * n, rowb, rowb, H, dst->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
     if (!dst->on_device) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return ARTGPU_OK;
 }
@@ -3608,6 +3627,302 @@ int artgpu_texture_boost(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_texture_
 }
 
 // ---------------------------------------------------------------------------------------------
+// region masks: rtengine::generateMasks, parametric path (masks.cc:1037-1516)
+// ---------------------------------------------------------------------------------------------
+namespace {
+// one rtengine::guidedFilter call as artgpu_guided_filter will run it: decided in the plan, so that nothing starts before everything fits
+struct MkFilter { int on, r; };
+struct MkRegionPlan {
+    MkCurve curve[3];                 // offsets inside the region's own table
+    std::vector<double> tab;
+    float ldetail;
+    int blurred, r1, r2;
+    int cthr, cthr_neg, cw, ch; float cthr_thresh, cthr_blur;
+    float post_p; int smooth, smooth_r; float fillval;
+    int inverted, has_opacity; float opacity;
+};
+struct MkPlan {
+    int W, H, lab, want_L, want_ab, has_mask, need_ll, need_guide, ll_r_small, ll_r;
+    std::vector<MkRegionPlan> reg;
+};
+
+// ParametricMask's default curves (procparams.cc:1014-1053)
+const double MK_DEFAULT_HUE[9] = {1 /* FCT_MinMaxCPoints */, 0.166666667, 1., 0.35, 0.35, 0.8287775246, 1., 0.35, 0.35};
+const double MK_DEFAULT_CL[9] = {1, 0., 1., 0.35, 0.35, 1., 1., 0.35, 0.35};
+
+// L1068-1080: enabled, not empty, not FCT_Linear, not the default
+bool mk_curve_present(const artgpu_mask_params &m, const double *pts, int n, const double *dflt)
+{
+    if (!m.parametric_enabled || !pts || n <= 0 || pts[0] == 0 /* FCT_Linear */) return false;
+    return !(n == 9 && std::equal(pts, pts + 9, dflt));
+}
+int mk_filter_check(artgpu_ctx *ctx, int W, int H, int r, const char *who, const char *what)
+{
+    const int sub = gf_subsampling(W, H, r), w = W / sub, h = H / sub;
+    if (w < 1 || h < 1) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %s: a %dx%d image has a side shorter than the guided filter's subsampling %d", who, what, W, H, sub);
+    int rad = (int)(float(r) / sub);
+    { const int hi = ((w < h ? w : h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }
+    if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %s: box radius %d (radius %d / subsampling %d) is above the %d the blur kernels hold in LDS", who, what, rad, r, sub, HBLUR_MAX_RADIUS);
+    return ARTGPU_OK;
+}
+
+// everything generateMasks decides before its first pixel loop, and every reason not to run
+int mk_plan(artgpu_ctx *ctx, int W, int H, int mode, const double *ws, const artgpu_mask_params *masks, int n, int full_w, int full_h, double scale,
+            bool want_L, bool want_ab, const char *who, MkPlan *pl, artgpu_masks_info *info)
+{
+    if (!masks || n <= 0 || !(scale > 0.0) || (!want_L && !want_ab)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
+    if (mode != ARTGPU_MASKS_MODE_RGB && mode != ARTGPU_MASKS_MODE_LAB) {
+        if (mode == ARTGPU_MASKS_MODE_YUV || mode == ARTGPU_MASKS_MODE_XYZ) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: image mode %d (RGB and LAB are on the device path)", who, mode);
+        return fail(ctx, ARTGPU_EINVAL, "%s: image mode %d", who, mode);
+    }
+    if (mode == ARTGPU_MASKS_MODE_RGB && !ws) return fail(ctx, ARTGPU_EINVAL, "%s: RGB mode needs the working-space matrix", who);
+    if (W < ARTGPU_MASKS_MIN_SIZE || H < ARTGPU_MASKS_MIN_SIZE)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %dx%d is below %dx%d", who, W, H, ARTGPU_MASKS_MIN_SIZE, ARTGPU_MASKS_MIN_SIZE);
+    *pl = MkPlan{};
+    pl->W = W; pl->H = H; pl->lab = mode == ARTGPU_MASKS_MODE_LAB; pl->want_L = want_L; pl->want_ab = want_ab;
+    pl->reg.resize(n);
+    bool any_light = false;
+    int rc;
+    for (int i = 0; i < n; ++i) {
+        const artgpu_mask_params &m = masks[i];
+        MkRegionPlan &r = pl->reg[i];
+        if (m.deltae_enabled) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: the deltaE mask (cmsCIE2000DeltaE) is not on the device path", who, i);
+        if (m.drawn_enabled || m.external_enabled || m.linked_enabled) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: drawn, external and linked masks are not on the device path", who, i);
+        if (!m.curve_is_identity) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a mask curve other than the identity is not on the device path", who, i);
+        if (m.show_mask) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: show_mask is not on the device path", who, i);
+        if (m.nhue < 0 || m.nchromaticity < 0 || m.nlightness < 0 || m.posterization < 0) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: negative curve length or posterization", who, i);
+        if (m.area && (!plane_ok(m.area) || m.area->w != W || m.area->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: the area plane of region %d must be a %dx%d plane", who, i, W, H);
+        const double *pts[3] = {m.hue, m.chromaticity, m.lightness};
+        const int npts[3] = {m.nhue, m.nchromaticity, m.nlightness};
+        for (int k = 0; k < 3; ++k) {
+            r.curve[k] = MkCurve{0, 0};
+            if (!mk_curve_present(m, pts[k], npts[k], k == MK_HUE ? MK_DEFAULT_HUE : MK_DEFAULT_CL)) continue;
+            pl->has_mask = 1;
+            std::vector<double> x, y, sl;
+            if (flat_curve_polyline(pts[k], npts[k], k == MK_HUE, 1000 /* CURVES_MIN_POLY_POINTS */, 0.5, x, y, sl)) {
+                r.curve[k] = MkCurve{(int)r.tab.size(), (int)x.size()};
+                r.tab.insert(r.tab.end(), x.begin(), x.end());
+                r.tab.insert(r.tab.end(), y.begin(), y.end());
+                r.tab.insert(r.tab.end(), sl.begin(), sl.end());
+            } else {
+                r.curve[k] = MkCurve{0, -1};        // FCT_Empty: getVal returns identityValue
+            }
+            if (k == MK_LIGHT) {
+                any_light = true;
+                const float d = float(m.lightness_detail) / 100.f;
+                r.ldetail = d < 0.f ? 0.f : (d > 1.f ? 1.f : d);
+            }
+        }
+        if (r.tab.size() * sizeof(double) > (size_t)MK_LDS_BYTES) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: the curves' polylines (%zu bytes) do not fit LDS", who, i, r.tab.size() * 8);
+        if (m.opacity < 100) pl->has_mask = 1;
+    }
+    pl->need_ll = want_L && any_light;
+    if (pl->need_ll) {
+        const int m1 = full_w > W ? full_w : W, m2 = full_h > H ? full_h : H;
+        const float radius = (m1 > m2 ? m1 : m2) / 30.f;
+        pl->ll_r = (int)radius;
+        pl->ll_r_small = (int)(10.f / scale);
+        if (pl->ll_r_small > 0 && (rc = mk_filter_check(ctx, W, H, pl->ll_r_small, who, "lightness detail"))) return rc;
+        if ((rc = mk_filter_check(ctx, W, H, pl->ll_r, who, "lightness detail"))) return rc;
+    }
+    if (full_w < 0) full_w = W;
+    if (full_h < 0) full_h = H;
+    pl->need_guide = pl->has_mask;
+    for (int i = 0; i < n; ++i) {
+        const artgpu_mask_params &m = masks[i];
+        MkRegionPlan &r = pl->reg[i];
+        float blur = m.parametric_enabled ? (float)m.blur : 0.f;
+        if (pl->has_mask && blur > -10.f) {
+            blur = blur < 0.f ? -1.f / blur : 1.f + blur;
+            r.blurred = 1;
+            r.r1 = std::max(int(4 / scale * blur + 0.5), 1);
+            r.r2 = std::max(int(25 / scale * blur + 0.5), 1);
+            if (want_ab && (rc = mk_filter_check(ctx, W, H, r.r1, who, "ab mask blur"))) return rc;
+            if (want_L && (rc = mk_filter_check(ctx, W, H, r.r2, who, "L mask blur"))) return rc;
+        }
+        if (m.parametric_enabled && m.contrast_threshold != 0) {        // contrast_threshold_mask (L696-734)
+            float fscale = (float)scale;
+            const int d = std::max(W, H);
+            const float s = float(d) / 1920.f;
+            r.cthr = 1; r.cthr_neg = m.contrast_threshold < 0; r.cw = W; r.ch = H;
+            if (s > 1.f) { fscale *= s; r.cw = W / s; r.ch = H / s; }
+            const float s_scale = std::sqrt(fscale);
+            r.cthr_thresh = float(std::abs(m.contrast_threshold)) / 100.f * s_scale;
+            r.cthr_blur = std::max(m.blur, 2.0) / s_scale;
+            if (r.cw < 8 || r.ch < 8) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: the contrast threshold's %dx%d plane is below 8x8", who, i, r.cw, r.ch);
+            pl->need_guide = 1;
+        }
+        if (m.posterization) {                                          // mask_postprocess (L737-802)
+            static const float pp[] = {30.f, 20.f, 10.f, 5.f, 3.f, 2.f};
+            r.post_p = pp[std::min(std::max(m.posterization, 0), 6) - 1];
+            if (m.smoothing) {
+                const float radius_coeff = 10.f * (101.f - float(std::min(std::max(m.smoothing, 0), 100)));
+                const float radius = std::max(full_w, full_h) / radius_coeff;
+                r.smooth = 1; r.smooth_r = (int)radius;
+                const float l = 0.0f, h = 0.25f;
+                const float f0 = float(m.smoothing) / 100.f, f = f0 < 0.f ? 0.f : (f0 > 1.f ? 1.f : f0);
+                const float f2 = std::max(f - l, 0.f) / (h - l);
+                const float v = f < l ? 0.f : (f > h ? 1.f : (f2 < 0.5f ? 2.f * (f2 * f2) : 1.f - 2.f * ((1.f - f2) * (1.f - f2))));
+                r.fillval = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+                if ((rc = mk_filter_check(ctx, W, H, r.smooth_r, who, "mask smoothing"))) return rc;
+                pl->need_guide = 1;
+            }
+        }
+        r.inverted = m.inverted ? 1 : 0;
+        if (m.opacity < 100) {
+            const float b = float(m.opacity) / 100.f;
+            r.has_opacity = 1; r.opacity = b < 0.f ? 0.f : (b > 1.f ? 1.f : b);
+        }
+    }
+    if (info)
+        for (int i = 0; i < n; ++i) {
+            const MkRegionPlan &r = pl->reg[i];
+            info[i] = artgpu_masks_info{pl->has_mask, pl->need_ll, pl->need_ll ? pl->ll_r_small : 0, pl->need_ll ? pl->ll_r : 0, r.blurred, r.r1, r.r2,
+                                        r.cthr ? r.cw : 0, r.cthr ? r.ch : 0, r.smooth ? r.smooth_r : -1};
+        }
+    return ARTGPU_OK;
+}
+
+artgpu_plane mk_dev_plane(float *p, int w, int h) { return artgpu_plane{p, w, h, (int64_t)w * 4, 1}; }
+
+// generateMasks on a device image (rows of `stride` floats), enqueued on ctx->stream.  Lout / about: n contiguous W x H device planes each,
+// or nullptr.  `masks` is read for the area planes only.
+int masks_dev(artgpu_ctx *ctx, float *const img[3], size_t stride, const double *ws, const artgpu_mask_params *masks, const MkPlan &pl,
+              float *Lout, float *about)
+{
+    const int W = pl.W, H = pl.H, n = (int)pl.reg.size();
+    const size_t np = (size_t)W * H;
+    float *work, *cplanes = nullptr, *tabs = nullptr;
+    int rc;
+    // guide | LL | thr | one blend plane per region
+    if ((rc = pool_get(ctx, P_MK_WORK, (size_t)(3 + (pl.has_mask ? n : 0)) * np * 4, &work))) return rc;
+    float *guide = work, *LL = work + np, *thr = work + 2 * np, *blend = work + 3 * np;
+    MkImage im = {{img[0], img[1], img[2]}, stride, W, H, pl.lab};
+    float wp[9] = {};
+    if (!pl.lab) {
+        for (int k = 0; k < 9; ++k) wp[k] = (float)ws[k];
+        if ((rc = lab_tabs_dev(ctx, &tabs))) return rc;
+    }
+    if (pl.need_ll) {                                                   // L1113-1137
+        MkLLArgs a = {};
+        a.im = im; std::copy(wp, wp + 9, a.wp); a.cachef = tabs; a.cachefy = tabs ? tabs + 65536 : nullptr; a.guide = guide; a.LL = LL;
+        HIPCHK(ctx, launch_mk_ll(a, ctx->stream));
+        if (pl.ll_r_small > 0 && (rc = guided_filter_dev(ctx, guide, guide, guide, W, W, H, pl.ll_r_small, 0.01f, 0, "generate_masks"))) return rc;
+        if ((rc = guided_filter_dev(ctx, guide, LL, LL, W, W, H, pl.ll_r, 0.001f, 0, "generate_masks"))) return rc;
+    }
+    if (pl.need_guide) {                                                // L1171-1241, MK_GROUP regions (and MK_LDS_BYTES of polylines) per launch
+        MkFusedArgs a = {};
+        a.im = im; std::copy(wp, wp + 9, a.wp); a.cachef = tabs; a.cachefy = tabs ? tabs + 65536 : nullptr; a.guide = guide;
+        a.LL = pl.need_ll ? LL : nullptr;
+        if (!pl.has_mask) {
+            HIPCHK(ctx, launch_mk_fused(a, ctx->stream));
+        } else {
+            size_t total = 0;
+            for (const MkRegionPlan &r : pl.reg) total += r.tab.size();
+            float *tabf;
+            if ((rc = pool_get(ctx, P_MK_TAB, total * 8 + 64, &tabf))) return rc;
+            double *dtab = reinterpret_cast<double *>(tabf);
+            std::vector<double> host;
+            host.reserve(total);
+            for (const MkRegionPlan &r : pl.reg) host.insert(host.end(), r.tab.begin(), r.tab.end());
+            if (total && (rc = h2d_table(ctx, dtab, host.data(), total * 8))) return rc;
+            size_t base = 0;
+            for (int i0 = 0; i0 < n;) {
+                a.nreg = 0; a.tab = dtab + base; a.tab_len = 0;
+                while (i0 + a.nreg < n && a.nreg < MK_GROUP) {
+                    const MkRegionPlan &r = pl.reg[i0 + a.nreg];
+                    if (a.nreg && ((size_t)a.tab_len + r.tab.size()) * 8 > (size_t)MK_LDS_BYTES) break;
+                    for (int k = 0; k < 3; ++k) a.curve[a.nreg][k] = MkCurve{r.curve[k].off + a.tab_len, r.curve[k].n};
+                    a.ldetail[a.nreg] = r.ldetail;
+                    a.out[a.nreg] = blend + (size_t)(i0 + a.nreg) * np;
+                    a.tab_len += (int)r.tab.size();
+                    ++a.nreg;
+                }
+                HIPCHK(ctx, launch_mk_fused(a, ctx->stream));
+                base += a.tab_len; i0 += a.nreg;
+            }
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const MkRegionPlan &r = pl.reg[i];
+        const float *cthr = nullptr;
+        if (r.cthr) {                                                   // contrast_threshold_mask (L696-734)
+            const size_t ns = (size_t)r.cw * r.ch;
+            if ((rc = pool_get(ctx, P_MK_CTHR, (np + 3 * ns) * 4, &cplanes))) return rc;
+            float *full = cplanes, *src = cplanes + np, *dst = src + ns, *gtmp = dst + ns;
+            const bool rescaled = r.cw != W || r.ch != H;
+            if (rescaled) HIPCHK(ctx, launch_mk_rescale(guide, W, H, src, r.cw, r.ch, ctx->stream));
+            DualArgs da = {};
+            da.L = rescaled ? src : guide; da.blend = rescaled ? dst : full; da.w = r.cw; da.h = r.ch; da.threshold = r.cthr_thresh;
+            HIPCHK(ctx, launch_blend_mask_lum(da, 32768.f, ctx->stream));
+            if ((rc = gaussian_dev(ctx, da.blend, gtmp, r.cw, r.ch, (double)r.cthr_blur))) return rc;
+            if (rescaled) HIPCHK(ctx, launch_mk_rescale(dst, r.cw, r.ch, full, W, H, ctx->stream));
+            cthr = full;
+        }
+        const float *area = nullptr; size_t area_stride = 0;
+        if (masks[i].area) {
+            if (masks[i].area->on_device) { area = masks[i].area->p; area_stride = (size_t)(masks[i].area->row_stride_bytes / 4); }
+            else { float *ap; if ((rc = plane_to_pool(ctx, masks[i].area, P_MK_AREA, &ap))) return rc; area = ap; area_stride = W; }
+        }
+        for (int which = 0; which < 2; ++which) {                       // abmask first, like L1264-1269
+            float *out = which == 0 ? about : Lout;
+            if (!out) continue;
+            out += (size_t)i * np;
+            if (pl.has_mask) {
+                float *b = blend + (size_t)i * np;
+                if (r.blurred) {
+                    if ((rc = guided_filter_dev(ctx, guide, b, out, W, W, H, which == 0 ? r.r1 : r.r2, which == 0 ? 0.001f : 0.0001f, 0, "generate_masks"))) return rc;
+                } else {
+                    HIPCHK(ctx, hipMemcpyAsync(out, b, np * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                }
+            }
+            MkTailArgs t = {};
+            t.m = out; t.w = W; t.h = H; t.fill_one = !pl.has_mask; t.clamp = pl.has_mask;
+            t.cthr = cthr; t.cthr_neg = r.cthr_neg; t.area = area; t.area_stride = area_stride; t.post_p = r.post_p;
+            if (r.smooth) { t.thr_out = thr; t.fillval = r.fillval; }
+            else { t.inverted = r.inverted; t.has_opacity = r.has_opacity; t.opacity = r.opacity; }
+            HIPCHK(ctx, launch_mk_tail(t, ctx->stream));
+            if (r.smooth) {                                             // L772-799, then L1438-1467
+                if ((rc = guided_filter_dev(ctx, guide, out, out, W, W, H, r.smooth_r, 0.015f, 0, "generate_masks"))) return rc;
+                MkTailArgs t2 = {};
+                t2.m = out; t2.w = W; t2.h = H; t2.thr_in = thr; t2.inverted = r.inverted; t2.has_opacity = r.has_opacity; t2.opacity = r.opacity;
+                HIPCHK(ctx, launch_mk_tail(t2, ctx->stream));
+            }
+        }
+    }
+    return ARTGPU_OK;
+}
+} // namespace
+
+int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, const double ws[9], const artgpu_mask_params *masks, int n,
+                          int full_w, int full_h, double scale, artgpu_plane *Lmask, artgpu_plane *abmask, artgpu_masks_info *info)
+{
+    StageScope scope_(ctx, "generateMasks");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!img || !plane_ok(&img->r)) return fail(ctx, ARTGPU_EINVAL, "generate_masks: bad image");
+    const int W = img->r.w, H = img->r.h;
+    MkPlan pl;
+    int rc;
+    if ((rc = mk_plan(ctx, W, H, mode, ws, masks, n, full_w, full_h, scale, Lmask != nullptr, abmask != nullptr, "generate_masks", &pl, info))) return rc;
+    for (artgpu_plane *set : {Lmask, abmask})
+        for (int i = 0; set && i < n; ++i)
+            if (!plane_ok(&set[i]) || set[i].w != W || set[i].h != H) return fail(ctx, ARTGPU_EINVAL, "generate_masks: output plane %d must be a %dx%d plane", i, W, H);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevRGB d;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "generate_masks"))) return rc;
+    const size_t np = (size_t)W * H;
+    float *outs;
+    if ((rc = pool_get(ctx, P_MK_OUT, (size_t)n * np * 4 * ((Lmask ? 1 : 0) + (abmask ? 1 : 0)), &outs))) return rc;
+    float *Lout = Lmask ? outs : nullptr, *about = abmask ? outs + (Lmask ? (size_t)n * np : 0) : nullptr;
+    if ((rc = masks_dev(ctx, d.p, d.stride, ws, masks, pl, Lout, about))) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (Lmask && (rc = pool_to_plane(ctx, Lout + (size_t)i * np, &Lmask[i]))) return rc;
+        if (abmask && (rc = pool_to_plane(ctx, about + (size_t)i * np, &abmask[i]))) return rc;
+    }
+    return ARTGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // capture sharpening: ImProcFunctions::doSharpening, method "rld"
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -3917,6 +4232,33 @@ static int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, in
 static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca);
 } // namespace
 
+int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *lc, int nlc, const artgpu_mask_params *tb, int ntb)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (nlc < 0 || ntb < 0 || (nlc > 0 && !lc) || (ntb > 0 && !tb)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_masks: bad arguments");
+    const auto own = [](artgpu_ctx::PipeMasks &o, const artgpu_mask_params *src, int n) -> const artgpu_mask_params * {
+        o.m.assign(src, src + n);
+        o.curves.assign((size_t)3 * n, std::vector<double>());
+        o.areas.assign(n, artgpu_plane{});
+        for (int i = 0; i < n; ++i) {
+            artgpu_mask_params &m = o.m[i];
+            const double **pts[3] = {&m.hue, &m.chromaticity, &m.lightness};
+            int32_t *cnt[3] = {&m.nhue, &m.nchromaticity, &m.nlightness};
+            for (int k = 0; k < 3; ++k) {
+                if (*cnt[k] < 0) *cnt[k] = 0;
+                if (*pts[k] && *cnt[k] > 0) o.curves[3 * i + k].assign(*pts[k], *pts[k] + *cnt[k]);
+                *pts[k] = o.curves[3 * i + k].empty() ? nullptr : o.curves[3 * i + k].data();
+                if (!*pts[k]) *cnt[k] = 0;
+            }
+            if (m.area) { o.areas[i] = *m.area; m.area = &o.areas[i]; }
+        }
+        return n > 0 ? o.m.data() : nullptr;
+    };
+    ctx->pipe_lc = own(ctx->pipe_lc_own, lc, nlc); ctx->pipe_nlc = nlc;
+    ctx->pipe_tb = own(ctx->pipe_tb_own, tb, ntb); ctx->pipe_ntb = ntb;
+    return ARTGPU_OK;
+}
+
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *p, artgpu_rgb *out)
 {
     return pipeline_run_impl(ctx, raw, p, out, true);
@@ -3933,8 +4275,46 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
     if (out->r.w != W - 2 * b || out->r.h != H - 2 * b) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", W - 2 * b, H - 2 * b);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
-    if (p->local_contrast_enabled && p->local_contrast_nregions > 0 &&
-        (rc = local_contrast_check(ctx, W - 2 * b, H - 2 * b, p->local_contrast_regions, p->local_contrast_nregions, p->scale > 0 ? p->scale : 1.0, "pipeline_run(local contrast)")))
+    // regions whose blend planes the pipe generates itself (artgpu_set_pipeline_masks): the regions' own `mask` pointers are
+    // not read, the planes of artgpu_generate_masks take their place; what it does not support fails the frame here
+    const bool lc_on = p->local_contrast_enabled && p->local_contrast_nregions > 0;
+    const bool lc_gen = lc_on && ctx->pipe_lc, tb_gen = p->texture_boost_enabled && p->texture_boost_nregions > 0 && ctx->pipe_tb;
+    if ((lc_gen && ctx->pipe_nlc != p->local_contrast_nregions) || (tb_gen && ctx->pipe_ntb != p->texture_boost_nregions))
+        return fail(ctx, ARTGPU_EINVAL, "pipeline_run: artgpu_set_pipeline_masks holds %d / %d entries, the frame has %d / %d regions", ctx->pipe_nlc, ctx->pipe_ntb,
+                    p->local_contrast_nregions, p->texture_boost_nregions);
+    std::vector<artgpu_local_contrast_region> lc_regs;
+    std::vector<artgpu_texture_boost_region> tb_regs;
+    MkPlan lc_mk, tb_mk;
+    if (lc_gen) {
+        if (!p->local_contrast_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(local contrast): bad region list");
+        lc_regs.assign(p->local_contrast_regions, p->local_contrast_regions + p->local_contrast_nregions);
+        for (auto &r : lc_regs) r.mask = nullptr;
+        if ((rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_LAB, nullptr, ctx->pipe_lc, p->local_contrast_nregions, W - 2 * b, H - 2 * b,
+                          p->scale > 0 ? p->scale : 1.0, true, false, "pipeline_run(local contrast masks)", &lc_mk, nullptr)))
+            return rc;
+    }
+    if (tb_gen) {
+        if (!p->texture_boost_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(texture boost): bad region list");
+        tb_regs.assign(p->texture_boost_regions, p->texture_boost_regions + p->texture_boost_nregions);
+        for (auto &r : tb_regs) r.mask = nullptr;
+        if ((rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_tb, p->texture_boost_nregions, W - 2 * b, H - 2 * b,
+                          p->scale > 0 ? p->scale : 1.0, true, false, "pipeline_run(texture boost masks)", &tb_mk, nullptr)))
+            return rc;
+    }
+    const artgpu_local_contrast_region *lc_regions = lc_gen ? lc_regs.data() : p->local_contrast_regions;
+    const artgpu_texture_boost_region *tb_regions = tb_gen ? tb_regs.data() : p->texture_boost_regions;
+    std::vector<artgpu_plane> gen_planes;
+    // generateMasks(rgb, ., masks, 0, 0, full size, scale, ., -1, &mask, nullptr) on the device image, the L planes handed to the regions
+    auto generate = [&](float *const planes[3], size_t stride, int w, int h, const artgpu_mask_params *masks, const MkPlan &mk, int n, auto &regs) -> int {
+        float *mo;
+        int rc2;
+        if ((rc2 = pool_get(ctx, P_MK_OUT, (size_t)n * w * h * 4, &mo)) || (rc2 = masks_dev(ctx, planes, stride, p->ws, masks, mk, mo, nullptr))) return rc2;
+        gen_planes.resize(n);
+        for (int i = 0; i < n; ++i) { gen_planes[i] = mk_dev_plane(mo + (size_t)i * w * h, w, h); regs[i].mask = &gen_planes[i]; }
+        return ARTGPU_OK;
+    };
+    if (lc_on &&
+        (rc = local_contrast_check(ctx, W - 2 * b, H - 2 * b, lc_regions, p->local_contrast_nregions, p->scale > 0 ? p->scale : 1.0, "pipeline_run(local contrast)")))
         return rc;
     DehazePlan dhp;
     if (p->dehaze_enabled && (rc = dehaze_check(ctx, W - 2 * b, H - 2 * b, &p->dehaze, p->ws, p->scale > 0 ? p->scale : 1.0, "pipeline_run(dehaze)", &dhp))) return rc;
@@ -3950,7 +4330,7 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
     }
     std::vector<TbPlan> tbp;
     if (p->texture_boost_enabled &&
-        (rc = tb_check(ctx, W - 2 * b, H - 2 * b, p->texture_boost_regions, p->texture_boost_nregions, p->ws, p->scale > 0 ? p->scale : 1.0, 1, "pipeline_run(texture boost)", &tbp)))
+        (rc = tb_check(ctx, W - 2 * b, H - 2 * b, tb_regions, p->texture_boost_nregions, p->ws, p->scale > 0 ? p->scale : 1.0, 1, "pipeline_run(texture boost)", &tbp)))
         return rc;
     // RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy: the caller's raw is never written
     artgpu_plane rawc = *raw_in;
@@ -4040,8 +4420,9 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
         if ((rc = sharpen_dev(ctx, d.p, d.stride, d.w, d.h, &shpar, p->ws, shp, nullptr))) return rc;
     }
     // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
+    if (tb_gen && (rc = generate(d.p, d.stride, d.w, d.h, ctx->pipe_tb, tb_mk, p->texture_boost_nregions, tb_regs))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     if (p->texture_boost_enabled &&
-        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, p->texture_boost_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr)))
+        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, tb_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr)))
         return rc;
     if (p->tone_enabled) {
         if (p->tone_mode == ARTGPU_TONE_NEUTRAL) {
@@ -4053,10 +4434,12 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
         }
         if (rc) return rc;
     }
-    if (p->local_contrast_enabled && p->local_contrast_nregions > 0) {
-        // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), the regions on the L plane (Imagefloat::g), back to RGB
+    if (lc_on) {
+        // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
+        // L plane (Imagefloat::g), back to RGB
         if ((rc = artgpu_rgb_to_lab(ctx, &img, p->ws)) ||
-            (rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, p->local_contrast_regions, p->local_contrast_nregions, nullptr)) ||
+            (lc_gen && (rc = generate(d.p, d.stride, d.w, d.h, ctx->pipe_lc, lc_mk, p->local_contrast_nregions, lc_regs))) ||
+            (rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, lc_regions, p->local_contrast_nregions, nullptr)) ||
             (rc = artgpu_lab_to_rgb(ctx, &img, p->iws)))
             return rc;
     }
@@ -4116,6 +4499,7 @@ int batch_prepare_lanes(artgpu_ctx *ctx, int L)
         peer->opt_rcd_rows = ctx->opt_rcd_rows; peer->opt_roctx = ctx->opt_roctx; peer->opt_lut_lds = ctx->opt_lut_lds; peer->opt_sharpen_fused = ctx->opt_sharpen_fused; peer->opt_dn_streams = ctx->opt_dn_streams; peer->opt_dn_fused = ctx->opt_dn_fused; peer->opt_dn_detail_plain = ctx->opt_dn_detail_plain;
         peer->opt_dn_wait_ms = ctx->opt_dn_wait_ms; peer->opt_dn_debug_stall = ctx->opt_dn_debug_stall; peer->opt_io_direct = ctx->opt_io_direct;
         peer->progress_fn = ctx->progress_fn; peer->progress_user = ctx->progress_user;
+        peer->pipe_lc = ctx->pipe_lc; peer->pipe_nlc = ctx->pipe_nlc; peer->pipe_tb = ctx->pipe_tb; peer->pipe_ntb = ctx->pipe_ntb;
         peer->frames_in_flight = L;
     }
     ctx->frames_in_flight = L;

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "devmath.h"
 #include "devsleef.h"
+#include "labdev.h"
 #include "kernels.h"
 
 namespace artgpu {
@@ -64,26 +65,10 @@ __device__ __forceinline__ float lutf_noclip(const float *__restrict__ data, flo
     const float p1 = data[idx], p2 = data[idx + 1] - p1;
     return p1 + p2 * diff;
 }
-// Color::computeXYZ2Lab (color.cc:1247-1259)
-__device__ __forceinline__ float xyz2lab_f(const float *__restrict__ cachef, float f)
-{
-    if (f != f) return f;
-    if (f < 0.f) return (float)(327.68 * (((24389.0 / 27.0) * (double)f / (double)65535.f + 16.0) / 116.0));
-    if (f > 65535.f) return 327.68f * xcbrtf_s(f / 65535.f);
-    return lutf_lookup<false>(cachef, 65536, f);
-}
-// Color::rgb2lab with a float matrix = rgbxyz + XYZ2Lab (color.h:630-636, color.cc:1262-1275,1382-1397)
+// Color::computeXYZ2Lab and Color::rgb2lab with a float matrix: labdev.h
 __device__ __forceinline__ void rgb2lab_dev(const DnPixArgs &a, float R, float G, float B, float &l, float &la, float &lb)
 {
-    const float X = a.wpi[0] * R + a.wpi[1] * G + a.wpi[2] * B, Y = a.wpi[3] * R + a.wpi[4] * G + a.wpi[5] * B, Z = a.wpi[6] * R + a.wpi[7] * G + a.wpi[8] * B;
-    const float x = X / 0.9642f, z = Z / 0.8249f, y = Y;
-    const float fx = xyz2lab_f(a.cachef, x), fy = xyz2lab_f(a.cachef, y), fz = xyz2lab_f(a.cachef, z);
-    if (y != y) l = y;
-    else if (y < 0.f) l = (float)(327.68 * ((24389.0 / 27.0) * (double)y / (double)65535.f));
-    else if (y > 65535.f) l = 327.68f * (116.f * xcbrtf_s(y / 65535.f) - 16.f);
-    else l = lutf_lookup<false>(a.cachefy, 65536, y);
-    la = 500.0f * (fx - fy);
-    lb = 200.0f * (fy - fz);
+    rgb2lab_px(a.wpi, a.cachef, a.cachefy, R, G, B, l, la, lb);
 }
 // Color::lab2rgb = Lab2XYZ + xyz2rgb (color.h:638-644,767-770, color.cc:1203-1214)
 __device__ __forceinline__ float f2xyz_f(float f)

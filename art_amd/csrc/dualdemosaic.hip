@@ -15,6 +15,7 @@
 #include "devmath.h"
 #include "devsleef.h"
 #include "kernels.h"
+#include "masks.h"
 
 namespace artgpu {
 namespace {
@@ -56,10 +57,10 @@ __device__ __forceinline__ float blend_factor(float val, float thr, bool vec)
     return 1.f / (1.f + (vec ? xexpf_v(e) : xexpf_s(e)));
 }
 // rt_algo.cc:436-461: interior of the mask
-__global__ void __launch_bounds__(256) blend_contrast_kernel(DualArgs a)
+__global__ void __launch_bounds__(256) blend_contrast_kernel(DualArgs a, float lum_factor)
 {
     const int W = a.w, H = a.h;
-    const float scale = 0.0625f / 327.68f * 1.f;
+    const float scale = 0.0625f / 327.68f * lum_factor;
     const int nvec = W - 5 > 2 ? 4 * ((W - 7 + 3) / 4) : 0;      // columns [2, 2 + nvec) are covered by the 4-wide loop
     FOR_IMAGE_XY(j, i, W, H) {
         if (j < 2 || j >= H - 2 || i < 2 || i >= W - 2) continue;
@@ -184,17 +185,19 @@ hipError_t launch_rgb2l(const DualArgs &a, hipStream_t s)
     hipLaunchKernelGGL(rgb2l_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_blend_mask(const DualArgs &a, hipStream_t s)
+// buildBlendMask(L, blend, w, h, threshold, 1.f, false, ., luminance_factor) ahead of its gaussian (rt_algo.cc:416-478)
+hipError_t launch_blend_mask_lum(const DualArgs &a, float lum_factor, hipStream_t s)
 {
     if (a.threshold == 0.f) {
         hipLaunchKernelGGL(blend_fill_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a, 1.f);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(blend_contrast_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(blend_contrast_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a, lum_factor);
     hipLaunchKernelGGL(blend_frame_kernel, dim3((a.w + 255) / 256), dim3(256), 0, s, a, 0);
     hipLaunchKernelGGL(blend_frame_kernel, dim3((a.h + 255) / 256), dim3(256), 0, s, a, 1);
     return hipGetLastError();
 }
+hipError_t launch_blend_mask(const DualArgs &a, hipStream_t s) { return launch_blend_mask_lum(a, 1.f, s); }
 hipError_t launch_tile_stats(const DualArgs &a, int nH, int nW, int y0, int x0, int step, int ts, float *var, hipStream_t s)
 {
     const long long threads = (long long)nH * nW * 4;

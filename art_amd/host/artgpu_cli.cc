@@ -15,8 +15,11 @@
 //              [--sharpen contrast[,radius|auto[,amount[,cornerboost[,latitude]]]]]   (ImProcFunctions::sharpening in STAGE_2, method rld; `auto`
 //                                                      (the default) takes the radius from RawImageSource::getDeconvAutoRadius as simpleprocess.cc:274-278 does)
 //              [--texture-boost strength,threshold,iterations]   (ImProcFunctions::textureBoost, the first step of STAGE_3: one region, no mask)
+//              [--texture-boost-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]]   (a parametric mask on that region, generated on the device by
+//                                                      generateMasks: a lightness curve that is 1 between lo and hi and 0 outside, ParametricMask's
+//                                                      blur, lightnessDetail, contrastThreshold and Mask::opacity)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--texture-boost ..] [--out prefix]
+//              [--texture-boost ..] [--texture-boost-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <chrono>
@@ -73,6 +76,9 @@ int main(int argc, char **argv)
     bool tb_enable = false;                                        // TextureBoostParams::enabled, one region
     double tb_strength = 0.0, tb_threshold = 0.2;
     int tb_iterations = 1;
+    bool tbm_enable = false;                                       // a parametric Mask on the texture-boost region
+    double tbm_lo = 0.0, tbm_hi = 1.0, tbm_blur = 0.0;
+    int tbm_detail = 0, tbm_threshold = 0, tbm_opacity = 100;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -141,8 +147,18 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%lf,%lf,%d", &tb_strength, &tb_threshold, &tb_iterations) != 3) { std::fprintf(stderr, "--texture-boost strength,threshold,iterations\n"); return 2; }
             tb_enable = true;
         }
+        else if (a == "--texture-boost-mask") {
+            if (std::sscanf(next(), "%lf,%lf,%lf,%d,%d,%d", &tbm_lo, &tbm_hi, &tbm_blur, &tbm_detail, &tbm_threshold, &tbm_opacity) < 2) {
+                std::fprintf(stderr, "--texture-boost-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]\n"); return 2;
+            }
+            tbm_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    ProcParams::Mask tb_mask;
+    tb_mask.parametricMask.enabled = true; tb_mask.parametricMask.blur = tbm_blur; tb_mask.parametricMask.lightnessDetail = tbm_detail;
+    tb_mask.parametricMask.contrastThreshold = tbm_threshold; tb_mask.opacity = tbm_opacity;
+    tb_mask.parametricMask.lightness = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.0, 0.35, 0.35, tbm_lo, 1.0, 0.35, 0.35, tbm_hi, 1.0, 0.35, 0.35, 1.0, 0.0, 0.35, 0.35};
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
     if (!batch.empty()) {
         try {
@@ -159,6 +175,7 @@ int main(int argc, char **argv)
             params.sharpening.enabled = sh_enable; params.sharpening.contrast = sh_contrast; params.sharpening.deconvradius = sh_radius; params.sharpening.deconvAutoRadius = sh_auto;
             params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
             params.textureBoost.enabled = tb_enable; params.textureBoost.regions = {{tb_strength, tb_threshold, tb_iterations}};
+        if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -233,6 +250,7 @@ int main(int argc, char **argv)
         params.sharpening.enabled = sh_enable; params.sharpening.contrast = sh_contrast; params.sharpening.deconvradius = sh_radius; params.sharpening.deconvAutoRadius = sh_auto;
         params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
         params.textureBoost.enabled = tb_enable; params.textureBoost.regions = {{tb_strength, tb_threshold, tb_iterations}};
+        if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;

@@ -15,6 +15,7 @@
 #include <stdexcept>
 #include <string>
 #include <functional>
+#include <memory>
 #include <vector>
 #include "../../include/artgpu.h"
 
@@ -121,15 +122,55 @@ struct ProcParams {
                                         sharpening.deconvradius, sharpening.deconvCornerBoost, sharpening.deconvCornerLatitude, offset_x, offset_y,
                                         full_width, full_height, 0};
     }
-    // LocalContrastParams (procparams.cc:1700-1760): regions {contrast, curve as FlatCurve control points}; masks[i].enabled and the blend
-    // plane generateMasks makes of masks[i] (host code of the application; nullptr = all ones), one per region
+    // rtengine::procparams::Mask (procparams.cc:1014-1053, 1122-1137) as generateMasks' parametric path reads it.  `area` is
+    // generate_area_mask's finished plane (rasterising the shapes is host code of the application).  deltaE, drawn, external and linked masks,
+    // a mask curve other than the identity: flags only, artgpu_generate_masks answers them with ARTGPU_EUNSUPPORTED
+    struct Mask {
+        bool enabled = true, inverted = false;
+        struct {
+            bool enabled = false; double blur = 0;
+            std::vector<double> hue = {1 /*FCT_MinMaxCPoints*/, 0.166666667, 1., 0.35, 0.35, 0.8287775246, 1., 0.35, 0.35};
+            std::vector<double> chromaticity = {1, 0., 1., 0.35, 0.35, 1., 1., 0.35, 0.35}, lightness = {1, 0., 1., 0.35, 0.35, 1., 1., 0.35, 0.35};
+            int lightnessDetail = 0, contrastThreshold = 0;
+        } parametricMask;
+        const DevicePlane *area = nullptr;
+        bool deltaEEnabled = false, drawnEnabled = false, externalEnabled = false, linkedEnabled = false, curveIsIdentity = true;
+        int posterization = 0, smoothing = 0, opacity = 100;
+        // `areaView` keeps the view `area` points to
+        artgpu_mask_params params(artgpu_plane &areaView, bool show = false) const
+        {
+            const auto &pm = parametricMask;
+            artgpu_mask_params m = {};
+            m.parametric_enabled = pm.enabled ? 1 : 0; m.lightness_detail = pm.lightnessDetail;
+            m.hue = pm.hue.data(); m.chromaticity = pm.chromaticity.data(); m.lightness = pm.lightness.data();
+            m.nhue = (int32_t)pm.hue.size(); m.nchromaticity = (int32_t)pm.chromaticity.size(); m.nlightness = (int32_t)pm.lightness.size();
+            m.contrast_threshold = pm.contrastThreshold; m.blur = pm.blur;
+            if (area) { areaView = area->view(); m.area = &areaView; }
+            m.posterization = posterization; m.smoothing = smoothing; m.inverted = inverted ? 1 : 0; m.opacity = opacity;
+            m.deltae_enabled = deltaEEnabled ? 1 : 0; m.drawn_enabled = drawnEnabled ? 1 : 0; m.external_enabled = externalEnabled ? 1 : 0;
+            m.linked_enabled = linkedEnabled ? 1 : 0; m.curve_is_identity = curveIsIdentity ? 1 : 0; m.show_mask = show ? 1 : 0;
+            return m;
+        }
+    };
+    // the artgpu_mask_params of a list of Masks; `areas` keeps the views they point to
+    static std::vector<artgpu_mask_params> maskParams(const std::vector<const Mask *> &masks, std::vector<artgpu_plane> &areas, int show_mask_idx = -1)
+    {
+        static const Mask dflt;
+        areas.assign(masks.size(), artgpu_plane{});
+        std::vector<artgpu_mask_params> out;
+        for (size_t k = 0; k < masks.size(); ++k) out.push_back((masks[k] ? masks[k] : &dflt)->params(areas[k], (int)k == show_mask_idx));
+        return out;
+    }
+    // LocalContrastParams (procparams.cc:1700-1760): regions {contrast, curve as FlatCurve control points}; masks[i].enabled and either the
+    // blend plane the application's generateMasks made of masks[i] (`blend`; nullptr = all ones) or the Mask itself (`mask`: the plane is
+    // generated on the device, ImProcFunctions::generateMasks below), one per region
     struct LocalContrastRegion { double contrast = 0; std::vector<double> curve = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.5, 0.0, 0.0, 1.0, 0.5, 0.0, 0.0}; };
-    struct LocalContrastMask { bool enabled = true; const DevicePlane *blend = nullptr; };
+    struct LocalContrastMask { bool enabled = true; const DevicePlane *blend = nullptr; const Mask *mask = nullptr; };
     struct { bool enabled = false; std::vector<LocalContrastRegion> regions; std::vector<LocalContrastMask> masks; } localContrast;
     // TextureBoostParams (procparams.cc:1950-2022): regions {strength, detailThreshold, iterations}; masks[i].enabled and the blend plane
     // generateMasks makes of masks[i] (host code of the application; nullptr = all ones), one per region
     struct TextureBoostRegion { double strength = 0; double detailThreshold = 0.2; int iterations = 1; };
-    struct TextureBoostMask { bool enabled = true; const DevicePlane *blend = nullptr; };
+    struct TextureBoostMask { bool enabled = true; const DevicePlane *blend = nullptr; const Mask *mask = nullptr; };
     struct { bool enabled = false; std::vector<TextureBoostRegion> regions = {TextureBoostRegion()}; std::vector<TextureBoostMask> masks; } textureBoost;
     // the enabled regions as the library takes them; `blends` keeps the mask views the regions point to
     std::vector<artgpu_texture_boost_region> textureBoostRegions(std::vector<artgpu_plane> &blends) const
@@ -144,6 +185,18 @@ struct ProcParams {
             regions.push_back(reg);
         }
         return regions;
+    }
+    // the Masks of the enabled regions (nullptr: the region carries none), and whether any region carries one
+    template <class Tool> static bool regionMasks(const Tool &p, std::vector<const Mask *> &masks)
+    {
+        bool any = false;
+        masks.clear();
+        for (size_t k = 0; k < p.regions.size(); ++k) {
+            if (k < p.masks.size() && !p.masks[k].enabled) continue;
+            masks.push_back(k < p.masks.size() ? p.masks[k].mask : nullptr);
+            any = any || masks.back();
+        }
+        return any;
     }
     struct { bool enabled = false; std::vector<float> rlut, glut, blut; } rgbCurves;                                             // RGBCurvesParams, as outCurve LUTs
     struct { bool enabled = true; int curveMode = ARTGPU_TONE_STD; std::vector<float> lut; float whitePoint = 1.f; bool basecurveLinear = true; } toneCurve;
@@ -267,13 +320,45 @@ public:
         return false;
     }
     Pipeline cur_pipeline = Pipeline::OUTPUT;
+    // rtengine::generateMasks (masks.cc:1037-1516) over artgpu_generate_masks: the reference's arguments but the tool name and the linked-mask
+    // manager (linked masks are not on the device path), the image's mode as ARTGPU_MASKS_MODE_*, and device planes for the results.  A null
+    // entry of `masks` stands for a default Mask.  offset_x / offset_y place the shapes of the area mask, which the caller rasterised.  Returns
+    // false where the reference does (a shown mask); what the library does not support throws through Context::check
+    bool generateMasks(Imagefloat *rgb, int mode, const std::vector<const ProcParams::Mask *> &masks, int offset_x, int offset_y, int full_width, int full_height,
+                       double scale_, int show_mask_idx, std::vector<std::unique_ptr<DevicePlane>> *Lmask, std::vector<std::unique_ptr<DevicePlane>> *abmask)
+    {
+        (void)offset_x; (void)offset_y;
+        std::vector<artgpu_plane> areas;
+        const std::vector<artgpu_mask_params> mp = ProcParams::maskParams(masks, areas, show_mask_idx);
+        std::vector<artgpu_plane> lv, av;
+        for (auto *set : {Lmask, abmask}) {
+            if (!set) continue;
+            set->clear();
+            for (size_t k = 0; k < masks.size(); ++k) {
+                set->emplace_back(new DevicePlane(rgb->getWidth(), rgb->getHeight()));
+                (set == Lmask ? lv : av).push_back(set->back()->view());
+            }
+        }
+        artgpu_rgb i = rgb->view();
+        ctx.check(artgpu_generate_masks(ctx.get(), &i, mode, params->workingSpace, mp.data(), (int)mp.size(), full_width, full_height, scale_,
+                                        Lmask ? lv.data() : nullptr, abmask ? av.data() : nullptr, nullptr));
+        return true;
+    }
     // ImProcFunctions::textureBoost (iptextureboost.cc:183-248): setMode(YUV), every enabled region with strength != 0 through texture_boost and
     // the mask blend on the Y plane; this mirror has no mode tracking and converts back at once (Imagefloat::yuv_to_rgb)
     bool textureBoost(Imagefloat *img)
     {
         if (!params->textureBoost.enabled) return false;
         std::vector<artgpu_plane> blends;
-        const std::vector<artgpu_texture_boost_region> regions = params->textureBoostRegions(blends);
+        std::vector<artgpu_texture_boost_region> regions = params->textureBoostRegions(blends);
+        std::vector<const ProcParams::Mask *> masks;
+        std::vector<std::unique_ptr<DevicePlane>> generated;
+        std::vector<artgpu_plane> views(regions.size());
+        if (ProcParams::regionMasks(params->textureBoost, masks)) {                      // iptextureboost.cc:210, on the RGB image
+            generateMasks(img, ARTGPU_MASKS_MODE_RGB, masks, 0, 0, -1, -1, scale, -1, &generated, nullptr);
+            for (size_t k = 0; k < regions.size(); ++k)
+                if (masks[k]) { views[k] = generated[k]->view(); regions[k].mask = &views[k]; }
+        }
         artgpu_rgb i = img->view();
         ctx.check(artgpu_texture_boost(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, scale,
                                        (scale == 1 || cur_pipeline == Pipeline::OUTPUT) ? 1 : 0, 1, nullptr));
@@ -367,6 +452,14 @@ public:
         }
         artgpu_rgb i = img->view();
         ctx.check(artgpu_rgb_to_lab(ctx.get(), &i, params->workingSpace));
+        std::vector<const ProcParams::Mask *> masks;
+        std::vector<std::unique_ptr<DevicePlane>> generated;
+        std::vector<artgpu_plane> views(regions.size());
+        if (ProcParams::regionMasks(p, masks)) {                                        // iplocalcontrast.cc:454, on the LAB image
+            generateMasks(img, ARTGPU_MASKS_MODE_LAB, masks, 0, 0, -1, -1, scale, -1, &generated, nullptr);
+            for (size_t k = 0; k < regions.size(); ++k)
+                if (masks[k]) { views[k] = generated[k]->view(); regions[k].mask = &views[k]; }
+        }
         ctx.check(artgpu_local_contrast(ctx.get(), &i.g, regions.data(), (int)regions.size(), scale, nullptr));
         ctx.check(artgpu_lab_to_rgb(ctx.get(), &i, params->workingSpaceInverse));
         return false;
@@ -503,6 +596,12 @@ public:
         std::vector<artgpu_plane> tb_blends;
         const std::vector<artgpu_texture_boost_region> tb_regions = p.textureBoostRegions(tb_blends);
         pp.texture_boost_enabled = p.textureBoost.enabled ? 1 : 0; pp.texture_boost_nregions = (int32_t)tb_regions.size(); pp.texture_boost_regions = tb_regions.data();
+        // regions that carry Masks: the pipe generates the tool's planes itself (a region without one gets a default Mask)
+        std::vector<const ProcParams::Mask *> tb_masks;
+        std::vector<artgpu_plane> tb_areas;
+        std::vector<artgpu_mask_params> tb_mp;
+        if (ProcParams::regionMasks(p.textureBoost, tb_masks)) tb_mp = ProcParams::maskParams(tb_masks, tb_areas);
+        ctx.check(artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, tb_mp.empty() ? nullptr : tb_mp.data(), (int)tb_mp.size()));
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -515,6 +614,7 @@ public:
         }
         ctx.check(artgpu_set_batch_lanes(ctx.get(), lanes));
         const int rc = artgpu_batch_run_io(ctx.get(), (int)jobs.size(), in.data(), &pp, out.data());
+        (void)artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, nullptr, 0);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

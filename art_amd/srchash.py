@@ -13,6 +13,7 @@ KERNEL_SOURCES = {
     "xtrans_tiles_kernel": ["xtrans.hip"],
     "nlm_group_kernel": ["nlm_sweep.hip"],
     "shrink_blur_kernel": ["shrinkblur.hip"],
+    "mk_fused_kernel": ["masks.hip", "masks.h", "labdev.h"],
 }
 
 

@@ -734,6 +734,78 @@ int artgpu_texture_boost_plane(artgpu_ctx *ctx, artgpu_plane *Y, const artgpu_te
 int artgpu_texture_boost(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_texture_boost_region *regions, int nregions, const double ws[9],
                          double scale, int high_detail, int to_rgb, artgpu_texture_boost_info *info /* may be NULL */);
 
+/* Region masks: rtengine::generateMasks (rtengine/masks.cc:1037-1516), the parametric path -- the blend planes ImProcFunctions::localContrast,
+ * textureBoost, colorCorrection and guidedSmoothing multiply their regions with.  `img` is the image the tool hands over, in RGB mode
+ * (Color::rgb2lab with `ws`, L617) or in LAB mode (L = g, a = r, b = b, L626-630; `ws` is not read); YUV and XYZ: ARTGPU_EUNSUPPORTED.
+ * `masks` holds one entry per region (the caller passes the regions generateMasks would treat as needed; `Mask::enabled` is the tool's
+ * test, as for the tools' region lists).  Lmask / abmask: n planes of the image's size each, host or device, any row stride; NULL = not
+ * asked for (localContrast and textureBoost ask for Lmask only).  At least one of the two.  Per pixel and region, in the reference's order:
+ *   - a curve counts as present when parametric_enabled and it is not empty, not FCT_Linear and not Mask's default (L1068-1080, defaults of
+ *     procparams.cc:1014-1053 below); has_mask = some region has a curve or opacity < 100 (L1059-1084: global over the regions);
+ *   - lightness-detail plane (L1113-1137), built only when Lmask is asked for and some region has a lightness curve (the reference builds it
+ *     whenever Lmask is asked for and reads it under the same condition only): guide = L / 32768.f, LL = round(l * 40.f) / 40.f,
+ *     guidedFilter(guide, guide, guide, int(10.f / scale), 0.01f) when that radius is > 0, guidedFilter(guide, LL, LL,
+ *     int(max(max(full_w, W), max(full_h, H)) / 30.f), 0.001f);
+ *   - the fused pass (L1171-1241): l /= 32768.f, a /= 42000.f, b /= 42000.f, guide = LIM01(l), c = xlin2log(sqrtf(a * a + b * b) / 327.68f *
+ *     c_factor, 50.f), h = xlin2log(wrap(float(huelab_to_huehsv2(xatan2f(b, a))) + 1.f / 6.f), 3.f), blend = float(1.f * hue(h) * chroma(c) *
+ *     lightness(Lmask ? intp(LIM01(lightness_detail / 100.f), LL, l) : l)) -- a double product of FlatCurve::getVal values, 1.f for an absent
+ *     curve (FlatCurve(points, periodic = hue only), 1000 polygon points).  The 4-wide Color::Lab2Lch the reference's SSE2 build takes below
+ *     4 * (W / 4) is the scalar one's arithmetic lane by lane (sleefsseavx.h:1168-1208 selects where sleef.h:1155-1188 branches);
+ *   - without has_mask every plane is 1.f (L1296-1308); with it EVERY region, one without curves included, is blurred when blur > -10.f
+ *     (blur = blur < 0 ? -1.f / blur : 1.f + blur; blur = 0 while !parametric_enabled): abmask guidedFilter(guide, ., ., r1 = max(int(4 /
+ *     scale * blur + 0.5), 1), 0.001), Lmask r2 = max(int(25 / scale * blur + 0.5), 1), 0.0001; then LIM01 (L1244-1295);
+ *   - contrast threshold (L1359-1376, L696-734) when parametric_enabled && contrast_threshold != 0: above 1920 px on the longer side
+ *     rescaleBilinear(guide) down by s = max(W, H) / 1920.f to int(W / s) x int(H / s) and scale *= s; buildBlendMask(., ., w, h,
+ *     |threshold| / 100.f * sqrt(scale), 1.f, false, max(blur, 2.0) / sqrt(scale), 32768.f); rescaleBilinear back; the planes are multiplied
+ *     by it, or by 1.f - it for a negative threshold;
+ *   - `area`: generate_area_mask's finished plane (the shapes' rasterisation stays with the caller), multiplied in (L1380-1393);
+ *   - mask_postprocess (L737-802): posterization p = {30, 20, 10, 5, 3, 2}[LIM(posterization, 0, 6) - 1]: int(m * p + 0.5) / p; with
+ *     smoothing also the threshold plane (m > 1e-4f ? 1.f : fillval), guidedFilter(guide, m, m, int(max(full_w, full_h) / (10.f * (101.f -
+ *     smoothing))), 0.015f) and their product;
+ *   - inverted: 1.f - m; opacity < 100: m * LIM01(opacity / 100.f).
+ * full_w / full_h < 0 stand for the image's size, like the reference's (L1310-1315).  Asynchronous on the context's stream for device planes.
+ * A non-NULL `info` receives n entries with what the call derived on the host (no extra wait).
+ * ARTGPU_EUNSUPPORTED, decided before any kernel runs, outputs untouched:
+ *   - deltae_enabled (lcms2's double-precision cmsCIE2000DeltaE), drawn_enabled, external_enabled, linked_enabled;
+ *   - !curve_is_identity (Mask::curve, a DiagonalCurve evaluated per pixel); show_mask;
+ *   - mode YUV or XYZ;
+ *   - a guided filter whose box radius (r / subsampling) is above 900, or a statistics grid without pixels; an image with a side below
+ *     ARTGPU_MASKS_MIN_SIZE (what the filters' subsampling of up to 5, buildBlendMask's frame and the gaussian need).
+ * Device scratch (context pool, artgpu_trim_scratch returns it): guide, LL, the posterization's threshold plane, one blend plane per region,
+ * the contrast threshold's planes (up to four), one plane per output, the guided filter's statistics grid. */
+#define ARTGPU_MASKS_MIN_SIZE 8
+#define ARTGPU_MASKS_MODE_RGB 0
+#define ARTGPU_MASKS_MODE_LAB 1
+#define ARTGPU_MASKS_MODE_YUV 2
+#define ARTGPU_MASKS_MODE_XYZ 3
+typedef struct artgpu_mask_params {
+    int32_t parametric_enabled;       /* ParametricMask::enabled (procparams.h; defaults: false, blur 0, lightnessDetail 0, contrastThreshold 0) */
+    int32_t lightness_detail;         /* ::lightnessDetail */
+    const double *hue;                /* ::hue, ::chromaticity, ::lightness: FlatCurve points as artgpu_hsl_equalizer takes them; the defaults are */
+    const double *chromaticity;       /*   hue {1, 0.166666667, 1, 0.35, 0.35, 0.8287775246, 1, 0.35, 0.35}, the others {1, 0, 1, 0.35, 0.35, 1, 1, 0.35, 0.35} */
+    const double *lightness;
+    int32_t nhue, nchromaticity, nlightness;
+    int32_t contrast_threshold;       /* ::contrastThreshold */
+    double blur;                      /* ::blur */
+    const artgpu_plane *area;         /* generate_area_mask's plane for this region (host or device, the image's size); NULL = none */
+    int32_t posterization, smoothing; /* Mask::posterization, ::smoothing (defaults 0, 0) */
+    int32_t inverted, opacity;        /* Mask::inverted, ::opacity (defaults false, 100) */
+    int32_t deltae_enabled, drawn_enabled, external_enabled, linked_enabled;   /* non-zero: ARTGPU_EUNSUPPORTED */
+    int32_t curve_is_identity;        /* Mask::curve is the identity (its default, DCT_Linear); 0: ARTGPU_EUNSUPPORTED */
+    int32_t show_mask;                /* this region is the one show_mask_idx names; non-zero: ARTGPU_EUNSUPPORTED */
+} artgpu_mask_params;
+typedef struct artgpu_masks_info {    /* one per region */
+    int32_t has_mask;                 /* (the same in every entry) */
+    int32_t has_lmask;                /* the lightness-detail plane was built (the same in every entry) */
+    int32_t ll_radius_small, ll_radius;   /* its two guided-filter radii */
+    int32_t blurred, r1, r2;          /* the region went through the guided blur; its radii */
+    int32_t cthr_w, cthr_h;           /* the size contrast_threshold_mask worked at; 0 x 0 when it did not run */
+    int32_t smoothing_radius;         /* mask_postprocess's guided-filter radius; -1 when it did not run */
+} artgpu_masks_info;
+int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, const double ws[9], const artgpu_mask_params *masks, int n,
+                          int full_w, int full_h, double scale, artgpu_plane *Lmask /* n planes or NULL */, artgpu_plane *abmask /* n planes or NULL */,
+                          artgpu_masks_info *info /* n entries or NULL */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -798,6 +870,17 @@ typedef struct {
     const artgpu_texture_boost_region *texture_boost_regions;   /* masks: planes of the output size */
 } artgpu_pipeline_params;
 int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *params, artgpu_rgb *out);
+/* Region masks the per-frame pipe generates itself, a setting of the context like artgpu_set_curve_tail (artgpu_pipeline_params keeps its
+ * layout; its last fields stay the texture-boost ones).  local_contrast_masks: nlc entries,
+ * one per region of params->local_contrast_regions; texture_boost_masks: ntb entries, one per region of params->texture_boost_regions; NULL / 0
+ * = that tool's regions use their own `mask` planes (or all ones), the default.  The entries, their curves and the area planes' descriptors
+ * are copied (the area planes' memory stays the caller's).  While set, artgpu_pipeline_run, artgpu_batch_run and artgpu_batch_run_io generate
+ * that tool's L planes with artgpu_generate_masks' code where the reference calls generateMasks -- texture boost on the RGB image ahead of
+ * setMode(YUV) (iptextureboost.cc:210), local contrast on the LAB image (iplocalcontrast.cc:454) -- with the output's size as the full size and
+ * params->scale, and feed them to the regions without leaving the device; the regions' own `mask` pointers are not read.  A count that differs
+ * from the frame's region count is ARTGPU_EINVAL, what artgpu_generate_masks does not support ARTGPU_EUNSUPPORTED, both before any stage runs. */
+int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *local_contrast_masks, int nlc,
+                              const artgpu_mask_params *texture_boost_masks, int ntb);
 
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
