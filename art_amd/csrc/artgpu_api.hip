@@ -36,7 +36,6 @@ struct artgpu_ctx {
     int opt_dn_streams = 0;        // 1: the DCT detail recovery of L on a side stream beside the reconstructions of a and b.  The default until round 5, when the
                                    // stage waited on LDS round trips and left the chip half idle; since detail_blocks_kernel lost a fifth of its time (detail.hip) the
                                    // two chains only get in each other's way: one kernel after the other is 0.1 - 0.15 ms per 45 MP frame faster (scripts/r5_ab9.sh)
-    int ccalc_nonneg = 0;          // set by artgpu_improc_denoise around RGB_denoise: the chroma noise map is the one chroma_map_kernel has just written (squares: no negative value)
     int opt_dn_fused = 1;          // ShrinkAllL / ShrinkAllAB -- 0: three kernels per channel (factors, row sums, column sums + update); 2: one kernel per
                                    // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
     int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
@@ -78,12 +77,7 @@ struct artgpu_ctx {
     int cu_reserve = 0;            // set around a batch whose downloads run as a kernel of a few workgroups: the persistent one-workgroup-per-CU pixel passes leave those CUs alone
     int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
                                    // hipMemcpy; -1 (default): 8 with two lanes, 0 otherwise (io_frame has the measurements)
-    float fuse_pre = 0.f, fuse_post = 0.f;   // improc_denoise -> rgb_denoise: exposure compensation fused into rgb2yuv / yuv2rgb
-    GetImageFuse fuse_gi = {};               // improc_denoise_fused -> chroma map, rgb2yuv: getImage + matrix read from the demosaiced planes
-    float fuse_exp_scale = 0.f, fuse_exp_black = 0.f;   // improc_denoise_fused -> yuv2rgb: ImProcFunctions::exposure behind the last pass
-    int fuse_exp_on = 0;
-    int tail_exp_on = 0;                      // improc_denoise_fused: the exposure rides on the tool's LAST pixel pass when that is not yuv2rgb
-    float tail_exp_scale = 0.f, tail_exp_black = 0.f;
+    // (what artgpu_improc_denoise_fused fuses into the denoise tool's pixel passes is not state of the context: it travels as a DnFusion argument)
     float *bbox = nullptr; // AMaZE: per-tile nyquist bounding boxes
     size_t bbox_bytes = 0;
     // AMaZE v2: tile lists on the device (ints).  [stream tiles | arena-tile template: count, tiles | working copy: count, tiles + room
@@ -1223,28 +1217,112 @@ int artgpu_wavelet_mad(artgpu_ctx *ctx, const artgpu_wavelet *wv, float *mad_sqr
     return ARTGPU_OK;
 }
 
-int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_params *p, const float ws[9], const float *iws,
-                       double expcomp, double scale, const artgpu_plane *ccalc, uint32_t flags,
-                       float *nresi, float *highresi)
+} // extern "C"
+
+namespace {
+
+// What of the neighbouring stages rides inside the denoise tool's pixel passes.  artgpu_improc_denoise_fused decides it and hands
+// it down as an argument; the public entry points pass an empty one.  A zero-initialised value means "nothing fused".
+struct DnFusion {
+    float pre_scale, post_scale;      // != 0: the tool's expcomp(+ecomp) in front of rgb2yuv / expcomp(-ecomp) behind yuv2rgb
+    GetImageFuse gi;                  // getImage + matrix read from the demosaiced planes by the chroma map and rgb2yuv
+    int exp_on;                       // ImProcFunctions::exposure (process STAGE_1) behind yuv2rgb
+    float exp_scale, exp_black;
+    int tail_on;                      // ... or on the tool's LAST pixel pass when that is not yuv2rgb (guided smoothing / NL-means behind it)
+    float tail_scale, tail_black;
+    int ccalc_nonneg;                 // the chroma noise map is the one chroma_map_kernel has just written (squares: no negative value)
+};
+
+// A table of constants in a pool slot of its own, built on the host by `fill` (which gets `nfloats` zeroed floats) and uploaded once per
+// context.  The slot doubles as the "uploaded" flag.  The host waits for the copy because the host vector dies with this call -- a bubble in
+// the stream, which is why these tables have slots that nothing else grows -- and on a failed upload the slot is given back, or the next call
+// would skip the upload and read an empty table.
+int const_table_dev(artgpu_ctx *ctx, int slot, size_t nfloats, void (*fill)(float *), const char *what, float **out)
 {
-    StageScope scope_(ctx, "denoise::RGB_denoise");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!img || !p || !ws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: null argument");
-    if (p->color_space != 0 && p->color_space != 1) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: color_space must be 0 (RGB) or 1 (LAB)");
-    const bool lab_mode = p->color_space == 1;
-    if (lab_mode && !iws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: LAB mode needs the inverse working-space matrix");
-    if (p->chrominance_method != 0 && p->chrominance_method != 1) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: chrominance_method must be 0 (MANUAL) or 1 (AUTOMATIC)");
-    const bool do_detail = !(flags & ARTGPU_DN_SKIP_DETAIL_RECOVERY);
-    if (!(scale >= 1.0)) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: scale must be >= 1");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevRGB d;
-    int rc = bind_rgb(ctx, img, 4, true, &d, "rgb_denoise");
-    if (rc) return rc;
-    const int w = d.w, h = d.h, w2 = (w + 1) / 2, h2 = (h + 1) / 2;
-    if (w > 32767 || h > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: the reference holds the size in short (FTblockDN.cc:1779)");
-    const size_t n = (size_t)w * h, n2 = (size_t)w2 * h2;
-    const bool useNoiseCCurve = ccalc != nullptr;
-    if (p->luminance == 0 && p->chrominance == 0 && !useNoiseCCurve) return unbind_rgb(ctx, img, &d); // L1655-1668: nothing to do
+    const bool fresh = ctx->pool[slot] == nullptr;
+    const int rc = pool_get(ctx, slot, nfloats * 4, out);
+    if (rc || !fresh) return rc;
+    std::vector<float> host(nfloats);
+    fill(host.data());
+    hipError_t e = hipMemcpyAsync(*out, host.data(), nfloats * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(ctx->pool[slot]); ctx->pool[slot] = nullptr; ctx->pool_bytes[slot] = 0;
+        *out = nullptr;
+        return fail(ctx, ARTGPU_EHIP, "upload of the %s failed: %s", what, hipGetErrorString(e));
+    }
+    return ARTGPU_OK;
+}
+
+// Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292)
+void build_lab_tabs(float *host)
+{
+    build_cachef(host); build_cachefy(host + 65536);
+    build_denoise_gamma_tabs(host + 2 * 65536, host + 3 * 65536);
+}
+
+int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out)
+{
+    return const_table_dev(ctx, P_LABTABS, 4 * 65536, build_lab_tabs, "Lab tables", tabs_out);
+}
+
+// detail_recovery's tile masks and the 64-point cosine table with its transpose (L1479-1635), exactly as the reference builds them:
+// [tilemask_in | tilemask_out | C | C^T], 64 x 64 each
+void build_dct_tabs(float *host)
+{
+    float *tm_in = host, *tm_out = tm_in + 4096, *ct = tm_out + 4096, *ctt = ct + 4096;
+    const float epsilon = 0.001f / (64 * 64);
+    const int border = 4; // MAX(2, TS/16)
+    for (int i = 0; i < 64; ++i) {
+        const float i1 = std::abs((i > 32 ? i - 64 + 1 : i));
+        const float vmask = (i1 < border ? (float)0 + (std::sin((M_PI * i1) / (2 * border)) * std::sin((M_PI * i1) / (2 * border))) : 1.0f);
+        const float vmask2 = (i1 < 2 * border ? (std::sin((M_PI * i1) / (2 * border)) * std::sin((M_PI * i1) / (2 * border))) : 1.0f);
+        for (int j = 0; j < 64; ++j) {
+            const float j1 = std::abs((j > 32 ? j - 64 + 1 : j));
+            const double sj = std::sin((M_PI * j1) / (2 * border));
+            tm_in[i * 64 + j] = (vmask * (j1 < border ? sj * sj : 1.0f)) + epsilon;
+            tm_out[i * 64 + j] = (vmask2 * (j1 < 2 * border ? sj * sj : 1.0f)) + epsilon;
+            ct[i * 64 + j] = (float)std::cos(M_PI * (j + 0.5) * i / 64.0);
+            ctt[j * 64 + i] = ct[i * 64 + j];
+        }
+    }
+}
+
+// Everything RGB_denoise decides on the host before it touches the device: the reference's scalars and the form the shrink passes take.
+struct DnPlan {
+    int w, h, w2, h2;
+    size_t n, n2;                  // pixels of a full-size / a half-size plane
+    bool lab_mode, do_detail, useNoiseCCurve;
+    float noisevarL;
+    bool denoiseLuminance;
+    float gam, gamthresh, gamslope, igam, igamthresh, igamslope, gain;
+    float realred, realblue, noisevarab_r, noisevarab_b, maxNoiseVarab;
+    bool aggressive, autoch;
+    int levwav, nsub;
+    bool too_small;                // the planes do not hold `levwav` levels on the device path: nothing below is filled
+    int rad[10], maxrad;           // box radius of the shrink factors per level
+    bool fork;                     // the DCT detail recovery of L on the side stream
+    bool fused, merged, merged_mad;   // ShrinkAll: one kernel per channel / one launch for all three / with one MadRgb launch set
+    bool two_chroma;               // a and b keep their own decomposition (otherwise b reuses a's)
+    int detail_plain;              // DetailArgs::plain
+    long long wait_ticks;          // FusedShrinkArgs: bounded wait, test stall
+    int stall_band, stall_strip;
+};
+
+// Pure: no context, no HIP call.
+DnPlan dn_plan(int w, int h, const artgpu_denoise_params *p, double scale, double expcomp, uint32_t flags, bool want_resid, bool has_ccalc,
+               int opt_dn_streams, int opt_dn_fused, int opt_dn_detail_plain, long opt_dn_wait_ms, int opt_dn_debug_stall)
+{
+    DnPlan pl = {};
+    const int w2 = (w + 1) / 2, h2 = (h + 1) / 2;
+    pl.w = w; pl.h = h; pl.w2 = w2; pl.h2 = h2; pl.n = (size_t)w * h; pl.n2 = (size_t)w2 * h2;
+    pl.lab_mode = p->color_space == 1;
+    pl.do_detail = !(flags & ARTGPU_DN_SKIP_DETAIL_RECOVERY);
+    pl.useNoiseCCurve = has_ccalc;
+    pl.detail_plain = opt_dn_detail_plain == 1 ? 3 : opt_dn_detail_plain == 2 ? 1 : opt_dn_detail_plain == 3 ? 2 : 0;
+    pl.wait_ticks = (long long)opt_dn_wait_ms * 100000LL;
+    pl.stall_band = opt_dn_debug_stall < 0 ? -1 : opt_dn_debug_stall >> 16;
+    pl.stall_strip = opt_dn_debug_stall < 0 ? -1 : opt_dn_debug_stall & 0xffff;
 
     // ---- scalar set-up, as the reference computes it on the host (L1687-1688,1795-1825,2032-2082,2246-2293)
     const float noiseluma = (float)p->luminance;
@@ -1254,8 +1332,10 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     const float gam = (float)p->gamma;
     const float gamthresh = 0.001f;
     const float gamslope = (float)(std::exp(std::log((double)gamthresh) / gam) / gamthresh);
-    const float igam = 1.f / gam, igamthresh = gamthresh * gamslope, igamslope = 1.f / gamslope;
-    const float gain = std::pow(2.0f, float(expcomp));
+    pl.noisevarL = noisevarL; pl.denoiseLuminance = denoiseLuminance;
+    pl.gam = gam; pl.gamthresh = gamthresh; pl.gamslope = gamslope;
+    pl.igam = 1.f / gam; pl.igamthresh = gamthresh * gamslope; pl.igamslope = 1.f / gamslope;
+    pl.gain = std::pow(2.0f, float(expcomp));
     const float interm_med = (float)p->chrominance / 10.0;
     float intermred = p->chrominance_red_green > 0. ? (p->chrominance_red_green / 10.) : (float)p->chrominance_red_green / 7.0;
     float intermblue = p->chrominance_blue_yellow > 0. ? (p->chrominance_blue_yellow / 10.) : (float)p->chrominance_blue_yellow / 7.0;
@@ -1264,7 +1344,8 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     float realblue = interm_med + intermblue;
     if (realblue <= 0.f) realblue = 0.001f;
     const float noisevarab_r = realred * realred, noisevarab_b = realblue * realblue;
-    const float maxNoiseVarab = noisevarab_b > noisevarab_r ? noisevarab_b : noisevarab_r;
+    pl.realred = realred; pl.realblue = realblue; pl.noisevarab_r = noisevarab_r; pl.noisevarab_b = noisevarab_b;
+    pl.maxNoiseVarab = noisevarab_b > noisevarab_r ? noisevarab_b : noisevarab_r;
     int levwav = 5;
     const float maxreal = realred > realblue ? realred : realblue;
     if (maxreal < 8.f) levwav = 5; else if (maxreal < 10.f) levwav = 6; else if (maxreal < 15.f) levwav = 7; else levwav = 8;
@@ -1280,10 +1361,11 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     if (minsizetile < 32) maxlev2 = 4;
     if (minsizetile < 16) maxlev2 = 3;
     levwav = levwav < maxlev2 ? levwav : maxlev2;
-    if ((w2 < h2 ? w2 : h2) < 2 * wavelet_skip(levwav - 1) || w < 8 || h < 8)
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: %dx%d too small for %d wavelet levels on the device path", w, h, levwav);
     const int nsub = 3 * levwav;
-    bool autoch = p->chrominance_method == 1;
+    const bool autoch = p->chrominance_method == 1;
+    pl.aggressive = aggressive; pl.autoch = autoch; pl.levwav = levwav; pl.nsub = nsub;
+    pl.too_small = (w2 < h2 ? w2 : h2) < 2 * wavelet_skip(levwav - 1) || w < 8 || h < 8;
+    if (pl.too_small) return pl;
 
     // ---- streams.  The reference runs a, then b, then L (L2328-2438).  The chains only meet in the untouched L coefficients and their MADs
     // (read by the chroma shrink factors) and in yuv2rgb, so their order is free.  With option "dn_streams" 1 the DCT detail recovery of L -- bound by
@@ -1291,48 +1373,65 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     // HBM: L goes first for that, after the chroma shrink factors have read its coefficients.  Same kernels on the same data: the same bits.
     // (Rounds 3 and 4: -0.3 ms per frame, the default.  Round 5: off by default -- see opt_dn_streams.)
     // (Running all three chains side by side was measured too: 9.7 ms against 9.2 -- three HBM-bound chains only get in each other's way.)
-    const bool fork = ctx->opt_dn_streams != 0 && do_detail && denoiseLuminance;
+    pl.fork = opt_dn_streams != 0 && pl.do_detail && denoiseLuminance;
 
-    // ---- device buffers; nothing is allocated in steady state.  Scratch planes are shared wherever the order of the kernels allows it:
-    // one `tmp` (horizontally blurred factors) serves all three channels -- its producer and its consumer are neighbours on the context's
-    // stream --; in the reference's order one `sf` plane set and one chroma decomposition do too, with the side stream a and b keep theirs
-    // across the L chain.
-    float *L, *A, *B, *gamlut, *mad, *ccalc_dev = nullptr, *tmp1 = nullptr;
-    float *sfc[3] = {nullptr, nullptr, nullptr}, *tmpc[3], *histo_fc[3];          // 0: L, 1: a, 2: b
-    DevDecomp Ld = {}, Cdd[2] = {};
-    Ld.w = w; Ld.h = h; Ld.w2 = w2; Ld.h2 = h2; Ld.n = n2; Ld.nlevels = levwav;
-    Cdd[0] = Cdd[1] = Ld;
-    BlurArgs bl0 = {};
-    bl0.n = n2; bl0.w = w2; bl0.h = h2;
-    int maxrad = 1;
-    for (int l = 0; l < levwav; ++l) { const int r = int((l + 2) / scale); bl0.rad[l] = r > 1 ? r : 1; maxrad = bl0.rad[l] > maxrad ? bl0.rad[l] : maxrad; }
+    pl.maxrad = 1;
+    for (int l = 0; l < levwav; ++l) { const int r = int((l + 2) / scale); pl.rad[l] = r > 1 ? r : 1; pl.maxrad = pl.rad[l] > pl.maxrad ? pl.rad[l] : pl.maxrad; }
     // ShrinkAllL / ShrinkAllAB as one kernel per channel (shrinkblur.hip: factors, both running sums and the coefficient update in one pass
     // over the coefficients) instead of three with the factor and the row-blurred planes in between: no `sf` / `tmp` planes at all
-    const bool fused = ctx->opt_dn_fused != 0 && shrink_blur_supported(w2, h2, bl0.rad, 0, nsub);
+    pl.fused = opt_dn_fused != 0 && shrink_blur_supported(w2, h2, pl.rad, 0, nsub);
     // ... and for all three channels in ONE launch where nothing has to happen between them (no residuals to read back, no BiShrink
     // passes, every level of L shrunk, both chroma channels denoised): the strips of a band can only follow each other a few blocks apart, so
     // it takes the bands of all channels to keep every CU busy, and one launch instead of three has one ragged end instead of three
-    const bool merged = fused && ctx->opt_dn_fused != 2 && !aggressive && !nresi && !highresi && denoiseLuminance && levwav <= 5 &&
-                        (autoch || (noisevarab_r > 0.001f && noisevarab_b > 0.001f));
-    const bool merged_mad = merged && ctx->opt_dn_fused != 3;      // (3: test switch, MadRgb per channel)
-    const bool two_chroma = fork || merged;        // a and b keep their own decomposition (otherwise b reuses a's)
-    float *fused_scratch = nullptr, *Lbands2 = nullptr;
+    pl.merged = pl.fused && opt_dn_fused != 2 && !aggressive && !want_resid && denoiseLuminance && levwav <= 5 &&
+                (autoch || (noisevarab_r > 0.001f && noisevarab_b > 0.001f));
+    pl.merged_mad = pl.merged && opt_dn_fused != 3;      // (3: test switch, MadRgb per channel)
+    pl.two_chroma = pl.fork || pl.merged;
+    return pl;
+}
+
+// The planes, decompositions and scratch of one RGB_denoise call, all of them pool slots
+struct DnBuffers {
+    float *L, *A, *B, *gamlut, *mad, *ccalc_dev;
+    float *sfc[3], *tmpc[3], *histo_fc[3];          // 0: L, 1: a, 2: b
+    DevDecomp Ld, Cdd[2];
+    float *fused_scratch, *Lbands2;
+};
+
+// a context that changes between the two forms of the passes gives back what only the other form uses (everything else is shared)
+int pool_drop(artgpu_ctx *ctx, int slot)
+{
+    if (!ctx->pool[slot]) return ARTGPU_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->dn_stream[0]) HIPCHK(ctx, hipStreamSynchronize(ctx->dn_stream[0]));
+    HIPCHK(ctx, hipFree(ctx->pool[slot]));
+    ctx->pool[slot] = nullptr; ctx->pool_bytes[slot] = 0;
+    return ARTGPU_OK;
+}
+
+// ---- device buffers; nothing is allocated in steady state.  Scratch planes are shared wherever the order of the kernels allows it:
+// one `tmp` (horizontally blurred factors) serves all three channels -- its producer and its consumer are neighbours on the context's
+// stream --; in the reference's order one `sf` plane set and one chroma decomposition do too, with the side stream a and b keep theirs
+// across the L chain.
+int dn_buffers(artgpu_ctx *ctx, const DnPlan &pl, const artgpu_plane *ccalc, DnBuffers *out)
+{
+    const int w2 = pl.w2, h2 = pl.h2, nsub = pl.nsub;
+    const size_t n = pl.n, n2 = pl.n2;
+    const bool fused = pl.fused, merged = pl.merged, merged_mad = pl.merged_mad;
+    DnBuffers &b = *out;
+    b = DnBuffers{};
+    float *tmp1 = nullptr;
+    DevDecomp &Ld = b.Ld, *Cdd = b.Cdd;
+    Ld.w = pl.w; Ld.h = pl.h; Ld.w2 = w2; Ld.h2 = h2; Ld.n = n2; Ld.nlevels = pl.levwav;
+    Cdd[0] = Cdd[1] = Ld;
+    int rc;
     const size_t histo_bytes = (size_t)nsub * (65536 + MAD_SCRATCH_INTS_PER_BAND) * 4, band_bytes = (size_t)nsub * n2 * 4;
-    if ((rc = pool_get(ctx, P_L, n * 4, &L)) || (rc = pool_get(ctx, P_A, n * 4, &A)) || (rc = pool_get(ctx, P_B, n * 4, &B)) ||
+    if ((rc = pool_get(ctx, P_L, n * 4, &b.L)) || (rc = pool_get(ctx, P_A, n * 4, &b.A)) || (rc = pool_get(ctx, P_B, n * 4, &b.B)) ||
         (rc = pool_get(ctx, P_LBANDS, (merged_mad ? 3 : 1) * band_bytes, &Ld.bands)) || (rc = pool_get(ctx, P_LLOW0, n2 * 4, &Ld.low[0])) || (rc = pool_get(ctx, P_LLOW1, n2 * 4, &Ld.low[1])) ||
         (rc = merged_mad ? ARTGPU_OK : pool_get(ctx, P_CBANDS, (merged ? 2 : 1) * band_bytes, &Cdd[0].bands)) || (rc = pool_get(ctx, P_CLOW0, n2 * 4, &Cdd[0].low[0])) || (rc = pool_get(ctx, P_CLOW1, n2 * 4, &Cdd[0].low[1])) ||
-        (rc = pool_get(ctx, P_HISTO, (merged_mad ? 3 : 1) * histo_bytes, &histo_fc[0])) ||
-        (rc = pool_get(ctx, P_MAD, 3 * 32 * 4, &mad)) || (rc = pool_get(ctx, P_GAM, 2 * 65536 * 4, &gamlut)))
+        (rc = pool_get(ctx, P_HISTO, (merged_mad ? 3 : 1) * histo_bytes, &b.histo_fc[0])) ||
+        (rc = pool_get(ctx, P_MAD, 3 * 32 * 4, &b.mad)) || (rc = pool_get(ctx, P_GAM, 2 * 65536 * 4, &b.gamlut)))
         return rc;
-    // a context that changes between the two forms of the passes gives back what only the other form uses (everything else is shared)
-    auto pool_drop = [&](int slot) -> int {
-        if (!ctx->pool[slot]) return ARTGPU_OK;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->dn_stream[0]) HIPCHK(ctx, hipStreamSynchronize(ctx->dn_stream[0]));
-        HIPCHK(ctx, hipFree(ctx->pool[slot]));
-        ctx->pool[slot] = nullptr; ctx->pool_bytes[slot] = 0;
-        return ARTGPU_OK;
-    };
     // What only the OTHER form of the shrink passes uses (band-sized slots) is given back, but not on every switch: `fused` depends on the
     // frame (w2, h2 >= 64, radii <= 15), so a context or a batch that alternates small and large frames would pay a stream drain and a band-sized
     // hipFree / hipMalloc per frame -- the allocation the pool exists to avoid.  The slots go after FOUR calls in a row in the same form
@@ -1340,43 +1439,314 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     if (ctx->dn_form == (fused ? 1 : 0)) ++ctx->dn_form_streak; else { ctx->dn_form = fused ? 1 : 0; ctx->dn_form_streak = 1; }
     const bool settle = ctx->dn_form_streak >= 4;
     if (fused) {
-        if (settle && ((rc = pool_drop(P_SF_A)) || (rc = pool_drop(P_SF_B)) || (merged && (rc = pool_drop(P_CBANDS2))))) return rc;
+        if (settle && ((rc = pool_drop(ctx, P_SF_A)) || (rc = pool_drop(ctx, P_SF_B)) || (merged && (rc = pool_drop(ctx, P_CBANDS2))))) return rc;
         if (!ctx->fs_diag) {      // (optional: without it a timed-out wait still traps, merely unattributed)
             if (hipHostMalloc(reinterpret_cast<void **>(&ctx->fs_diag), 64, hipHostMallocDefault) == hipSuccess) std::memset(ctx->fs_diag, 0, 64);
             else { ctx->fs_diag = nullptr; (void)hipGetLastError(); }
         }
-        if ((rc = pool_get(ctx, P_FUSED, shrink_blur_scratch_floats(w2, h2, merged ? 3 * nsub : nsub, maxrad) * 4, &fused_scratch))) return rc;
+        if ((rc = pool_get(ctx, P_FUSED, shrink_blur_scratch_floats(w2, h2, merged ? 3 * nsub : nsub, pl.maxrad) * 4, &b.fused_scratch))) return rc;
         // the chroma factors need the L coefficients as the decomposition left them: whenever they are evaluated beside or after the L pass
         // (one launch for all channels; the side stream's order) the L pass writes a second band set instead of updating the first
-        if ((fork || merged) && (rc = pool_get(ctx, P_LBANDS2, band_bytes, &Lbands2))) return rc;
-    } else if ((settle && ((rc = pool_drop(P_FUSED)) || (rc = pool_drop(P_LBANDS2)))) || (rc = pool_get(ctx, P_SF, band_bytes, &sfc[0])) || (rc = pool_get(ctx, P_TMP, band_bytes, &tmp1))) return rc;
-    tmpc[0] = tmpc[1] = tmpc[2] = tmp1;
-    if (two_chroma) {
+        if ((pl.fork || merged) && (rc = pool_get(ctx, P_LBANDS2, band_bytes, &b.Lbands2))) return rc;
+    } else if ((settle && ((rc = pool_drop(ctx, P_FUSED)) || (rc = pool_drop(ctx, P_LBANDS2)))) || (rc = pool_get(ctx, P_SF, band_bytes, &b.sfc[0])) || (rc = pool_get(ctx, P_TMP, band_bytes, &tmp1))) return rc;
+    b.tmpc[0] = b.tmpc[1] = b.tmpc[2] = tmp1;
+    if (pl.two_chroma) {
         if (merged_mad) Cdd[0].bands = Ld.bands + (size_t)nsub * n2;       // (one MadRgb launch set walks the bands of all three channels)
         if (merged) Cdd[1].bands = Cdd[0].bands + (size_t)nsub * n2;       // (one launch walks both channels' bands: back to back)
         else if ((rc = pool_get(ctx, P_CBANDS2, band_bytes, &Cdd[1].bands))) return rc;
         if ((rc = pool_get(ctx, P_CLOW0_2, n2 * 4, &Cdd[1].low[0])) || (rc = pool_get(ctx, P_CLOW1_2, n2 * 4, &Cdd[1].low[1])) ||
-            (rc = pool_get(ctx, P_HISTO_A, (merged ? 2 : 1) * histo_bytes, &histo_fc[1])) || (rc = pool_get(ctx, P_HISTO_B, histo_bytes, &histo_fc[2])))
+            (rc = pool_get(ctx, P_HISTO_A, (merged ? 2 : 1) * histo_bytes, &b.histo_fc[1])) || (rc = pool_get(ctx, P_HISTO_B, histo_bytes, &b.histo_fc[2])))
             return rc;
-        if (!fused && ((rc = pool_get(ctx, P_SF_A, band_bytes, &sfc[1])) || (rc = pool_get(ctx, P_SF_B, band_bytes, &sfc[2])))) return rc;
+        if (!fused && ((rc = pool_get(ctx, P_SF_A, band_bytes, &b.sfc[1])) || (rc = pool_get(ctx, P_SF_B, band_bytes, &b.sfc[2])))) return rc;
     } else {
-        sfc[1] = sfc[2] = sfc[0];
-        histo_fc[1] = histo_fc[2] = histo_fc[0];
+        b.sfc[1] = b.sfc[2] = b.sfc[0];
+        b.histo_fc[1] = b.histo_fc[2] = b.histo_fc[0];
         Cdd[1] = Cdd[0];
     }
-    float *madL = mad;
-    if (useNoiseCCurve) {
+    if (pl.useNoiseCCurve) {
         if (!plane_ok(ccalc) || ccalc->w != w2 || ccalc->h != h2) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: ccalc must be %dx%d", w2, h2);
         if (ccalc->on_device && (size_t)ccalc->row_stride_bytes == (size_t)w2 * 4) {
-            ccalc_dev = ccalc->p;              // dense and on the device already (the map artgpu_improc_denoise has just computed): read in place
+            b.ccalc_dev = ccalc->p;            // dense and on the device already (the map artgpu_improc_denoise has just computed): read in place
         } else {
-            if ((rc = pool_get(ctx, P_CCALC, n2 * 4, &ccalc_dev))) return rc;
-            HIPCHK(ctx, hipMemcpy2DAsync(ccalc_dev, (size_t)w2 * 4, ccalc->p, (size_t)ccalc->row_stride_bytes, (size_t)w2 * 4, h2,
+            if ((rc = pool_get(ctx, P_CCALC, n2 * 4, &b.ccalc_dev))) return rc;
+            HIPCHK(ctx, hipMemcpy2DAsync(b.ccalc_dev, (size_t)w2 * 4, ccalc->p, (size_t)ccalc->row_stride_bytes, (size_t)w2 * 4, h2,
                                          ccalc->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
         }
     }
+    return ARTGPU_OK;
+}
 
-    if (fork && !ctx->dn_stream[0]) {
+// The steps of one RGB_denoise call on the device: each queues its kernels on the context's stream `sL` (the detail recovery on `sd`)
+struct DnRun {
+    artgpu_ctx *ctx;
+    const DnPlan &pl;
+    DnBuffers &b;
+    const DnFusion &fu;
+    const artgpu_denoise_params *p;
+    double scale;
+    float *nresi, *highresi;
+    hipStream_t sL;
+    float noisevar_abc[2];
+    float chresidtemp, chmaxresidtemp;
+    float *Lout;                     // where the denoised L ends up: yuv2rgb reads it
+
+    BlurArgs blur0() const
+    {
+        BlurArgs bl0 = {};
+        bl0.n = pl.n2; bl0.w = pl.w2; bl0.h = pl.h2;
+        for (int l = 0; l < 10; ++l) bl0.rad[l] = pl.rad[l];
+        return bl0;
+    }
+    // what every launch of the fused ShrinkAll pass has in common
+    FusedShrinkArgs fused_args(float nv_const) const
+    {
+        FusedShrinkArgs fa = {};
+        fa.n = pl.n2; fa.w = pl.w2; fa.h = pl.h2;
+        fa.noisevar = b.ccalc_dev; fa.noisevar_nonneg = fu.ccalc_nonneg; fa.noisevar_const = nv_const; fa.noisevar_scale = pl.maxNoiseVarab;
+        fa.useNoiseCCurve = pl.useNoiseCCurve ? 1 : 0;
+        for (int l = 0; l < 10; ++l) fa.rad[l] = pl.rad[l];
+        fa.diag = ctx->fs_diag; fa.wait_ticks = pl.wait_ticks; fa.stall_band = pl.stall_band; fa.stall_strip = pl.stall_strip;
+        return fa;
+    }
+    int fused_pass(bool ab, const float *cin, float *cout, const float *cL, const float *mL, const float *mab, int lev0, int nb, float nv_const, float noisevar_ab);
+    int chroma_front(int ch);
+    int chroma_back(int ch);
+    int luma(hipStream_t sd);
+    int detail_recovery(hipStream_t sd);
+    int merged_pass();
+};
+
+// one fused ShrinkAll pass over `nb` bands starting at level `lev0` (pointers already offset to the first band)
+int DnRun::fused_pass(bool ab, const float *cin, float *cout, const float *cL, const float *mL, const float *mab, int lev0, int nb,
+                      float nv_const, float noisevar_ab)
+{
+    FusedShrinkArgs fa = fused_args(nv_const);
+    if (ab) { fa.coefC = cout; fa.nL = 0; fa.nsub_ch = nb; }           // (chroma bands are updated in place: cin == cout)
+    else { fa.coef = cin; fa.coef_out = cout; fa.nL = nb; }
+    fa.coefL = cL;
+    fa.madL = mL; fa.madab = mab;
+    fa.noisevar_ab[0] = fa.noisevar_ab[1] = noisevar_ab;
+    fa.level0 = lev0; fa.nsub = nb;
+    HIPCHK(ctx, launch_shrink_blur(fa, b.fused_scratch, sL));
+    return ARTGPU_OK;
+}
+
+// ---- a and b (L2328-2402), first half: decompose, MADs, shrink factors against the untouched L coefficients
+int DnRun::chroma_front(int ch)
+{
+    const int nsub = pl.nsub;
+    const size_t n2 = pl.n2;
+    const DevDecomp &Ld = b.Ld;
+    DevDecomp &Cd = b.Cdd[ch];
+    float *sf = b.sfc[1 + ch], *tmp = b.tmpc[1 + ch], *madL = b.mad, *madab = b.mad + 32 * (1 + ch);
+    int *histo = reinterpret_cast<int *>(b.histo_fc[1 + ch]);
+    float noisevar_ab = ch == 0 ? pl.noisevarab_r : pl.noisevarab_b;
+    if (pl.autoch && noisevar_ab <= 0.001f) noisevar_ab = 0.02f;
+    noisevar_abc[ch] = noisevar_ab;
+    int rc2;
+    if ((rc2 = decompose_dev(ctx, Cd, ch == 0 ? b.A : b.B, sL))) return rc2;
+    if (pl.aggressive && noisevar_ab > 0.001f) {
+        // WaveletDenoiseAll_BiShrinkAB (L976-1108): MAD of all untouched bands, ShrinkAllAB on the top level (same MAD),
+        // point-wise shrink of the levels below
+        HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, madab, sL));
+        ShrinkArgs sa = {};
+        sa.n = n2; sa.noisevar = b.ccalc_dev; sa.noisevar_scale = pl.maxNoiseVarab; sa.noisevar_ab = noisevar_ab; sa.useNoiseCCurve = pl.useNoiseCCurve ? 1 : 0;
+        const size_t top = (size_t)(nsub - 3) * n2;
+        sa.coef = Cd.bands + top; sa.coefL = Ld.bands + top; sa.sfave = sf; sa.madL = madL + (nsub - 3); sa.madab = madab + (nsub - 3);
+        if (pl.fused) {
+            if ((rc2 = fused_pass(true, Cd.bands + top, Cd.bands + top, Ld.bands + top, madL + (nsub - 3), madab + (nsub - 3), pl.levwav - 1, 3, 0.f, noisevar_ab))) return rc2;
+        } else {
+            HIPCHK(ctx, launch_shrink_sf(sa, 3, true, sL));
+            BlurArgs bt = blur0();
+            bt.level0 = pl.levwav - 1;
+            bt.src = sf; bt.dst = tmp;
+            HIPCHK(ctx, launch_hblur(bt, 3, sL));
+            bt.src = tmp; bt.sfave = sf; bt.coef = Cd.bands + top;
+            HIPCHK(ctx, launch_vblur_combine(bt, 3, sL));
+        }
+        if (nsub > 3) {
+            sa.coef = Cd.bands; sa.coefL = Ld.bands; sa.madL = madL; sa.madab = madab;
+            HIPCHK(ctx, launch_bishrink_AB(sa, nsub - 3, sL));
+        }
+    }
+    if (noisevar_ab > 0.001f && !pl.merged_mad) {
+        HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, ch == 1 && pl.merged ? b.mad + 32 + nsub : madab, sL));
+        if (!pl.fused) {
+            ShrinkArgs sa = {};
+            sa.coef = Cd.bands; sa.coefL = Ld.bands; sa.sfave = sf; sa.n = n2; sa.madL = madL; sa.madab = madab;
+            sa.noisevar = b.ccalc_dev; sa.noisevar_scale = pl.maxNoiseVarab; sa.noisevar_ab = noisevar_ab; sa.useNoiseCCurve = pl.useNoiseCCurve ? 1 : 0;
+            HIPCHK(ctx, launch_shrink_sf(sa, nsub, true, sL));
+        }
+    }
+    return ARTGPU_OK;
+}
+
+// second half: box blur of the shrink factors, coefficient update, residuals, reconstruction
+int DnRun::chroma_back(int ch)
+{
+    const int nsub = pl.nsub;
+    DevDecomp &Cd = b.Cdd[ch];
+    float *sf = b.sfc[1 + ch], *tmp = b.tmpc[1 + ch], *madab = b.mad + 32 * (1 + ch);
+    int *histo = reinterpret_cast<int *>(b.histo_fc[1 + ch]);
+    if (noisevar_abc[ch] > 0.001f && !pl.merged) {
+        if (pl.fused) {
+            // (the factors read the L coefficients as the decomposition left them: in the reference's order L comes last, with the side
+            // stream the L pass has written a second band set)
+            int rc2 = fused_pass(true, Cd.bands, Cd.bands, b.Ld.bands, b.mad, madab, 0, nsub, 0.f, noisevar_abc[ch]);
+            if (rc2) return rc2;
+        } else {
+            BlurArgs bl = blur0();
+            bl.src = sf; bl.dst = tmp;
+            HIPCHK(ctx, launch_hblur(bl, nsub, sL));
+            bl.src = tmp; bl.sfave = sf; bl.coef = Cd.bands;
+            HIPCHK(ctx, launch_vblur_combine(bl, nsub, sL));
+        }
+    }
+    if (nresi || highresi) {
+        // Noise_residualAB (FTblockDN.cc:605-635, kall == 0): SQR(MadRgb) of the shrunk chroma bands, summed in level/dir order
+        float host[32];
+        HIPCHK(ctx, launch_mad(Cd.bands, pl.n2, nsub, histo, madab, sL));
+        HIPCHK(ctx, hipMemcpyAsync(host, madab, (size_t)nsub * sizeof(float), hipMemcpyDeviceToHost, sL));
+        HIPCHK(ctx, hipStreamSynchronize(sL));
+        float resid = 0.f, maxresid = 0.f;
+        for (int k = 0; k < nsub; ++k) {
+            resid += host[k];
+            if (host[k] > maxresid) maxresid = host[k];
+        }
+        if (ch == 0) { chresidtemp = resid; chmaxresidtemp = maxresid; }
+        else {
+            float chresid = resid + chresidtemp, chmaxresid = maxresid + chmaxresidtemp;      // L2389-2396
+            chresid = std::sqrt(chresid / (6 * (pl.levwav)));
+            if (highresi) *highresi = chresid + 0.66f * (std::sqrt(chmaxresid) - chresid);
+            if (nresi) *nresi = chresid;
+        }
+    }
+    return reconstruct_dev(ctx, Cd, ch == 0 ? b.A : b.B, sL);
+}
+
+// ---- L: shrink the first min(levels,5) levels, reconstruct (L2405-2438); detail recovery on stream `sd`
+int DnRun::luma(hipStream_t sd)
+{
+    if (!pl.denoiseLuminance) return ARTGPU_OK;
+    int rc2;
+    const int nsub = pl.nsub, nsubL = 3 * (pl.levwav < 5 ? pl.levwav : 5);
+    const size_t n2 = pl.n2;
+    const DevDecomp &Ld = b.Ld;
+    float *sf = b.sfc[0], *tmp = b.tmpc[0];
+    BlurArgs bl = blur0();
+    ShrinkArgs sa = {};
+    sa.coef = Ld.bands; sa.sfave = sf; sa.n = n2; sa.madL = b.mad; sa.noisevar = nullptr; sa.noisevar_const = pl.noisevarL;
+    // QUALITY_HIGH runs WaveletDenoiseAll_BiShrinkL first (L842-973); its per-band body is ShrinkAllL's (top level included),
+    // and madL is not recomputed in between (L2408-2421): the standard pass simply runs twice
+    DevDecomp Lrec = Ld;                   // what the reconstruction reads
+    if (pl.merged) Lrec.bands = b.Lbands2;
+    for (int rep = pl.aggressive ? 0 : 1; rep < 2 && !pl.merged; ++rep) {
+        if (pl.fused) {
+            // the first pass reads the decomposition; with a second band set it writes there, and a second pass (QUALITY_HIGH) works on that
+            float *dstb = b.Lbands2 ? b.Lbands2 : Ld.bands;
+            if ((rc2 = fused_pass(false, Lrec.bands, dstb, nullptr, b.mad, nullptr, 0, nsubL, pl.noisevarL, 0.f))) return rc2;
+            Lrec.bands = dstb;
+        } else {
+            HIPCHK(ctx, launch_shrink_sf(sa, nsubL, false, sL));
+            bl.src = sf; bl.dst = tmp;
+            HIPCHK(ctx, launch_hblur(bl, nsubL, sL));
+            bl.src = tmp; bl.sfave = sf; bl.coef = Ld.bands;
+            HIPCHK(ctx, launch_vblur_combine(bl, nsubL, sL));
+        }
+    }
+    if (Lrec.bands != Ld.bands && nsubL < nsub)          // levels beyond the fifth are reconstructed as they are
+        HIPCHK(ctx, hipMemcpyAsync(Lrec.bands + (size_t)nsubL * n2, Ld.bands + (size_t)nsubL * n2, (size_t)(nsub - nsubL) * n2 * 4, hipMemcpyDeviceToDevice, sL));
+    if (pl.do_detail) {
+        // labdn->L is kept as Lin before the reconstruction modifies it (L2423-2432): here the reconstruction writes a second plane
+        // instead of the first being copied
+        if ((rc2 = pool_get(ctx, P_LIN, pl.n * 4, &Lout))) return rc2;
+    }
+    Lrec.cur = Ld.cur;
+    if ((rc2 = reconstruct_dev(ctx, Lrec, Lout, sL))) return rc2;
+    return pl.do_detail ? detail_recovery(sd) : ARTGPU_OK;
+}
+
+// ---- detail_recovery (L1479-1635) of the reconstructed L in `Lout` against the L the decomposition read; host-side scalars exactly as
+// the reference computes them.  The detail mask is built on `sL`, the two DCT kernels run on `sd`.
+int DnRun::detail_recovery(hipStream_t sd)
+{
+    const int w = pl.w, h = pl.h;
+    int rc2;
+    DetailArgs da = {};
+    da.w = w; da.h = h;
+    da.numblox_W = (int)std::ceil(((float)w) / 25) + 2;
+    da.numblox_H = (int)std::ceil(((float)h) / 25) + 2;
+    const float params_Ldetail = std::min(float(p->luminance_detail), 99.9f);
+    auto compute_detail = [](float dd) -> float { const float t = static_cast<float>((100. - dd) * (100. - dd) + 50. * (100. - dd)) * 64 * 0.5f; return t * t; };
+    da.detail_hi = compute_detail(params_Ldetail);
+    da.detail_lo = compute_detail(0.f);
+    { const int br = int(3 / scale); da.blur_rad = br > 1 ? br : 1; }
+    float *dtab;
+    // the tables are constants: built and uploaded once per context (a slot of their own: the upload needs a stream
+    // synchronisation, i.e. a bubble in the middle of every frame)
+    if ((rc2 = const_table_dev(ctx, P_DCTTAB, 4 * 4096, build_dct_tabs, "DCT tables", &dtab))) return rc2;
+    if ((rc2 = pool_get(ctx, P_BLOCKS, (size_t)da.numblox_W * da.numblox_H * 4096 * 4, &da.blocks))) return rc2;
+    da.tm_in = dtab; da.tm_out = dtab + 4096; da.costab = dtab + 2 * 4096; da.costab_t = dtab + 3 * 4096;
+    da.L = Lout; da.Lin = b.L;
+    da.plain = pl.detail_plain;
+    if (p->luminance_detail_threshold > 0) {
+        // detail_mask(LL, mask, 65535, 25, 10000, amount, GAUSS, 25 / scale) on the denoised L (FTblockDN.cc:1502-1507)
+        float *dmask;
+        if ((rc2 = pool_get(ctx, P_DMASK, pl.n * 4, &dmask))) return rc2;
+        const float amount = std::max(0.f, std::min(float(p->luminance_detail_threshold) / 100.f, 1.f));
+        float *dm_scratch = b.tmpc[0];
+        if (!dm_scratch && (rc2 = pool_get(ctx, P_TMP, ((size_t)w * h + 2 * (size_t)(w / 4) * (h / 4)) * 4, &dm_scratch))) return rc2;   // (fused: no `tmp` plane set)
+        if ((rc2 = detail_mask_dev(ctx, Lout, (size_t)w, dmask, w, h, 65535.f, 25.f, 10000.f, amount, (float)(25.f / scale), dm_scratch))) return rc2;
+        da.mask = dmask; da.params_Ldetail = params_Ldetail;
+    }
+    if (sd != sL) {
+        HIPCHK(ctx, hipEventRecord(ctx->dn_ev[0], sL));
+        HIPCHK(ctx, hipStreamWaitEvent(sd, ctx->dn_ev[0], 0));
+    }
+    HIPCHK(ctx, launch_detail_blocks(da, sd));
+    HIPCHK(ctx, launch_detail_gather(da, sd));
+    if (sd != sL) HIPCHK(ctx, hipEventRecord(ctx->dn_ev[1], sd));
+    return ARTGPU_OK;
+}
+
+// the ShrinkAll passes of L, a and b as one launch (DnPlan::merged)
+int DnRun::merged_pass()
+{
+    const int nsub = pl.nsub;
+    FusedShrinkArgs fa = fused_args(pl.noisevarL);
+    fa.coef = b.Ld.bands; fa.coef_out = b.Lbands2; fa.coefC = b.Cdd[0].bands; fa.coefL = b.Ld.bands;
+    fa.madL = b.mad; fa.madab = pl.merged_mad ? b.mad + nsub : b.mad + 32; fa.mad_ch_stride = nsub;
+    fa.noisevar_ab[0] = noisevar_abc[0]; fa.noisevar_ab[1] = noisevar_abc[1];
+    fa.level0 = 0; fa.nsub = 3 * nsub; fa.nL = nsub; fa.nsub_ch = nsub;
+    HIPCHK(ctx, launch_shrink_blur(fa, b.fused_scratch, sL));
+    return ARTGPU_OK;
+}
+
+// the checks of RGB_denoise's parameters that the public entry point and the tool share
+int rgb_denoise_args_ok(artgpu_ctx *ctx, const artgpu_denoise_params *p, const float *iws, double scale)
+{
+    if (p->color_space != 0 && p->color_space != 1) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: color_space must be 0 (RGB) or 1 (LAB)");
+    if (p->color_space == 1 && !iws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: LAB mode needs the inverse working-space matrix");
+    if (p->chrominance_method != 0 && p->chrominance_method != 1) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: chrominance_method must be 0 (MANUAL) or 1 (AUTOMATIC)");
+    if (!(scale >= 1.0)) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: scale must be >= 1");
+    return ARTGPU_OK;
+}
+
+// RGB_denoise on device planes (the caller has checked the parameters and bound the image); `fu`: what the tool around it has fused into
+// the first and the last pixel pass
+int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_params *p, const float ws[9], const float *iws,
+                    double expcomp, double scale, const artgpu_plane *ccalc, uint32_t flags, float *nresi, float *highresi, const DnFusion &fu)
+{
+    const int w = d.w, h = d.h;
+    if (w > 32767 || h > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: the reference holds the size in short (FTblockDN.cc:1779)");
+    if (p->luminance == 0 && p->chrominance == 0 && !ccalc) return ARTGPU_OK; // L1655-1668: nothing to do
+    const DnPlan pl = dn_plan(w, h, p, scale, expcomp, flags, nresi || highresi, ccalc != nullptr,
+                              ctx->opt_dn_streams, ctx->opt_dn_fused, ctx->opt_dn_detail_plain, ctx->opt_dn_wait_ms, ctx->opt_dn_debug_stall);
+    if (pl.too_small) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: %dx%d too small for %d wavelet levels on the device path", w, h, pl.levwav);
+    DnBuffers b;
+    int rc = dn_buffers(ctx, pl, ccalc, &b);
+    if (rc) return rc;
+    if (pl.fork && !ctx->dn_stream[0]) {
         HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dn_stream[0], hipStreamNonBlocking));
         for (int k = 0; k < 2; ++k) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->dn_ev[k], hipEventDisableTiming));
     }
@@ -1385,307 +1755,95 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     // ---- gamma LUTs (built on the device with the SSE-form sleef, color.cc:1128-1161)
     //      -- once per set of parameters: the pair built by the previous call on this context is still there when they have not changed
     {
-        const float key[6] = {gam, gamthresh, gamslope, igam, igamthresh, igamslope};
-        if (ctx->gam_tab != gamlut || std::memcmp(ctx->gam_key, key, sizeof key) != 0) {
+        const float key[6] = {pl.gam, pl.gamthresh, pl.gamslope, pl.igam, pl.igamthresh, pl.igamslope};
+        if (ctx->gam_tab != b.gamlut || std::memcmp(ctx->gam_key, key, sizeof key) != 0) {
             ctx->gam_tab = nullptr;
-            HIPCHK(ctx, launch_gamma_lut(gamlut, gam, gamthresh, gamslope, 65535.f, 65535.f, sL));
-            HIPCHK(ctx, launch_gamma_lut(gamlut + 65536, igam, igamthresh, igamslope, 65535.f, 65535.f, sL));
+            HIPCHK(ctx, launch_gamma_lut(b.gamlut, pl.gam, pl.gamthresh, pl.gamslope, 65535.f, 65535.f, sL));
+            HIPCHK(ctx, launch_gamma_lut(b.gamlut + 65536, pl.igam, pl.igamthresh, pl.igamslope, 65535.f, 65535.f, sL));
             std::memcpy(ctx->gam_key, key, sizeof key);
-            ctx->gam_tab = gamlut;
+            ctx->gam_tab = b.gamlut;
         }
     }
 
     DnPixArgs px = {};
     for (int k = 0; k < 3; ++k) { px.rgb[k] = d.p[k]; px.ws1[k] = ws[3 + k]; }
-    px.stride = d.stride; px.L = L; px.A = A; px.B = B; px.w = w; px.h = h;
-    px.gain = gain; px.newGain = 1.f / gain;
-    px.gam = gam; px.gamthresh = gamthresh; px.gamslope = gamslope; px.igam = igam; px.igamthresh = igamthresh; px.igamslope = igamslope;
-    px.gamcurve = gamlut; px.igamcurve = gamlut + 65536;
-    px.pre_scale = ctx->fuse_pre; px.post_scale = ctx->fuse_post; px.no_lds_lut = !ctx->opt_lut_lds; px.cu_reserve = ctx->cu_reserve;
-    px.gi = ctx->fuse_gi; px.exp_on = ctx->fuse_exp_on; px.exp_scale = ctx->fuse_exp_scale; px.exp_black = ctx->fuse_exp_black;
+    px.stride = d.stride; px.L = b.L; px.A = b.A; px.B = b.B; px.w = w; px.h = h;
+    px.gain = pl.gain; px.newGain = 1.f / pl.gain;
+    px.gam = pl.gam; px.gamthresh = pl.gamthresh; px.gamslope = pl.gamslope; px.igam = pl.igam; px.igamthresh = pl.igamthresh; px.igamslope = pl.igamslope;
+    px.gamcurve = b.gamlut; px.igamcurve = b.gamlut + 65536;
+    px.pre_scale = fu.pre_scale; px.post_scale = fu.post_scale; px.no_lds_lut = !ctx->opt_lut_lds; px.cu_reserve = ctx->cu_reserve;
+    px.gi = fu.gi; px.exp_on = fu.exp_on; px.exp_scale = fu.exp_scale; px.exp_black = fu.exp_black;
     // the inverse-gamma pass looks up gamma-encoded values: the mid-tones sit in the middle of the table, so the 40704 entries kept in LDS
     // start at 8000 (gamma 1.7: linear 0.03 .. 0.60 of white); the forward pass and the tone curve index with linear data and keep [0, 40704)
     px.igam_lds_lo = 8000;
-    if (lab_mode) {
-        // Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292)
+    if (pl.lab_mode) {
         float *tabs;
-        const bool fresh = ctx->pool[P_LABTABS] == nullptr;
-        if ((rc = pool_get(ctx, P_LABTABS, 4 * 65536 * 4, &tabs))) return rc;
-        if (fresh) {
-            std::vector<float> host(4 * 65536);
-            build_cachef(host.data()); build_cachefy(host.data() + 65536);
-            build_denoise_gamma_tabs(host.data() + 2 * 65536, host.data() + 3 * 65536);
-            hipError_t e = hipMemcpyAsync(tabs, host.data(), host.size() * 4, hipMemcpyHostToDevice, sL);
-            if (e == hipSuccess) e = hipStreamSynchronize(sL);
-            if (e != hipSuccess) {     // the slot doubles as the "tables are there" flag: give it back, or the next call would skip the upload
-                (void)hipFree(ctx->pool[P_LABTABS]); ctx->pool[P_LABTABS] = nullptr; ctx->pool_bytes[P_LABTABS] = 0;
-                return fail(ctx, ARTGPU_EHIP, "rgb_denoise: upload of the Lab tables failed: %s", hipGetErrorString(e));
-            }
-        }
+        if ((rc = lab_tabs_dev(ctx, &tabs))) return rc;
         px.lab_mode = 1;
         px.cachef = tabs; px.cachefy = tabs + 65536; px.dn_gamma = tabs + 2 * 65536; px.dn_igamma = tabs + 3 * 65536;
         for (int k = 0; k < 9; ++k) { px.wpi[k] = ws[k]; px.iws[k] = iws[k]; }
     }
-    px.realred = realred; px.realblue = realblue; px.qhighFactor = aggressive ? 1.f / static_cast<float>(0.9) : 1.0f;   // L1672
+    px.realred = pl.realred; px.realblue = pl.realblue; px.qhighFactor = pl.aggressive ? 1.f / static_cast<float>(0.9) : 1.0f;   // L1672
     HIPCHK(ctx, launch_rgb2yuv(px, sL));
 
     // ---- L decomposition and its MADs (L2296-2320)
-    if ((rc = decompose_dev(ctx, Ld, L, sL))) return rc;
-    if (!merged_mad) HIPCHK(ctx, launch_mad(Ld.bands, n2, nsub, reinterpret_cast<int *>(histo_fc[0]), madL, sL));
+    if ((rc = decompose_dev(ctx, b.Ld, b.L, sL))) return rc;
+    if (!pl.merged_mad) HIPCHK(ctx, launch_mad(b.Ld.bands, pl.n2, pl.nsub, reinterpret_cast<int *>(b.histo_fc[0]), b.mad, sL));
 
-    // one fused ShrinkAll pass over `nb` bands starting at level `lev0` (pointers already offset to the first band)
-    auto fused_pass = [&](bool ab, const float *cin, float *cout, const float *cL, const float *mL, const float *mab, int lev0, int nb,
-                          float nv_const, float noisevar_ab) -> int {
-        FusedShrinkArgs fa = {};
-        if (ab) { fa.coefC = cout; fa.nL = 0; fa.nsub_ch = nb; }           // (chroma bands are updated in place: cin == cout)
-        else { fa.coef = cin; fa.coef_out = cout; fa.nL = nb; }
-        fa.coefL = cL; fa.n = n2; fa.w = w2; fa.h = h2;
-        fa.madL = mL; fa.madab = mab;
-        fa.noisevar = ccalc_dev; fa.noisevar_nonneg = ctx->ccalc_nonneg; fa.noisevar_const = nv_const; fa.noisevar_scale = maxNoiseVarab; fa.noisevar_ab[0] = fa.noisevar_ab[1] = noisevar_ab;
-        fa.useNoiseCCurve = useNoiseCCurve ? 1 : 0;
-        for (int l = 0; l < 10; ++l) fa.rad[l] = bl0.rad[l];
-        fa.level0 = lev0; fa.nsub = nb; fa.diag = ctx->fs_diag; fa.wait_ticks = (long long)ctx->opt_dn_wait_ms * 100000LL; fa.stall_band = ctx->opt_dn_debug_stall < 0 ? -1 : ctx->opt_dn_debug_stall >> 16; fa.stall_strip = ctx->opt_dn_debug_stall < 0 ? -1 : ctx->opt_dn_debug_stall & 0xffff;
-        HIPCHK(ctx, launch_shrink_blur(fa, fused_scratch, sL));
-        return ARTGPU_OK;
-    };
-
-    // ---- a and b (L2328-2402), first half: decompose, MADs, shrink factors against the untouched L coefficients
-    float noisevar_abc[2];
-    auto chroma_front = [&](int ch) -> int {
-        DevDecomp &Cd = Cdd[ch];
-        float *sf = sfc[1 + ch], *tmp = tmpc[1 + ch], *madab = mad + 32 * (1 + ch);
-        int *histo = reinterpret_cast<int *>(histo_fc[1 + ch]);
-        float noisevar_ab = ch == 0 ? noisevarab_r : noisevarab_b;
-        if (autoch && noisevar_ab <= 0.001f) noisevar_ab = 0.02f;
-        noisevar_abc[ch] = noisevar_ab;
-        int rc2;
-        if ((rc2 = decompose_dev(ctx, Cd, ch == 0 ? A : B, sL))) return rc2;
-        if (aggressive && noisevar_ab > 0.001f) {
-            // WaveletDenoiseAll_BiShrinkAB (L976-1108): MAD of all untouched bands, ShrinkAllAB on the top level (same MAD),
-            // point-wise shrink of the levels below
-            HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, madab, sL));
-            ShrinkArgs sa = {};
-            sa.n = n2; sa.noisevar = ccalc_dev; sa.noisevar_scale = maxNoiseVarab; sa.noisevar_ab = noisevar_ab; sa.useNoiseCCurve = useNoiseCCurve ? 1 : 0;
-            const size_t top = (size_t)(nsub - 3) * n2;
-            sa.coef = Cd.bands + top; sa.coefL = Ld.bands + top; sa.sfave = sf; sa.madL = madL + (nsub - 3); sa.madab = madab + (nsub - 3);
-            if (fused) {
-                if ((rc2 = fused_pass(true, Cd.bands + top, Cd.bands + top, Ld.bands + top, madL + (nsub - 3), madab + (nsub - 3), levwav - 1, 3, 0.f, noisevar_ab))) return rc2;
-            } else {
-                HIPCHK(ctx, launch_shrink_sf(sa, 3, true, sL));
-                BlurArgs bt = bl0;
-                bt.level0 = levwav - 1;
-                bt.src = sf; bt.dst = tmp;
-                HIPCHK(ctx, launch_hblur(bt, 3, sL));
-                bt.src = tmp; bt.sfave = sf; bt.coef = Cd.bands + top;
-                HIPCHK(ctx, launch_vblur_combine(bt, 3, sL));
-            }
-            if (nsub > 3) {
-                sa.coef = Cd.bands; sa.coefL = Ld.bands; sa.madL = madL; sa.madab = madab;
-                HIPCHK(ctx, launch_bishrink_AB(sa, nsub - 3, sL));
-            }
-        }
-        if (noisevar_ab > 0.001f && !merged_mad) {
-            HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, ch == 1 && merged ? mad + 32 + nsub : madab, sL));
-            if (!fused) {
-                ShrinkArgs sa = {};
-                sa.coef = Cd.bands; sa.coefL = Ld.bands; sa.sfave = sf; sa.n = n2; sa.madL = madL; sa.madab = madab;
-                sa.noisevar = ccalc_dev; sa.noisevar_scale = maxNoiseVarab; sa.noisevar_ab = noisevar_ab; sa.useNoiseCCurve = useNoiseCCurve ? 1 : 0;
-                HIPCHK(ctx, launch_shrink_sf(sa, nsub, true, sL));
-            }
-        }
-        return ARTGPU_OK;
-    };
-    // second half: box blur of the shrink factors, coefficient update, residuals, reconstruction
-    float chresidtemp = 0.f, chmaxresidtemp = 0.f;
-    auto chroma_back = [&](int ch) -> int {
-        DevDecomp &Cd = Cdd[ch];
-        float *sf = sfc[1 + ch], *tmp = tmpc[1 + ch], *madab = mad + 32 * (1 + ch);
-        int *histo = reinterpret_cast<int *>(histo_fc[1 + ch]);
-        if (noisevar_abc[ch] > 0.001f && !merged) {
-            if (fused) {
-                // (the factors read the L coefficients as the decomposition left them: in the reference's order L comes last, with the side
-                // stream the L pass has written a second band set)
-                int rc2 = fused_pass(true, Cd.bands, Cd.bands, Ld.bands, madL, madab, 0, nsub, 0.f, noisevar_abc[ch]);
-                if (rc2) return rc2;
-            } else {
-                BlurArgs bl = bl0;
-                bl.src = sf; bl.dst = tmp;
-                HIPCHK(ctx, launch_hblur(bl, nsub, sL));
-                bl.src = tmp; bl.sfave = sf; bl.coef = Cd.bands;
-                HIPCHK(ctx, launch_vblur_combine(bl, nsub, sL));
-            }
-        }
-        if (nresi || highresi) {
-            // Noise_residualAB (FTblockDN.cc:605-635, kall == 0): SQR(MadRgb) of the shrunk chroma bands, summed in level/dir order
-            float host[32];
-            HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, madab, sL));
-            HIPCHK(ctx, hipMemcpyAsync(host, madab, (size_t)nsub * sizeof(float), hipMemcpyDeviceToHost, sL));
-            HIPCHK(ctx, hipStreamSynchronize(sL));
-            float resid = 0.f, maxresid = 0.f;
-            for (int k = 0; k < nsub; ++k) {
-                resid += host[k];
-                if (host[k] > maxresid) maxresid = host[k];
-            }
-            if (ch == 0) { chresidtemp = resid; chmaxresidtemp = maxresid; }
-            else {
-                float chresid = resid + chresidtemp, chmaxresid = maxresid + chmaxresidtemp;      // L2389-2396
-                chresid = std::sqrt(chresid / (6 * (levwav)));
-                if (highresi) *highresi = chresid + 0.66f * (std::sqrt(chmaxresid) - chresid);
-                if (nresi) *nresi = chresid;
-            }
-        }
-        return reconstruct_dev(ctx, Cd, ch == 0 ? A : B, sL);
-    };
-
-    // ---- L: shrink the first min(levels,5) levels, reconstruct (L2405-2438); detail recovery on stream `sd`
-    float *Lout = L;
-    auto luma = [&](hipStream_t sd) -> int {
-        if (!denoiseLuminance) return ARTGPU_OK;
-        int rc2;
-        const int nsubL = 3 * (levwav < 5 ? levwav : 5);
-        float *sf = sfc[0], *tmp = tmpc[0];
-        BlurArgs bl = bl0;
-        ShrinkArgs sa = {};
-        sa.coef = Ld.bands; sa.sfave = sf; sa.n = n2; sa.madL = madL; sa.noisevar = nullptr; sa.noisevar_const = noisevarL;
-        // QUALITY_HIGH runs WaveletDenoiseAll_BiShrinkL first (L842-973); its per-band body is ShrinkAllL's (top level included),
-        // and madL is not recomputed in between (L2408-2421): the standard pass simply runs twice
-        DevDecomp Lrec = Ld;                   // what the reconstruction reads
-        if (merged) Lrec.bands = Lbands2;
-        for (int rep = aggressive ? 0 : 1; rep < 2 && !merged; ++rep) {
-            if (fused) {
-                // the first pass reads the decomposition; with a second band set it writes there, and a second pass (QUALITY_HIGH) works on that
-                float *dstb = Lbands2 ? Lbands2 : Ld.bands;
-                if ((rc2 = fused_pass(false, Lrec.bands, dstb, nullptr, madL, nullptr, 0, nsubL, noisevarL, 0.f))) return rc2;
-                Lrec.bands = dstb;
-            } else {
-                HIPCHK(ctx, launch_shrink_sf(sa, nsubL, false, sL));
-                bl.src = sf; bl.dst = tmp;
-                HIPCHK(ctx, launch_hblur(bl, nsubL, sL));
-                bl.src = tmp; bl.sfave = sf; bl.coef = Ld.bands;
-                HIPCHK(ctx, launch_vblur_combine(bl, nsubL, sL));
-            }
-        }
-        if (Lrec.bands != Ld.bands && nsubL < nsub)          // levels beyond the fifth are reconstructed as they are
-            HIPCHK(ctx, hipMemcpyAsync(Lrec.bands + (size_t)nsubL * n2, Ld.bands + (size_t)nsubL * n2, (size_t)(nsub - nsubL) * n2 * 4, hipMemcpyDeviceToDevice, sL));
-        if (do_detail) {
-            // labdn->L is kept as Lin before the reconstruction modifies it (L2423-2432): here the reconstruction writes a second plane
-            // instead of the first being copied
-            if ((rc2 = pool_get(ctx, P_LIN, n * 4, &Lout))) return rc2;
-        }
-        Lrec.cur = Ld.cur;
-        if ((rc2 = reconstruct_dev(ctx, Lrec, Lout, sL))) return rc2;
-        if (do_detail) {
-            float *Lin = L;
-            // ---- detail_recovery (L1479-1635): host-side tables exactly as the reference builds them
-            DetailArgs da = {};
-            da.w = w; da.h = h;
-            da.numblox_W = (int)std::ceil(((float)w) / 25) + 2;
-            da.numblox_H = (int)std::ceil(((float)h) / 25) + 2;
-            const float params_Ldetail = std::min(float(p->luminance_detail), 99.9f);
-            auto compute_detail = [](float dd) -> float { const float t = static_cast<float>((100. - dd) * (100. - dd) + 50. * (100. - dd)) * 64 * 0.5f; return t * t; };
-            da.detail_hi = compute_detail(params_Ldetail);
-            da.detail_lo = compute_detail(0.f);
-            { const int br = int(3 / scale); da.blur_rad = br > 1 ? br : 1; }
-            float *dtab;
-            // the tables are constants: built and uploaded once per context (a slot of their own: the upload needs a stream
-            // synchronisation, i.e. a bubble in the middle of every frame)
-            const bool fresh_dtab = ctx->pool[P_DCTTAB] == nullptr;
-            if ((rc2 = pool_get(ctx, P_DCTTAB, 4 * 4096 * 4, &dtab))) return rc2;
-            if ((rc2 = pool_get(ctx, P_BLOCKS, (size_t)da.numblox_W * da.numblox_H * 4096 * 4, &da.blocks))) return rc2;
-            if (fresh_dtab) {
-                std::vector<float> host(4 * 4096);
-                float *tm_in = host.data(), *tm_out = tm_in + 4096, *ct = tm_out + 4096, *ctt = ct + 4096;
-                const float epsilon = 0.001f / (64 * 64);
-                const int border = 4; // MAX(2, TS/16)
-                for (int i = 0; i < 64; ++i) {
-                    const float i1 = std::abs((i > 32 ? i - 64 + 1 : i));
-                    const float vmask = (i1 < border ? (float)0 + (std::sin((M_PI * i1) / (2 * border)) * std::sin((M_PI * i1) / (2 * border))) : 1.0f);
-                    const float vmask2 = (i1 < 2 * border ? (std::sin((M_PI * i1) / (2 * border)) * std::sin((M_PI * i1) / (2 * border))) : 1.0f);
-                    for (int j = 0; j < 64; ++j) {
-                        const float j1 = std::abs((j > 32 ? j - 64 + 1 : j));
-                        const double sj = std::sin((M_PI * j1) / (2 * border));
-                        tm_in[i * 64 + j] = (vmask * (j1 < border ? sj * sj : 1.0f)) + epsilon;
-                        tm_out[i * 64 + j] = (vmask2 * (j1 < 2 * border ? sj * sj : 1.0f)) + epsilon;
-                        ct[i * 64 + j] = (float)std::cos(M_PI * (j + 0.5) * i / 64.0);
-                        ctt[j * 64 + i] = ct[i * 64 + j];
-                    }
-                }
-                hipError_t e = hipMemcpyAsync(dtab, host.data(), host.size() * 4, hipMemcpyHostToDevice, sL);
-                if (e == hipSuccess) e = hipStreamSynchronize(sL); // host vector goes out of scope
-                if (e != hipSuccess) {     // (see P_LABTABS above)
-                    (void)hipFree(ctx->pool[P_DCTTAB]); ctx->pool[P_DCTTAB] = nullptr; ctx->pool_bytes[P_DCTTAB] = 0;
-                    return fail(ctx, ARTGPU_EHIP, "rgb_denoise: upload of the DCT tables failed: %s", hipGetErrorString(e));
-                }
-            }
-            da.tm_in = dtab; da.tm_out = dtab + 4096; da.costab = dtab + 2 * 4096; da.costab_t = dtab + 3 * 4096;
-            da.L = Lout; da.Lin = Lin;
-            da.plain = ctx->opt_dn_detail_plain == 1 ? 3 : ctx->opt_dn_detail_plain == 2 ? 1 : ctx->opt_dn_detail_plain == 3 ? 2 : 0;
-            if (p->luminance_detail_threshold > 0) {
-                // detail_mask(LL, mask, 65535, 25, 10000, amount, GAUSS, 25 / scale) on the denoised L (FTblockDN.cc:1502-1507)
-                float *dmask;
-                if ((rc2 = pool_get(ctx, P_DMASK, n * 4, &dmask))) return rc2;
-                const float amount = std::max(0.f, std::min(float(p->luminance_detail_threshold) / 100.f, 1.f));
-                float *dm_scratch = tmp;
-                if (!dm_scratch && (rc2 = pool_get(ctx, P_TMP, ((size_t)w * h + 2 * (size_t)(w / 4) * (h / 4)) * 4, &dm_scratch))) return rc2;   // (fused: no `tmp` plane set)
-                if ((rc2 = detail_mask_dev(ctx, Lout, (size_t)w, dmask, w, h, 65535.f, 25.f, 10000.f, amount, (float)(25.f / scale), dm_scratch))) return rc2;
-                da.mask = dmask; da.params_Ldetail = params_Ldetail;
-            }
-            if (sd != sL) {
-                HIPCHK(ctx, hipEventRecord(ctx->dn_ev[0], sL));
-                HIPCHK(ctx, hipStreamWaitEvent(sd, ctx->dn_ev[0], 0));
-            }
-            HIPCHK(ctx, launch_detail_blocks(da, sd));
-            HIPCHK(ctx, launch_detail_gather(da, sd));
-            if (sd != sL) HIPCHK(ctx, hipEventRecord(ctx->dn_ev[1], sd));
-        }
-        return ARTGPU_OK;
-    };
-
-    auto merged_pass = [&]() -> int {
-        FusedShrinkArgs fa = {};
-        fa.coef = Ld.bands; fa.coef_out = Lbands2; fa.coefC = Cdd[0].bands; fa.coefL = Ld.bands; fa.n = n2; fa.w = w2; fa.h = h2;
-        fa.madL = madL; fa.madab = merged_mad ? mad + nsub : mad + 32; fa.mad_ch_stride = nsub;
-        fa.noisevar = ccalc_dev; fa.noisevar_nonneg = ctx->ccalc_nonneg; fa.noisevar_const = noisevarL; fa.noisevar_scale = maxNoiseVarab;
-        fa.noisevar_ab[0] = noisevar_abc[0]; fa.noisevar_ab[1] = noisevar_abc[1];
-        fa.useNoiseCCurve = useNoiseCCurve ? 1 : 0;
-        for (int l = 0; l < 10; ++l) fa.rad[l] = bl0.rad[l];
-        fa.level0 = 0; fa.nsub = 3 * nsub; fa.nL = nsub; fa.nsub_ch = nsub; fa.diag = ctx->fs_diag; fa.wait_ticks = (long long)ctx->opt_dn_wait_ms * 100000LL; fa.stall_band = ctx->opt_dn_debug_stall < 0 ? -1 : ctx->opt_dn_debug_stall >> 16; fa.stall_strip = ctx->opt_dn_debug_stall < 0 ? -1 : ctx->opt_dn_debug_stall & 0xffff;
-        HIPCHK(ctx, launch_shrink_blur(fa, fused_scratch, sL));
-        return ARTGPU_OK;
-    };
-    if (merged) {
+    DnRun run = {ctx, pl, b, fu, p, scale, nresi, highresi, sL, {0.f, 0.f}, 0.f, 0.f, b.L};
+    if (pl.merged) {
         // decompositions and MADs of a and b, the three channels' ShrinkAll passes as one launch, then the reconstructions -- L first, so that
         // its DCT detail recovery (side stream) runs beside those of a and b
-        if ((rc = chroma_front(0)) || (rc = chroma_front(1))) return rc;
+        if ((rc = run.chroma_front(0)) || (rc = run.chroma_front(1))) return rc;
         // MadRgb of all three channels' bands as one launch set (the bands are back to back: L, a, b; the medians land at mad + band)
-        if (merged_mad) HIPCHK(ctx, launch_mad(Ld.bands, n2, 3 * nsub, reinterpret_cast<int *>(histo_fc[0]), mad, sL));
-        if ((rc = merged_pass())) return rc;
+        if (pl.merged_mad) HIPCHK(ctx, launch_mad(b.Ld.bands, pl.n2, 3 * pl.nsub, reinterpret_cast<int *>(b.histo_fc[0]), b.mad, sL));
+        if ((rc = run.merged_pass())) return rc;
         SideStreamJoin dn_join;
-        if (fork) dn_join.arm(ctx->dn_stream[0]);
-        if ((rc = luma(fork ? ctx->dn_stream[0] : sL))) return rc;
-        if ((rc = chroma_back(0)) || (rc = chroma_back(1))) return rc;
-        if (fork) {
+        if (pl.fork) dn_join.arm(ctx->dn_stream[0]);
+        if ((rc = run.luma(pl.fork ? ctx->dn_stream[0] : sL))) return rc;
+        if ((rc = run.chroma_back(0)) || (rc = run.chroma_back(1))) return rc;
+        if (pl.fork) {
             HIPCHK(ctx, hipStreamWaitEvent(sL, ctx->dn_ev[1], 0));
             dn_join.disarm();
         }
-    } else if (!fork) {
+    } else if (!pl.fork) {
         // the reference's order
         for (int ch = 0; ch < 2; ++ch)
-            if ((rc = chroma_front(ch)) || (rc = chroma_back(ch))) return rc;
-        if ((rc = luma(sL))) return rc;
+            if ((rc = run.chroma_front(ch)) || (rc = run.chroma_back(ch))) return rc;
+        if ((rc = run.luma(sL))) return rc;
     } else {
-        if ((rc = chroma_front(0)) || (rc = chroma_front(1))) return rc;      // the last readers of the untouched L coefficients
+        if ((rc = run.chroma_front(0)) || (rc = run.chroma_front(1))) return rc;      // the last readers of the untouched L coefficients
         SideStreamJoin dn_join;
         dn_join.arm(ctx->dn_stream[0]);                                       // any return below leaves with the side stream drained
-        if ((rc = luma(ctx->dn_stream[0]))) return rc;
-        if ((rc = chroma_back(0)) || (rc = chroma_back(1))) return rc;
+        if ((rc = run.luma(ctx->dn_stream[0]))) return rc;
+        if ((rc = run.chroma_back(0)) || (rc = run.chroma_back(1))) return rc;
         HIPCHK(ctx, hipStreamWaitEvent(sL, ctx->dn_ev[1], 0));                // join: the context's stream is behind all the work of the call
         dn_join.disarm();
     }
-    px.L = Lout;
+    px.L = run.Lout;
 
     // ---- back to RGB (L2502-2550)
     HIPCHK(ctx, launch_yuv2rgb(px, ctx->stream));
+    return ARTGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_params *p, const float ws[9], const float *iws,
+                       double expcomp, double scale, const artgpu_plane *ccalc, uint32_t flags,
+                       float *nresi, float *highresi)
+{
+    StageScope scope_(ctx, "denoise::RGB_denoise");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!img || !p || !ws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: null argument");
+    int rc = rgb_denoise_args_ok(ctx, p, iws, scale);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevRGB d;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "rgb_denoise"))) return rc;
+    if ((rc = rgb_denoise_dev(ctx, d, p, ws, iws, expcomp, scale, ccalc, flags, nresi, highresi, DnFusion{}))) return rc;
     return unbind_rgb(ctx, img, &d);
 }
 
@@ -1812,7 +1970,6 @@ int artgpu_guided_filter(artgpu_ctx *ctx, const artgpu_plane *guide, const artgp
     return ARTGPU_OK;
 }
 
-static int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out);
 // RawImageSource::vng4_demosaic on device planes (vng4_demosaic_RT.cc:62-397)
 static int vng4_dev(artgpu_ctx *ctx, const float *raw, size_t raw_stride, float *r, float *g, float *b, size_t out_stride, int W, int H, uint32_t filters)
 {
@@ -2408,29 +2565,19 @@ int artgpu_noise_curve_lut(const double *points, int npoints, float lut[501], fl
     return ARTGPU_OK;
 }
 
-// fills P_CCMAP ((w+1)/2 x (h+1)/2, contiguous) from device planes
+// fills P_CCMAP ((w+1)/2 x (h+1)/2, contiguous) from device planes, or, with `gi` on, from the demosaiced planes getImage would have read
 static int chroma_map_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int w, int h, const double *mat, const double ws[9],
-                          const float *curve, float **out)
+                          const float *curve, const GetImageFuse &gi, float **out)
 {
     const int wid = (w + 1) / 2, hei = (h + 1) / 2;
     float *map, *tab;
     int rc;
-    const bool fresh = ctx->pool[P_CACHEF] == nullptr;
-    if ((rc = pool_get(ctx, P_CCMAP, (size_t)wid * hei * 4, &map)) || (rc = pool_get(ctx, P_CACHEF, (65536 + 512) * 4, &tab))) return rc;
-    if (fresh) {
-        std::vector<float> host(65536);
-        build_cachef(host.data());
-        ctx->ncurve_host.clear();
-        hipError_t e = hipMemcpyAsync(tab, host.data(), 65536 * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // host vector goes out of scope
-        if (e != hipSuccess) {      // the slot is the "table uploaded" flag: give it back
-            (void)hipFree(ctx->pool[P_CACHEF]); ctx->pool[P_CACHEF] = nullptr; ctx->pool_bytes[P_CACHEF] = 0;
-            return fail(ctx, ARTGPU_EHIP, "chroma map: upload of the cachef table failed: %s", hipGetErrorString(e));
-        }
-    }
+    // P_CACHEF: [cachef, 65536 | the caller's noise curve, 512]; a slot that has just been made holds no curve
+    if (!ctx->pool[P_CACHEF]) ctx->ncurve_host.clear();
+    if ((rc = pool_get(ctx, P_CCMAP, (size_t)wid * hei * 4, &map)) || (rc = const_table_dev(ctx, P_CACHEF, 65536 + 512, build_cachef, "cachef table", &tab))) return rc;
     // the same curve frame after frame is uploaded once: the copy needs a stream synchronisation (the caller's curve may be a
     // temporary), i.e. a bubble in the middle of every frame
-    if (fresh || ctx->ncurve_host.size() != 501 || std::memcmp(ctx->ncurve_host.data(), curve, 501 * 4) != 0) {
+    if (ctx->ncurve_host.size() != 501 || std::memcmp(ctx->ncurve_host.data(), curve, 501 * 4) != 0) {
         ctx->ncurve_host.assign(curve, curve + 501);
         hipError_t e = hipMemcpyAsync(tab + 65536, ctx->ncurve_host.data(), 501 * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -2440,7 +2587,7 @@ static int chroma_map_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride
         }
     }
     ChromaMapArgs a = {};
-    a.gi = ctx->fuse_gi;
+    a.gi = gi;
     for (int k = 0; k < 3; ++k) a.src[k] = planes[k];
     a.stride = stride; a.wid = wid; a.hei = hei;
     a.has_mat = mat ? 1 : 0;
@@ -2448,24 +2595,6 @@ static int chroma_map_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride
     a.cachef = tab; a.curve = tab + 65536; a.out = map; a.no_lds_lut = !ctx->opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
     HIPCHK(ctx, launch_chroma_map(a, ctx->stream));
     *out = map;
-    return ARTGPU_OK;
-}
-
-// Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab on the device, built on the host like the reference's (color.cc:202-292)
-static int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out)
-{
-    float *tabs;
-    const bool fresh = ctx->pool[P_LABTABS] == nullptr;
-    int rc = pool_get(ctx, P_LABTABS, 4 * 65536 * 4, &tabs);
-    if (rc) return rc;
-    if (fresh) {
-        std::vector<float> host(4 * 65536);
-        build_cachef(host.data()); build_cachefy(host.data() + 65536);
-        build_denoise_gamma_tabs(host.data() + 2 * 65536, host.data() + 3 * 65536);
-        HIPCHK(ctx, hipMemcpyAsync(tabs, host.data(), host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    *tabs_out = tabs;
     return ARTGPU_OK;
 }
 
@@ -2639,82 +2768,27 @@ int artgpu_denoise_chroma_map(artgpu_ctx *ctx, const artgpu_rgb *img, const doub
     const int wid = (d.w + 1) / 2, hei = (d.h + 1) / 2;
     if (!plane_ok(ccalc) || ccalc->w != wid || ccalc->h != hei) return fail(ctx, ARTGPU_EINVAL, "denoise_chroma_map: ccalc must be %dx%d", wid, hei);
     float *map;
-    if ((rc = chroma_map_dev(ctx, d.p, d.stride, d.w, d.h, calclum_mat, ws, noise_c_curve, &map))) return rc;
+    if ((rc = chroma_map_dev(ctx, d.p, d.stride, d.w, d.h, calclum_mat, ws, noise_c_curve, GetImageFuse{}, &map))) return rc;
     HIPCHK(ctx, hipMemcpy2DAsync(ccalc->p, (size_t)ccalc->row_stride_bytes, map, (size_t)wid * 4, (size_t)wid * 4, hei,
                                  ccalc->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
     if (!ccalc->on_device) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return ARTGPU_OK;
 }
 
-int artgpu_improc_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_tool_params *p, const double ws[9], const double *iws,
-                          double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags)
+// useNoiseCCurve (FTblockDN.cc:1672): the chroma noise curve counts when NoiseCurve::getSum (ipdenoise.cc:698) of its 501 entries is above 5
+static bool noise_curve_on(const float *curve)
 {
-    return artgpu_improc_denoise_fused(ctx, img, nullptr, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags);
+    if (!curve) return false;
+    float sum = 0.f;
+    for (int i = 0; i < 501; ++i) sum += curve[i];
+    return sum > 5.f;
 }
 
-int artgpu_improc_denoise_fused(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_fusion *fu, const artgpu_denoise_tool_params *p,
-                                const double ws[9], const double *iws, double ecomp, double scale, const double *calclum_mat,
-                                const float *noise_c_curve, uint32_t flags)
+// ImProcFunctions::denoise on device planes; `fu0`: what artgpu_improc_denoise_fused has decided to fuse of the stages around the tool (the
+// tool's own expcomp passes and `ccalc_nonneg` are decided here)
+static int improc_denoise_dev(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_tool_params *p, const double ws[9], const double *iws,
+                              double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags, const DnFusion &fu0)
 {
-    StageScope scope_(ctx, "ImProcFunctions::denoise");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!img || !p || !ws) return fail(ctx, ARTGPU_EINVAL, "improc_denoise: null argument");
-    // what of the neighbouring stages can really live inside the tool's pixel passes: the wavelet denoise has to run (its first pass reads the
-    // image, its last one writes it), on device planes; the exposure only when nothing stands between RGB_denoise and it
-    bool use_curve0 = false;
-    if (noise_c_curve) {
-        float sum = 0.f;
-        for (int i = 0; i < 501; ++i) sum += noise_c_curve[i];
-        use_curve0 = sum > 5.f;                                        // (as below: NoiseCurve::getSum, FTblockDN.cc:1672)
-    }
-    const bool dn_runs0 = !(p->dn.luminance == 0 && p->dn.chrominance == 0 && !use_curve0);
-    const bool dev_planes = img->r.on_device && (!fu || !fu->demosaiced || (fu->demosaiced->r.on_device && fu->demosaiced->g.on_device && fu->demosaiced->b.on_device));
-    bool fuse_gi = fu && fu->demosaiced && dn_runs0 && dev_planes;
-    const bool fuse_exp = fu && fu->exposure_enabled && dn_runs0 && dev_planes && !p->smoothing_enabled;
-    // with guided smoothing / NL-means behind the wavelet denoise the tool's last pixel pass is setMode(RGB) or its own expcomp(-ecomp):
-    // the exposure rides on that one
-    const bool tail_exp = fu && fu->exposure_enabled && dn_runs0 && dev_planes && p->smoothing_enabled && (p->nl_strength || ecomp > 0);
-    if (fu && fu->demosaiced) {
-        const artgpu_rgb *dm = fu->demosaiced;
-        if (!plane_ok(&dm->r) || !plane_ok(&dm->g) || !plane_ok(&dm->b) || dm->g.row_stride_bytes != dm->r.row_stride_bytes || dm->b.row_stride_bytes != dm->r.row_stride_bytes ||
-            fu->sx1 < 0 || fu->sy1 < 0 || fu->sx1 + img->r.w > dm->r.w || fu->sy1 + img->r.h > dm->r.h)
-            return fail(ctx, ARTGPU_EINVAL, "improc_denoise_fused: crop %dx%d+%d+%d outside the demosaiced planes", img->r.w, img->r.h, fu->sx1, fu->sy1);
-        if (!fuse_gi) {     // the separate call it stands for
-            int rc0 = artgpu_get_image(ctx, dm, fu->sx1, fu->sy1, fu->mul, fu->do_clip, fu->cam_to_work, img);
-            if (rc0) return rc0;
-        }
-    }
-    if (fu && (fu->demosaiced || fu->exposure_enabled)) {
-        // one level down with what is left to fuse; the exposure that could not be fused follows as its own call
-        struct Restore { artgpu_ctx *c; ~Restore() { c->fuse_gi.on = 0; c->fuse_exp_on = 0; c->tail_exp_on = 0; } } restore{ctx};
-        if (fuse_gi) {
-            GetImageFuse &g = ctx->fuse_gi;
-            g.on = 1;
-            g.src[0] = fu->demosaiced->r.p; g.src[1] = fu->demosaiced->g.p; g.src[2] = fu->demosaiced->b.p;
-            g.stride = (size_t)(fu->demosaiced->r.row_stride_bytes / 4);
-            g.sx1 = fu->sx1; g.sy1 = fu->sy1;
-            for (int k = 0; k < 3; ++k) g.mul[k] = fu->mul[k];
-            g.do_clip = fu->do_clip ? 1 : 0; g.has_mat = fu->cam_to_work ? 1 : 0;
-            for (int k = 0; k < 9; ++k) g.mat[k] = fu->cam_to_work ? fu->cam_to_work[k] : 0.0;
-        }
-        if (fuse_exp) { ctx->fuse_exp_on = 1; ctx->fuse_exp_scale = fu->exp_scale; ctx->fuse_exp_black = fu->black; }
-        if (tail_exp) { ctx->tail_exp_on = 1; ctx->tail_exp_scale = fu->exp_scale; ctx->tail_exp_black = fu->black; }
-        int rc0 = artgpu_improc_denoise_fused(ctx, img, nullptr, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags);
-        if (rc0) return rc0;
-        if (fu->exposure_enabled && !fuse_exp && !tail_exp) return artgpu_exposure(ctx, img, fu->exp_scale, fu->black);
-        return ARTGPU_OK;
-    }
-    if (!img->r.on_device) {
-        // host planes: stage once, run the whole tool on the staged copy, copy back
-        DevRGB d;
-        int rc0 = bind_rgb(ctx, img, 4, true, &d, "improc_denoise");
-        if (rc0) return rc0;
-        artgpu_rgb dv;
-        artgpu_plane *pl[3] = {&dv.r, &dv.g, &dv.b};
-        for (int k = 0; k < 3; ++k) { pl[k]->p = d.p[k]; pl[k]->w = d.w; pl[k]->h = d.h; pl[k]->row_stride_bytes = (int64_t)d.stride * 4; pl[k]->on_device = 1; }
-        if ((rc0 = artgpu_improc_denoise(ctx, &dv, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags))) return rc0;
-        return unbind_rgb(ctx, img, &d);
-    }
     float wsf[9];
     for (int k = 0; k < 9; ++k) wsf[k] = (float)ws[k];
     int rc;
@@ -2737,38 +2811,40 @@ int artgpu_improc_denoise_fused(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_d
     }
     p = &adj;
     artgpu_plane ccalc = {}, *ccalc_p = nullptr;
-    if (noise_c_curve) {
-        float sum = 0.f;
-        for (int i = 0; i < 501; ++i) sum += noise_c_curve[i];      // NoiseCurve::getSum (ipdenoise.cc:698)
-        if (sum > 5.f) {                                            // useNoiseCCurve, FTblockDN.cc:1672
-            float *pl[3] = {img->r.p, img->g.p, img->b.p}, *map;
-            if (img->g.row_stride_bytes != img->r.row_stride_bytes || img->b.row_stride_bytes != img->r.row_stride_bytes)
-                return fail(ctx, ARTGPU_EINVAL, "improc_denoise: planes must share one row stride");
-            if ((rc = chroma_map_dev(ctx, pl, (size_t)(img->r.row_stride_bytes / 4), img->r.w, img->r.h, calclum_mat, ws, noise_c_curve, &map))) return rc;
-            ccalc.p = map; ccalc.w = (img->r.w + 1) / 2; ccalc.h = (img->r.h + 1) / 2; ccalc.row_stride_bytes = (int64_t)ccalc.w * 4; ccalc.on_device = 1;
-            ccalc_p = &ccalc;
-        }
+    if (noise_curve_on(noise_c_curve)) {
+        float *pl[3] = {img->r.p, img->g.p, img->b.p}, *map;
+        if (img->g.row_stride_bytes != img->r.row_stride_bytes || img->b.row_stride_bytes != img->r.row_stride_bytes)
+            return fail(ctx, ARTGPU_EINVAL, "improc_denoise: planes must share one row stride");
+        if ((rc = chroma_map_dev(ctx, pl, (size_t)(img->r.row_stride_bytes / 4), img->r.w, img->r.h, calclum_mat, ws, noise_c_curve, fu0.gi, &map))) return rc;
+        ccalc.p = map; ccalc.w = (img->r.w + 1) / 2; ccalc.h = (img->r.h + 1) / 2; ccalc.row_stride_bytes = (int64_t)ccalc.w * 4; ccalc.on_device = 1;
+        ccalc_p = &ccalc;
     }
     // expcomp(+ecomp) / expcomp(-ecomp) (ipdenoise.cc:1161-1163,1181-1184) are fused into RGB_denoise's first and last pixel
-    // passes when RGB_denoise will actually run them (same operations on the same values, two fewer passes over the image)
+    // passes when RGB_denoise will actually run them (same operations on the same values, two fewer passes over the image).
+    // (Whether it runs is asked of the ADJUSTED strengths here and of the caller's in artgpu_improc_denoise_fused: both are kept, see there.)
     const bool dn_runs = !(p->dn.luminance == 0 && p->dn.chrominance == 0 && !ccalc_p);
     const bool fuse_pre = ecomp > 0 && dn_runs, fuse_post = fuse_pre && !p->smoothing_enabled;
     if (ecomp > 0 && !fuse_pre) { if ((rc = artgpu_exposure(ctx, img, (float)std::pow(2.0, ecomp), 0.f))) return rc; }
-    ctx->fuse_pre = fuse_pre ? (float)std::pow(2.0, ecomp) : 0.f;
-    ctx->fuse_post = fuse_post ? (float)std::pow(2.0, -ecomp) : 0.f;
+    DnFusion fu = fu0;
+    fu.pre_scale = fuse_pre ? (float)std::pow(2.0, ecomp) : 0.f;
+    fu.post_scale = fuse_post ? (float)std::pow(2.0, -ecomp) : 0.f;
+    fu.ccalc_nonneg = ccalc_p ? 1 : 0;
     float iwsf[9];
     if (iws) for (int k = 0; k < 9; ++k) iwsf[k] = (float)iws[k];
-    ctx->ccalc_nonneg = ccalc_p ? 1 : 0;
-    rc = artgpu_rgb_denoise(ctx, img, &p->dn, wsf, iws ? iwsf : nullptr, 0.0, scale, ccalc_p, flags, nullptr, nullptr);
-    ctx->ccalc_nonneg = 0;
-    ctx->fuse_pre = ctx->fuse_post = 0.f;
-    if (rc) return rc;
+    {
+        StageScope scope_(ctx, "denoise::RGB_denoise");
+        if ((rc = rgb_denoise_args_ok(ctx, &p->dn, iws ? iwsf : nullptr, scale))) return rc;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        DevRGB d;
+        if ((rc = bind_rgb(ctx, img, 4, true, &d, "rgb_denoise"))) return rc;       // (device planes: nothing is staged)
+        if ((rc = rgb_denoise_dev(ctx, d, &p->dn, wsf, iws ? iwsf : nullptr, 0.0, scale, ccalc_p, flags, nullptr, nullptr, fu))) return rc;
+    }
     // the exposure steps behind the tool's last stage -- its own expcomp(-ecomp) (L1181-1184) where yuv2rgb could not take it, and the STAGE_1
     // exposure of artgpu_improc_denoise_fused -- ride on the last pixel pass there is: setMode(RGB) behind NL-means, or one exposure pass
     int chain_n = 0;
     float chain_scale[2], chain_black[2];
     if (ecomp > 0 && !fuse_post) { chain_scale[chain_n] = (float)std::pow(2.0, -ecomp); chain_black[chain_n] = 0.f; ++chain_n; }
-    if (ctx->tail_exp_on) { chain_scale[chain_n] = ctx->tail_exp_scale; chain_black[chain_n] = ctx->tail_exp_black; ++chain_n; }
+    if (fu.tail_on) { chain_scale[chain_n] = fu.tail_scale; chain_black[chain_n] = fu.tail_black; ++chain_n; }
     bool chained = false;
     if (p->smoothing_enabled) {
         if ((rc = artgpu_denoise_guided_smoothing(ctx, img, ws, p->guided_chroma_radius, scale))) return rc;
@@ -2798,6 +2874,65 @@ int artgpu_improc_denoise_fused(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_d
         HIPCHK(ctx, launch_exposure(a, ctx->stream));
     }
     return ARTGPU_OK;
+}
+
+int artgpu_improc_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_tool_params *p, const double ws[9], const double *iws,
+                          double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags)
+{
+    return artgpu_improc_denoise_fused(ctx, img, nullptr, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags);
+}
+
+int artgpu_improc_denoise_fused(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_fusion *fu, const artgpu_denoise_tool_params *p,
+                                const double ws[9], const double *iws, double ecomp, double scale, const double *calclum_mat,
+                                const float *noise_c_curve, uint32_t flags)
+{
+    StageScope scope_(ctx, "ImProcFunctions::denoise");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!img || !p || !ws) return fail(ctx, ARTGPU_EINVAL, "improc_denoise: null argument");
+    // what of the neighbouring stages can really live inside the tool's pixel passes: the wavelet denoise has to run (its first pass reads the
+    // image, its last one writes it), on device planes; the exposure only when nothing stands between RGB_denoise and it.
+    // `dn_runs0` asks the caller's strengths, improc_denoise_dev's `dn_runs` the ones adjust_params has scaled.  adjust_params maps 0 to 0 and
+    // any other strength to another one of the same sign, so the two agree for every strength and scale a caller can mean; they part only
+    // where the arithmetic underflows (a denormal strength, an infinite scale).  Both are kept as they were.
+    const bool dn_runs0 = !(p->dn.luminance == 0 && p->dn.chrominance == 0 && !noise_curve_on(noise_c_curve));
+    const bool dev_planes = img->r.on_device && (!fu || !fu->demosaiced || (fu->demosaiced->r.on_device && fu->demosaiced->g.on_device && fu->demosaiced->b.on_device));
+    const bool fuse_gi = fu && fu->demosaiced && dn_runs0 && dev_planes;
+    const bool fuse_exp = fu && fu->exposure_enabled && dn_runs0 && dev_planes && !p->smoothing_enabled;
+    // with guided smoothing / NL-means behind the wavelet denoise the tool's last pixel pass is setMode(RGB) or its own expcomp(-ecomp):
+    // the exposure rides on that one
+    const bool tail_exp = fu && fu->exposure_enabled && dn_runs0 && dev_planes && p->smoothing_enabled && (p->nl_strength || ecomp > 0);
+    int rc;
+    DnFusion f = {};
+    if (fu && fu->demosaiced) {
+        const artgpu_rgb *dm = fu->demosaiced;
+        if (!plane_ok(&dm->r) || !plane_ok(&dm->g) || !plane_ok(&dm->b) || dm->g.row_stride_bytes != dm->r.row_stride_bytes || dm->b.row_stride_bytes != dm->r.row_stride_bytes ||
+            fu->sx1 < 0 || fu->sy1 < 0 || fu->sx1 + img->r.w > dm->r.w || fu->sy1 + img->r.h > dm->r.h)
+            return fail(ctx, ARTGPU_EINVAL, "improc_denoise_fused: crop %dx%d+%d+%d outside the demosaiced planes", img->r.w, img->r.h, fu->sx1, fu->sy1);
+        if (fuse_gi) {
+            GetImageFuse &g = f.gi;
+            g.on = 1;
+            g.src[0] = dm->r.p; g.src[1] = dm->g.p; g.src[2] = dm->b.p;
+            g.stride = (size_t)(dm->r.row_stride_bytes / 4);
+            g.sx1 = fu->sx1; g.sy1 = fu->sy1;
+            for (int k = 0; k < 3; ++k) g.mul[k] = fu->mul[k];
+            g.do_clip = fu->do_clip ? 1 : 0; g.has_mat = fu->cam_to_work ? 1 : 0;
+            for (int k = 0; k < 9; ++k) g.mat[k] = fu->cam_to_work ? fu->cam_to_work[k] : 0.0;
+        } else if ((rc = artgpu_get_image(ctx, dm, fu->sx1, fu->sy1, fu->mul, fu->do_clip, fu->cam_to_work, img))) {     // the separate call it stands for
+            return rc;
+        }
+    }
+    if (fuse_exp) { f.exp_on = 1; f.exp_scale = fu->exp_scale; f.exp_black = fu->black; }
+    if (tail_exp) { f.tail_on = 1; f.tail_scale = fu->exp_scale; f.tail_black = fu->black; }
+    // host planes: stage once, run the whole tool on the staged copy, copy back (device planes are used in place)
+    DevRGB d;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "improc_denoise"))) return rc;
+    artgpu_rgb dv;
+    artgpu_plane *pl[3] = {&dv.r, &dv.g, &dv.b};
+    for (int k = 0; k < 3; ++k) { pl[k]->p = d.p[k]; pl[k]->w = d.w; pl[k]->h = d.h; pl[k]->row_stride_bytes = (int64_t)d.stride * 4; pl[k]->on_device = 1; }
+    if ((rc = improc_denoise_dev(ctx, &dv, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags, f))) return rc;
+    // the exposure that could not be fused follows as its own call
+    if (fu && fu->exposure_enabled && !fuse_exp && !tail_exp && (rc = artgpu_exposure(ctx, &dv, fu->exp_scale, fu->black))) return rc;
+    return unbind_rgb(ctx, img, &d);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -534,6 +534,87 @@ def test_improc_denoise_fused_equals_the_separate_calls(gpu_ctx, w, h, smoothing
     assert _same([t.cpu().numpy() for t in d_img], ref) == [0, 0, 0]
 
 
+def _fused_call(ctx, dem, w, h, tp, ecomp=0.3):
+    """improc_denoise_fused on device planes with getImage + matrix in front and the exposure behind (the arguments of the 300 x 260 case
+    above); returns the planes on the host"""
+    import torch
+    mat = np.array([[0.6325, 0.2312, 0.0921], [0.2198, 0.7712, 0.0090], [0.0166, 0.0713, 0.7514]])
+    curve, _ = capi.noise_curve_lut()
+    d_dem = [torch.from_numpy(p).cuda() for p in dem]
+    d_img = [torch.full((h, w), float("nan"), dtype=torch.float32, device="cuda") for _ in range(3)]
+    ctx.improc_denoise_fused(capi.RGB(*[capi.device_plane(t) for t in d_img]), tp, O.REC2020_WS_D,
+                             demosaiced=capi.RGB(*[capi.device_plane(t) for t in d_dem]), sx1=4, sy1=4, mul=(2.1374, 1.0, 1.5918), do_clip=True,
+                             cam_to_work=mat, exposure=(float(np.float32(2.0 ** 0.3)), 12.5), ecomp=ecomp, calclum_mat=mat, noise_c_curve=curve,
+                             flags=capi.DN_SKIP_DETAIL_RECOVERY)
+    torch.cuda.synchronize()
+    return [t.cpu().numpy() for t in d_img]
+
+
+def test_fusion_does_not_outlive_the_call():
+    """What artgpu_improc_denoise_fused fuses into the tool's pixel passes belongs to that one call: after fused calls of both forms (front +
+    exposure in rgb2yuv / yuv2rgb; the exposure on the tail pass behind NL-means) and one that fails inside RGB_denoise after the fusion has
+    been decided, the plain entry points compute on that context what they compute on a fresh one."""
+    w, h = 300, 260                      # the merged one-launch form of the shrink passes
+    dem = _rgb(w + 8, h + 8, w)
+    img = _rgb(w, h, 7)
+    curve, _ = capi.noise_curve_lut()
+    rng = np.random.default_rng(0)
+    ccalc = (1.0 + 4.0 * rng.uniform(0.01, 0.5, ((h + 1) // 2, (w + 1) // 2))).astype(np.float32) ** 2
+    mat = np.array([[0.6325, 0.2312, 0.0921], [0.2198, 0.7712, 0.0090], [0.0166, 0.0713, 0.7514]])
+
+    def plain_calls(ctx):
+        a = [p.copy() for p in img]
+        ctx.rgb_denoise(capi.host_rgb(a), _params(), O.REC2020_WS, ccalc=capi.host_plane(ccalc))
+        m = np.zeros(((h + 1) // 2, (w + 1) // 2), np.float32)
+        ctx.denoise_chroma_map(capi.host_rgb(img), mat, O.REC2020_WS_D, curve, capi.host_plane(m))
+        c = [p.copy() for p in img]
+        ctx.improc_denoise(capi.host_rgb(c), capi.DenoiseToolParams(_params(), 0, 3, 0, 80), O.REC2020_WS_D, ecomp=0.3, calclum_mat=mat,
+                           noise_c_curve=curve, flags=capi.DN_SKIP_DETAIL_RECOVERY)
+        return a + [m] + c
+
+    used, fresh = capi.Context(0), capi.Context(0)
+    try:
+        out = _fused_call(used, dem, w, h, capi.DenoiseToolParams(_params(luminance=0.0), 0, 3, 0, 80))
+        assert all(np.isfinite(p).all() for p in out)
+        out = _fused_call(used, dem, w, h, capi.DenoiseToolParams(_params(), 1, 3, 50, 80))
+        assert all(np.isfinite(p).all() for p in out)
+        with pytest.raises(capi.ArtGpuError):
+            _fused_call(used, dem, w, h, capi.DenoiseToolParams(_params(color_space=2), 0, 3, 0, 80))
+        got, ref = plain_calls(used), plain_calls(fresh)
+    finally:
+        used.close()
+        fresh.close()
+    assert _same(got, ref) == [0] * 7
+    assert ref[3].any() and not any(np.array_equal(r, p) for r, p in zip(ref[:3] + ref[4:], img + img))
+
+
+def test_one_progress_pair_per_call(gpu_ctx):
+    """artgpu.h promises one (name, 0.0) / (name, 1.0) pair per entry point: the fused tool and its host-plane form report
+    ImProcFunctions::denoise once around everything else, and the RGB_denoise they run once inside it."""
+    w, h = 300, 260
+    dem = _rgb(w + 8, h + 8, w)
+    curve, _ = capi.noise_curve_lut()
+    tp = capi.DenoiseToolParams(_params(), 0, 3, 0, 80)
+    host = [p.copy() for p in _rgb(w, h, 7)]
+    calls = {
+        "fused, device planes": lambda: _fused_call(gpu_ctx, dem, w, h, tp),
+        "host planes": lambda: gpu_ctx.improc_denoise(capi.host_rgb(host), tp, O.REC2020_WS_D, ecomp=0.3, noise_c_curve=curve,
+                                                      flags=capi.DN_SKIP_DETAIL_RECOVERY),
+    }
+    for what, call in calls.items():
+        events = []
+        gpu_ctx.set_progress_callback(lambda stage, frac: events.append((stage, frac)))
+        try:
+            call()
+        finally:
+            gpu_ctx.set_progress_callback(None)
+        tool, inner = "ImProcFunctions::denoise", "denoise::RGB_denoise"
+        assert events[0] == (tool, 0.0) and events[-1] == (tool, 1.0), (what, events)
+        for ev in ((tool, 0.0), (tool, 1.0), (inner, 0.0), (inner, 1.0)):
+            assert events.count(ev) == 1, (what, ev, events)
+        assert 0 < events.index((inner, 0.0)) < events.index((inner, 1.0)) < len(events) - 1, (what, events)
+
+
 def test_trim_scratch_gives_the_pool_back_and_the_next_call_rebuilds_it():
     """artgpu_trim_scratch (round 5): the context's arenas / staging / pool go back to the driver, the next call grows them again and rebuilds
     the tables that lived there (gamma pair, chroma noise curve table) -- same bits; the fused pass's hand-over ring is a few MB, not a slot
