@@ -93,6 +93,56 @@ class TextureBoostInfo(C.Structure):
                 ("kernel_size", C.c_int32), ("minval", C.c_float), ("strength", C.c_float), ("strength2", C.c_float)]
 
 
+class ColorCorrectionRegion(C.Structure):
+    """artgpu_color_correction_region: one ColorCorrectionParams::Region and its two blend planes"""
+    _fields_ = [("mode", C.c_int32), ("rgbluminance", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("in_saturation", C.c_double),
+                ("out_saturation", C.c_double), ("hueshift", C.c_double), ("hsl_gamma", C.c_double), ("slope", C.c_double * 3),
+                ("offset", C.c_double * 3), ("power", C.c_double * 3), ("pivot", C.c_double * 3), ("compression", C.c_double * 3),
+                ("hue", C.c_double * 3), ("sat", C.c_double * 3), ("factor", C.c_double * 3), ("lmask", C.POINTER(Plane)),
+                ("abmask", C.POINTER(Plane))]
+
+
+class ColorCorrectionInfo(C.Structure):
+    """artgpu_color_correction_info, one per region"""
+    _fields_ = [("abca", C.c_float), ("abcb", C.c_float), ("enabled", C.c_int32), ("rgbmode", C.c_int32), ("slope", C.c_float * 3),
+                ("offset", C.c_float * 3), ("power", C.c_float * 3), ("pivot", C.c_float * 3), ("compression", C.c_float * 6), ("rhs", C.c_float),
+                ("oor_pixels", C.c_int64)]
+
+
+CC_YUV, CC_RGB, CC_HSL, CC_JZAZBZ, CC_LUT = 0, 1, 2, 3, 4
+CC_MODES = {"yuv": CC_YUV, "rgb": CC_RGB, "hsl": CC_HSL, "jzazbz": CC_JZAZBZ, "lut": CC_LUT}
+
+
+def color_correction_regions(regions):
+    """[dict, ...] -> (ColorCorrectionRegion array, objects to keep alive with it).  A dict holds Region's fields under the names of
+    ColorCorrectionRegion with Region's defaults (procparams.cc:2834-2855) for what it leaves out: mode JZAZBZ (an ARTGPU_CC_* value or its
+    name), slope / power / pivot 1, hsl_gamma 2.4, everything else 0; a per-channel field takes one number for all three channels or three;
+    lmask / abmask are Planes or None."""
+    arr = (ColorCorrectionRegion * max(len(regions), 1))()
+    keep = []
+    for k, r in enumerate(regions):
+        r = dict(r)
+        a = arr[k]
+        mode = r.pop("mode", CC_JZAZBZ)
+        a.mode = CC_MODES[mode.lower()] if isinstance(mode, str) else int(mode)
+        a.rgbluminance = 1 if r.pop("rgbluminance", False) else 0
+        for name, dflt in (("a", 0.0), ("b", 0.0), ("in_saturation", 0.0), ("out_saturation", 0.0), ("hueshift", 0.0), ("hsl_gamma", 2.4)):
+            setattr(a, name, float(r.pop(name, dflt)))
+        for name, dflt in (("slope", 1.0), ("offset", 0.0), ("power", 1.0), ("pivot", 1.0), ("compression", 0.0), ("hue", 0.0), ("sat", 0.0),
+                           ("factor", 0.0)):
+            v = r.pop(name, dflt)
+            v = [float(v)] * 3 if np.isscalar(v) else [float(x) for x in v]
+            assert len(v) == 3, name
+            setattr(a, name, (C.c_double * 3)(*v))
+        for name in ("lmask", "abmask"):
+            pl = r.pop(name, None)
+            if pl is not None:
+                keep.append(pl)
+                setattr(a, name, C.pointer(pl))
+        assert not r, "unknown colour-correction fields: %s" % sorted(r)
+    return arr, keep
+
+
 class MaskParams(C.Structure):
     """artgpu_mask_params: one rtengine::procparams::Mask as the parametric path of generateMasks reads it"""
     _fields_ = [("parametric_enabled", C.c_int32), ("lightness_detail", C.c_int32), ("hue", C.POINTER(C.c_double)),
@@ -385,6 +435,9 @@ def _load():
     lib.artgpu_generate_masks.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.POINTER(C.c_double), C.POINTER(MaskParams), C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.POINTER(Plane), C.POINTER(Plane), C.POINTER(MasksInfo)]
     lib.artgpu_set_pipeline_masks.argtypes = [C.c_void_p, C.POINTER(MaskParams), C.c_int, C.POINTER(MaskParams), C.c_int]
+    lib.artgpu_color_correction.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(ColorCorrectionRegion), C.c_int, C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.c_int, C.POINTER(ColorCorrectionInfo)]
+    lib.artgpu_set_pipeline_color_correction.argtypes = [C.c_void_p, C.POINTER(ColorCorrectionRegion), C.c_int, C.POINTER(MaskParams)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -465,7 +518,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
            "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
            "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
-           "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks"]
+           "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks",
+           "artgpu_color_correction", "artgpu_set_pipeline_color_correction"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -697,6 +751,27 @@ class Context:
         tb, k2 = mask_params(texture_boost_masks or [])
         self._chk(LIB.artgpu_set_pipeline_masks(self._h, lc if local_contrast_masks else None, len(local_contrast_masks or []),
                                                 tb if texture_boost_masks else None, len(texture_boost_masks or [])))
+        del k1, k2
+
+    def color_correction(self, image: RGB, regions, ws, iws, to_rgb: bool = False, want_info: bool = False):
+        """ImProcFunctions::colorCorrection in place on an RGB image (left in YUV mode unless to_rgb).  regions: what
+        color_correction_regions() takes.  Returns the list of ColorCorrectionInfo (one per region) when want_info."""
+        arr, keep = color_correction_regions(regions)
+        n = len(regions)
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        iwsd = (C.c_double * 9)(*np.asarray(iws, np.float64).ravel())
+        info = (ColorCorrectionInfo * max(n, 1))() if want_info else None
+        self._chk(LIB.artgpu_color_correction(self._h, C.byref(image), arr, n, wsd, iwsd, 1 if to_rgb else 0, info))
+        del keep
+        return list(info)[:n] if want_info else None
+
+    def set_pipeline_color_correction(self, regions=None, masks=None):
+        """the colour correction pipeline_run / batch_run / batch_run_io run behind the sharpening (what color_correction_regions() takes;
+        None: off) and, optionally, the masks they generate its planes from (what mask_params() takes, one per region).  The library copies both."""
+        arr, k1 = color_correction_regions(regions or [])
+        mk, k2 = mask_params(masks or [])
+        assert not masks or len(masks) == len(regions or [])
+        self._chk(LIB.artgpu_set_pipeline_color_correction(self._h, arr if regions else None, len(regions or []), mk if masks else None))
         del k1, k2
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):

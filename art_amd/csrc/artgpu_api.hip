@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "dehaze.h"
 #include "textureboost.h"
+#include "colorcorrection.h"
 #include "masks.h"
 #include "sharpen.h"
 
@@ -46,6 +47,11 @@ struct artgpu_ctx {
     struct PipeMasks { std::vector<artgpu_mask_params> m; std::vector<std::vector<double>> curves; std::vector<artgpu_plane> areas; } pipe_lc_own, pipe_tb_own;
     const artgpu_mask_params *pipe_lc = nullptr, *pipe_tb = nullptr;
     int pipe_nlc = 0, pipe_ntb = 0;
+    // artgpu_set_pipeline_color_correction: the regions, their mask planes' descriptors and the mask parameters; lanes point at their parent's
+    struct PipeCc { std::vector<artgpu_color_correction_region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; } pipe_cc_own;
+    const artgpu_color_correction_region *pipe_cc = nullptr;
+    const artgpu_mask_params *pipe_cc_masks = nullptr;
+    int pipe_ncc = 0;
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
     int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
@@ -1138,6 +1144,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_SH_PLANES, P_SH_BYTES, P_SH_STATE,                                                                             // artgpu_sharpening
        P_TB_PLANES, P_TB_LOW, P_TB_TMP, P_TB_STATE, P_TB_MASK, P_TB_Y,                                                  // artgpu_texture_boost
        P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
+       P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 
@@ -2523,6 +2530,7 @@ int artgpu_demosaic_xtrans(artgpu_ctx *ctx, int passes, int use_cielab, const ar
 // ---------------------------------------------------------------------------------------------
 // NEUTRAL tone curve
 // ---------------------------------------------------------------------------------------------
+namespace { int pq_tables_dev(artgpu_ctx *ctx, float **out); }       // (defined with the colour correction, its other user)
 int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *lut65536, float whitecoeff, const artgpu_neutral_state *st)
 {
     StageScope scope_(ctx, "ImProcFunctions::toneCurve (NEUTRAL)");
@@ -2532,14 +2540,7 @@ int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *l
     int rc = bind_rgb(ctx, image, 4, true, &d, "tone_curve_neutral");
     if (rc) return rc;
     float *pq;
-    const bool fresh = ctx->pool[P_PQ] == nullptr;
-    if ((rc = pool_get(ctx, P_PQ, (2 * 65536 + 64) * 4, &pq))) return rc;
-    if (fresh) {
-        std::vector<float> host(2 * 65536);
-        build_pq_luts(host.data(), host.data() + 65536);
-        HIPCHK(ctx, hipMemcpyAsync(pq, host.data(), host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if ((rc = pq_tables_dev(ctx, &pq))) return rc;
     if ((rc = upload_curve(ctx, lut65536))) return rc;
     NeutralArgs a = {};
     for (int k = 0; k < 3; ++k) a.img[k] = d.p[k];
@@ -2548,7 +2549,6 @@ int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *l
     for (int k = 0; k < 9; ++k) { a.ws[k] = (float)st->ws[k]; a.iws[k] = (float)st->iws[k]; a.to_out[k] = st->to_out[k]; a.to_work[k] = st->to_work[k]; }
     a.whitecoeff = whitecoeff;
     a.tail_kind = ctx->curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->curve_tail_kind; a.tail_y = ctx->curve_tail_y; a.tail_pc = ctx->curve_tail_pc;
-    if (fresh) HIPCHK(ctx, launch_neutral_hues(a, ctx->stream));
     a.no_lds_lut = !ctx->opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
     HIPCHK(ctx, launch_tone_neutral(a, ctx->stream));
     return unbind_rgb(ctx, image, &d);
@@ -3696,14 +3696,15 @@ static int tb_fill_info(artgpu_ctx *ctx, const TbPlan &pl, const TbState *st, ar
     return ARTGPU_OK;
 }
 
-// ImProcFunctions::textureBoost (L198-242) on device planes in RGB mode: setMode(YUV), the regions that run, setMode(RGB) when asked for
+// ImProcFunctions::textureBoost (L198-242) on device planes in RGB mode: setMode(YUV), the regions that run, setMode(RGB) when asked for.
+// already_yuv: the tool ahead (colorCorrection) left the image in YUV mode, where the reference's setMode(YUV) does nothing
 static int texture_boost_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_texture_boost_region *regions, int nregions,
-                             const double ws[9], const std::vector<TbPlan> &plans, int to_rgb, artgpu_texture_boost_info *info)
+                             const double ws[9], const std::vector<TbPlan> &plans, int to_rgb, artgpu_texture_boost_info *info, int already_yuv = 0)
 {
     PixArgs ya = {};                                                   // Imagefloat::setMode (yuv_mode_kernel: do_clip 0 = to YUV, 1 = to RGB)
     for (int k = 0; k < 3; ++k) { ya.dst[k] = planes[k]; ya.mul[k] = (float)ws[3 + k]; }
     ya.dst_stride = stride; ya.w = W; ya.h = H;
-    HIPCHK(ctx, launch_yuv_mode(ya, ctx->stream));
+    if (!already_yuv) HIPCHK(ctx, launch_yuv_mode(ya, ctx->stream));
     int rc;
     size_t k = 0;
     TbState *st = nullptr;
@@ -4058,6 +4059,201 @@ int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, cons
 }
 
 // ---------------------------------------------------------------------------------------------
+// colour correction: ImProcFunctions::colorCorrection (ipcolorcorrection.cc:39-866)
+// ---------------------------------------------------------------------------------------------
+namespace {
+// a deep copy of n mask entries (their curves and the area planes' descriptors) for a setting of the context
+const artgpu_mask_params *own_pipe_masks(artgpu_ctx::PipeMasks &o, const artgpu_mask_params *src, int n)
+{
+    o.m.assign(src, src + n);
+    o.curves.assign((size_t)3 * n, std::vector<double>());
+    o.areas.assign(n, artgpu_plane{});
+    for (int i = 0; i < n; ++i) {
+        artgpu_mask_params &m = o.m[i];
+        const double **pts[3] = {&m.hue, &m.chromaticity, &m.lightness};
+        int32_t *cnt[3] = {&m.nhue, &m.nchromaticity, &m.nlightness};
+        for (int k = 0; k < 3; ++k) {
+            if (*cnt[k] < 0) *cnt[k] = 0;
+            if (*pts[k] && *cnt[k] > 0) o.curves[3 * i + k].assign(*pts[k], *pts[k] + *cnt[k]);
+            *pts[k] = o.curves[3 * i + k].empty() ? nullptr : o.curves[3 * i + k].data();
+            if (!*pts[k]) *cnt[k] = 0;
+        }
+        if (m.area) { o.areas[i] = *m.area; m.area = &o.areas[i]; }
+    }
+    return n > 0 ? o.m.data() : nullptr;
+}
+
+// the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)
+int pq_tables_dev(artgpu_ctx *ctx, float **out)
+{
+    float *pq;
+    int rc;
+    const bool fresh = ctx->pool[P_PQ] == nullptr;
+    if ((rc = pool_get(ctx, P_PQ, (2 * 65536 + 64) * 4, &pq))) return rc;
+    if (fresh) {
+        std::vector<float> host(2 * 65536);
+        build_pq_luts(host.data(), host.data() + 65536);
+        HIPCHK(ctx, hipMemcpyAsync(pq, host.data(), host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        NeutralArgs a = {};
+        a.pq = pq; a.pq_inv = pq + 65536; a.hues = pq + 2 * 65536;
+        HIPCHK(ctx, launch_neutral_hues(a, ctx->stream));
+    }
+    *out = pq;
+    return ARTGPU_OK;
+}
+
+// what a call derives on the host before it touches anything (L88-141, L280-414), and every reason not to run
+struct CcPlan { std::vector<CcRegion> regs; float ws[9], iws[9], fR, fG, fB; bool any_jz; };
+static int cc_check(artgpu_ctx *ctx, int W, int H, const artgpu_color_correction_region *regions, int nregions, const double *ws, const double *iws, bool read_masks,
+             const char *who, CcPlan *pl)
+{
+    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !iws) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
+    for (int k = 0; k < 9; ++k) { pl->ws[k] = (float)ws[k]; pl->iws[k] = (float)iws[k]; }      // TMatrix -> float ws[3][3], once (L94-108)
+    cc_luminance_factors(pl->ws, &pl->fR, &pl->fG, &pl->fB);
+    pl->regs.assign(nregions, CcRegion{});
+    pl->any_jz = false;
+    for (int i = 0; i < nregions; ++i) {
+        const artgpu_color_correction_region &r = regions[i];
+        if (r.mode == ARTGPU_CC_LUT) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: LUT mode (CLUT files) is not on the device path", who, i);
+        if (r.mode < ARTGPU_CC_YUV || r.mode > ARTGPU_CC_LUT) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: mode %d", who, i, r.mode);
+        if (r.mode == ARTGPU_CC_HSL && !(r.hsl_gamma > 0.0)) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: hsl_gamma %g", who, i, r.hsl_gamma);
+        CcRegionParams p;
+        p.mode = r.mode; p.rgbluminance = r.rgbluminance;
+        p.a = r.a; p.b = r.b; p.in_saturation = r.in_saturation; p.out_saturation = r.out_saturation; p.hueshift = r.hueshift; p.hsl_gamma = r.hsl_gamma;
+        for (int c = 0; c < 3; ++c) {
+            p.slope[c] = r.slope[c]; p.offset[c] = r.offset[c]; p.power[c] = r.power[c]; p.pivot[c] = r.pivot[c]; p.compression[c] = r.compression[c];
+            p.hue[c] = r.hue[c]; p.sat[c] = r.sat[c]; p.factor[c] = r.factor[c];
+        }
+        cc_derive_region(p, pl->ws, &pl->regs[i]);
+        if (!cc_region_finite(pl->regs[i]))
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a derived scalar is not finite (power 0, pivot 0 or a value out of range)", who, i);
+        pl->any_jz = pl->any_jz || pl->regs[i].jzazbz;
+        for (const artgpu_plane *m : {r.lmask, r.abmask})
+            if (read_masks && m && (!plane_ok(m) || m->w != W || m->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: a mask must be a %dx%d plane", who, i, W, H);
+    }
+    if (!std::isfinite(pl->fR) || !std::isfinite(pl->fG) || !std::isfinite(pl->fB)) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: the working space's luminance row", who);
+    return ARTGPU_OK;
+}
+
+// the tool on device planes (rows of `stride` floats) in RGB mode, or in YUV mode with `from_yuv`; enqueued on ctx->stream, one host wait with `info`
+static int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_color_correction_region *regions,
+                         const CcPlan &pl, int from_yuv, int to_rgb, artgpu_color_correction_info *info)
+{
+    const int n = (int)pl.regs.size();
+    const size_t np = (size_t)W * H;
+    int rc;
+    std::vector<CcRegion> regs = pl.regs;
+    // host planes are staged once each (one plane may serve as both masks, and several regions may share one)
+    std::vector<const artgpu_plane *> host;
+    for (int i = 0; i < n; ++i)
+        for (const artgpu_plane *m : {regions[i].lmask, regions[i].abmask})
+            if (m && !m->on_device && std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) == host.end()) host.push_back(m);
+    float *staged = nullptr;
+    if (!host.empty()) {
+        if ((rc = pool_get(ctx, P_CC_MASK, host.size() * np * 4, &staged))) return rc;
+        for (size_t k = 0; k < host.size(); ++k)
+            HIPCHK(ctx, hipMemcpy2DAsync(staged + k * np, (size_t)W * 4, host[k]->p, (size_t)host[k]->row_stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const auto bind = [&](const artgpu_plane *m, const float **p, size_t *s) {
+        *p = nullptr; *s = 0;
+        if (!m) return;
+        if (m->on_device) { *p = m->p; *s = (size_t)(m->row_stride_bytes / 4); return; }
+        const size_t k = std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) - host.begin();
+        *p = staged + k * np; *s = W;
+    };
+    for (int i = 0; i < n; ++i) { bind(regions[i].lmask, &regs[i].lmask, &regs[i].l_stride); bind(regions[i].abmask, &regs[i].abmask, &regs[i].ab_stride); }
+    CcArgs a = {};
+    for (int k = 0; k < 3; ++k) a.img[k] = planes[k];
+    a.stride = stride; a.w = W; a.h = H;
+    for (int k = 0; k < 9; ++k) { a.ws[k] = pl.ws[k]; a.iws[k] = pl.iws[k]; }
+    a.fR = pl.fR; a.fG = pl.fG; a.fB = pl.fB;
+    if (pl.any_jz) {
+        float *pq;
+        if ((rc = pq_tables_dev(ctx, &pq))) return rc;
+        a.pq = pq; a.pq_inv = pq + 65536;
+        cc_pq_low(&a.pq_low, &a.pq_inv_low);
+    }
+    unsigned long long *count = nullptr;
+    if (info && pl.any_jz) {
+        float *buf;
+        if ((rc = pool_get(ctx, P_CC_OOR, 64 + np, &buf))) return rc;
+        HIPCHK(ctx, hipMemsetAsync(buf, 0, 64 + np, ctx->stream));
+        count = reinterpret_cast<unsigned long long *>(buf);
+        a.oor = reinterpret_cast<unsigned char *>(buf) + 64;
+    }
+    // launches: up to CC_MAX_REGIONS regions each, cut earlier where Jzazbz and the HSL hue shift would meet (they share no instantiation).
+    // The tool is in place and pointwise, so the launches compose: the first does setMode(YUV), the last setMode(RGB)
+    int first = 0;
+    do {
+        int cnt = 0, need = 0;
+        while (first + cnt < n && cnt < CC_MAX_REGIONS && cc_need_fits(need | cc_region_need(regs[first + cnt]))) need |= cc_region_need(regs[first + cnt++]);
+        for (int k = 0; k < cnt; ++k) a.r[k] = regs[first + k];
+        a.nregions = cnt;
+        a.from_yuv = first > 0 ? 1 : from_yuv;
+        a.to_rgb = first + cnt == n ? to_rgb : 0;
+        HIPCHK(ctx, launch_cc(a, need, ctx->stream));
+        first += cnt;
+    } while (first < n);
+    if (info) {
+        long long oor = 0;
+        if (count) {
+            HIPCHK(ctx, launch_cc_count(a.oor, np, count, ctx->stream));
+            unsigned long long c = 0;
+            HIPCHK(ctx, hipMemcpyAsync(&c, count, 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            oor = (long long)c;
+        }
+        for (int i = 0; i < n; ++i) {
+            const CcRegion &r = pl.regs[i];
+            artgpu_color_correction_info &o = info[i];
+            o = artgpu_color_correction_info{};
+            o.abca = r.abca; o.abcb = r.abcb; o.enabled = r.enabled; o.rgbmode = r.rgbmode; o.rhs = r.rhs; o.oor_pixels = oor;
+            for (int c = 0; c < 3; ++c) {
+                o.slope[c] = r.slope[c]; o.offset[c] = r.offset[c]; o.power[c] = r.power[c]; o.pivot[c] = r.pivot[c];
+                o.compression[c][0] = r.comp[c][0]; o.compression[c][1] = r.comp[c][1];
+            }
+        }
+    }
+    return ARTGPU_OK;
+}
+} // namespace
+
+int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
+                            const double iws[9], int to_rgb, artgpu_color_correction_info *info)
+{
+    StageScope scope_(ctx, "ImProcFunctions::colorCorrection");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!img || !plane_ok(&img->r)) return fail(ctx, ARTGPU_EINVAL, "color_correction: bad image");
+    CcPlan pl;
+    int rc;
+    if ((rc = cc_check(ctx, img->r.w, img->r.h, regions, nregions, ws, iws, true, "color_correction", &pl))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevRGB d;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "color_correction"))) return rc;
+    if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regions, pl, 0, to_rgb, info))) return rc;
+    return unbind_rgb(ctx, img, &d);
+}
+
+int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_correction_region *regions, int n, const artgpu_mask_params *masks)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_color_correction: bad arguments");
+    artgpu_ctx::PipeCc &o = ctx->pipe_cc_own;
+    o.regs.assign(regions, regions + n);
+    o.planes.assign((size_t)2 * n, artgpu_plane{});
+    for (int i = 0; i < n; ++i) {                               // the planes' descriptors are copied, their memory stays the caller's
+        if (o.regs[i].lmask) { o.planes[2 * i] = *o.regs[i].lmask; o.regs[i].lmask = &o.planes[2 * i]; }
+        if (o.regs[i].abmask) { o.planes[2 * i + 1] = *o.regs[i].abmask; o.regs[i].abmask = &o.planes[2 * i + 1]; }
+    }
+    ctx->pipe_cc_masks = masks ? own_pipe_masks(o.masks, masks, n) : nullptr;
+    if (!masks) o.masks = artgpu_ctx::PipeMasks{};
+    ctx->pipe_cc = n > 0 ? o.regs.data() : nullptr;
+    ctx->pipe_ncc = n;
+    return ARTGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // capture sharpening: ImProcFunctions::doSharpening, method "rld"
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -4371,26 +4567,8 @@ int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *lc, int
 {
     if (!ctx) return ARTGPU_EINVAL;
     if (nlc < 0 || ntb < 0 || (nlc > 0 && !lc) || (ntb > 0 && !tb)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_masks: bad arguments");
-    const auto own = [](artgpu_ctx::PipeMasks &o, const artgpu_mask_params *src, int n) -> const artgpu_mask_params * {
-        o.m.assign(src, src + n);
-        o.curves.assign((size_t)3 * n, std::vector<double>());
-        o.areas.assign(n, artgpu_plane{});
-        for (int i = 0; i < n; ++i) {
-            artgpu_mask_params &m = o.m[i];
-            const double **pts[3] = {&m.hue, &m.chromaticity, &m.lightness};
-            int32_t *cnt[3] = {&m.nhue, &m.nchromaticity, &m.nlightness};
-            for (int k = 0; k < 3; ++k) {
-                if (*cnt[k] < 0) *cnt[k] = 0;
-                if (*pts[k] && *cnt[k] > 0) o.curves[3 * i + k].assign(*pts[k], *pts[k] + *cnt[k]);
-                *pts[k] = o.curves[3 * i + k].empty() ? nullptr : o.curves[3 * i + k].data();
-                if (!*pts[k]) *cnt[k] = 0;
-            }
-            if (m.area) { o.areas[i] = *m.area; m.area = &o.areas[i]; }
-        }
-        return n > 0 ? o.m.data() : nullptr;
-    };
-    ctx->pipe_lc = own(ctx->pipe_lc_own, lc, nlc); ctx->pipe_nlc = nlc;
-    ctx->pipe_tb = own(ctx->pipe_tb_own, tb, ntb); ctx->pipe_ntb = ntb;
+    ctx->pipe_lc = own_pipe_masks(ctx->pipe_lc_own, lc, nlc); ctx->pipe_nlc = nlc;
+    ctx->pipe_tb = own_pipe_masks(ctx->pipe_tb_own, tb, ntb); ctx->pipe_ntb = ntb;
     return ARTGPU_OK;
 }
 
@@ -4438,6 +4616,18 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
     }
     const artgpu_local_contrast_region *lc_regions = lc_gen ? lc_regs.data() : p->local_contrast_regions;
     const artgpu_texture_boost_region *tb_regions = tb_gen ? tb_regs.data() : p->texture_boost_regions;
+    // ImProcFunctions::colorCorrection (artgpu_set_pipeline_color_correction): derived and checked here, run behind the sharpening
+    const bool cc_on = ctx->pipe_ncc > 0 && ctx->pipe_cc;
+    CcPlan ccp;
+    MkPlan cc_mk;
+    if (cc_on) {
+        if (tb_gen) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate texture boost's masks from");
+        if ((rc = cc_check(ctx, W - 2 * b, H - 2 * b, ctx->pipe_cc, ctx->pipe_ncc, p->ws, p->iws, !ctx->pipe_cc_masks, "pipeline_run(colour correction)", &ccp))) return rc;
+        if (ctx->pipe_cc_masks &&
+            (rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_cc_masks, ctx->pipe_ncc, W - 2 * b, H - 2 * b, p->scale > 0 ? p->scale : 1.0, true, true,
+                          "pipeline_run(colour correction masks)", &cc_mk, nullptr)))
+            return rc;
+    }
     std::vector<artgpu_plane> gen_planes;
     // generateMasks(rgb, ., masks, 0, 0, full size, scale, ., -1, &mask, nullptr) on the device image, the L planes handed to the regions
     auto generate = [&](float *const planes[3], size_t stride, int w, int h, const artgpu_mask_params *masks, const MkPlan &mk, int n, auto &regs) -> int {
@@ -4554,10 +4744,28 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
         }
         if ((rc = sharpen_dev(ctx, d.p, d.stride, d.w, d.h, &shpar, p->ws, shp, nullptr))) return rc;
     }
+    // ImProcFunctions::colorCorrection, STAGE_2 behind the sharpening (improcfun.cc:601): generateMasks(rgb, ., &Lmask, &abmask) on the RGB image
+    // (ipcolorcorrection.cc:236), then the tool.  It leaves the image in YUV mode for textureBoost, whose setMode(YUV) is then a no-op
+    if (cc_on) {
+        std::vector<artgpu_color_correction_region> cc_regs(ctx->pipe_cc, ctx->pipe_cc + ctx->pipe_ncc);
+        std::vector<artgpu_plane> cc_planes;
+        if (ctx->pipe_cc_masks) {
+            const int n = ctx->pipe_ncc;
+            const size_t np = (size_t)d.w * d.h;
+            float *mo;
+            if ((rc = pool_get(ctx, P_CC_GEN, 2 * n * np * 4, &mo)) || (rc = masks_dev(ctx, d.p, d.stride, p->ws, ctx->pipe_cc_masks, cc_mk, mo, mo + n * np))) return rc;
+            cc_planes.resize((size_t)2 * n);
+            for (int i = 0; i < n; ++i) {
+                cc_planes[2 * i] = mk_dev_plane(mo + i * np, d.w, d.h); cc_planes[2 * i + 1] = mk_dev_plane(mo + (n + i) * np, d.w, d.h);
+                cc_regs[i].lmask = &cc_planes[2 * i]; cc_regs[i].abmask = &cc_planes[2 * i + 1];
+            }
+        }
+        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, cc_regs.data(), ccp, 0, p->texture_boost_enabled ? 0 : 1, nullptr))) return rc;
+    }
     // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
     if (tb_gen && (rc = generate(d.p, d.stride, d.w, d.h, ctx->pipe_tb, tb_mk, p->texture_boost_nregions, tb_regs))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     if (p->texture_boost_enabled &&
-        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, tb_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr)))
+        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, tb_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr, cc_on ? 1 : 0)))
         return rc;
     if (p->tone_enabled) {
         if (p->tone_mode == ARTGPU_TONE_NEUTRAL) {
@@ -4635,6 +4843,7 @@ int batch_prepare_lanes(artgpu_ctx *ctx, int L)
         peer->opt_dn_wait_ms = ctx->opt_dn_wait_ms; peer->opt_dn_debug_stall = ctx->opt_dn_debug_stall; peer->opt_io_direct = ctx->opt_io_direct;
         peer->progress_fn = ctx->progress_fn; peer->progress_user = ctx->progress_user;
         peer->pipe_lc = ctx->pipe_lc; peer->pipe_nlc = ctx->pipe_nlc; peer->pipe_tb = ctx->pipe_tb; peer->pipe_ntb = ctx->pipe_ntb;
+        peer->pipe_cc = ctx->pipe_cc; peer->pipe_ncc = ctx->pipe_ncc; peer->pipe_cc_masks = ctx->pipe_cc_masks;
         peer->frames_in_flight = L;
     }
     ctx->frames_in_flight = L;

@@ -18,8 +18,13 @@
 //              [--texture-boost-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]]   (a parametric mask on that region, generated on the device by
 //                                                      generateMasks: a lightness curve that is 1 between lo and hi and 0 outside, ParametricMask's
 //                                                      blur, lightnessDetail, contrastThreshold and Mask::opacity)
+//              [--color-correction mode[,key=value...]]   (ImProcFunctions::colorCorrection in STAGE_2 behind the sharpening: one region; mode yuv | rgb |
+//                                                      hsl | jzazbz; keys a, b, in_saturation, out_saturation, hueshift, hsl_gamma, rgbluminance and, with one
+//                                                      value for all three channels or r:g:b, slope, offset, power, pivot, compression, hue, sat, factor)
+//              [--color-correction-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]]   (a parametric mask on that region, in the form of
+//                                                      --texture-boost-mask: generateMasks makes its Lmask and abmask on the device)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--texture-boost ..] [--texture-boost-mask ..] [--out prefix]
+//              [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <chrono>
@@ -79,6 +84,11 @@ int main(int argc, char **argv)
     bool tbm_enable = false;                                       // a parametric Mask on the texture-boost region
     double tbm_lo = 0.0, tbm_hi = 1.0, tbm_blur = 0.0;
     int tbm_detail = 0, tbm_threshold = 0, tbm_opacity = 100;
+    bool cc_enable = false;                                        // ColorCorrectionParams::enabled, one region
+    ProcParams::ColorCorrectionRegion cc_region;
+    bool ccm_enable = false;                                       // a parametric Mask on the colour-correction region
+    double ccm_lo = 0.0, ccm_hi = 1.0, ccm_blur = 0.0;
+    int ccm_detail = 0, ccm_threshold = 0, ccm_opacity = 100;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -153,8 +163,53 @@ int main(int argc, char **argv)
             }
             tbm_enable = true;
         }
+        else if (a == "--color-correction") {
+            std::vector<std::string> f;
+            const std::string v = next();
+            for (size_t pos = 0; pos <= v.size();) {
+                const size_t e = v.find(',', pos);
+                f.push_back(v.substr(pos, e == std::string::npos ? std::string::npos : e - pos));
+                if (e == std::string::npos) break;
+                pos = e + 1;
+            }
+            const char *usage = "--color-correction yuv|rgb|hsl|jzazbz[,key=value...] (a triple as r:g:b or one value)\n";
+            if (f[0] == "yuv") cc_region.mode = ARTGPU_CC_YUV;
+            else if (f[0] == "rgb") cc_region.mode = ARTGPU_CC_RGB;
+            else if (f[0] == "hsl") cc_region.mode = ARTGPU_CC_HSL;
+            else if (f[0] == "jzazbz") cc_region.mode = ARTGPU_CC_JZAZBZ;
+            else { std::fprintf(stderr, "%s", usage); return 2; }
+            for (size_t k = 1; k < f.size(); ++k) {
+                const size_t eq = f[k].find('=');
+                if (eq == std::string::npos) { std::fprintf(stderr, "%s", usage); return 2; }
+                const std::string key = f[k].substr(0, eq), val = f[k].substr(eq + 1);
+                double t[3];
+                const int nt = std::sscanf(val.c_str(), "%lf:%lf:%lf", &t[0], &t[1], &t[2]);
+                if (nt == 1) t[1] = t[2] = t[0];
+                double *scalar = key == "a" ? &cc_region.a : key == "b" ? &cc_region.b : key == "in_saturation" ? &cc_region.inSaturation :
+                                 key == "out_saturation" ? &cc_region.outSaturation : key == "hueshift" ? &cc_region.hueshift :
+                                 key == "hsl_gamma" ? &cc_region.hsl_gamma : nullptr;
+                double *triple = key == "slope" ? cc_region.slope : key == "offset" ? cc_region.offset : key == "power" ? cc_region.power :
+                                 key == "pivot" ? cc_region.pivot : key == "compression" ? cc_region.compression : key == "hue" ? cc_region.hue :
+                                 key == "sat" ? cc_region.sat : key == "factor" ? cc_region.factor : nullptr;
+                if (scalar && nt == 1) *scalar = t[0];
+                else if (triple && (nt == 1 || nt == 3)) { triple[0] = t[0]; triple[1] = t[1]; triple[2] = t[2]; }
+                else if (key == "rgbluminance" && nt == 1) cc_region.rgbluminance = t[0] != 0;
+                else { std::fprintf(stderr, "%s", usage); return 2; }
+            }
+            cc_enable = true;
+        }
+        else if (a == "--color-correction-mask") {
+            if (std::sscanf(next(), "%lf,%lf,%lf,%d,%d,%d", &ccm_lo, &ccm_hi, &ccm_blur, &ccm_detail, &ccm_threshold, &ccm_opacity) < 2) {
+                std::fprintf(stderr, "--color-correction-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]\n"); return 2;
+            }
+            ccm_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    ProcParams::Mask cc_mask;
+    cc_mask.parametricMask.enabled = true; cc_mask.parametricMask.blur = ccm_blur; cc_mask.parametricMask.lightnessDetail = ccm_detail;
+    cc_mask.parametricMask.contrastThreshold = ccm_threshold; cc_mask.opacity = ccm_opacity;
+    cc_mask.parametricMask.lightness = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.0, 0.35, 0.35, ccm_lo, 1.0, 0.35, 0.35, ccm_hi, 1.0, 0.35, 0.35, 1.0, 0.0, 0.35, 0.35};
     ProcParams::Mask tb_mask;
     tb_mask.parametricMask.enabled = true; tb_mask.parametricMask.blur = tbm_blur; tb_mask.parametricMask.lightnessDetail = tbm_detail;
     tb_mask.parametricMask.contrastThreshold = tbm_threshold; tb_mask.opacity = tbm_opacity;
@@ -176,6 +231,8 @@ int main(int argc, char **argv)
             params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
             params.textureBoost.enabled = tb_enable; params.textureBoost.regions = {{tb_strength, tb_threshold, tb_iterations}};
         if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
+        params.colorcorrection.enabled = cc_enable; params.colorcorrection.regions = {cc_region};
+        if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -251,6 +308,8 @@ int main(int argc, char **argv)
         params.sharpening.deconvamount = sh_amount; params.sharpening.deconvCornerBoost = sh_boost; params.sharpening.deconvCornerLatitude = sh_latitude;
         params.textureBoost.enabled = tb_enable; params.textureBoost.regions = {{tb_strength, tb_threshold, tb_iterations}};
         if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
+        params.colorcorrection.enabled = cc_enable; params.colorcorrection.regions = {cc_region};
+        if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;

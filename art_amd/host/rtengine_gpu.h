@@ -186,6 +186,39 @@ struct ProcParams {
         }
         return regions;
     }
+    // ColorCorrectionParams (procparams.cc:2834-2855, 2906-2920): regions with the reference's defaults (mode JZAZBZ); masks[i].enabled and either
+    // the two blend planes the application's generateMasks made of masks[i] (`lblend` / `abblend`; nullptr = all ones) or the Mask itself
+    struct ColorCorrectionRegion {
+        int mode = ARTGPU_CC_JZAZBZ;
+        bool rgbluminance = false;
+        double a = 0, b = 0, inSaturation = 0, outSaturation = 0, hueshift = 0, hsl_gamma = 2.4;
+        double slope[3] = {1, 1, 1}, offset[3] = {0, 0, 0}, power[3] = {1, 1, 1}, pivot[3] = {1, 1, 1}, compression[3] = {0, 0, 0};
+        double hue[3] = {0, 0, 0}, sat[3] = {0, 0, 0}, factor[3] = {0, 0, 0};
+    };
+    struct ColorCorrectionMask { bool enabled = true; const DevicePlane *lblend = nullptr, *abblend = nullptr; const Mask *mask = nullptr; };
+    struct { bool enabled = false; std::vector<ColorCorrectionRegion> regions = {ColorCorrectionRegion()}; std::vector<ColorCorrectionMask> masks; } colorcorrection;
+    // the enabled regions as the library takes them; `blends` keeps the mask views the regions point to (two per region)
+    std::vector<artgpu_color_correction_region> colorCorrectionRegions(std::vector<artgpu_plane> &blends) const
+    {
+        const auto &p = colorcorrection;
+        blends.assign(2 * p.regions.size(), artgpu_plane{});
+        std::vector<artgpu_color_correction_region> regions;
+        for (size_t k = 0; k < p.regions.size(); ++k) {
+            if (k < p.masks.size() && !p.masks[k].enabled) continue;
+            const ColorCorrectionRegion &r = p.regions[k];
+            artgpu_color_correction_region reg = {};
+            reg.mode = r.mode; reg.rgbluminance = r.rgbluminance ? 1 : 0;
+            reg.a = r.a; reg.b = r.b; reg.in_saturation = r.inSaturation; reg.out_saturation = r.outSaturation; reg.hueshift = r.hueshift; reg.hsl_gamma = r.hsl_gamma;
+            for (int c = 0; c < 3; ++c) {
+                reg.slope[c] = r.slope[c]; reg.offset[c] = r.offset[c]; reg.power[c] = r.power[c]; reg.pivot[c] = r.pivot[c]; reg.compression[c] = r.compression[c];
+                reg.hue[c] = r.hue[c]; reg.sat[c] = r.sat[c]; reg.factor[c] = r.factor[c];
+            }
+            if (k < p.masks.size() && p.masks[k].lblend) { blends[2 * k] = p.masks[k].lblend->view(); reg.lmask = &blends[2 * k]; }
+            if (k < p.masks.size() && p.masks[k].abblend) { blends[2 * k + 1] = p.masks[k].abblend->view(); reg.abmask = &blends[2 * k + 1]; }
+            regions.push_back(reg);
+        }
+        return regions;
+    }
     // the Masks of the enabled regions (nullptr: the region carries none), and whether any region carries one
     template <class Tool> static bool regionMasks(const Tool &p, std::vector<const Mask *> &masks)
     {
@@ -314,7 +347,7 @@ public:
         switch (stage) {
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
-        case Stage::STAGE_2: sharpening(img); break;                                          // improcfun.cc:595
+        case Stage::STAGE_2: sharpening(img); colorCorrection(img); break;                    // improcfun.cc:595, 601
         case Stage::STAGE_3: textureBoost(img); logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:606-625 (the steps this library has)
         }
         return false;
@@ -362,6 +395,28 @@ public:
         artgpu_rgb i = img->view();
         ctx.check(artgpu_texture_boost(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, scale,
                                        (scale == 1 || cur_pipeline == Pipeline::OUTPUT) ? 1 : 0, 1, nullptr));
+        return false;
+    }
+    // ImProcFunctions::colorCorrection (ipcolorcorrection.cc:39-866): generateMasks(rgb, ., &Lmask, &abmask) on the RGB image (L236), setMode(YUV),
+    // every enabled region; this mirror has no mode tracking and converts back at once, like textureBoost above
+    bool colorCorrection(Imagefloat *img)
+    {
+        if (!params->colorcorrection.enabled) return false;
+        std::vector<artgpu_plane> blends;
+        std::vector<artgpu_color_correction_region> regions = params->colorCorrectionRegions(blends);
+        std::vector<const ProcParams::Mask *> masks;
+        std::vector<std::unique_ptr<DevicePlane>> Lmask, abmask;
+        std::vector<artgpu_plane> views(2 * regions.size());
+        if (ProcParams::regionMasks(params->colorcorrection, masks)) {
+            generateMasks(img, ARTGPU_MASKS_MODE_RGB, masks, 0, 0, -1, -1, scale, -1, &Lmask, &abmask);
+            for (size_t k = 0; k < regions.size(); ++k)
+                if (masks[k]) {
+                    views[2 * k] = Lmask[k]->view(); views[2 * k + 1] = abmask[k]->view();
+                    regions[k].lmask = &views[2 * k]; regions[k].abmask = &views[2 * k + 1];
+                }
+        }
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_color_correction(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, params->workingSpaceInverse, 1, nullptr));
         return false;
     }
     // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
@@ -602,6 +657,17 @@ public:
         std::vector<artgpu_mask_params> tb_mp;
         if (ProcParams::regionMasks(p.textureBoost, tb_masks)) tb_mp = ProcParams::maskParams(tb_masks, tb_areas);
         ctx.check(artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, tb_mp.empty() ? nullptr : tb_mp.data(), (int)tb_mp.size()));
+        // ImProcFunctions::colorCorrection behind the sharpening: the regions (and their Masks, generated by the pipe) as a setting of the context
+        std::vector<artgpu_plane> cc_blends, cc_areas;
+        std::vector<artgpu_color_correction_region> cc_regions;
+        std::vector<const ProcParams::Mask *> cc_masks;
+        std::vector<artgpu_mask_params> cc_mp;
+        if (p.colorcorrection.enabled) {
+            cc_regions = p.colorCorrectionRegions(cc_blends);
+            if (ProcParams::regionMasks(p.colorcorrection, cc_masks)) cc_mp = ProcParams::maskParams(cc_masks, cc_areas);
+        }
+        ctx.check(artgpu_set_pipeline_color_correction(ctx.get(), cc_regions.empty() ? nullptr : cc_regions.data(), (int)cc_regions.size(),
+                                                       cc_mp.empty() ? nullptr : cc_mp.data()));
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -615,6 +681,7 @@ public:
         ctx.check(artgpu_set_batch_lanes(ctx.get(), lanes));
         const int rc = artgpu_batch_run_io(ctx.get(), (int)jobs.size(), in.data(), &pp, out.data());
         (void)artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, nullptr, 0);
+        (void)artgpu_set_pipeline_color_correction(ctx.get(), nullptr, 0, nullptr);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

@@ -806,6 +806,51 @@ int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, cons
                           int full_w, int full_h, double scale, artgpu_plane *Lmask /* n planes or NULL */, artgpu_plane *abmask /* n planes or NULL */,
                           artgpu_masks_info *info /* n entries or NULL */);
 
+/* Colour correction: ImProcFunctions::colorCorrection (rtengine/ipcolorcorrection.cc:39-866), ART's colour-grading tool, on an image in RGB
+ * mode (host or device, any row stride): setMode(YUV) (L770; always, also without regions), every region in order, setMode(RGB) when `to_rgb`
+ * (the reference leaves the image in YUV mode) -- one pass over the image for up to four regions, further passes for a longer list.
+ * Per region the host derives what L88-141 and L280-414 derive, in the reference's types: abca / abcb from a / b through abcoord2 and hs2uv
+ * (zero in the RGB and HSL modes), rs = 1.f + in_saturation / 100.f, rsout, rhs = hueshift * RT_PI_F_180 (0 in RGB mode), rgbmode 0 (YUV,
+ * JZAZBZ: channel 0's slope / offset / power / pivot / compression serve all three), 1 (RGB, HSL) or 2 (with rgbluminance), rpower = 1.0 /
+ * power, compression {c * 100, log(1 + y0 * c * 100) / slope} for c > 0; in HSL mode slope / offset / power from hue / sat / factor (satcoeff
+ * 2.5, pivot 1); enabled = some channel differs from the identity.  Per pixel the CDL lambda (L416-554): the hue shift (in HSL, plain yuv or
+ * Jzazbz terms), then in the RGB modes in-saturation, the per-channel chain v = rgb / 65535 * slope + offset / 2, v > 0 ? pow_F(v / pivot,
+ * power) * pivot : 0, xlogf(v * c0 + 1) / c1, with pow_F(., 1 / hsl_gamma) before and pow_F(., hsl_gamma) after it in HSL mode, back through
+ * rgb2yuv or, with rgbluminance, Y1 = rgbLuminance(old + (new - old) * max(ws[1]) / ws[1][c]) and u, v *= Y1 / Y; in the YUV and JZAZBZ modes
+ * the chain on Y with u, v *= YY / Y, yuv2jzazbz, in-saturation; in all modes u += max(Y, 0) * abcb, v += max(Y, 0) * abca, out-saturation
+ * (and jzazbz2yuv); then Y = intp(lmask, Y_new, Y), u, v = intp(abmask, ., .).  Columns below 4 * (W / 4) take the reference's 4-wide CDL_v
+ * (a group of four runs when any of its lanes has a blend above 0, vector sleef forms, vmaxf), the others the scalar CDL: see DESIGN.md.
+ * The caller keeps `masks[i].enabled` (a disabled region is not passed) and calls artgpu_generate_masks(img in RGB mode, Lmask, abmask)
+ * first, as for texture boost.  lmask / abmask: planes of the image's size, host or device; NULL = all ones; one plane may serve as both.
+ * A non-NULL `info` receives nregions entries with the derived scalars, each with the call's count of pixels that took a per-pixel powf in
+ * PQ / PQ_inv (a Jzazbz argument above 1: the device's powf there, everything else is the reference's bits); the count costs the call's one
+ * host wait and is not taken without `info`.  Asynchronous on the context's stream for a device image without `info`.
+ * ARTGPU_EUNSUPPORTED, decided before any kernel runs, image untouched: mode LUT (CLUT files); a non-finite derived scalar (power[j] == 0
+ * among them); hsl_gamma <= 0 in HSL mode.  Not built: show_mask and the pipette buffers. */
+#define ARTGPU_CC_YUV 0                /* ColorCorrectionParams::Mode (procparams.h:1351-1357) */
+#define ARTGPU_CC_RGB 1
+#define ARTGPU_CC_HSL 2
+#define ARTGPU_CC_JZAZBZ 3
+#define ARTGPU_CC_LUT 4
+typedef struct artgpu_color_correction_region {   /* ColorCorrectionParams::Region, defaults procparams.cc:2834-2855 */
+    int32_t mode;                     /* ARTGPU_CC_YUV / RGB / HSL / JZAZBZ / LUT (LUT: unsupported); default JZAZBZ */
+    int32_t rgbluminance;             /* ::rgbluminance (false) */
+    double a, b, in_saturation, out_saturation, hueshift, hsl_gamma;       /* 0, 0, 0, 0, 0, 2.4 */
+    double slope[3], offset[3], power[3], pivot[3], compression[3];        /* 1, 0, 1, 1, 0 */
+    double hue[3], sat[3], factor[3];                                      /* 0, 0, 0 */
+    const artgpu_plane *lmask, *abmask;   /* generateMasks' planes; NULL = all ones */
+} artgpu_color_correction_region;
+typedef struct artgpu_color_correction_info {     /* one per region */
+    float abca, abcb;
+    int32_t enabled, rgbmode;
+    float slope[3], offset[3], power[3], pivot[3];
+    float compression[3][2];
+    float rhs;
+    int64_t oor_pixels;               /* of the whole call (the same in every entry) */
+} artgpu_color_correction_info;
+int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
+                            const double iws[9], int to_rgb, artgpu_color_correction_info *info /* nregions entries or NULL */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -881,6 +926,16 @@ int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_p
  * from the frame's region count is ARTGPU_EINVAL, what artgpu_generate_masks does not support ARTGPU_EUNSUPPORTED, both before any stage runs. */
 int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *local_contrast_masks, int nlc,
                               const artgpu_mask_params *texture_boost_masks, int ntb);
+/* Colour correction in the per-frame pipe, a setting of the context for the same reason.  regions: n entries (deep-copied; batch lanes share
+ * the copy); NULL / 0 = off, the default.  masks: n entries or NULL, copied as artgpu_set_pipeline_masks copies them.  While set, the three
+ * pipe entries run artgpu_color_correction's code after the sharpening and before texture boost (STAGE_2, improcfun.cc:601).  With `masks`
+ * both planes of every region are generated on the RGB image (ipcolorcorrection.cc:236), the output's size as the full size, params->scale,
+ * and never leave the device; the regions' own lmask / abmask are then not read.  When texture boost follows, the image stays in YUV mode
+ * between the two (in the reference textureBoost's setMode(YUV) is then a no-op); otherwise the tool ends with setMode(RGB).  Colour
+ * correction ahead of pipe-generated texture-boost masks is ARTGPU_EUNSUPPORTED (the mask engine has no YUV mode), like everything
+ * artgpu_color_correction and artgpu_generate_masks do not support: before any stage runs.  n < 0 or a NULL list with n > 0: ARTGPU_EINVAL. */
+int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_correction_region *regions, int n,
+                                         const artgpu_mask_params *masks /* n entries or NULL */);
 
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
