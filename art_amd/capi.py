@@ -143,6 +143,57 @@ def color_correction_regions(regions):
     return arr, keep
 
 
+SMOOTHING_REGION_FIELDS = (("mode", C.c_int32, 0), ("channel", C.c_int32, 2), ("radius", C.c_int32, 0), ("epsilon", C.c_int32, 0), ("sigma", C.c_double, 0.0),
+                           ("iterations", C.c_int32, 1), ("nldetail", C.c_int32, 50), ("falloff", C.c_double, 1.0), ("nlstrength", C.c_int32, 0),
+                           ("numblades", C.c_int32, 9), ("angle", C.c_double, 0.0), ("curvature", C.c_double, 0.0), ("offset", C.c_double, 0.0),
+                           ("noise_strength", C.c_int32, 10), ("noise_coarseness", C.c_int32, 30), ("halation_size", C.c_double, 1.0),
+                           ("halation_color", C.c_double, 0.0), ("wav_strength", C.c_double, 0.0), ("wav_levels", C.c_int32, 5), ("pad_", C.c_int32, 0),
+                           ("wav_gamma", C.c_double, 2.2))
+
+
+class SmoothingRegion(C.Structure):
+    """artgpu_smoothing_region: one SmoothingParams::Region (defaults procparams.cc:2753-2775) and its blend plane"""
+    _fields_ = [(n, t) for n, t, _ in SMOOTHING_REGION_FIELDS] + [("mask", C.POINTER(Plane))]
+
+
+class SmoothingInfo(C.Structure):
+    """artgpu_smoothing_info, one per region"""
+    _fields_ = [("r", C.c_int32), ("epsilon", C.c_float), ("min_x", C.c_int32), ("min_y", C.c_int32), ("max_x", C.c_int32), ("max_y", C.c_int32),
+                ("cropped", C.c_int32), ("work_w", C.c_int32), ("work_h", C.c_int32), ("subsampling", C.c_int32), ("box_radius", C.c_int32),
+                ("skipped", C.c_int32)]
+
+
+(SMOOTHING_GUIDED, SMOOTHING_GAUSSIAN, SMOOTHING_GAUSSIAN_GLOW, SMOOTHING_NLMEANS, SMOOTHING_MOTION, SMOOTHING_LENS, SMOOTHING_NOISE,
+ SMOOTHING_HALATION, SMOOTHING_WAVELETS) = range(9)
+SMOOTHING_MODES = {"guided": 0, "gaussian": 1, "gaussian_glow": 2, "nlmeans": 3, "motion": 4, "lens": 5, "noise": 6, "halation": 7, "wavelets": 8}
+SMOOTHING_LUMINANCE, SMOOTHING_CHROMINANCE, SMOOTHING_RGB = 0, 1, 2
+SMOOTHING_CHANNELS = {"l": 0, "luminance": 0, "c": 1, "chrominance": 1, "lc": 2, "rgb": 2}
+SMOOTHING_MIN_SIZE = 5
+SMOOTHING_SKIP_RADIUS, SMOOTHING_SKIP_STRENGTH, SMOOTHING_SKIP_EMPTY = 1, 2, 3
+
+
+def smoothing_regions(regions):
+    """[dict, ...] -> (SmoothingRegion array, objects to keep alive with it).  A dict holds Region's fields under SmoothingRegion's names with
+    Region's defaults for what it leaves out; mode and channel are ARTGPU_SMOOTHING_* values or their names; mask is a Plane or None."""
+    arr = (SmoothingRegion * max(len(regions), 1))()
+    keep = []
+    for k, r in enumerate(regions):
+        r = dict(r)
+        a = arr[k]
+        mode, channel = r.pop("mode", SMOOTHING_GUIDED), r.pop("channel", SMOOTHING_RGB)
+        a.mode = SMOOTHING_MODES[mode.lower()] if isinstance(mode, str) else int(mode)
+        a.channel = SMOOTHING_CHANNELS[channel.lower()] if isinstance(channel, str) else int(channel)
+        for name, typ, dflt in SMOOTHING_REGION_FIELDS[2:]:
+            v = r.pop(name, dflt)
+            setattr(a, name, float(v) if typ is C.c_double else int(v))
+        pl = r.pop("mask", None)
+        if pl is not None:
+            keep.append(pl)
+            a.mask = C.pointer(pl)
+        assert not r, "unknown smoothing fields: %s" % sorted(r)
+    return arr, keep
+
+
 class MaskParams(C.Structure):
     """artgpu_mask_params: one rtengine::procparams::Mask as the parametric path of generateMasks reads it"""
     _fields_ = [("parametric_enabled", C.c_int32), ("lightness_detail", C.c_int32), ("hue", C.POINTER(C.c_double)),
@@ -438,6 +489,9 @@ def _load():
     lib.artgpu_color_correction.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(ColorCorrectionRegion), C.c_int, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.c_int, C.POINTER(ColorCorrectionInfo)]
     lib.artgpu_set_pipeline_color_correction.argtypes = [C.c_void_p, C.POINTER(ColorCorrectionRegion), C.c_int, C.POINTER(MaskParams)]
+    lib.artgpu_smoothing.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(SmoothingRegion), C.c_int, C.POINTER(C.c_double), C.c_double,
+                                     C.POINTER(SmoothingInfo)]
+    lib.artgpu_set_pipeline_smoothing.argtypes = [C.c_void_p, C.POINTER(SmoothingRegion), C.c_int, C.POINTER(MaskParams)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -519,7 +573,7 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
            "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
            "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks",
-           "artgpu_color_correction", "artgpu_set_pipeline_color_correction"]
+           "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -772,6 +826,26 @@ class Context:
         mk, k2 = mask_params(masks or [])
         assert not masks or len(masks) == len(regions or [])
         self._chk(LIB.artgpu_set_pipeline_color_correction(self._h, arr if regions else None, len(regions or []), mk if masks else None))
+        del k1, k2
+
+    def smoothing(self, image: RGB, regions, ws, scale: float = 1.0, want_info: bool = False):
+        """ImProcFunctions::guidedSmoothing (modes GUIDED and NLMEANS) in place on an RGB image.  regions: what smoothing_regions() takes.
+        Returns the list of SmoothingInfo (one per region) when want_info."""
+        arr, keep = smoothing_regions(regions)
+        n = len(regions)
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        info = (SmoothingInfo * max(n, 1))() if want_info else None
+        self._chk(LIB.artgpu_smoothing(self._h, C.byref(image), arr, n, wsd, float(scale), info))
+        del keep
+        return list(info)[:n] if want_info else None
+
+    def set_pipeline_smoothing(self, regions=None, masks=None):
+        """the Smoothing tool pipeline_run / batch_run / batch_run_io run behind colour correction (what smoothing_regions() takes; None: off)
+        and, optionally, the masks they generate its planes from (what mask_params() takes, one per region).  The library copies both."""
+        arr, k1 = smoothing_regions(regions or [])
+        mk, k2 = mask_params(masks or [])
+        assert not masks or len(masks) == len(regions or [])
+        self._chk(LIB.artgpu_set_pipeline_smoothing(self._h, arr if regions else None, len(regions or []), mk if masks else None))
         del k1, k2
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):

@@ -18,6 +18,7 @@
 #include "dehaze.h"
 #include "textureboost.h"
 #include "colorcorrection.h"
+#include "smoothing.h"
 #include "masks.h"
 #include "sharpen.h"
 
@@ -52,6 +53,11 @@ struct artgpu_ctx {
     const artgpu_color_correction_region *pipe_cc = nullptr;
     const artgpu_mask_params *pipe_cc_masks = nullptr;
     int pipe_ncc = 0;
+    // artgpu_set_pipeline_smoothing: likewise
+    struct PipeSm { std::vector<artgpu_smoothing_region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; } pipe_sm_own;
+    const artgpu_smoothing_region *pipe_sm = nullptr;
+    const artgpu_mask_params *pipe_sm_masks = nullptr;
+    int pipe_nsm = 0;
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
     int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
@@ -1145,6 +1151,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_TB_PLANES, P_TB_LOW, P_TB_TMP, P_TB_STATE, P_TB_MASK, P_TB_Y,                                                  // artgpu_texture_boost
        P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
        P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
+       P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 
@@ -2379,17 +2386,11 @@ int artgpu_detail_mask(artgpu_ctx *ctx, const artgpu_plane *src, artgpu_plane *m
     return pool_to_plane(ctx, m, mask);
 }
 
-int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int strength, int detail_thresh, float scale)
+namespace {
+// denoise::NLMeans (nlmeans.cc:44-320) on a contiguous device plane (rows of W floats), in place; enqueued on ctx->stream.  The caller has checked
+// strength != 0, W, H >= 32, (W + 14) * (H + 14) < 2^30 and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
+int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, int strength, int detail_thresh, float scale)
 {
-    StageScope scope_(ctx, "denoise::NLMeans");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(img) || !(scale >= 1.f)) return fail(ctx, ARTGPU_EINVAL, "nlmeans: bad arguments");
-    if (!strength) return ARTGPU_OK;                       // nlmeans.cc:52-54
-    if (img->w < 32 || img->h < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image smaller than 32x32");
-    // (the tile kernel addresses a plane through 32-bit byte offsets)
-    if ((unsigned long long)(img->w + 14) * (unsigned long long)(img->h + 14) >= (1ull << 30)) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image of %dx%d exceeds 2^30 pixels", img->w, img->h);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int W = img->w, H = img->h;
     NlmArgs a = {};
     a.search_radius = int(std::ceil(5.f / scale));
     a.patch_radius = int(std::ceil(2.f / scale));
@@ -2401,13 +2402,8 @@ int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int stre
     a.W = W; a.H = H; a.WW = W + 2 * a.border; a.HH = H + 2 * a.border; a.factor = normcoeff;
     a.ntiles_x = int(std::ceil(float(a.WW) / (150 - 2 * a.border)));
     a.ntiles_y = int(std::ceil(float(a.HH) / (150 - 2 * a.border)));
-    float *work, *scratch, *pad;
-    // a contiguous device plane is worked on where it lies (the kernels read the padded copy `pad` and the mask, and write the plane): two plane
-    // copies less per call, 0.16 ms of a 45 MP frame; anything else goes through a contiguous working copy
-    const bool in_place = img->on_device && img->row_stride_bytes == (int64_t)W * 4;
+    float *scratch, *pad;
     int rc = ARTGPU_OK;
-    if (in_place) work = img->p;
-    else if ((rc = plane_to_pool(ctx, img, P_SF, &work))) return rc;
     if ((rc = pool_get(ctx, P_TMP, (size_t)W * H * 4 * 2 + 8192 * 4, &a.mask))) return rc;
     a.SW = a.mask + (size_t)W * H; a.explut = a.SW + (size_t)W * H;
     if ((rc = pool_get(ctx, P_LIN, ((size_t)W * H + 2 * (size_t)(W / 4) * (H / 4)) * 4, &scratch))) return rc;
@@ -2415,6 +2411,29 @@ int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int stre
     if ((rc = detail_mask_dev(ctx, work, W, a.mask, W, H, normcoeff, 1e-3f * normcoeff, normcoeff, amount, 2.f / scale, scratch))) return rc;
     a.img = work; a.img_stride = W; a.src = pad;
     HIPCHK(ctx, launch_nlm(a, ctx->stream));
+    return ARTGPU_OK;
+}
+} // namespace
+
+int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int strength, int detail_thresh, float scale)
+{
+    StageScope scope_(ctx, "denoise::NLMeans");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!plane_ok(img) || !(scale >= 1.f)) return fail(ctx, ARTGPU_EINVAL, "nlmeans: bad arguments");
+    if (!strength) return ARTGPU_OK;                       // nlmeans.cc:52-54
+    if (img->w < 32 || img->h < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image smaller than 32x32");
+    // (the tile kernel addresses a plane through 32-bit byte offsets)
+    if ((unsigned long long)(img->w + 14) * (unsigned long long)(img->h + 14) >= (1ull << 30)) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image of %dx%d exceeds 2^30 pixels", img->w, img->h);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int W = img->w, H = img->h;
+    float *work;
+    // a contiguous device plane is worked on where it lies (the kernels read the padded copy `pad` and the mask, and write the plane): two plane
+    // copies less per call, 0.16 ms of a 45 MP frame; anything else goes through a contiguous working copy
+    const bool in_place = img->on_device && img->row_stride_bytes == (int64_t)W * 4;
+    int rc = ARTGPU_OK;
+    if (in_place) work = img->p;
+    else if ((rc = plane_to_pool(ctx, img, P_SF, &work))) return rc;
+    if ((rc = nlm_plane_dev(ctx, work, W, H, normcoeff, strength, detail_thresh, scale))) return rc;
     return in_place ? ARTGPU_OK : pool_to_plane(ctx, work, img);
 }
 
@@ -4254,6 +4273,275 @@ int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_cor
 }
 
 // ---------------------------------------------------------------------------------------------
+// smoothing: ImProcFunctions::guidedSmoothing, modes GUIDED and NLMEANS
+// ---------------------------------------------------------------------------------------------
+namespace {
+// what a call derives per region on the host before any kernel writes the image (ipsmoothing.cc:943-980, L348, L1040)
+struct SmRegionPlan {
+    int mode, channel, iterations, r, nlstrength, nldetail;
+    float epsilon;
+    int x0, y0, x1, y1, cropped, ww, hh;       // the box (max exclusive) and the working size
+    int sub, w, h, rad;                        // GUIDED: subsampling, statistics grid, f_mean's radius
+    int skipped;
+};
+
+// everything that does not depend on a mask's box: what the pipe checks before any stage runs
+int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regions, int nregions, const double *ws, double scale, bool read_masks, const char *who)
+{
+    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !(scale > 0.0) || std::isinf(scale)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
+    for (int i = 0; i < nregions; ++i) {
+        const artgpu_smoothing_region &r = regions[i];
+        if (r.mode < ARTGPU_SMOOTHING_GUIDED || r.mode > ARTGPU_SMOOTHING_WAVELETS) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: mode %d", who, i, r.mode);
+        if (r.channel < ARTGPU_SMOOTHING_LUMINANCE || r.channel > ARTGPU_SMOOTHING_RGB) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: channel %d", who, i, r.channel);
+        if (r.mode != ARTGPU_SMOOTHING_GUIDED && r.mode != ARTGPU_SMOOTHING_NLMEANS)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: mode %d is not on the device path (only GUIDED and NLMEANS are)", who, i, r.mode);
+        if (r.iterations < 1) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: iterations %d", who, i, r.iterations);
+        if (r.mode == ARTGPU_SMOOTHING_NLMEANS && r.nlstrength != 0 && !(scale >= 1.0))
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means at scale %g (below 1) is not on the device path", who, i, scale);
+        if (read_masks && r.mask && (!plane_ok(r.mask) || r.mask->w != W || r.mask->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: the mask must be a %dx%d plane", who, i, W, H);
+    }
+    return ARTGPU_OK;
+}
+
+// one region's plan from its box (inclusive maxima as the reduction leaves them; nullptr: a NULL mask, the frame)
+int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl)
+{
+    *pl = SmRegionPlan{};
+    pl->mode = r.mode; pl->channel = r.channel; pl->iterations = r.iterations; pl->nlstrength = r.nlstrength; pl->nldetail = r.nldetail;
+    if (box && box[2] < box[0]) { pl->skipped = ARTGPU_SMOOTHING_SKIP_EMPTY; return ARTGPU_OK; }
+    int min_x = box ? box[0] : 0, min_y = box ? box[1] : 0, max_x = box ? box[2] + 1 : W, max_y = box ? box[3] + 1 : H;
+    int ww = max_x - min_x, hh = max_y - min_y;
+    if (ww * hh < (W * H) / 2) pl->cropped = 1;                    // L957 (int arithmetic, as there)
+    else { min_x = 0; min_y = 0; max_x = W; max_y = H; ww = W; hh = H; }
+    pl->x0 = min_x; pl->y0 = min_y; pl->x1 = max_x; pl->y1 = max_y; pl->ww = ww; pl->hh = hh;
+    if (r.mode == ARTGPU_SMOOTHING_GUIDED) {
+        pl->epsilon = (float)std::max(0.001f * std::pow(2.0, (double)-r.epsilon), 1e-6);        // L1040: a double narrowed at the call
+        const int rr = (int)std::round(r.radius / scale);             // L348
+        pl->r = rr > 0 ? rr : 0;
+        if (pl->r == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_RADIUS; return ARTGPU_OK; }
+        pl->sub = gf_subsampling(ww, hh, pl->r);
+        pl->w = ww / pl->sub; pl->h = hh / pl->sub;
+        if (pl->w < ARTGPU_SMOOTHING_MIN_SIZE || pl->h < ARTGPU_SMOOTHING_MIN_SIZE)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a %dx%d working plane leaves a %dx%d statistics grid, below %d", who, i, ww, hh, pl->w, pl->h, ARTGPU_SMOOTHING_MIN_SIZE);
+        const float r1 = float(pl->r) / pl->sub;                      // f_mean (guidedfilter.cc:160-167)
+        int rad = (int)r1;
+        const int hi = ((pl->w < pl->h ? pl->w : pl->h) - 1) / 2 - 1;
+        rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0;
+        pl->rad = rad;
+        if (rad > HBLUR_MAX_RADIUS)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, i, rad, HBLUR_MAX_RADIUS);
+    } else {
+        if (r.nlstrength == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_STRENGTH; return ARTGPU_OK; }
+        if (ww < 32 || hh < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane, smaller than 32x32", who, i, ww, hh);
+        if ((unsigned long long)(ww + 14) * (unsigned long long)(hh + 14) >= (1ull << 30))
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane exceeds 2^30 pixels", who, i, ww, hh);
+    }
+    return ARTGPU_OK;
+}
+
+// floats of P_SM_PLANES a region needs
+size_t sm_region_floats(const SmRegionPlan &p)
+{
+    const size_t nw = (size_t)p.ww * p.hh;
+    if (p.skipped == ARTGPU_SMOOTHING_SKIP_EMPTY || p.skipped == ARTGPU_SMOOTHING_SKIP_RADIUS) return 0;
+    if (p.mode == ARTGPU_SMOOTHING_GUIDED) return ((p.channel == SM_CH_LC ? 3 : 7) + (p.iterations > 1 ? 3 : 0)) * nw;
+    return (p.channel == SM_CH_L ? 1 : p.channel == SM_CH_LC ? (p.skipped ? 0 : 3) : 4) * nw;
+}
+
+int sm_blur_planes(artgpu_ctx *ctx, float *planes, float *tmp, int count, int w, int h, int rad)
+{
+    if (rad == 0) return ARTGPU_OK;
+    BlurArgs bl = {};
+    bl.n = (size_t)w * h; bl.w = w; bl.h = h; bl.steady_div = 1; bl.plain = 1;      // boxblur.h:318 variant, as artgpu_denoise_guided_smoothing runs it
+    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
+    bl.src = planes; bl.dst = tmp;
+    HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
+    bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
+    HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
+    return ARTGPU_OK;
+}
+
+// one region on the normalised device image; `mask`: the region's blend plane on the device (rows of mstride floats) or nullptr
+// norm_in: the image is not normalised yet and this (full-frame) region does it; denorm_out: this (full-frame) region stores * 65535.f
+int sm_region_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, const SmRegionPlan &p, const float *mask, size_t mstride, const double *ws, double scale, float *big,
+                  bool norm_in, bool denorm_out)
+{
+    int rc;
+    const size_t nw = (size_t)p.ww * p.hh, off = (size_t)p.y0 * stride + p.x0;
+    SmArgs a = {};
+    for (int k = 0; k < 3; ++k) { a.img[k] = planes[k] + off; a.ws1[k] = ws[3 + k]; }
+    a.stride = stride;
+    a.mask = mask ? mask + (size_t)p.y0 * mstride + p.x0 : nullptr; a.mask_stride = mstride;
+    a.ww = p.ww; a.hh = p.hh; a.channel = p.channel;
+    a.img_norm = norm_in ? 1 : 0; a.out_denorm = denorm_out ? 1 : 0;
+    if (p.mode == ARTGPU_SMOOTHING_GUIDED) {
+        if (p.skipped) {                                              // r == 0: working == rgb, blended all the same (L1050-1064)
+            a.channel = SM_CH_LC;
+            HIPCHK(ctx, launch_sm_nlm_merge(a, ctx->stream));
+            return ARTGPU_OK;
+        }
+        const bool self = p.channel == SM_CH_LC;
+        const size_t nl = (size_t)p.w * p.h;
+        float *low, *tmp, *q = big;
+        if ((rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
+        if (!self) { for (int k = 0; k < 3; ++k) { a.in[k] = q; q += nw; } a.guide = q; q += nw; }
+        for (int k = 0; k < 3; ++k) { a.chan[k] = q; q += nw; }
+        if (p.iterations > 1) for (int k = 0; k < 3; ++k) { a.work[k] = q; q += nw; }
+        a.w = p.w; a.h = p.h; a.epsilon = p.epsilon; a.low = low;
+        for (int k = 0; k < 3; ++k) { a.a[k] = self ? low + (2 * k) * nl : low + (2 + k) * nl; a.b[k] = self ? low + (2 * k + 1) * nl : low + (5 + k) * nl; }
+        GuidedArgs g = {};
+        g.W = p.ww; g.H = p.hh; g.w = p.w; g.h = p.h; g.epsilon = p.epsilon; g.guide = a.guide;
+        for (int k = 0; k < 3; ++k) g.chan[k] = a.chan[k];
+        for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
+        for (int it = 0; it < p.iterations; ++it) {
+            for (int k = 0; k < 3; ++k) a.src[k] = it == 0 ? a.img[k] : a.work[k];
+            a.src_stride = it == 0 ? stride : (size_t)p.ww;
+            a.src_norm = it == 0 && norm_in ? 1 : 0;
+            a.last = it == p.iterations - 1;
+            HIPCHK(ctx, launch_sm_prepare(a, ctx->stream));
+            if (self) {
+                HIPCHK(ctx, launch_sm_subsample_self(a, ctx->stream));
+                if ((rc = sm_blur_planes(ctx, low, tmp, 6, p.w, p.h, p.rad))) return rc;        // mean I, corr I per channel
+                HIPCHK(ctx, launch_sm_ab_self(a, ctx->stream));
+                if ((rc = sm_blur_planes(ctx, low, tmp, 6, p.w, p.h, p.rad))) return rc;        // mean a, mean b per channel
+            } else {
+                HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
+                if ((rc = sm_blur_planes(ctx, low, tmp, 8, p.w, p.h, p.rad))) return rc;        // meanI, corrI, meanp[3], corrIp[3]
+                HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
+                if ((rc = sm_blur_planes(ctx, low + 2 * nl, tmp, 6, p.w, p.h, p.rad))) return rc;   // mean a[3], mean b[3]
+            }
+            HIPCHK(ctx, launch_sm_finish(a, ctx->stream));
+        }
+        return ARTGPU_OK;
+    }
+    // NLMEANS
+    float *q = big;
+    const int nplanes = p.channel == SM_CH_L ? 1 : 3;
+    if (!(p.skipped && p.channel == SM_CH_LC)) {
+        for (int k = 0; k < nplanes; ++k) { a.work[k] = q; q += nw; }
+        if (p.channel == SM_CH_C) a.in[0] = q;
+        HIPCHK(ctx, launch_sm_nlm_split(a, ctx->stream));
+        if (!p.skipped)
+            for (int it = 0; it < p.iterations; ++it)
+                for (int k = 0; k < nplanes; ++k)
+                    if ((rc = nlm_plane_dev(ctx, a.work[k], p.ww, p.hh, 1.f, p.nlstrength, p.nldetail, (float)scale))) return rc;
+    }
+    HIPCHK(ctx, launch_sm_nlm_merge(a, ctx->stream));
+    return ARTGPU_OK;
+}
+
+// the tool on device planes (rows of `stride` floats) in RGB mode; enqueued on ctx->stream, one host wait when a region has a mask
+int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
+                  artgpu_smoothing_info *info, const char *who)
+{
+    int rc;
+    const size_t np = (size_t)W * H;
+    // host planes are staged once each (several regions may share one)
+    std::vector<const artgpu_plane *> host;
+    for (int i = 0; i < n; ++i) {
+        const artgpu_plane *m = regions[i].mask;
+        if (m && !m->on_device && std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) == host.end()) host.push_back(m);
+    }
+    float *staged = nullptr;
+    if (!host.empty()) {
+        if ((rc = pool_get(ctx, P_SM_MASK, host.size() * np * 4, &staged))) return rc;
+        for (size_t k = 0; k < host.size(); ++k)
+            HIPCHK(ctx, hipMemcpy2DAsync(staged + k * np, (size_t)W * 4, host[k]->p, (size_t)host[k]->row_stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, ctx->stream));
+    }
+    std::vector<const float *> mp(n, nullptr);
+    std::vector<size_t> ms(n, 0);
+    std::vector<int> masked;
+    for (int i = 0; i < n; ++i) {
+        const artgpu_plane *m = regions[i].mask;
+        if (!m) continue;
+        if (m->on_device) { mp[i] = m->p; ms[i] = (size_t)(m->row_stride_bytes / 4); }
+        else { mp[i] = staged + (std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) - host.begin()) * np; ms[i] = W; }
+        masked.push_back(i);
+    }
+    // find_region of every mask: one pass (SM_MAX_BOX_REGIONS planes per launch), one wait for 4 ints per mask
+    std::vector<int> boxes(4 * masked.size());
+    if (!masked.empty()) {
+        for (size_t k = 0; k < masked.size(); ++k) { boxes[4 * k] = W; boxes[4 * k + 1] = H; boxes[4 * k + 2] = -1; boxes[4 * k + 3] = -1; }
+        float *bx;
+        if ((rc = pool_get(ctx, P_SM_BOX, boxes.size() * 4, &bx))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(bx, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        for (size_t k0 = 0; k0 < masked.size(); k0 += SM_MAX_BOX_REGIONS) {
+            SmBoxArgs b = {};
+            b.n = (int)std::min(masked.size() - k0, (size_t)SM_MAX_BOX_REGIONS); b.W = W; b.H = H; b.box = reinterpret_cast<int *>(bx) + 4 * k0;
+            for (int k = 0; k < b.n; ++k) { b.mask[k] = mp[masked[k0 + k]]; b.stride[k] = ms[masked[k0 + k]]; }
+            HIPCHK(ctx, launch_sm_box(b, ctx->stream));
+        }
+        HIPCHK(ctx, hipMemcpyAsync(boxes.data(), bx, boxes.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // the whole plan, before any kernel writes the image
+    std::vector<SmRegionPlan> plans(n);
+    size_t need = 0;
+    for (int i = 0, k = 0; i < n; ++i) {
+        if ((rc = sm_plan_region(ctx, W, H, regions[i], regions[i].mask ? &boxes[4 * k++] : nullptr, scale, who, i, &plans[i]))) return rc;
+        need = std::max(need, sm_region_floats(plans[i]));
+    }
+    float *big = nullptr;
+    if (need && (rc = pool_get(ctx, P_SM_PLANES, need * 4, &big))) return rc;
+    int first = -1, last = -1;
+    for (int i = 0; i < n; ++i)
+        if (plans[i].skipped != ARTGPU_SMOOTHING_SKIP_EMPTY) { if (first < 0) first = i; last = i; }
+    if (first < 0) {
+        HIPCHK(ctx, launch_sm_scale(planes, stride, W, H, 2, ctx->stream));        // normalizeFloatTo1, normalizeFloatTo65535 (L938, L1067)
+    } else {
+        // a full-frame region at either end takes that end's normalise pass into its own passes (every pixel still sees exactly one of each)
+        const bool fuse_in = !plans[first].cropped, fuse_out = !plans[last].cropped;
+        if (!fuse_in) HIPCHK(ctx, launch_sm_scale(planes, stride, W, H, 0, ctx->stream));
+        for (int i = 0; i < n; ++i)
+            if (plans[i].skipped != ARTGPU_SMOOTHING_SKIP_EMPTY &&
+                (rc = sm_region_dev(ctx, planes, stride, plans[i], mp[i], ms[i], ws, scale, big, fuse_in && i == first, fuse_out && i == last)))
+                return rc;
+        if (!fuse_out) HIPCHK(ctx, launch_sm_scale(planes, stride, W, H, 1, ctx->stream));
+    }
+    if (info)
+        for (int i = 0; i < n; ++i) {
+            const SmRegionPlan &p = plans[i];
+            artgpu_smoothing_info &o = info[i];
+            o = artgpu_smoothing_info{};
+            o.r = p.r; o.epsilon = p.epsilon; o.min_x = p.x0; o.min_y = p.y0; o.max_x = p.x1; o.max_y = p.y1; o.cropped = p.cropped; o.work_w = p.ww; o.work_h = p.hh;
+            o.subsampling = p.sub; o.box_radius = p.rad; o.skipped = p.skipped;
+        }
+    return ARTGPU_OK;
+}
+} // namespace
+
+int artgpu_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_smoothing_region *regions, int nregions, const double ws[9], double scale,
+                     artgpu_smoothing_info *info)
+{
+    StageScope scope_(ctx, "ImProcFunctions::guidedSmoothing");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!img || !plane_ok(&img->r)) return fail(ctx, ARTGPU_EINVAL, "smoothing: bad image");
+    int rc;
+    if ((rc = sm_check(ctx, img->r.w, img->r.h, regions, nregions, ws, scale, true, "smoothing"))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevRGB d;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "smoothing"))) return rc;
+    if ((rc = smoothing_dev(ctx, d.p, d.stride, d.w, d.h, regions, nregions, ws, scale, info, "smoothing"))) return rc;
+    return unbind_rgb(ctx, img, &d);
+}
+
+int artgpu_set_pipeline_smoothing(artgpu_ctx *ctx, const artgpu_smoothing_region *regions, int n, const artgpu_mask_params *masks)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_smoothing: bad arguments");
+    artgpu_ctx::PipeSm &o = ctx->pipe_sm_own;
+    o.regs.assign(regions, regions + n);
+    o.planes.assign((size_t)n, artgpu_plane{});
+    for (int i = 0; i < n; ++i)                                 // the planes' descriptors are copied, their memory stays the caller's
+        if (o.regs[i].mask) { o.planes[i] = *o.regs[i].mask; o.regs[i].mask = &o.planes[i]; }
+    ctx->pipe_sm_masks = masks ? own_pipe_masks(o.masks, masks, n) : nullptr;
+    if (!masks) o.masks = artgpu_ctx::PipeMasks{};
+    ctx->pipe_sm = n > 0 ? o.regs.data() : nullptr;
+    ctx->pipe_nsm = n;
+    return ARTGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // capture sharpening: ImProcFunctions::doSharpening, method "rld"
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -4621,11 +4909,29 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
     CcPlan ccp;
     MkPlan cc_mk;
     if (cc_on) {
-        if (tb_gen) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate texture boost's masks from");
+        if (tb_gen && !(ctx->pipe_nsm > 0 && ctx->pipe_sm))        // (smoothing in between ends in RGB mode)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate texture boost's masks from");
         if ((rc = cc_check(ctx, W - 2 * b, H - 2 * b, ctx->pipe_cc, ctx->pipe_ncc, p->ws, p->iws, !ctx->pipe_cc_masks, "pipeline_run(colour correction)", &ccp))) return rc;
         if (ctx->pipe_cc_masks &&
             (rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_cc_masks, ctx->pipe_ncc, W - 2 * b, H - 2 * b, p->scale > 0 ? p->scale : 1.0, true, true,
                           "pipeline_run(colour correction masks)", &cc_mk, nullptr)))
+            return rc;
+    }
+    // ImProcFunctions::guidedSmoothing (artgpu_set_pipeline_smoothing): what does not depend on a mask's box is checked here, the tool runs behind
+    // colour correction; its masks are generated on the RGB image, so colour correction (which leaves YUV) cannot come ahead of them
+    const bool sm_on = ctx->pipe_nsm > 0 && ctx->pipe_sm;
+    MkPlan sm_mk;
+    if (sm_on) {
+        if (cc_on && ctx->pipe_sm_masks)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate smoothing's masks from");
+        if ((rc = sm_check(ctx, W - 2 * b, H - 2 * b, ctx->pipe_sm, ctx->pipe_nsm, p->ws, p->scale > 0 ? p->scale : 1.0, !ctx->pipe_sm_masks, "pipeline_run(smoothing)"))) return rc;
+        for (int i = 0; i < ctx->pipe_nsm && !ctx->pipe_sm_masks; ++i) {       // a region without a mask is the frame: its limits are known now
+            SmRegionPlan sp;
+            if (!ctx->pipe_sm[i].mask && (rc = sm_plan_region(ctx, W - 2 * b, H - 2 * b, ctx->pipe_sm[i], nullptr, p->scale > 0 ? p->scale : 1.0, "pipeline_run(smoothing)", i, &sp))) return rc;
+        }
+        if (ctx->pipe_sm_masks &&
+            (rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_sm_masks, ctx->pipe_nsm, W - 2 * b, H - 2 * b, p->scale > 0 ? p->scale : 1.0, true, false,
+                          "pipeline_run(smoothing masks)", &sm_mk, nullptr)))
             return rc;
     }
     std::vector<artgpu_plane> gen_planes;
@@ -4760,12 +5066,27 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
                 cc_regs[i].lmask = &cc_planes[2 * i]; cc_regs[i].abmask = &cc_planes[2 * i + 1];
             }
         }
-        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, cc_regs.data(), ccp, 0, p->texture_boost_enabled ? 0 : 1, nullptr))) return rc;
+        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, cc_regs.data(), ccp, 0, p->texture_boost_enabled && !sm_on ? 0 : 1, nullptr))) return rc;
+    }
+    // ImProcFunctions::guidedSmoothing, the last step of STAGE_2 (improcfun.cc:602): generateMasks on the image (ipsmoothing.cc:929), setMode(RGB)
+    // (colour correction ahead of it ends with that switch), the tool
+    if (sm_on) {
+        std::vector<artgpu_smoothing_region> sm_regs(ctx->pipe_sm, ctx->pipe_sm + ctx->pipe_nsm);
+        std::vector<artgpu_plane> sm_planes;
+        if (ctx->pipe_sm_masks) {
+            const int n = ctx->pipe_nsm;
+            const size_t np = (size_t)d.w * d.h;
+            float *mo;
+            if ((rc = pool_get(ctx, P_SM_GEN, n * np * 4, &mo)) || (rc = masks_dev(ctx, d.p, d.stride, p->ws, ctx->pipe_sm_masks, sm_mk, mo, nullptr))) return rc;
+            sm_planes.resize((size_t)n);
+            for (int i = 0; i < n; ++i) { sm_planes[i] = mk_dev_plane(mo + i * np, d.w, d.h); sm_regs[i].mask = &sm_planes[i]; }
+        }
+        if ((rc = smoothing_dev(ctx, d.p, d.stride, d.w, d.h, sm_regs.data(), ctx->pipe_nsm, p->ws, p->scale > 0 ? p->scale : 1.0, nullptr, "pipeline_run(smoothing)"))) return rc;
     }
     // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
     if (tb_gen && (rc = generate(d.p, d.stride, d.w, d.h, ctx->pipe_tb, tb_mk, p->texture_boost_nregions, tb_regs))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     if (p->texture_boost_enabled &&
-        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, tb_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr, cc_on ? 1 : 0)))
+        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, tb_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr, cc_on && !sm_on ? 1 : 0)))
         return rc;
     if (p->tone_enabled) {
         if (p->tone_mode == ARTGPU_TONE_NEUTRAL) {
@@ -4844,6 +5165,7 @@ int batch_prepare_lanes(artgpu_ctx *ctx, int L)
         peer->progress_fn = ctx->progress_fn; peer->progress_user = ctx->progress_user;
         peer->pipe_lc = ctx->pipe_lc; peer->pipe_nlc = ctx->pipe_nlc; peer->pipe_tb = ctx->pipe_tb; peer->pipe_ntb = ctx->pipe_ntb;
         peer->pipe_cc = ctx->pipe_cc; peer->pipe_ncc = ctx->pipe_ncc; peer->pipe_cc_masks = ctx->pipe_cc_masks;
+        peer->pipe_sm = ctx->pipe_sm; peer->pipe_nsm = ctx->pipe_nsm; peer->pipe_sm_masks = ctx->pipe_sm_masks;
         peer->frames_in_flight = L;
     }
     ctx->frames_in_flight = L;

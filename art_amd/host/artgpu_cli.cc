@@ -23,10 +23,16 @@
 //                                                      value for all three channels or r:g:b, slope, offset, power, pivot, compression, hue, sat, factor)
 //              [--color-correction-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]]   (a parametric mask on that region, in the form of
 //                                                      --texture-boost-mask: generateMasks makes its Lmask and abmask on the device)
+//              [--smoothing mode,channel,a,b,iterations]   (ImProcFunctions::guidedSmoothing, the last step of STAGE_2: one region; mode guided | nlmeans;
+//                                                      channel l | c | lc; a,b = radius,epsilon for guided and nlstrength,nldetail for nlmeans;
+//                                                      a value that starts with a digit is the denoiser's --smoothing radius,nlStrength,nlDetail)
+//              [--smoothing-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]]   (a parametric mask on that region, in the form of
+//                                                      --color-correction-mask: generateMasks makes its Lmask on the device)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--out prefix]
+//              [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
+#include <cctype>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -89,6 +95,11 @@ int main(int argc, char **argv)
     bool ccm_enable = false;                                       // a parametric Mask on the colour-correction region
     double ccm_lo = 0.0, ccm_hi = 1.0, ccm_blur = 0.0;
     int ccm_detail = 0, ccm_threshold = 0, ccm_opacity = 100;
+    bool sm_enable = false;                                        // SmoothingParams::enabled, one region
+    ProcParams::SmoothingRegion sm_region;
+    bool smm_enable = false;                                       // a parametric Mask on the smoothing region
+    double smm_lo = 0.0, smm_hi = 1.0, smm_blur = 0.0;
+    int smm_detail = 0, smm_threshold = 0, smm_opacity = 100;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -108,7 +119,8 @@ int main(int argc, char **argv)
         else if (a == "--denoise") { dn = true; if (std::sscanf(next(), "%lf,%lf", &lum, &chroma) != 2) { std::fprintf(stderr, "--denoise L,C\n"); return 2; } }
         else if (a == "--xtrans") { xtrans_passes = std::atoi(next()); border = 7; }
         else if (a == "--tone") { std::string m = next(); tone_mode = (m == "neutral") ? ARTGPU_TONE_NEUTRAL : ARTGPU_TONE_STD; }
-        else if (a == "--smoothing") { smoothing = true; if (std::sscanf(next(), "%d,%d,%d", &gradius, &nlstrength, &nldetail) != 3) { std::fprintf(stderr, "--smoothing radius,nlStrength,nlDetail\n"); return 2; } }
+        // (a value that starts with a digit is the denoiser's smoothing; one that starts with a mode's name is the Smoothing tool, further down)
+        else if (a == "--smoothing" && i + 1 < argc && !std::isalpha((unsigned char)argv[i + 1][0])) { smoothing = true; if (std::sscanf(next(), "%d,%d,%d", &gradius, &nlstrength, &nldetail) != 3) { std::fprintf(stderr, "--smoothing radius,nlStrength,nlDetail\n"); return 2; } }
         else if (a == "--dual") { std::string m = next(); dual = true; dual_second = (m == "vng4") ? ARTGPU_DUAL_VNG4 : ARTGPU_DUAL_BILINEAR; }
         else if (a == "--dual-contrast") { dual_contrast = std::atof(next()); dual_auto = false; }
         else if (a == "--logenc") { logenc = true; logenc_reg = std::atoi(next()); }
@@ -204,12 +216,38 @@ int main(int argc, char **argv)
             }
             ccm_enable = true;
         }
+        else if (a == "--smoothing") {
+            char mode[16] = {0}, channel[8] = {0};
+            int va = 0, vb = 0, it = 1;
+            const char *usage = "--smoothing guided|nlmeans,l|c|lc,a,b,iterations (a,b: radius,epsilon or nlstrength,nldetail)\n";
+            if (std::sscanf(next(), "%15[a-z],%7[a-z],%d,%d,%d", mode, channel, &va, &vb, &it) != 5) { std::fprintf(stderr, "%s", usage); return 2; }
+            const std::string m = mode, c = channel;
+            if (m == "guided") { sm_region.mode = ARTGPU_SMOOTHING_GUIDED; sm_region.radius = va; sm_region.epsilon = vb; }
+            else if (m == "nlmeans") { sm_region.mode = ARTGPU_SMOOTHING_NLMEANS; sm_region.nlstrength = va; sm_region.nldetail = vb; }
+            else { std::fprintf(stderr, "%s", usage); return 2; }
+            if (c == "l") sm_region.channel = ARTGPU_SMOOTHING_LUMINANCE;
+            else if (c == "c") sm_region.channel = ARTGPU_SMOOTHING_CHROMINANCE;
+            else if (c == "lc") sm_region.channel = ARTGPU_SMOOTHING_RGB;
+            else { std::fprintf(stderr, "%s", usage); return 2; }
+            sm_region.iterations = it;
+            sm_enable = true;
+        }
+        else if (a == "--smoothing-mask") {
+            if (std::sscanf(next(), "%lf,%lf,%lf,%d,%d,%d", &smm_lo, &smm_hi, &smm_blur, &smm_detail, &smm_threshold, &smm_opacity) < 2) {
+                std::fprintf(stderr, "--smoothing-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]\n"); return 2;
+            }
+            smm_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     ProcParams::Mask cc_mask;
     cc_mask.parametricMask.enabled = true; cc_mask.parametricMask.blur = ccm_blur; cc_mask.parametricMask.lightnessDetail = ccm_detail;
     cc_mask.parametricMask.contrastThreshold = ccm_threshold; cc_mask.opacity = ccm_opacity;
     cc_mask.parametricMask.lightness = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.0, 0.35, 0.35, ccm_lo, 1.0, 0.35, 0.35, ccm_hi, 1.0, 0.35, 0.35, 1.0, 0.0, 0.35, 0.35};
+    ProcParams::Mask sm_mask;
+    sm_mask.parametricMask.enabled = true; sm_mask.parametricMask.blur = smm_blur; sm_mask.parametricMask.lightnessDetail = smm_detail;
+    sm_mask.parametricMask.contrastThreshold = smm_threshold; sm_mask.opacity = smm_opacity;
+    sm_mask.parametricMask.lightness = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.0, 0.35, 0.35, smm_lo, 1.0, 0.35, 0.35, smm_hi, 1.0, 0.35, 0.35, 1.0, 0.0, 0.35, 0.35};
     ProcParams::Mask tb_mask;
     tb_mask.parametricMask.enabled = true; tb_mask.parametricMask.blur = tbm_blur; tb_mask.parametricMask.lightnessDetail = tbm_detail;
     tb_mask.parametricMask.contrastThreshold = tbm_threshold; tb_mask.opacity = tbm_opacity;
@@ -233,6 +271,8 @@ int main(int argc, char **argv)
         if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
         params.colorcorrection.enabled = cc_enable; params.colorcorrection.regions = {cc_region};
         if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
+        params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
+        if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -310,6 +350,8 @@ int main(int argc, char **argv)
         if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
         params.colorcorrection.enabled = cc_enable; params.colorcorrection.regions = {cc_region};
         if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
+        params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
+        if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;

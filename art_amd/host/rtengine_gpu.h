@@ -219,6 +219,43 @@ struct ProcParams {
         }
         return regions;
     }
+    // SmoothingParams (procparams.cc:2753-2775, procparams.h:1289-1347): regions with the reference's defaults (mode GUIDED, channel RGB);
+    // masks[i].enabled and either the blend plane the application's generateMasks made of masks[i] (`blend`; nullptr = all ones) or the Mask itself
+    struct SmoothingRegion {
+        int mode = ARTGPU_SMOOTHING_GUIDED, channel = ARTGPU_SMOOTHING_RGB;
+        int radius = 0;
+        double sigma = 0;
+        int epsilon = 0, iterations = 1;
+        double falloff = 1;
+        int nldetail = 50, nlstrength = 0, numblades = 9;
+        double angle = 0, curvature = 0, offset = 0;
+        int noise_strength = 10, noise_coarseness = 30;
+        double halation_size = 1.0, halation_color = 0.0, wav_strength = 0;
+        int wav_levels = 5;
+        double wav_gamma = 2.2;
+    };
+    struct SmoothingMask { bool enabled = true; const DevicePlane *blend = nullptr; const Mask *mask = nullptr; };
+    struct { bool enabled = false; std::vector<SmoothingRegion> regions = {SmoothingRegion()}; std::vector<SmoothingMask> masks; } smoothing;
+    // the enabled regions as the library takes them; `blends` keeps the mask views the regions point to
+    std::vector<artgpu_smoothing_region> smoothingRegions(std::vector<artgpu_plane> &blends) const
+    {
+        const auto &p = smoothing;
+        blends.assign(p.regions.size(), artgpu_plane{});
+        std::vector<artgpu_smoothing_region> regions;
+        for (size_t k = 0; k < p.regions.size(); ++k) {
+            if (k < p.masks.size() && !p.masks[k].enabled) continue;
+            const SmoothingRegion &r = p.regions[k];
+            artgpu_smoothing_region reg = {};
+            reg.mode = r.mode; reg.channel = r.channel; reg.radius = r.radius; reg.epsilon = r.epsilon; reg.sigma = r.sigma; reg.iterations = r.iterations;
+            reg.nldetail = r.nldetail; reg.falloff = r.falloff; reg.nlstrength = r.nlstrength; reg.numblades = r.numblades; reg.angle = r.angle;
+            reg.curvature = r.curvature; reg.offset = r.offset; reg.noise_strength = r.noise_strength; reg.noise_coarseness = r.noise_coarseness;
+            reg.halation_size = r.halation_size; reg.halation_color = r.halation_color; reg.wav_strength = r.wav_strength; reg.wav_levels = r.wav_levels;
+            reg.wav_gamma = r.wav_gamma;
+            if (k < p.masks.size() && p.masks[k].blend) { blends[k] = p.masks[k].blend->view(); reg.mask = &blends[k]; }
+            regions.push_back(reg);
+        }
+        return regions;
+    }
     // the Masks of the enabled regions (nullptr: the region carries none), and whether any region carries one
     template <class Tool> static bool regionMasks(const Tool &p, std::vector<const Mask *> &masks)
     {
@@ -347,7 +384,7 @@ public:
         switch (stage) {
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
-        case Stage::STAGE_2: sharpening(img); colorCorrection(img); break;                    // improcfun.cc:595, 601
+        case Stage::STAGE_2: sharpening(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595, 601, 602
         case Stage::STAGE_3: textureBoost(img); logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:606-625 (the steps this library has)
         }
         return false;
@@ -417,6 +454,25 @@ public:
         }
         artgpu_rgb i = img->view();
         ctx.check(artgpu_color_correction(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, params->workingSpaceInverse, 1, nullptr));
+        return false;
+    }
+    // ImProcFunctions::guidedSmoothing (ipsmoothing.cc:902-1073), modes GUIDED and NLMEANS: generateMasks on the image (L929), setMode(RGB) -- a
+    // no-op here, the mirror's tools hand back RGB --, every enabled region
+    bool guidedSmoothing(Imagefloat *img)
+    {
+        if (!params->smoothing.enabled) return false;
+        std::vector<artgpu_plane> blends;
+        std::vector<artgpu_smoothing_region> regions = params->smoothingRegions(blends);
+        std::vector<const ProcParams::Mask *> masks;
+        std::vector<std::unique_ptr<DevicePlane>> generated;
+        std::vector<artgpu_plane> views(regions.size());
+        if (ProcParams::regionMasks(params->smoothing, masks)) {
+            generateMasks(img, ARTGPU_MASKS_MODE_RGB, masks, 0, 0, -1, -1, scale, -1, &generated, nullptr);
+            for (size_t k = 0; k < regions.size(); ++k)
+                if (masks[k]) { views[k] = generated[k]->view(); regions[k].mask = &views[k]; }
+        }
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_smoothing(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, scale, nullptr));
         return false;
     }
     // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
@@ -668,6 +724,17 @@ public:
         }
         ctx.check(artgpu_set_pipeline_color_correction(ctx.get(), cc_regions.empty() ? nullptr : cc_regions.data(), (int)cc_regions.size(),
                                                        cc_mp.empty() ? nullptr : cc_mp.data()));
+        // ImProcFunctions::guidedSmoothing behind it, likewise
+        std::vector<artgpu_plane> sm_blends, sm_areas;
+        std::vector<artgpu_smoothing_region> sm_regions;
+        std::vector<const ProcParams::Mask *> sm_masks;
+        std::vector<artgpu_mask_params> sm_mp;
+        if (p.smoothing.enabled) {
+            sm_regions = p.smoothingRegions(sm_blends);
+            if (ProcParams::regionMasks(p.smoothing, sm_masks)) sm_mp = ProcParams::maskParams(sm_masks, sm_areas);
+        }
+        ctx.check(artgpu_set_pipeline_smoothing(ctx.get(), sm_regions.empty() ? nullptr : sm_regions.data(), (int)sm_regions.size(),
+                                                sm_mp.empty() ? nullptr : sm_mp.data()));
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -682,6 +749,7 @@ public:
         const int rc = artgpu_batch_run_io(ctx.get(), (int)jobs.size(), in.data(), &pp, out.data());
         (void)artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, nullptr, 0);
         (void)artgpu_set_pipeline_color_correction(ctx.get(), nullptr, 0, nullptr);
+        (void)artgpu_set_pipeline_smoothing(ctx.get(), nullptr, 0, nullptr);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

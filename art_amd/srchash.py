@@ -14,6 +14,7 @@ KERNEL_SOURCES = {
     "nlm_group_kernel": ["nlm_sweep.hip"],
     "shrink_blur_kernel": ["shrinkblur.hip"],
     "mk_fused_kernel": ["masks.hip", "masks.h", "labdev.h"],
+    "sm_finish_kernel": ["smoothing.hip", "smoothing.h"],
 }
 
 

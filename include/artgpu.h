@@ -851,6 +851,86 @@ typedef struct artgpu_color_correction_info {     /* one per region */
 int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
                             const double iws[9], int to_rgb, artgpu_color_correction_info *info /* nregions entries or NULL */);
 
+/* ImProcFunctions::guidedSmoothing (rtengine/ipsmoothing.cc:902-1073), ART's "Smoothing" tool, modes GUIDED and NLMEANS: the last step of
+ * STAGE_2, behind colorCorrection (improcfun.cc:602).  `img`: RGB mode, 0..65535, host or device, any row stride, in place.  The image is
+ * normalised (x * (1.f / 65535.f), imagefloat.cc:396-432); every region in order, each reading what the previous one wrote: find_region
+ * (L411-434) gives the box of mask > 0 (max exclusive); with ww * hh < (W * H) / 2 (int, strict) the region works on a copy of the box,
+ * otherwise on a copy of the frame (L957-980);
+ *   GUIDED  (L1039-1045, L334-409): epsilon = (float)max(0.001f * pow(2, -epsilon), 1e-6); `iterations` times, with r = max(int(round(radius
+ *           / scale)), 0) and nothing when r == 0: LC three self-guided guidedFilterLog(10.f, chan, r, epsilon); L and C the guide
+ *           xlin2log(max(rgbLuminance, 0), 10) for all three and the YUV recombination of L382-406 (L keeps the input's u, v; C the input's Y
+ *           with bump = oY > 1e-5f ? iY / oY : 1.f), ws in double;
+ *   NLMEANS (L500-562): denoise::NLMeans(., 1.f, nlstrength, nldetail, scale) `iterations` times -- L on the Y plane, then yuv2rgb(Y, u, v)
+ *           with u, v of the untouched channels; LC on R, G, B; C as LC with the input's Y put back;
+ * then rgb = intp(mask, working, rgb) over the box (L1050-1064), and after the last region x * 65535.f on every pixel: a pixel no region
+ * touches comes out as (x * (1.f / 65535.f)) * 65535.f.  As in the reference a region whose filter does nothing (r == 0, nlstrength == 0)
+ * still goes through its blend (and, NLMEANS L / C, the YUV round trip); `skipped` says why the filter did not run.
+ * mask: generateMasks' Lmask plane for the region (artgpu_generate_masks on the RGB image), of the image's size, host or device; NULL = all
+ * ones.  The caller keeps `masks[i].enabled` and does not pass a disabled region.  The boxes of all regions come from one device pass over
+ * the mask planes and one host wait for 4 * nregions ints (neither with NULL masks only); the whole plan is made after that wait and before
+ * any kernel writes the image.  A mask with no pixel above zero (undefined in the reference: an inverted box, negative sizes) skips the
+ * region: nothing of it runs, skipped = ARTGPU_SMOOTHING_SKIP_EMPTY.  nregions == 0: the normalise round trip.  NaN-free input is the
+ * contract.
+ * ARTGPU_EUNSUPPORTED, image untouched: the modes GAUSSIAN, GAUSSIAN_GLOW, MOTION, LENS, NOISE, HALATION (Convolution is an FFTW product;
+ * inpaint; the reference's RNG stream) and WAVELETS; iterations < 1; a GUIDED region (r > 0) whose statistics grid (working size /
+ * subsampling) has a side below ARTGPU_SMOOTHING_MIN_SIZE, or whose box radius is above the blur kernels' 900; an NLMEANS region
+ * (nlstrength != 0) with a working plane below 32 x 32, (ww + 14) * (hh + 14) >= 2^30, or scale < 1.  Not built: show_mask, the pipette
+ * buffers. */
+#define ARTGPU_SMOOTHING_GUIDED 0         /* SmoothingParams::Region::Mode (procparams.h:1296-1306) */
+#define ARTGPU_SMOOTHING_GAUSSIAN 1
+#define ARTGPU_SMOOTHING_GAUSSIAN_GLOW 2
+#define ARTGPU_SMOOTHING_NLMEANS 3
+#define ARTGPU_SMOOTHING_MOTION 4
+#define ARTGPU_SMOOTHING_LENS 5
+#define ARTGPU_SMOOTHING_NOISE 6
+#define ARTGPU_SMOOTHING_HALATION 7
+#define ARTGPU_SMOOTHING_WAVELETS 8
+#define ARTGPU_SMOOTHING_LUMINANCE 0      /* SmoothingParams::Region::Channel (procparams.h:1291-1295) */
+#define ARTGPU_SMOOTHING_CHROMINANCE 1
+#define ARTGPU_SMOOTHING_RGB 2
+/* the smallest side of a GUIDED region's statistics grid (working size / subsampling).  It comes from f_mean's clamp of the box radius,
+ * LIM(int(r / subsampling), 0, (min(w, h) - 1) / 2 - 1) (guidedfilter.cc:160-164): a side of 5 is the first at which a radius of 1 survives
+ * it, and a radius >= 1 with 2 * radius + 3 <= side is what the shared hblur / vblur_combine kernels take (their first rows and columns sum
+ * radius + 1 values without looking at the size).  Below it every radius clamps to 0, no blur would run and the "filter" is the identity
+ * through a log / exp round trip: refused, so that a region that small is noticed */
+#define ARTGPU_SMOOTHING_MIN_SIZE 5
+#define ARTGPU_SMOOTHING_SKIP_RADIUS 1    /* artgpu_smoothing_info::skipped: GUIDED with r == 0 */
+#define ARTGPU_SMOOTHING_SKIP_STRENGTH 2  /* NLMEANS with nlstrength == 0 */
+#define ARTGPU_SMOOTHING_SKIP_EMPTY 3     /* no mask pixel above zero */
+typedef struct artgpu_smoothing_region {  /* SmoothingParams::Region, defaults procparams.cc:2753-2775 */
+    int32_t mode;                     /* ARTGPU_SMOOTHING_GUIDED .. WAVELETS; default GUIDED */
+    int32_t channel;                  /* ARTGPU_SMOOTHING_LUMINANCE / CHROMINANCE / RGB; default RGB */
+    int32_t radius;                   /* 0 */
+    int32_t epsilon;                  /* 0 */
+    double sigma;                     /* 0 */
+    int32_t iterations;               /* 1 */
+    int32_t nldetail;                 /* 50 */
+    double falloff;                   /* 1 */
+    int32_t nlstrength;               /* 0 */
+    int32_t numblades;                /* 9 */
+    double angle, curvature, offset;  /* 0, 0, 0 */
+    int32_t noise_strength;           /* 10 */
+    int32_t noise_coarseness;         /* 30 */
+    double halation_size;             /* 1.0 */
+    double halation_color;            /* 0.0 */
+    double wav_strength;              /* 0 */
+    int32_t wav_levels;               /* 5 */
+    int32_t pad_;
+    double wav_gamma;                 /* 2.2 */
+    const artgpu_plane *mask;         /* generateMasks' Lmask plane; NULL = all ones */
+} artgpu_smoothing_region;
+typedef struct artgpu_smoothing_info {    /* one per region: what the host derived */
+    int32_t r;                        /* max(int(round(radius / scale)), 0) (GUIDED; 0 otherwise) */
+    float epsilon;                    /* GUIDED; 0 otherwise */
+    int32_t min_x, min_y, max_x, max_y;   /* the box the region blends over (max exclusive); the frame when not cropped; zeros when skipped for an empty mask */
+    int32_t cropped;
+    int32_t work_w, work_h;
+    int32_t subsampling, box_radius;  /* GUIDED with r > 0: calculate_subsampling, f_mean's radius; 0 otherwise */
+    int32_t skipped;                  /* 0 or ARTGPU_SMOOTHING_SKIP_* */
+} artgpu_smoothing_info;
+int artgpu_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_smoothing_region *regions, int nregions, const double ws[9], double scale,
+                     artgpu_smoothing_info *info /* nregions entries or NULL */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -936,6 +1016,18 @@ int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *local_c
  * artgpu_color_correction and artgpu_generate_masks do not support: before any stage runs.  n < 0 or a NULL list with n > 0: ARTGPU_EINVAL. */
 int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_correction_region *regions, int n,
                                          const artgpu_mask_params *masks /* n entries or NULL */);
+/* The Smoothing tool in the per-frame pipe, a setting of the context for the same reason.  regions: n entries (deep-copied; batch lanes share
+ * the copy); NULL / 0 = off, the default.  masks: n entries or NULL, copied as artgpu_set_pipeline_masks copies them.  While set, the three
+ * pipe entries run artgpu_smoothing's code with params->scale after colour correction and before texture boost (the last step of STAGE_2,
+ * improcfun.cc:602).  The tool works in RGB mode (its setMode(RGB), ipsmoothing.cc:937): colour correction ahead of it then ends with the
+ * switch back to RGB even when texture boost follows, and texture boost does its own setMode(YUV) again; with smoothing unset the image
+ * stays in YUV between those two as before.  With `masks` the Lmask planes are generated on the RGB image, the output's size as the full
+ * size, params->scale, and never leave the device; the regions' own `mask` pointers are then not read.  Colour correction ahead of
+ * pipe-generated smoothing masks is ARTGPU_EUNSUPPORTED (the reference generates them on the YUV image, ipsmoothing.cc:929, and the mask
+ * engine has no YUV mode).  Modes, iterations, scale, what artgpu_generate_masks does not support, and the size limits of a region without a
+ * mask fail the frame before any stage runs; a limit that depends on a mask's box fails at the tool, before the tool writes. */
+int artgpu_set_pipeline_smoothing(artgpu_ctx *ctx, const artgpu_smoothing_region *regions, int n,
+                                  const artgpu_mask_params *masks /* n entries or NULL */);
 
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
