@@ -33,36 +33,60 @@ struct artgpu_ctx {
     hipStream_t dn_stream[1] = {nullptr};
     hipEvent_t dn_ev[2] = {nullptr, nullptr};
     const float *gam_tab = nullptr; float gam_key[6] = {};   // RGB_denoise's gamma / inverse-gamma tables in pool[P_GAM]: what they were built from
-    int opt_sharpen_fused = 1;     // RL deconvolution, stencil regimes -- 1: one kernel per iteration (rl_iter_kernel); 0: DIV, MULT and check_stop as three launches (timing)
-    int opt_lut_lds = 1;           // 0: never the LUT-in-LDS shapes of the pixel passes (tests compare the two)
-    int opt_dn_streams = 0;        // 1: the DCT detail recovery of L on a side stream beside the reconstructions of a and b.  The default until round 5, when the
-                                   // stage waited on LDS round trips and left the chip half idle; since detail_blocks_kernel lost a fifth of its time (detail.hip) the
-                                   // two chains only get in each other's way: one kernel after the other is 0.1 - 0.15 ms per 45 MP frame faster (scripts/r5_ab9.sh)
-    int opt_dn_fused = 1;          // ShrinkAllL / ShrinkAllAB -- 0: three kernels per channel (factors, row sums, column sums + update); 2: one kernel per
-                                   // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
-    int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
-                                   // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
+    // What a batch lane inherits from its parent context (batch_prepare_lanes copies the block as one value on every batch call).  A field
+    // belongs here exactly if a frame's result or its reporting must not depend on which lane ran it.  (cu_reserve is not one: io_frame sets it
+    // per lane; the *_own storage the pipe_* pointers point into stays with the parent.)
+    struct Shared {
+        // options (artgpu_set_option): test / profiling switches that used to be environment variables
+        int opt_sharpen_fused = 1;     // RL deconvolution, stencil regimes -- 1: one kernel per iteration (rl_iter_kernel); 0: DIV, MULT and check_stop as three launches (timing)
+        int opt_lut_lds = 1;           // 0: never the LUT-in-LDS shapes of the pixel passes (tests compare the two)
+        int opt_dn_streams = 0;        // 1: the DCT detail recovery of L on a side stream beside the reconstructions of a and b.  The default until round 5, when the
+                                       // stage waited on LDS round trips and left the chip half idle; since detail_blocks_kernel lost a fifth of its time (detail.hip) the
+                                       // two chains only get in each other's way: one kernel after the other is 0.1 - 0.15 ms per 45 MP frame faster (scripts/r5_ab9.sh)
+        int opt_dn_fused = 1;          // ShrinkAllL / ShrinkAllAB -- 0: three kernels per channel (factors, row sums, column sums + update); 2: one kernel per
+                                       // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
+        int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
+                                       // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
+        int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
+        long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
+        int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
+                                       // hipMemcpy; -1 (default): 8 with two lanes, 0 otherwise (io_frame has the measurements)
+        int opt_amaze_path = 0;        // 0: LDS streaming kernel for full tiles + arena kernel for the rest; 1: arena kernel for every tile
+        int opt_amaze_split = 0;       // 1 (with path 1): one launch per phase
+        long opt_amaze_zero_mask = 0x81f0;
+        int opt_amaze_zero_frame = 16;
+        int opt_amaze_poison = -1;     // >= 0: byte pattern the arenas are filled with before the launch
+        int opt_roctx = 0;             // 1: roctx ranges named after the reference functions around the entry points (rocprofv3 --marker-trace)
+        int opt_amaze_overlap = 1;     // 0: the arena kernel's static tiles behind the stream kernel instead of beside it
+        int opt_amaze_grid = 0;        // > 0: at most this many stream workgroups (each owns a CU): with several frames in flight the CUs left over
+                                       // take the other frames' bandwidth-bound passes while this frame's issue-bound demosaic runs
+        int opt_rcd_rows = 8;          // rows per iteration of the streaming kernel (4 or 8)
+        int curve_tail_kind = ARTGPU_CURVE_TAIL_HOST;   // artgpu_set_curve_tail
+        double curve_tail_y = 1.0;
+        ParamCurve curve_tail_pc = {};
+        artgpu_progress_fn progress_fn = nullptr;   // artgpu_set_progress_callback
+        void *progress_user = nullptr;
+        // artgpu_set_pipeline_masks / _color_correction / _smoothing: what the pipe reads (the parent's pipe_*_own hold the memory)
+        const artgpu_mask_params *pipe_lc = nullptr, *pipe_tb = nullptr;
+        int pipe_nlc = 0, pipe_ntb = 0;
+        const artgpu_color_correction_region *pipe_cc = nullptr;
+        const artgpu_mask_params *pipe_cc_masks = nullptr;
+        int pipe_ncc = 0;
+        const artgpu_smoothing_region *pipe_sm = nullptr;
+        const artgpu_mask_params *pipe_sm_masks = nullptr;
+        int pipe_nsm = 0;
+    } shared;
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
     // artgpu_set_pipeline_masks: deep copies (entries, curves, area descriptors); batch lanes point at their parent's
     struct PipeMasks { std::vector<artgpu_mask_params> m; std::vector<std::vector<double>> curves; std::vector<artgpu_plane> areas; } pipe_lc_own, pipe_tb_own;
-    const artgpu_mask_params *pipe_lc = nullptr, *pipe_tb = nullptr;
-    int pipe_nlc = 0, pipe_ntb = 0;
-    // artgpu_set_pipeline_color_correction: the regions, their mask planes' descriptors and the mask parameters; lanes point at their parent's
-    struct PipeCc { std::vector<artgpu_color_correction_region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; } pipe_cc_own;
-    const artgpu_color_correction_region *pipe_cc = nullptr;
-    const artgpu_mask_params *pipe_cc_masks = nullptr;
-    int pipe_ncc = 0;
-    // artgpu_set_pipeline_smoothing: likewise
-    struct PipeSm { std::vector<artgpu_smoothing_region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; } pipe_sm_own;
-    const artgpu_smoothing_region *pipe_sm = nullptr;
-    const artgpu_mask_params *pipe_sm_masks = nullptr;
-    int pipe_nsm = 0;
+    // artgpu_set_pipeline_color_correction / artgpu_set_pipeline_smoothing: the regions, their mask planes' descriptors and the mask parameters
+    template <typename Region> struct PipeRegions { std::vector<Region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; };
+    PipeRegions<artgpu_color_correction_region> pipe_cc_own;
+    PipeRegions<artgpu_smoothing_region> pipe_sm_own;
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
-    int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
-    long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
-    long long batch_px = 0;        // artgpu_batch_run: pixels of the largest frame this context's scratch was grown for since the last trim
+    long long batch_px = 0;       // artgpu_batch_run: pixels of the largest frame this context's scratch was grown for since the last trim
     int dn_form = -1, dn_form_streak = 0;   // RGB_denoise: the shrink passes' form of the last call (1 fused / 0 three kernels) and how many calls in a row used it
     // per-workgroup work arenas (demosaic)
     float *arena = nullptr;
@@ -87,8 +111,6 @@ struct artgpu_ctx {
     int *io_host = nullptr;        // pinned, 8 words per frame of the lane: channel maxima (bit patterns) x 3, -, rgb2out's count of unsupported values
     int io_host_cap = 0;
     int cu_reserve = 0;            // set around a batch whose downloads run as a kernel of a few workgroups: the persistent one-workgroup-per-CU pixel passes leave those CUs alone
-    int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
-                                   // hipMemcpy; -1 (default): 8 with two lanes, 0 otherwise (io_frame has the measurements)
     // (what artgpu_improc_denoise_fused fuses into the denoise tool's pixel passes is not state of the context: it travels as a DnFusion argument)
     float *bbox = nullptr; // AMaZE: per-tile nyquist bounding boxes
     size_t bbox_bytes = 0;
@@ -98,25 +120,9 @@ struct artgpu_ctx {
     size_t amz_lists_bytes = 0;
     int amz_w = 0, amz_h = 0, amz_nstream = 0, amz_narena = 0, amz_mode = -1;
     int num_cus = 0;
-    // options (artgpu_set_option): test / profiling switches that used to be environment variables
-    int opt_amaze_path = 0;        // 0: LDS streaming kernel for full tiles + arena kernel for the rest; 1: arena kernel for every tile
-    int opt_amaze_split = 0;       // 1 (with path 1): one launch per phase
-    long opt_amaze_zero_mask = 0x81f0;
-    int opt_amaze_zero_frame = 16;
-    int opt_amaze_poison = -1;     // >= 0: byte pattern the arenas are filled with before the launch
-    int opt_roctx = 0;             // 1: roctx ranges named after the reference functions around the entry points (rocprofv3 --marker-trace)
-    artgpu_progress_fn progress_fn = nullptr;   // artgpu_set_progress_callback
-    void *progress_user = nullptr;
-    int opt_amaze_overlap = 1;     // 0: the arena kernel's static tiles behind the stream kernel instead of beside it
-    int opt_amaze_grid = 0;        // > 0: at most this many stream workgroups (each owns a CU): with several frames in flight the CUs left over
-                                   // take the other frames' bandwidth-bound passes while this frame's issue-bound demosaic runs
     hipStream_t amz_side = nullptr;
     hipEvent_t amz_ev[2] = {nullptr, nullptr};
-    int opt_rcd_rows = 8;          // rows per iteration of the streaming kernel (4 or 8)
     int *rcd_counter = nullptr;    // RCD streaming kernel: tile counter
-    int curve_tail_kind = ARTGPU_CURVE_TAIL_HOST;   // artgpu_set_curve_tail
-    double curve_tail_y = 1.0;
-    ParamCurve curve_tail_pc = {};
     float *lut = nullptr; // 65536-entry tone LUT on the device
     size_t lut_bytes = 0;
     std::vector<float> lut_host;           // what ctx->lut holds (a curve that comes back unchanged is not uploaded again)
@@ -304,6 +310,14 @@ struct DevRGB {
     bool staged;
 };
 
+// descriptors of device memory: one dense w x h plane; three planes with rows of `stride` floats
+artgpu_plane mk_dev_plane(float *p, int w, int h) { return artgpu_plane{p, w, h, (int64_t)w * 4, 1}; }
+artgpu_rgb mk_dev_rgb(float *const p[3], int w, int h, size_t stride)
+{
+    const auto plane = [&](int k) { return artgpu_plane{p[k], w, h, (int64_t)stride * 4, 1}; };
+    return artgpu_rgb{plane(0), plane(1), plane(2)};
+}
+
 int bind_rgb(artgpu_ctx *ctx, const artgpu_rgb *img, int slot, bool copy_in, DevRGB *d, const char *what)
 {
     const artgpu_plane *pl[3] = {&img->r, &img->g, &img->b};
@@ -460,8 +474,8 @@ int artgpu_set_curve_tail(artgpu_ctx *ctx, int kind, double y_last)
 {
     if (!ctx) return ARTGPU_EINVAL;
     if (kind < ARTGPU_CURVE_TAIL_LUT || kind > ARTGPU_CURVE_TAIL_HOST) return fail(ctx, ARTGPU_EINVAL, "set_curve_tail: kind %d (a parametric curve: artgpu_set_curve_tail_parametric)", kind);
-    ctx->curve_tail_kind = kind;
-    ctx->curve_tail_y = y_last;
+    ctx->shared.curve_tail_kind = kind;
+    ctx->shared.curve_tail_y = y_last;
     return ARTGPU_OK;
 }
 
@@ -472,8 +486,8 @@ int artgpu_set_curve_tail_parametric(artgpu_ctx *ctx, const double *p, int np)
     // are all zero is the identity there (and `identity` curves never reach setLutVal with a Curve object: ARTGPU_CURVE_TAIL_LUT)
     if (!p || (np != 8 && np != 9)) return fail(ctx, ARTGPU_EINVAL, "set_curve_tail_parametric: 8 or 9 parameters (p[0] = DCT_Parametric)");
     if (p[4] == 0.0 && p[5] == 0.0 && p[6] == 0.0 && p[7] == 0.0) return fail(ctx, ARTGPU_EINVAL, "set_curve_tail_parametric: an identity curve has no Curve object (ARTGPU_CURVE_TAIL_LUT)");
-    pc_init(ctx->curve_tail_pc, p, np);
-    ctx->curve_tail_kind = ARTGPU_CURVE_TAIL_PARAMETRIC;
+    pc_init(ctx->shared.curve_tail_pc, p, np);
+    ctx->shared.curve_tail_kind = ARTGPU_CURVE_TAIL_PARAMETRIC;
     return ARTGPU_OK;
 }
 
@@ -500,24 +514,24 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
 {
     if (!ctx || !name) return ARTGPU_EINVAL;
     const std::string n(name);
-    if (n == "amaze_path") { if (value < 0 || value > 1) return fail(ctx, ARTGPU_EINVAL, "amaze_path: 0 or 1"); ctx->opt_amaze_path = (int)value; }
-    else if (n == "amaze_split") ctx->opt_amaze_split = value != 0;
-    else if (n == "amaze_overlap") ctx->opt_amaze_overlap = value != 0;
-    else if (n == "amaze_grid") { if (value < 0) return fail(ctx, ARTGPU_EINVAL, "amaze_grid: >= 0"); ctx->opt_amaze_grid = (int)value; }
-    else if (n == "amaze_zero_mask") ctx->opt_amaze_zero_mask = value;
-    else if (n == "amaze_zero_frame") ctx->opt_amaze_zero_frame = (int)value;
-    else if (n == "amaze_poison") ctx->opt_amaze_poison = (int)value;
-    else if (n == "roctx") ctx->opt_roctx = value != 0;
-    else if (n == "dn_streams") ctx->opt_dn_streams = value != 0;
-    else if (n == "dn_fused") ctx->opt_dn_fused = (int)value;
-    else if (n == "dn_detail_plain") { if (value < 0 || value > 3) return fail(ctx, ARTGPU_EINVAL, "dn_detail_plain: 0 .. 3"); ctx->opt_dn_detail_plain = (int)value; }
-    else if (n == "dn_debug_stall") ctx->opt_dn_debug_stall = (int)value;
-    else if (n == "dn_wait_ms") ctx->opt_dn_wait_ms = value < 0 ? 0 : value;
-    else if (n == "lut_lds") ctx->opt_lut_lds = value != 0;
-    else if (n == "sharpen_fused") ctx->opt_sharpen_fused = value != 0;
+    if (n == "amaze_path") { if (value < 0 || value > 1) return fail(ctx, ARTGPU_EINVAL, "amaze_path: 0 or 1"); ctx->shared.opt_amaze_path = (int)value; }
+    else if (n == "amaze_split") ctx->shared.opt_amaze_split = value != 0;
+    else if (n == "amaze_overlap") ctx->shared.opt_amaze_overlap = value != 0;
+    else if (n == "amaze_grid") { if (value < 0) return fail(ctx, ARTGPU_EINVAL, "amaze_grid: >= 0"); ctx->shared.opt_amaze_grid = (int)value; }
+    else if (n == "amaze_zero_mask") ctx->shared.opt_amaze_zero_mask = value;
+    else if (n == "amaze_zero_frame") ctx->shared.opt_amaze_zero_frame = (int)value;
+    else if (n == "amaze_poison") ctx->shared.opt_amaze_poison = (int)value;
+    else if (n == "roctx") ctx->shared.opt_roctx = value != 0;
+    else if (n == "dn_streams") ctx->shared.opt_dn_streams = value != 0;
+    else if (n == "dn_fused") ctx->shared.opt_dn_fused = (int)value;
+    else if (n == "dn_detail_plain") { if (value < 0 || value > 3) return fail(ctx, ARTGPU_EINVAL, "dn_detail_plain: 0 .. 3"); ctx->shared.opt_dn_detail_plain = (int)value; }
+    else if (n == "dn_debug_stall") ctx->shared.opt_dn_debug_stall = (int)value;
+    else if (n == "dn_wait_ms") ctx->shared.opt_dn_wait_ms = value < 0 ? 0 : value;
+    else if (n == "lut_lds") ctx->shared.opt_lut_lds = value != 0;
+    else if (n == "sharpen_fused") ctx->shared.opt_sharpen_fused = value != 0;
     else if (n == "cu_reserve") { if (value < 0 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "cu_reserve: 0 .. 4096"); ctx->cu_reserve = (int)value; }
-    else if (n == "io_direct") { if (value < -1 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "io_direct: -1 (automatic), 0 .. 4096 workgroups"); ctx->opt_io_direct = (int)value; }
-    else if (n == "rcd_rows") { if (value != 4 && value != 8) return fail(ctx, ARTGPU_EINVAL, "rcd_rows: 4 or 8"); ctx->opt_rcd_rows = (int)value; }
+    else if (n == "io_direct") { if (value < -1 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "io_direct: -1 (automatic), 0 .. 4096 workgroups"); ctx->shared.opt_io_direct = (int)value; }
+    else if (n == "rcd_rows") { if (value != 4 && value != 8) return fail(ctx, ARTGPU_EINVAL, "rcd_rows: 4 or 8"); ctx->shared.opt_rcd_rows = (int)value; }
     else return fail(ctx, ARTGPU_EINVAL, "set_option: unknown option '%s'", name);
     return ARTGPU_OK;
 }
@@ -525,8 +539,8 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
 int artgpu_set_progress_callback(artgpu_ctx *ctx, artgpu_progress_fn fn, void *user)
 {
     if (!ctx) return ARTGPU_EINVAL;
-    ctx->progress_fn = fn;
-    ctx->progress_user = user;
+    ctx->shared.progress_fn = fn;
+    ctx->shared.progress_user = user;
     return ARTGPU_OK;
 }
 
@@ -593,7 +607,7 @@ struct StageScope {
     StageScope(artgpu_ctx *c, const char *n) : ctx(c), name(n), range(false)
     {
         if (!ctx) return;
-        if (ctx->opt_roctx) {
+        if (ctx->shared.opt_roctx) {
             static bool tried = false;
             if (!tried) {
                 tried = true;
@@ -607,12 +621,12 @@ struct StageScope {
             }
             if (push() && pop()) { push()(name); range = true; }
         }
-        if (ctx->progress_fn) ctx->progress_fn(ctx->progress_user, name, 0.0);
+        if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 0.0);
     }
     ~StageScope()
     {
         if (!ctx) return;
-        if (ctx->progress_fn) ctx->progress_fn(ctx->progress_user, name, 1.0);
+        if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 1.0);
         if (range) pop()();
     }
 };
@@ -651,7 +665,7 @@ static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *
         // frame edge: exact only when a full-size tile ends 16 pixels past the frame); everything else -- narrower tiles, those
         // over-run tiles and streamed tiles whose Nyquist sites do not fit the stream's assumption -- is done by the arena kernel
         // (amaze.hip), which reproduces the reference's buffer layout literally.
-        const int mode = ctx->opt_amaze_path;
+        const int mode = ctx->shared.opt_amaze_path;
         if (ctx->amz_w != W || ctx->amz_h != H || ctx->amz_mode != mode) {
             std::vector<int> st, ar;
             for (int ty = 0; ty < nty; ++ty)
@@ -691,8 +705,8 @@ static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *
         // one workgroup each and a chain of twenty HBM round trips, 0.45 ms that used to follow the stream kernel; now they hold a few CUs
         // back for that long while the stream workgroups on the other CUs take tiles from the shared counter.  LATE, behind both: whatever
         // the stream handed back (tiles whose Nyquist sites did not fit its assumption and found no taker in the redo queue), normally nothing.
-        const bool split = mode == 1 && ctx->opt_amaze_split;
-        const bool early = ctx->amz_nstream > 0 && ctx->amz_narena > 0 && ctx->opt_amaze_overlap;
+        const bool split = mode == 1 && ctx->shared.opt_amaze_split;
+        const bool early = ctx->amz_nstream > 0 && ctx->amz_narena > 0 && ctx->shared.opt_amaze_overlap;
         const int nlist_max = ctx->amz_narena + ctx->amz_nstream;
         const int cap = split ? MAX_TILE_WORKGROUPS : 768;
         // (the per-phase profiling path runs one arena per tile of the grid, the tiles that write nothing included)
@@ -713,15 +727,15 @@ static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *
         // vcdalt, hcdalt, cddiffsq, nyquist (bits 4-8, 15): on a full tile every other position is written before it is read, for
         // every CFA phase, because the phase loops cover fixed index ranges (derivation: DESIGN.md section 10).
         // tests/test_gpu_demosaic.py re-checks it with poisoned arenas (artgpu_set_option "amaze_poison").  Partial tiles clear everything.
-        a.zero_mask = (unsigned)ctx->opt_amaze_zero_mask;
+        a.zero_mask = (unsigned)ctx->shared.opt_amaze_zero_mask;
         // ... and of the five full-size planes among them only positions within a few pixels of the tile edge (plus the gap behind each
         // plane): a frame of 4 already passes the poison test, 16 (the discarded tile border) is used.  0: whole planes.
-        a.zero_frame = ctx->opt_amaze_zero_frame;
+        a.zero_frame = ctx->shared.opt_amaze_zero_frame;
         a.split = split ? 1 : 0;
         a.queue_words = d_qwords;
         a.queue_counters = reinterpret_cast<int *>(d_qwords + ctx->amz_nstream);
-        if (ctx->opt_amaze_poison >= 0)   // test hook: fill the arenas with a byte pattern first
-            HIPCHK(ctx, hipMemsetAsync(ctx->arena, ctx->opt_amaze_poison, (size_t)grid * AMAZE_ARENA_FLOATS * sizeof(float), ctx->stream));
+        if (ctx->shared.opt_amaze_poison >= 0)   // test hook: fill the arenas with a byte pattern first
+            HIPCHK(ctx, hipMemsetAsync(ctx->arena, ctx->shared.opt_amaze_poison, (size_t)grid * AMAZE_ARENA_FLOATS * sizeof(float), ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(d_queue, 0, (4 + 2 * (size_t)ctx->amz_nstream + 8) * sizeof(int), ctx->stream));   // + the 8 counters behind it
         SideStreamJoin amz_join;
         if (early) {
@@ -767,7 +781,7 @@ static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *
             // frames in flight at 45 MP (scripts/r5_lanes.sh: 240 / 224 / 192 / 160 / 144 / 128 workgroups; one frame at a time: all CUs).
             // Option "amaze_grid" overrides.
             const int cu_auto = ctx->frames_in_flight > 1 ? std::max(1, ctx->num_cus * 5 / 8) : ctx->num_cus;
-            const int cu_cap = ctx->opt_amaze_grid > 0 ? std::min(ctx->opt_amaze_grid, ctx->num_cus) : cu_auto;
+            const int cu_cap = ctx->shared.opt_amaze_grid > 0 ? std::min(ctx->shared.opt_amaze_grid, ctx->num_cus) : cu_auto;
             HIPCHK(ctx, launch_amaze_stream(sa, std::min(ctx->amz_nstream, cu_cap), early ? ctx->amz_side : ctx->stream));
         }
         if (early) {
@@ -809,7 +823,7 @@ static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *
             a.filters = filters;
             a.vec2 = d.out_stride % 2 == 0 && (reinterpret_cast<uintptr_t>(d.r) | reinterpret_cast<uintptr_t>(d.g) | reinterpret_cast<uintptr_t>(d.b)) % 8 == 0;
             a.counter = ctx->rcd_counter;
-            const int R = ctx->opt_rcd_rows;
+            const int R = ctx->shared.opt_rcd_rows;
             HIPCHK(ctx, launch_rcd_stream(a, R, std::min(ntiles, ctx->num_cus * rcd_stream_workgroups_per_cu(R)), ctx->stream));
         }
         bord = RCD_BORDER; // rcd_demosaic.cc:342
@@ -961,7 +975,7 @@ int artgpu_tone_curve(artgpu_ctx *ctx, artgpu_rgb *image, int mode, const float 
     if (!image) return fail(ctx, ARTGPU_EINVAL, "tone_curve: null image");
     if (mode != ARTGPU_TONE_STD) return fail(ctx, ARTGPU_EUNSUPPORTED, "tone_curve: curve mode %d is not on the device path", mode);
     if (!(whitept > 0.f)) return fail(ctx, ARTGPU_EINVAL, "tone_curve: whitept %g", (double)whitept);
-    if (whitept > 1.f && ctx->curve_tail_kind == ARTGPU_CURVE_TAIL_HOST)
+    if (whitept > 1.f && ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "tone_curve: whitept %g needs the curve beyond the LUT (artgpu_set_curve_tail)", (double)whitept);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
@@ -971,12 +985,12 @@ int artgpu_tone_curve(artgpu_ctx *ctx, artgpu_rgb *image, int mode, const float 
     for (int k = 0; k < 3; ++k) a.dst[k] = d.p[k];
     a.dst_stride = d.stride; a.w = d.w; a.h = d.h;
     a.do_clip = filmlike_clip ? 1 : 0; a.whitept = whitept;
-    a.tail_kind = ctx->curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->curve_tail_kind; a.tail_y = ctx->curve_tail_y; a.tail_pc = ctx->curve_tail_pc;
+    a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
     if (lut65536) {
         if ((rc = upload_curve(ctx, lut65536))) return rc;
         a.lut = ctx->lut;
     }
-    a.no_lds_lut = !ctx->opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
+    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
     HIPCHK(ctx, launch_tone_std(a, ctx->stream));
     return unbind_rgb(ctx, image, &d);
 }
@@ -1755,7 +1769,7 @@ int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_param
     if (w > 32767 || h > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: the reference holds the size in short (FTblockDN.cc:1779)");
     if (p->luminance == 0 && p->chrominance == 0 && !ccalc) return ARTGPU_OK; // L1655-1668: nothing to do
     const DnPlan pl = dn_plan(w, h, p, scale, expcomp, flags, nresi || highresi, ccalc != nullptr,
-                              ctx->opt_dn_streams, ctx->opt_dn_fused, ctx->opt_dn_detail_plain, ctx->opt_dn_wait_ms, ctx->opt_dn_debug_stall);
+                              ctx->shared.opt_dn_streams, ctx->shared.opt_dn_fused, ctx->shared.opt_dn_detail_plain, ctx->shared.opt_dn_wait_ms, ctx->shared.opt_dn_debug_stall);
     if (pl.too_small) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: %dx%d too small for %d wavelet levels on the device path", w, h, pl.levwav);
     DnBuffers b;
     int rc = dn_buffers(ctx, pl, ccalc, &b);
@@ -1785,7 +1799,7 @@ int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_param
     px.gain = pl.gain; px.newGain = 1.f / pl.gain;
     px.gam = pl.gam; px.gamthresh = pl.gamthresh; px.gamslope = pl.gamslope; px.igam = pl.igam; px.igamthresh = pl.igamthresh; px.igamslope = pl.igamslope;
     px.gamcurve = b.gamlut; px.igamcurve = b.gamlut + 65536;
-    px.pre_scale = fu.pre_scale; px.post_scale = fu.post_scale; px.no_lds_lut = !ctx->opt_lut_lds; px.cu_reserve = ctx->cu_reserve;
+    px.pre_scale = fu.pre_scale; px.post_scale = fu.post_scale; px.no_lds_lut = !ctx->shared.opt_lut_lds; px.cu_reserve = ctx->cu_reserve;
     px.gi = fu.gi; px.exp_on = fu.exp_on; px.exp_scale = fu.exp_scale; px.exp_black = fu.exp_black;
     // the inverse-gamma pass looks up gamma-encoded values: the mid-tones sit in the middle of the table, so the 40704 entries kept in LDS
     // start at 8000 (gamma 1.7: linear 0.03 .. 0.60 of white); the forward pass and the tone curve index with linear data and keep [0, 40704)
@@ -2567,8 +2581,8 @@ int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *l
     a.lut = ctx->lut; a.pq = pq; a.pq_inv = pq + 65536; a.hues = pq + 2 * 65536;
     for (int k = 0; k < 9; ++k) { a.ws[k] = (float)st->ws[k]; a.iws[k] = (float)st->iws[k]; a.to_out[k] = st->to_out[k]; a.to_work[k] = st->to_work[k]; }
     a.whitecoeff = whitecoeff;
-    a.tail_kind = ctx->curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->curve_tail_kind; a.tail_y = ctx->curve_tail_y; a.tail_pc = ctx->curve_tail_pc;
-    a.no_lds_lut = !ctx->opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
+    a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
+    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
     HIPCHK(ctx, launch_tone_neutral(a, ctx->stream));
     return unbind_rgb(ctx, image, &d);
 }
@@ -2611,7 +2625,7 @@ static int chroma_map_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride
     a.stride = stride; a.wid = wid; a.hei = hei;
     a.has_mat = mat ? 1 : 0;
     for (int k = 0; k < 9; ++k) { a.mat[k] = mat ? mat[k] : 0.0; a.wpi[k] = (float)ws[k]; }
-    a.cachef = tab; a.curve = tab + 65536; a.out = map; a.no_lds_lut = !ctx->opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
+    a.cachef = tab; a.curve = tab + 65536; a.out = map; a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
     HIPCHK(ctx, launch_chroma_map(a, ctx->stream));
     *out = map;
     return ARTGPU_OK;
@@ -2945,9 +2959,7 @@ int artgpu_improc_denoise_fused(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_d
     // host planes: stage once, run the whole tool on the staged copy, copy back (device planes are used in place)
     DevRGB d;
     if ((rc = bind_rgb(ctx, img, 4, true, &d, "improc_denoise"))) return rc;
-    artgpu_rgb dv;
-    artgpu_plane *pl[3] = {&dv.r, &dv.g, &dv.b};
-    for (int k = 0; k < 3; ++k) { pl[k]->p = d.p[k]; pl[k]->w = d.w; pl[k]->h = d.h; pl[k]->row_stride_bytes = (int64_t)d.stride * 4; pl[k]->on_device = 1; }
+    artgpu_rgb dv = mk_dev_rgb(d.p, d.w, d.h, d.stride);
     if ((rc = improc_denoise_dev(ctx, &dv, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags, f))) return rc;
     // the exposure that could not be fused follows as its own call
     if (fu && fu->exposure_enabled && !fuse_exp && !tail_exp && (rc = artgpu_exposure(ctx, &dv, fu->exp_scale, fu->black))) return rc;
@@ -3938,8 +3950,6 @@ int mk_plan(artgpu_ctx *ctx, int W, int H, int mode, const double *ws, const art
     return ARTGPU_OK;
 }
 
-artgpu_plane mk_dev_plane(float *p, int w, int h) { return artgpu_plane{p, w, h, (int64_t)w * 4, 1}; }
-
 // generateMasks on a device image (rows of `stride` floats), enqueued on ctx->stream.  Lout / about: n contiguous W x H device planes each,
 // or nullptr.  `masks` is read for the area planes only.
 int masks_dev(artgpu_ctx *ctx, float *const img[3], size_t stride, const double *ws, const artgpu_mask_params *masks, const MkPlan &pl,
@@ -4102,6 +4112,29 @@ const artgpu_mask_params *own_pipe_masks(artgpu_ctx::PipeMasks &o, const artgpu_
     return n > 0 ? o.m.data() : nullptr;
 }
 
+// what artgpu_set_pipeline_color_correction and artgpu_set_pipeline_smoothing share: the regions are copied, the descriptors of their mask
+// planes (the members `fields` names) too -- the planes' memory stays the caller's --, the mask entries are owned or reset, and the pipe's
+// view of the setting (regions, entries, count) is written
+extern "C++" {
+template <typename Region>
+void own_pipe_regions(artgpu_ctx::PipeRegions<Region> &o, const Region *regions, int n, std::initializer_list<const artgpu_plane *Region::*> fields,
+                      const artgpu_mask_params *masks, const Region **regs, const artgpu_mask_params **entries, int *count)
+{
+    o.regs.assign(regions, regions + n);
+    o.planes.assign(fields.size() * n, artgpu_plane{});
+    artgpu_plane *next = o.planes.data();
+    for (Region &r : o.regs)
+        for (const auto f : fields) {
+            if (r.*f) { *next = *(r.*f); r.*f = next; }
+            ++next;
+        }
+    *entries = masks ? own_pipe_masks(o.masks, masks, n) : nullptr;
+    if (!masks) o.masks = artgpu_ctx::PipeMasks{};
+    *regs = n > 0 ? o.regs.data() : nullptr;
+    *count = n;
+}
+} // extern "C++"
+
 // the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)
 int pq_tables_dev(artgpu_ctx *ctx, float **out)
 {
@@ -4258,17 +4291,8 @@ int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_cor
 {
     if (!ctx) return ARTGPU_EINVAL;
     if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_color_correction: bad arguments");
-    artgpu_ctx::PipeCc &o = ctx->pipe_cc_own;
-    o.regs.assign(regions, regions + n);
-    o.planes.assign((size_t)2 * n, artgpu_plane{});
-    for (int i = 0; i < n; ++i) {                               // the planes' descriptors are copied, their memory stays the caller's
-        if (o.regs[i].lmask) { o.planes[2 * i] = *o.regs[i].lmask; o.regs[i].lmask = &o.planes[2 * i]; }
-        if (o.regs[i].abmask) { o.planes[2 * i + 1] = *o.regs[i].abmask; o.regs[i].abmask = &o.planes[2 * i + 1]; }
-    }
-    ctx->pipe_cc_masks = masks ? own_pipe_masks(o.masks, masks, n) : nullptr;
-    if (!masks) o.masks = artgpu_ctx::PipeMasks{};
-    ctx->pipe_cc = n > 0 ? o.regs.data() : nullptr;
-    ctx->pipe_ncc = n;
+    own_pipe_regions(ctx->pipe_cc_own, regions, n, {&artgpu_color_correction_region::lmask, &artgpu_color_correction_region::abmask}, masks,
+                     &ctx->shared.pipe_cc, &ctx->shared.pipe_cc_masks, &ctx->shared.pipe_ncc);
     return ARTGPU_OK;
 }
 
@@ -4529,15 +4553,7 @@ int artgpu_set_pipeline_smoothing(artgpu_ctx *ctx, const artgpu_smoothing_region
 {
     if (!ctx) return ARTGPU_EINVAL;
     if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_smoothing: bad arguments");
-    artgpu_ctx::PipeSm &o = ctx->pipe_sm_own;
-    o.regs.assign(regions, regions + n);
-    o.planes.assign((size_t)n, artgpu_plane{});
-    for (int i = 0; i < n; ++i)                                 // the planes' descriptors are copied, their memory stays the caller's
-        if (o.regs[i].mask) { o.planes[i] = *o.regs[i].mask; o.regs[i].mask = &o.planes[i]; }
-    ctx->pipe_sm_masks = masks ? own_pipe_masks(o.masks, masks, n) : nullptr;
-    if (!masks) o.masks = artgpu_ctx::PipeMasks{};
-    ctx->pipe_sm = n > 0 ? o.regs.data() : nullptr;
-    ctx->pipe_nsm = n;
+    own_pipe_regions(ctx->pipe_sm_own, regions, n, {&artgpu_smoothing_region::mask}, masks, &ctx->shared.pipe_sm, &ctx->shared.pipe_sm_masks, &ctx->shared.pipe_nsm);
     return ARTGPU_OK;
 }
 
@@ -4607,7 +4623,7 @@ static int rl_dev(artgpu_ctx *ctx, float *lum, const float *blend, const unsigne
             if ((rc = gaussian_dev(ctx, ratio, gtmp, W, H, sigma))) return rc;
             a.est_in = est; a.est_out = est;
             HIPCHK(ctx, launch_rl_point(a, 1, ctx->stream));
-        } else if (ctx->opt_sharpen_fused) {
+        } else if (ctx->shared.opt_sharpen_fused) {
             a.est_in = est; a.est_out = other;
             HIPCHK(ctx, launch_rl_iter(a, rg, ctx->stream));
             std::swap(est, other);
@@ -4848,173 +4864,196 @@ static int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, in
     if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on a frame smaller than 64x64");
     return ca_correct_dev(ctx, raw, stride, W, H, cfa, &p->ca, nullptr);
 }
-static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca);
-} // namespace
 
-int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *lc, int nlc, const artgpu_mask_params *tb, int ntb)
+enum PipeMode { PIPE_RGB, PIPE_YUV };
+// Everything a frame decides before its first launch (pipeline_plan).  The stages only read it, but for the `mask` pointers of lc_regs / tb_regs,
+// which pipe_stage3 aims at the planes it generates.
+struct PipePlan {
+    int W, H, b, w, h;             // the raw frame, its border, the image behind the demosaic (W - 2b x H - 2b)
+    double scale;
+    bool lc_on, lc_gen, tb_on, tb_gen, cc_on, cc_gen, sm_on, sm_gen;   // the local tools: on, and the pipe generates their masks (artgpu_set_pipeline_*)
+    bool cc_to_rgb, tb_in_yuv;     // the mode walk: colour correction ends with the switch back to RGB; texture boost finds the image in YUV mode
+    std::vector<artgpu_local_contrast_region> lc_regs;             // copies of the regions whose masks the pipe generates ...
+    std::vector<artgpu_texture_boost_region> tb_regs;
+    const artgpu_local_contrast_region *lc_regions;                // ... or the caller's
+    const artgpu_texture_boost_region *tb_regions;
+    MkPlan lc_mk, tb_mk, cc_mk, sm_mk;
+    CcPlan cc;
+    DehazePlan dehaze;
+    bool sh_on, sh_auto, sh_radius_pending;
+    artgpu_sharpening_params shpar;                                // (deconvradius: 0.75 stands in while the automatic radius is pending)
+    SharpenPlan sharpen;
+    std::vector<TbPlan> tb;
+};
+// What the stages hand on: the CFA plane the demosaic reads (the caller's, or its CA-corrected copy in the pool), the demosaiced W x H planes in the
+// pool, the w x h image the later stages work on (the caller's planes if they are on the device, else a staged copy) as launchers / entry points take it
+struct PipeFrame { artgpu_plane raw; artgpu_rgb dem; DevRGB d; artgpu_rgb img; };
+
+// the MkPlan of n regions whose masks the pipe generates on its own image (mode: ARTGPU_MASKS_MODE_LAB or _RGB; full size, no crop)
+static int pipe_plan_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, int mode, const artgpu_mask_params *masks, int n, bool want_ab, const char *who, MkPlan *mk)
 {
-    if (!ctx) return ARTGPU_EINVAL;
-    if (nlc < 0 || ntb < 0 || (nlc > 0 && !lc) || (ntb > 0 && !tb)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_masks: bad arguments");
-    ctx->pipe_lc = own_pipe_masks(ctx->pipe_lc_own, lc, nlc); ctx->pipe_nlc = nlc;
-    ctx->pipe_tb = own_pipe_masks(ctx->pipe_tb_own, tb, ntb); ctx->pipe_ntb = ntb;
+    return mk_plan(ctx, pl.w, pl.h, mode, mode == ARTGPU_MASKS_MODE_LAB ? nullptr : p->ws, masks, n, pl.w, pl.h, pl.scale, true, want_ab, who, mk, nullptr);
+}
+
+// generateMasks(rgb, ., masks, 0, 0, full size, scale, ., -1, &Lmask, [&abmask]) on the device image: the planes go to pool slot `slot` and never
+// leave the device.  *planes: their descriptors, n L planes, then n ab planes when asked for
+static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const DevRGB &d, int slot, const artgpu_mask_params *masks, const MkPlan &mk, int n, bool want_ab,
+                          std::vector<artgpu_plane> *planes)
+{
+    const size_t np = (size_t)d.w * d.h, count = (size_t)n * (want_ab ? 2 : 1);
+    float *mo;
+    int rc;
+    if ((rc = pool_get(ctx, slot, count * np * 4, &mo)) || (rc = masks_dev(ctx, d.p, d.stride, p->ws, masks, mk, mo, want_ab ? mo + n * np : nullptr))) return rc;
+    planes->resize(count);
+    for (size_t i = 0; i < count; ++i) (*planes)[i] = mk_dev_plane(mo + i * np, d.w, d.h);
     return ARTGPU_OK;
 }
 
-int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *p, artgpu_rgb *out)
+// Checks and derives everything; launches nothing and takes no pool slot, so a refused frame leaves the output planes alone.  The checks, in the
+// order they report (a frame that is wrong in two ways names the first):
+//   1. ctx, raw / p / out, the border, the output's size (then hipSetDevice, the one HIP call here)   2. artgpu_set_pipeline_masks' counts against the frame's
+//   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
+//   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
+//   8. dehaze_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
+static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, PipePlan *pl)
 {
-    return pipeline_run_impl(ctx, raw, p, out, true);
-}
-
-namespace {
-static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca)
-{
-    StageScope scope_(ctx, "ImageProcessor (stage_init .. stage_finish)");
     if (!ctx) return ARTGPU_EINVAL;
     if (!plane_ok(raw_in) || !p || !out) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: null/bad argument");
-    const int W = raw_in->w, H = raw_in->h, b = p->border;
-    if (b < 0 || W - 2 * b < 8 || H - 2 * b < 8) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: border %d leaves no image", b);
-    if (out->r.w != W - 2 * b || out->r.h != H - 2 * b) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", W - 2 * b, H - 2 * b);
+    const int b = p->border, w = raw_in->w - 2 * b, h = raw_in->h - 2 * b, nlc = p->local_contrast_nregions, ntb = p->texture_boost_nregions;
+    const double scale = p->scale > 0 ? p->scale : 1.0;
+    pl->W = raw_in->w; pl->H = raw_in->h; pl->b = b; pl->w = w; pl->h = h; pl->scale = scale;
+    if (b < 0 || w < 8 || h < 8) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: border %d leaves no image", b);
+    if (out->r.w != w || out->r.h != h) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", w, h);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
+    const artgpu_ctx::Shared &s = ctx->shared;
+    pl->lc_on = p->local_contrast_enabled && nlc > 0; pl->lc_gen = pl->lc_on && s.pipe_lc;
+    pl->tb_on = p->texture_boost_enabled != 0;        pl->tb_gen = pl->tb_on && ntb > 0 && s.pipe_tb;
+    pl->cc_on = s.pipe_ncc > 0 && s.pipe_cc;          pl->cc_gen = pl->cc_on && s.pipe_cc_masks;
+    pl->sm_on = s.pipe_nsm > 0 && s.pipe_sm;          pl->sm_gen = pl->sm_on && s.pipe_sm_masks;
+    // The image's colour mode in front of each tool, in pipe order, as the reference has it: sharpening works on RGB; colorCorrection generates its masks
+    // on RGB and leaves YUV; guidedSmoothing generates its masks on what it finds, then setMode(RGB); textureBoost likewise, then setMode(YUV), and ends in
+    // RGB for the tone curve and localContrast (whose LAB, masks included, is its own switch).  The mask engine reads RGB only: masks to be generated
+    // on a YUV image fail the frame.  Colour correction ends with the next tool's setMode(RGB) (to_rgb) unless that tool is texture boost, which then skips
+    // its own switch (in_yuv).  '-': not read; the mask columns say what happens where the pipe generates that tool's masks
+    //   cc sm | in front of sm | in front of tb | cc to_rgb (tb off / on) | tb in_yuv | sm's masks | tb's masks
+    //    0  0 |       -        |      RGB       |           -             |     0     |     -      |    ok
+    //    0  1 |      RGB       |      RGB       |           -             |     0     |     ok     |    ok
+    //    1  0 |       -        |      YUV       |         1 / 0           |     1     |     -      |  refused
+    //    1  1 |      YUV       |      RGB       |         1 / 1           |     0     |  refused   |    ok
+    PipeMode mode = pl->cc_on ? PIPE_YUV : PIPE_RGB;           // (sharpening: RGB in, RGB out)
+    const bool sm_masks_from_yuv = pl->sm_gen && mode == PIPE_YUV;
+    if (pl->sm_on) mode = PIPE_RGB;
+    const bool tb_masks_from_yuv = pl->tb_gen && mode == PIPE_YUV;
+    pl->tb_in_yuv = pl->tb_on && mode == PIPE_YUV;
+    pl->cc_to_rgb = !pl->tb_in_yuv;
     // regions whose blend planes the pipe generates itself (artgpu_set_pipeline_masks): the regions' own `mask` pointers are
     // not read, the planes of artgpu_generate_masks take their place; what it does not support fails the frame here
-    const bool lc_on = p->local_contrast_enabled && p->local_contrast_nregions > 0;
-    const bool lc_gen = lc_on && ctx->pipe_lc, tb_gen = p->texture_boost_enabled && p->texture_boost_nregions > 0 && ctx->pipe_tb;
-    if ((lc_gen && ctx->pipe_nlc != p->local_contrast_nregions) || (tb_gen && ctx->pipe_ntb != p->texture_boost_nregions))
-        return fail(ctx, ARTGPU_EINVAL, "pipeline_run: artgpu_set_pipeline_masks holds %d / %d entries, the frame has %d / %d regions", ctx->pipe_nlc, ctx->pipe_ntb,
-                    p->local_contrast_nregions, p->texture_boost_nregions);
-    std::vector<artgpu_local_contrast_region> lc_regs;
-    std::vector<artgpu_texture_boost_region> tb_regs;
-    MkPlan lc_mk, tb_mk;
-    if (lc_gen) {
+    if ((pl->lc_gen && s.pipe_nlc != nlc) || (pl->tb_gen && s.pipe_ntb != ntb))
+        return fail(ctx, ARTGPU_EINVAL, "pipeline_run: artgpu_set_pipeline_masks holds %d / %d entries, the frame has %d / %d regions", s.pipe_nlc, s.pipe_ntb, nlc, ntb);
+    const auto own = [](auto &regs, const auto *src, int n) { regs.assign(src, src + n); for (auto &r : regs) r.mask = nullptr; };
+    if (pl->lc_gen) {
         if (!p->local_contrast_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(local contrast): bad region list");
-        lc_regs.assign(p->local_contrast_regions, p->local_contrast_regions + p->local_contrast_nregions);
-        for (auto &r : lc_regs) r.mask = nullptr;
-        if ((rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_LAB, nullptr, ctx->pipe_lc, p->local_contrast_nregions, W - 2 * b, H - 2 * b,
-                          p->scale > 0 ? p->scale : 1.0, true, false, "pipeline_run(local contrast masks)", &lc_mk, nullptr)))
-            return rc;
+        own(pl->lc_regs, p->local_contrast_regions, nlc);
+        if ((rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_LAB, s.pipe_lc, nlc, false, "pipeline_run(local contrast masks)", &pl->lc_mk))) return rc;
     }
-    if (tb_gen) {
+    if (pl->tb_gen) {
         if (!p->texture_boost_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(texture boost): bad region list");
-        tb_regs.assign(p->texture_boost_regions, p->texture_boost_regions + p->texture_boost_nregions);
-        for (auto &r : tb_regs) r.mask = nullptr;
-        if ((rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_tb, p->texture_boost_nregions, W - 2 * b, H - 2 * b,
-                          p->scale > 0 ? p->scale : 1.0, true, false, "pipeline_run(texture boost masks)", &tb_mk, nullptr)))
-            return rc;
+        own(pl->tb_regs, p->texture_boost_regions, ntb);
+        if ((rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_tb, ntb, false, "pipeline_run(texture boost masks)", &pl->tb_mk))) return rc;
     }
-    const artgpu_local_contrast_region *lc_regions = lc_gen ? lc_regs.data() : p->local_contrast_regions;
-    const artgpu_texture_boost_region *tb_regions = tb_gen ? tb_regs.data() : p->texture_boost_regions;
-    // ImProcFunctions::colorCorrection (artgpu_set_pipeline_color_correction): derived and checked here, run behind the sharpening
-    const bool cc_on = ctx->pipe_ncc > 0 && ctx->pipe_cc;
-    CcPlan ccp;
-    MkPlan cc_mk;
-    if (cc_on) {
-        if (tb_gen && !(ctx->pipe_nsm > 0 && ctx->pipe_sm))        // (smoothing in between ends in RGB mode)
+    pl->lc_regions = pl->lc_gen ? pl->lc_regs.data() : p->local_contrast_regions;
+    pl->tb_regions = pl->tb_gen ? pl->tb_regs.data() : p->texture_boost_regions;
+    if (pl->cc_on) {      // ImProcFunctions::colorCorrection (artgpu_set_pipeline_color_correction)
+        if (tb_masks_from_yuv)
             return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate texture boost's masks from");
-        if ((rc = cc_check(ctx, W - 2 * b, H - 2 * b, ctx->pipe_cc, ctx->pipe_ncc, p->ws, p->iws, !ctx->pipe_cc_masks, "pipeline_run(colour correction)", &ccp))) return rc;
-        if (ctx->pipe_cc_masks &&
-            (rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_cc_masks, ctx->pipe_ncc, W - 2 * b, H - 2 * b, p->scale > 0 ? p->scale : 1.0, true, true,
-                          "pipeline_run(colour correction masks)", &cc_mk, nullptr)))
-            return rc;
+        if ((rc = cc_check(ctx, w, h, s.pipe_cc, s.pipe_ncc, p->ws, p->iws, !pl->cc_gen, "pipeline_run(colour correction)", &pl->cc))) return rc;
+        if (pl->cc_gen && (rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_cc_masks, s.pipe_ncc, true, "pipeline_run(colour correction masks)", &pl->cc_mk))) return rc;
     }
-    // ImProcFunctions::guidedSmoothing (artgpu_set_pipeline_smoothing): what does not depend on a mask's box is checked here, the tool runs behind
-    // colour correction; its masks are generated on the RGB image, so colour correction (which leaves YUV) cannot come ahead of them
-    const bool sm_on = ctx->pipe_nsm > 0 && ctx->pipe_sm;
-    MkPlan sm_mk;
-    if (sm_on) {
-        if (cc_on && ctx->pipe_sm_masks)
+    if (pl->sm_on) {      // ImProcFunctions::guidedSmoothing (artgpu_set_pipeline_smoothing): what does not depend on a mask's box is checked here
+        if (sm_masks_from_yuv)
             return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate smoothing's masks from");
-        if ((rc = sm_check(ctx, W - 2 * b, H - 2 * b, ctx->pipe_sm, ctx->pipe_nsm, p->ws, p->scale > 0 ? p->scale : 1.0, !ctx->pipe_sm_masks, "pipeline_run(smoothing)"))) return rc;
-        for (int i = 0; i < ctx->pipe_nsm && !ctx->pipe_sm_masks; ++i) {       // a region without a mask is the frame: its limits are known now
+        if ((rc = sm_check(ctx, w, h, s.pipe_sm, s.pipe_nsm, p->ws, scale, !pl->sm_gen, "pipeline_run(smoothing)"))) return rc;
+        for (int i = 0; i < s.pipe_nsm && !pl->sm_gen; ++i) {       // a region without a mask is the frame: its limits are known now
             SmRegionPlan sp;
-            if (!ctx->pipe_sm[i].mask && (rc = sm_plan_region(ctx, W - 2 * b, H - 2 * b, ctx->pipe_sm[i], nullptr, p->scale > 0 ? p->scale : 1.0, "pipeline_run(smoothing)", i, &sp))) return rc;
+            if (!s.pipe_sm[i].mask && (rc = sm_plan_region(ctx, w, h, s.pipe_sm[i], nullptr, scale, "pipeline_run(smoothing)", i, &sp))) return rc;
         }
-        if (ctx->pipe_sm_masks &&
-            (rc = mk_plan(ctx, W - 2 * b, H - 2 * b, ARTGPU_MASKS_MODE_RGB, p->ws, ctx->pipe_sm_masks, ctx->pipe_nsm, W - 2 * b, H - 2 * b, p->scale > 0 ? p->scale : 1.0, true, false,
-                          "pipeline_run(smoothing masks)", &sm_mk, nullptr)))
-            return rc;
+        if (pl->sm_gen && (rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_sm_masks, s.pipe_nsm, false, "pipeline_run(smoothing masks)", &pl->sm_mk))) return rc;
     }
-    std::vector<artgpu_plane> gen_planes;
-    // generateMasks(rgb, ., masks, 0, 0, full size, scale, ., -1, &mask, nullptr) on the device image, the L planes handed to the regions
-    auto generate = [&](float *const planes[3], size_t stride, int w, int h, const artgpu_mask_params *masks, const MkPlan &mk, int n, auto &regs) -> int {
-        float *mo;
-        int rc2;
-        if ((rc2 = pool_get(ctx, P_MK_OUT, (size_t)n * w * h * 4, &mo)) || (rc2 = masks_dev(ctx, planes, stride, p->ws, masks, mk, mo, nullptr))) return rc2;
-        gen_planes.resize(n);
-        for (int i = 0; i < n; ++i) { gen_planes[i] = mk_dev_plane(mo + (size_t)i * w * h, w, h); regs[i].mask = &gen_planes[i]; }
-        return ARTGPU_OK;
-    };
-    if (lc_on &&
-        (rc = local_contrast_check(ctx, W - 2 * b, H - 2 * b, lc_regions, p->local_contrast_nregions, p->scale > 0 ? p->scale : 1.0, "pipeline_run(local contrast)")))
-        return rc;
-    DehazePlan dhp;
-    if (p->dehaze_enabled && (rc = dehaze_check(ctx, W - 2 * b, H - 2 * b, &p->dehaze, p->ws, p->scale > 0 ? p->scale : 1.0, "pipeline_run(dehaze)", &dhp))) return rc;
+    if (pl->lc_on && (rc = local_contrast_check(ctx, w, h, pl->lc_regions, nlc, scale, "pipeline_run(local contrast)"))) return rc;
+    if (p->dehaze_enabled && (rc = dehaze_check(ctx, w, h, &p->dehaze, p->ws, scale, "pipeline_run(dehaze)", &pl->dehaze))) return rc;
     // sharpening (STAGE_2): method, scale and, with the automatic radius, the sensor are checked before any stage runs
-    SharpenPlan shp = {};
-    artgpu_sharpening_params shpar = p->sharpening;
-    const bool sh_on = p->sharpening_enabled != 0;
-    const bool sh_auto = sh_on && shpar.enabled && p->sharpening_auto_radius;        // simpleprocess.cc:274
-    if (sh_on) {
-        if (sh_auto && p->sensor != 0) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run(sharpening): the automatic radius of X-Trans frames is not on the device path");
-        if (sh_auto) shpar.deconvradius = 0.75;                                      // (replaced below; the check is about everything else)
-        if ((rc = sharpen_check(ctx, W - 2 * b, H - 2 * b, &shpar, p->scale > 0 ? p->scale : 1.0, "pipeline_run(sharpening)", &shp))) return rc;
+    pl->shpar = p->sharpening;
+    pl->sh_on = p->sharpening_enabled != 0;
+    pl->sh_auto = pl->sh_on && pl->shpar.enabled && p->sharpening_auto_radius;      // simpleprocess.cc:274
+    if (pl->sh_on) {
+        if (pl->sh_auto && p->sensor != 0) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run(sharpening): the automatic radius of X-Trans frames is not on the device path");
+        if (pl->sh_auto) pl->shpar.deconvradius = 0.75;                             // (replaced in pipe_stage2; the check is about everything else)
+        if ((rc = sharpen_check(ctx, w, h, &pl->shpar, scale, "pipeline_run(sharpening)", &pl->sharpen))) return rc;
     }
-    std::vector<TbPlan> tbp;
-    if (p->texture_boost_enabled &&
-        (rc = tb_check(ctx, W - 2 * b, H - 2 * b, tb_regions, p->texture_boost_nregions, p->ws, p->scale > 0 ? p->scale : 1.0, 1, "pipeline_run(texture boost)", &tbp)))
-        return rc;
-    // RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy: the caller's raw is never written
-    artgpu_plane rawc = *raw_in;
-    const artgpu_plane *raw = raw_in;
+    pl->sh_radius_pending = pl->sh_auto && !pl->sharpen.early;
+    if (pl->tb_on && (rc = tb_check(ctx, w, h, pl->tb_regions, ntb, p->ws, scale, 1, "pipeline_run(texture boost)", &pl->tb))) return rc;
+    return ARTGPU_OK;
+}
+
+// The raw side: RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy (the caller's raw is never written), and
+// RawImageSource::getDeconvAutoRadius on the plane the demosaic reads (simpleprocess.cc:274-278 after preprocess): launched here, its one
+// number is waited for where the sharpening needs it
+static int pipe_raw_side(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, const artgpu_plane *raw_in, bool do_ca, PipeFrame *fr)
+{
+    const int W = pl.W, H = pl.H;
+    int rc;
+    float *cp, *res;
+    fr->raw = *raw_in;
     if (do_ca && pipeline_ca(p)) {
-        float *cp;
         if ((rc = plane_to_pool(ctx, raw_in, P_CA_RAW, &cp)) || (rc = pipeline_ca_dev(ctx, cp, W, W, H, p))) return rc;
-        rawc.p = cp; rawc.row_stride_bytes = (int64_t)W * 4; rawc.on_device = 1;
-        raw = &rawc;
+        fr->raw = mk_dev_plane(cp, W, H);
     }
-    // RawImageSource::getDeconvAutoRadius on the plane the demosaic reads (simpleprocess.cc:274-278 after preprocess): launched here, its one
-    // number is waited for where the sharpening needs it
-    const bool sh_radius_pending = sh_auto && !shp.early;
-    if (sh_radius_pending) {
-        const float *rp = raw->p;
-        size_t rstride = (size_t)(raw->row_stride_bytes / 4);
-        if (!raw->on_device) {
-            float *cp;
-            const size_t need = std::max((size_t)W * H, (size_t)SHP_NPLANES * (W - 2 * b) * (H - 2 * b)) * 4;
-            if ((rc = pool_get(ctx, P_SH_PLANES, need, &cp)) || (rc = plane_into(ctx, raw, cp))) return rc;
-            rp = cp; rstride = W;
-        }
-        float *res;
-        if ((rc = auto_radius_dev(ctx, rp, rstride, W, H, p->filters, 1000.f, p->sharpening_clip_val, &res))) return rc;
-        if (!ctx->sh_host) {
-            if (hipHostMalloc(reinterpret_cast<void **>(&ctx->sh_host), 64, hipHostMallocDefault) != hipSuccess) { ctx->sh_host = nullptr; return fail(ctx, ARTGPU_ENOMEM, "pipeline_run(sharpening): pinned word"); }
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sh_ev, hipEventDisableTiming));
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sh_host, res, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(ctx->sh_ev, ctx->stream));
+    if (!pl.sh_radius_pending) return ARTGPU_OK;
+    const float *rp = fr->raw.p;
+    size_t rstride = (size_t)(fr->raw.row_stride_bytes / 4);
+    if (!fr->raw.on_device) {
+        const size_t need = std::max((size_t)W * H, (size_t)SHP_NPLANES * pl.w * pl.h) * 4;
+        if ((rc = pool_get(ctx, P_SH_PLANES, need, &cp)) || (rc = plane_into(ctx, &fr->raw, cp))) return rc;
+        rp = cp; rstride = W;
     }
-    // demosaiced planes live in the context pool (never leave the device)
-    float *pl[3];
+    if ((rc = auto_radius_dev(ctx, rp, rstride, W, H, p->filters, 1000.f, p->sharpening_clip_val, &res))) return rc;
+    if (!ctx->sh_host) {
+        if (hipHostMalloc(reinterpret_cast<void **>(&ctx->sh_host), 64, hipHostMallocDefault) != hipSuccess) { ctx->sh_host = nullptr; return fail(ctx, ARTGPU_ENOMEM, "pipeline_run(sharpening): pinned word"); }
+        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sh_ev, hipEventDisableTiming));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sh_host, res, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->sh_ev, ctx->stream));
+    return ARTGPU_OK;
+}
+
+// The demosaic into planes of the context pool (they never leave the device), and the image the remaining stages work on
+static int pipe_demosaic(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
+{
+    float *dp[3];
+    int rc;
     for (int k = 0; k < 3; ++k)
-        if ((rc = pool_get(ctx, P_PIPE_R + k, (size_t)W * H * 4, &pl[k]))) return rc;
-    artgpu_rgb dem;
-    artgpu_plane *dp[3] = {&dem.r, &dem.g, &dem.b};
-    for (int k = 0; k < 3; ++k) { dp[k]->p = pl[k]; dp[k]->w = W; dp[k]->h = H; dp[k]->row_stride_bytes = (int64_t)W * 4; dp[k]->on_device = 1; }
-    if (p->sensor == 0) rc = artgpu_demosaic_bayer(ctx, p->bayer_method, raw, p->filters, p->initial_gain, b, &dem);
-    else rc = artgpu_demosaic_xtrans(ctx, p->xtrans_passes, p->xtrans_passes > 1 ? 1 : 0, raw, p->xtrans, p->rgb_cam, &dem);
-    if (rc) return rc;
-    // the image the remaining stages work on: the caller's planes if they are on the device, else a staged copy
-    DevRGB d;
-    if ((rc = bind_rgb(ctx, out, 4, false, &d, "pipeline_run(out)"))) return rc;
-    artgpu_rgb img;
-    artgpu_plane *ip[3] = {&img.r, &img.g, &img.b};
-    for (int k = 0; k < 3; ++k) { ip[k]->p = d.p[k]; ip[k]->w = d.w; ip[k]->h = d.h; ip[k]->row_stride_bytes = (int64_t)d.stride * 4; ip[k]->on_device = 1; }
+        if ((rc = pool_get(ctx, P_PIPE_R + k, (size_t)pl.W * pl.H * 4, &dp[k]))) return rc;
+    fr->dem = mk_dev_rgb(dp, pl.W, pl.H, pl.W);
+    if (p->sensor == 0) rc = artgpu_demosaic_bayer(ctx, p->bayer_method, &fr->raw, p->filters, p->initial_gain, pl.b, &fr->dem);
+    else rc = artgpu_demosaic_xtrans(ctx, p->xtrans_passes, p->xtrans_passes > 1 ? 1 : 0, &fr->raw, p->xtrans, p->rgb_cam, &fr->dem);
+    if (rc || (rc = bind_rgb(ctx, out, 4, false, &fr->d, "pipeline_run(out)"))) return rc;
+    fr->img = mk_dev_rgb(fr->d.p, fr->d.w, fr->d.h, fr->d.stride);
+    return ARTGPU_OK;
+}
+
+// From the demosaiced planes to the exposed image: denoiseComputeParams, getImage + convertColorSpace + the denoise tool, dehaze (STAGE_0), the exposure (STAGE_1)
+static int pipe_input(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, PipeFrame *fr)
+{
+    const double *cam_to_work = p->has_cam_to_work ? p->cam_to_work : nullptr;
+    const DevRGB &d = fr->d;
+    int rc;
     artgpu_denoise_tool_params dnp = p->denoise;
     if (p->denoise_enabled && dnp.dn.chrominance_method == 1) {
         // ipf.denoiseComputeParams(imgsrc, currWB, dnstore, params.denoise) before getImage (simpleprocess.cc:254-256); a fresh store per frame
         static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         artgpu_denoise_info_store store = {};
-        if ((rc = artgpu_denoise_compute_params(ctx, &dem, b, p->mul, p->do_clip, p->has_cam_to_work ? p->cam_to_work : ident, p->ws,
+        if ((rc = artgpu_denoise_compute_params(ctx, &fr->dem, pl.b, p->mul, p->do_clip, cam_to_work ? cam_to_work : ident, p->ws,
                                                 p->chrominance_auto_factor != 0.0 ? p->chrominance_auto_factor : 1.0, &store, &dnp.dn)))
             return rc;
     }
@@ -5026,90 +5065,111 @@ static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const 
         (void)noise_curve_lut(curve_points, 9, curve);
         const double ecomp = p->exposure_enabled ? p->expcomp : 0.0;       // ipdenoise.cc:1155
         artgpu_denoise_fusion fu = {};
-        fu.demosaiced = &dem; fu.sx1 = b; fu.sy1 = b;
+        fu.demosaiced = &fr->dem; fu.sx1 = pl.b; fu.sy1 = pl.b;
         for (int k = 0; k < 3; ++k) fu.mul[k] = p->mul[k];
-        fu.do_clip = p->do_clip; fu.cam_to_work = p->has_cam_to_work ? p->cam_to_work : nullptr;
+        fu.do_clip = p->do_clip; fu.cam_to_work = cam_to_work;
         fu.exposure_enabled = p->exposure_enabled && !p->dehaze_enabled ? 1 : 0;      // (dehaze sits between the tool and the exposure)
         fu.exp_scale = (float)std::pow(2.0, p->expcomp); fu.black = (float)(p->black * 2000.0);
-        if ((rc = artgpu_improc_denoise_fused(ctx, &img, &fu, &dnp, p->ws, p->iws, ecomp, p->scale > 0 ? p->scale : 1.0,
-                                              p->has_cam_to_work ? p->cam_to_work : nullptr, curve, 0u)))
-            return rc;
-    } else {
-        if ((rc = artgpu_get_image(ctx, &dem, b, b, p->mul, p->do_clip, p->has_cam_to_work ? p->cam_to_work : nullptr, &img))) return rc;
-    }
+        if ((rc = artgpu_improc_denoise_fused(ctx, &fr->img, &fu, &dnp, p->ws, p->iws, ecomp, pl.scale, cam_to_work, curve, 0u))) return rc;
+    } else if ((rc = artgpu_get_image(ctx, &fr->dem, pl.b, pl.b, p->mul, p->do_clip, cam_to_work, &fr->img))) return rc;
     // ImProcFunctions::dehaze, STAGE_0 of ImProcFunctions::process (improcfun.cc:577), ahead of the exposure (STAGE_1)
-    if (p->dehaze_enabled && (rc = dehaze_dev(ctx, d.p, d.stride, d.w, d.h, &p->dehaze, p->ws, dhp, nullptr))) return rc;
-    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled))
-        if ((rc = artgpu_exposure(ctx, &img, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0)))) return rc;
+    if (p->dehaze_enabled && (rc = dehaze_dev(ctx, d.p, d.stride, d.w, d.h, &p->dehaze, p->ws, pl.dehaze, nullptr))) return rc;
+    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled)) return artgpu_exposure(ctx, &fr->img, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0));
+    return ARTGPU_OK;
+}
+
+// STAGE_2 of ImProcFunctions::process: sharpening, colorCorrection, guidedSmoothing
+static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, PipeFrame *fr)
+{
+    const DevRGB &d = fr->d;
+    const artgpu_ctx::Shared &s = ctx->shared;
+    std::vector<artgpu_plane> gen;
+    int rc;
     // ImProcFunctions::sharpening, the first step of STAGE_2 (improcfun.cc:595; simpleprocess.cc:395 between the exposure and the tone curve)
-    if (sh_on) {
-        if (sh_radius_pending) {
+    if (pl.sh_on) {
+        artgpu_sharpening_params shpar = pl.shpar;
+        SharpenPlan shp = pl.sharpen;
+        if (pl.sh_radius_pending) {
             HIPCHK(ctx, hipEventSynchronize(ctx->sh_ev));
             shpar.deconvradius = auto_radius_of(ctx->sh_host[0]);                    // params.sharpening.deconvradius = r
-            if ((rc = sharpen_check(ctx, d.w, d.h, &shpar, p->scale > 0 ? p->scale : 1.0, "pipeline_run(sharpening, automatic radius)", &shp))) return rc;
+            if ((rc = sharpen_check(ctx, d.w, d.h, &shpar, pl.scale, "pipeline_run(sharpening, automatic radius)", &shp))) return rc;
         }
         if ((rc = sharpen_dev(ctx, d.p, d.stride, d.w, d.h, &shpar, p->ws, shp, nullptr))) return rc;
     }
     // ImProcFunctions::colorCorrection, STAGE_2 behind the sharpening (improcfun.cc:601): generateMasks(rgb, ., &Lmask, &abmask) on the RGB image
     // (ipcolorcorrection.cc:236), then the tool.  It leaves the image in YUV mode for textureBoost, whose setMode(YUV) is then a no-op
-    if (cc_on) {
-        std::vector<artgpu_color_correction_region> cc_regs(ctx->pipe_cc, ctx->pipe_cc + ctx->pipe_ncc);
-        std::vector<artgpu_plane> cc_planes;
-        if (ctx->pipe_cc_masks) {
-            const int n = ctx->pipe_ncc;
-            const size_t np = (size_t)d.w * d.h;
-            float *mo;
-            if ((rc = pool_get(ctx, P_CC_GEN, 2 * n * np * 4, &mo)) || (rc = masks_dev(ctx, d.p, d.stride, p->ws, ctx->pipe_cc_masks, cc_mk, mo, mo + n * np))) return rc;
-            cc_planes.resize((size_t)2 * n);
-            for (int i = 0; i < n; ++i) {
-                cc_planes[2 * i] = mk_dev_plane(mo + i * np, d.w, d.h); cc_planes[2 * i + 1] = mk_dev_plane(mo + (n + i) * np, d.w, d.h);
-                cc_regs[i].lmask = &cc_planes[2 * i]; cc_regs[i].abmask = &cc_planes[2 * i + 1];
-            }
-        }
-        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, cc_regs.data(), ccp, 0, p->texture_boost_enabled && !sm_on ? 0 : 1, nullptr))) return rc;
+    if (pl.cc_on) {
+        const int n = s.pipe_ncc;
+        std::vector<artgpu_color_correction_region> regs(s.pipe_cc, s.pipe_cc + n);
+        if (pl.cc_gen && (rc = pipe_gen_masks(ctx, p, d, P_CC_GEN, s.pipe_cc_masks, pl.cc_mk, n, true, &gen))) return rc;
+        for (int i = 0; i < n && pl.cc_gen; ++i) { regs[i].lmask = &gen[i]; regs[i].abmask = &gen[n + i]; }
+        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), pl.cc, 0, pl.cc_to_rgb, nullptr))) return rc;
     }
     // ImProcFunctions::guidedSmoothing, the last step of STAGE_2 (improcfun.cc:602): generateMasks on the image (ipsmoothing.cc:929), setMode(RGB)
     // (colour correction ahead of it ends with that switch), the tool
-    if (sm_on) {
-        std::vector<artgpu_smoothing_region> sm_regs(ctx->pipe_sm, ctx->pipe_sm + ctx->pipe_nsm);
-        std::vector<artgpu_plane> sm_planes;
-        if (ctx->pipe_sm_masks) {
-            const int n = ctx->pipe_nsm;
-            const size_t np = (size_t)d.w * d.h;
-            float *mo;
-            if ((rc = pool_get(ctx, P_SM_GEN, n * np * 4, &mo)) || (rc = masks_dev(ctx, d.p, d.stride, p->ws, ctx->pipe_sm_masks, sm_mk, mo, nullptr))) return rc;
-            sm_planes.resize((size_t)n);
-            for (int i = 0; i < n; ++i) { sm_planes[i] = mk_dev_plane(mo + i * np, d.w, d.h); sm_regs[i].mask = &sm_planes[i]; }
-        }
-        if ((rc = smoothing_dev(ctx, d.p, d.stride, d.w, d.h, sm_regs.data(), ctx->pipe_nsm, p->ws, p->scale > 0 ? p->scale : 1.0, nullptr, "pipeline_run(smoothing)"))) return rc;
+    if (pl.sm_on) {
+        const int n = s.pipe_nsm;
+        std::vector<artgpu_smoothing_region> regs(s.pipe_sm, s.pipe_sm + n);
+        if (pl.sm_gen && (rc = pipe_gen_masks(ctx, p, d, P_SM_GEN, s.pipe_sm_masks, pl.sm_mk, n, false, &gen))) return rc;
+        for (int i = 0; i < n && pl.sm_gen; ++i) regs[i].mask = &gen[i];
+        if ((rc = smoothing_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), n, p->ws, pl.scale, nullptr, "pipeline_run(smoothing)"))) return rc;
     }
+    return ARTGPU_OK;
+}
+
+// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, the tone curve, localContrast; then the image goes back to the caller's planes
+static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
+{
+    const DevRGB &d = fr->d;
+    const int ntb = p->texture_boost_nregions, nlc = p->local_contrast_nregions;
+    std::vector<artgpu_plane> gen;
+    int rc;
     // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
-    if (tb_gen && (rc = generate(d.p, d.stride, d.w, d.h, ctx->pipe_tb, tb_mk, p->texture_boost_nregions, tb_regs))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
-    if (p->texture_boost_enabled &&
-        (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, tb_regions, p->texture_boost_nregions, p->ws, tbp, 1, nullptr, cc_on && !sm_on ? 1 : 0)))
-        return rc;
-    if (p->tone_enabled) {
-        if (p->tone_mode == ARTGPU_TONE_NEUTRAL) {
-            artgpu_neutral_state st;
-            for (int k = 0; k < 9; ++k) { st.ws[k] = p->ws[k]; st.iws[k] = p->iws[k]; st.to_out[k] = p->to_out[k]; st.to_work[k] = p->to_work[k]; }
-            rc = artgpu_tone_curve_neutral(ctx, &img, p->tone_lut, p->white_point, &st);
-        } else {
-            rc = artgpu_tone_curve(ctx, &img, p->tone_mode, p->tone_lut, p->white_point, 1);
-        }
-        if (rc) return rc;
-    }
-    if (lc_on) {
-        // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
-        // L plane (Imagefloat::g), back to RGB
-        if ((rc = artgpu_rgb_to_lab(ctx, &img, p->ws)) ||
-            (lc_gen && (rc = generate(d.p, d.stride, d.w, d.h, ctx->pipe_lc, lc_mk, p->local_contrast_nregions, lc_regs))) ||
-            (rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, lc_regions, p->local_contrast_nregions, nullptr)) ||
-            (rc = artgpu_lab_to_rgb(ctx, &img, p->iws)))
-            return rc;
+    if (pl.tb_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_tb, pl.tb_mk, ntb, false, &gen))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
+    for (int i = 0; i < ntb && pl.tb_gen; ++i) pl.tb_regs[i].mask = &gen[i];
+    if (pl.tb_on && (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, pl.tb_regions, ntb, p->ws, pl.tb, 1, nullptr, pl.tb_in_yuv))) return rc;
+    if (p->tone_enabled && p->tone_mode == ARTGPU_TONE_NEUTRAL) {
+        artgpu_neutral_state st;
+        for (int k = 0; k < 9; ++k) { st.ws[k] = p->ws[k]; st.iws[k] = p->iws[k]; st.to_out[k] = p->to_out[k]; st.to_work[k] = p->to_work[k]; }
+        if ((rc = artgpu_tone_curve_neutral(ctx, &fr->img, p->tone_lut, p->white_point, &st))) return rc;
+    } else if (p->tone_enabled && (rc = artgpu_tone_curve(ctx, &fr->img, p->tone_mode, p->tone_lut, p->white_point, 1))) return rc;
+    // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
+    // L plane (Imagefloat::g), back to RGB
+    if (pl.lc_on) {
+        if ((rc = artgpu_rgb_to_lab(ctx, &fr->img, p->ws)) || (pl.lc_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_lc, pl.lc_mk, nlc, false, &gen)))) return rc;
+        for (int i = 0; i < nlc && pl.lc_gen; ++i) pl.lc_regs[i].mask = &gen[i];
+        if ((rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, pl.lc_regions, nlc, nullptr)) || (rc = artgpu_lab_to_rgb(ctx, &fr->img, p->iws))) return rc;
     }
     return unbind_rgb(ctx, out, &d);
 }
+
+// One frame: the plan, then the stages (do_ca: artgpu_pipeline_run; io_frame has corrected its staged CFA plane itself)
+static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca)
+{
+    StageScope scope_(ctx, "ImageProcessor (stage_init .. stage_finish)");
+    PipePlan pl{};
+    PipeFrame fr;
+    int rc;
+    if ((rc = pipeline_plan(ctx, raw_in, p, out, &pl)) || (rc = pipe_raw_side(ctx, p, pl, raw_in, do_ca, &fr)) || (rc = pipe_demosaic(ctx, p, pl, out, &fr)) ||
+        (rc = pipe_input(ctx, p, pl, &fr)) || (rc = pipe_stage2(ctx, p, pl, &fr)))
+        return rc;
+    return pipe_stage3(ctx, p, pl, out, &fr);
+}
 } // namespace
+
+int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *lc, int nlc, const artgpu_mask_params *tb, int ntb)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (nlc < 0 || ntb < 0 || (nlc > 0 && !lc) || (ntb > 0 && !tb)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_masks: bad arguments");
+    ctx->shared.pipe_lc = own_pipe_masks(ctx->pipe_lc_own, lc, nlc); ctx->shared.pipe_nlc = nlc;
+    ctx->shared.pipe_tb = own_pipe_masks(ctx->pipe_tb_own, tb, ntb); ctx->shared.pipe_ntb = ntb;
+    return ARTGPU_OK;
+}
+
+int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *p, artgpu_rgb *out)
+{
+    return pipeline_run_impl(ctx, raw, p, out, true);
+}
 
 int artgpu_set_batch_lanes(artgpu_ctx *ctx, int lanes)
 {
@@ -5157,15 +5217,7 @@ int batch_prepare_lanes(artgpu_ctx *ctx, int L)
     // the lanes are this context as far as the caller can tell: its options, curve tail and progress listener apply to every frame,
     // whichever lane runs it (copied on every call -- they may change between calls)
     for (artgpu_ctx *peer : ctx->lanes) {
-        peer->curve_tail_kind = ctx->curve_tail_kind; peer->curve_tail_y = ctx->curve_tail_y; peer->curve_tail_pc = ctx->curve_tail_pc;
-        peer->opt_amaze_path = ctx->opt_amaze_path; peer->opt_amaze_split = ctx->opt_amaze_split; peer->opt_amaze_overlap = ctx->opt_amaze_overlap; peer->opt_amaze_grid = ctx->opt_amaze_grid;
-        peer->opt_amaze_zero_mask = ctx->opt_amaze_zero_mask; peer->opt_amaze_zero_frame = ctx->opt_amaze_zero_frame; peer->opt_amaze_poison = ctx->opt_amaze_poison;
-        peer->opt_rcd_rows = ctx->opt_rcd_rows; peer->opt_roctx = ctx->opt_roctx; peer->opt_lut_lds = ctx->opt_lut_lds; peer->opt_sharpen_fused = ctx->opt_sharpen_fused; peer->opt_dn_streams = ctx->opt_dn_streams; peer->opt_dn_fused = ctx->opt_dn_fused; peer->opt_dn_detail_plain = ctx->opt_dn_detail_plain;
-        peer->opt_dn_wait_ms = ctx->opt_dn_wait_ms; peer->opt_dn_debug_stall = ctx->opt_dn_debug_stall; peer->opt_io_direct = ctx->opt_io_direct;
-        peer->progress_fn = ctx->progress_fn; peer->progress_user = ctx->progress_user;
-        peer->pipe_lc = ctx->pipe_lc; peer->pipe_nlc = ctx->pipe_nlc; peer->pipe_tb = ctx->pipe_tb; peer->pipe_ntb = ctx->pipe_ntb;
-        peer->pipe_cc = ctx->pipe_cc; peer->pipe_ncc = ctx->pipe_ncc; peer->pipe_cc_masks = ctx->pipe_cc_masks;
-        peer->pipe_sm = ctx->pipe_sm; peer->pipe_nsm = ctx->pipe_nsm; peer->pipe_sm_masks = ctx->pipe_sm_masks;
+        peer->shared = ctx->shared;
         peer->frames_in_flight = L;
     }
     ctx->frames_in_flight = L;
@@ -5286,7 +5338,7 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
     // kernel, 268 MB in 4.9 ms -- 11.0 ms per frame with one lane, 10.6 - 13.8 with two (two modes: the lanes lock into step with the copy kernel in
     // about half the runs), 10.7 - 11.3 with three; eight workgroups writing directly 11.7 - 12.6 / 11.2 - 11.8 / 11.7 - 12.9 (they hold eight CUs for
     // 5 ms, and the one-workgroup-per-CU kernels of the next frame wait for a CU or run on fewer: cu_reserve).  So: the copy, except with two lanes.
-    const int direct_wgs = c->opt_io_direct >= 0 ? c->opt_io_direct : (c->frames_in_flight == 2 ? 8 : 0);
+    const int direct_wgs = c->shared.opt_io_direct >= 0 ? c->shared.opt_io_direct : (c->frames_in_flight == 2 ? 8 : 0);
     // A copy from / to PAGEABLE memory blocks the calling thread until it is done (the runtime stages it in pieces): nothing is gained by giving it a
     // stream of its own, so it stays on the context's stream like the copies of the four separate entry points; lanes still overlap each other.
     unsigned char *const out_pinned = out->on_device ? nullptr : static_cast<unsigned char *>(pinned_device_address(out->scanlines));
@@ -5332,9 +5384,9 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
     artgpu_plane raw = {cfa, W, H, (int64_t)W * 4, 1};
     // CA_correct_RT on the staged CFA plane itself, after scaleColors and before the demosaic (rawimagesource.cc:1666,1827)
     if (pipeline_ca(p) && (rc = pipeline_ca_dev(c, cfa, W, W, H, p))) return rc;
-    artgpu_rgb image;
-    artgpu_plane *ip[3] = {&image.r, &image.g, &image.b};
-    for (int k = 0; k < 3; ++k) { ip[k]->p = img[k]; ip[k]->w = iw; ip[k]->h = ih; ip[k]->row_stride_bytes = (int64_t)iw * 4; ip[k]->on_device = 1; }
+    artgpu_rgb image = mk_dev_rgb(img, iw, ih, iw);
+    // (the frame's plan -- pipeline_plan -- runs in here, behind the upload and scaleColors: a refused frame has done that work already.  Planning
+    // ahead of the upload would change what a refused frame leaves behind, so it stays)
     if ((rc = pipeline_run_impl(c, &raw, p, &image, false))) return rc;
 
     // ---- rgb2out (matrix + TRC, in place) and the writers' scanlines

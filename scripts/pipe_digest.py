@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""One line per configuration of artgpu_pipeline_run: the SHA-256 of the three output planes, or, for a refused frame, the error code and
+the full message.  Two builds of the library that print the same file run the same pipe:
+
+    ARTGPU_LIB=variants/libartgpu_parent.so python scripts/pipe_digest.py --out parent.txt
+    python scripts/pipe_digest.py --out new.txt && cmp parent.txt new.txt
+
+The matrix: every tool alone, all of them in one frame, the combinations of colour correction / smoothing / texture boost with and without
+pipe-generated masks (the legal ones and the refused ones), X-Trans with and without the automatic sharpening radius, a region count that
+is not the frame's, denoise x dehaze -- each at 392 x 296 and at 395 x 301 (a width that is no multiple of 4 behind the border)."""
+import argparse
+import ctypes as C
+import hashlib
+import itertools
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from art_amd import capi, synth  # noqa: E402
+
+MUL = (2.1374, 1.0, 1.5918)
+MAT = np.array([[0.6325, 0.2312, 0.0921], [0.2198, 0.7712, 0.0090], [0.0166, 0.0713, 0.7514]])
+WS = np.array([[0.6734241, 0.1656411, 0.1251286], [0.2790177, 0.6753402, 0.0456377], [-0.0019300, 0.0299784, 0.7973330]])
+IWS = np.linalg.inv(WS)
+LIGHT = (1.0, 0.0, 0.2, 0.35, 0.35, 0.4, 1.0, 0.3, 0.3, 1.0, 0.0, 0.35, 0.35)
+HUE = (1.0, 0.1, 1.0, 0.35, 0.35, 0.45, 0.0, 0.35, 0.35, 0.8, 0.6, 0.2, 0.2)
+MASKS = [dict(parametric_enabled=True, lightness=LIGHT, blur=2.0), dict(parametric_enabled=True, hue=HUE, inverted=True, opacity=60)]
+CC = [dict(mode=capi.CC_RGB, slope=(1.15, 0.9, 1.05), offset=(0.04, -0.3, 0.03), power=(1.2, 0.85, 1.1)), dict(mode="yuv", hueshift=20.0, out_saturation=0.2)]
+SM = [dict(mode="guided", channel="chrominance", radius=3, epsilon=1, iterations=2), dict(mode="nlmeans", channel="luminance", nlstrength=40, nldetail=60)]
+TB = [(1.0, 0.2, 1, None), (-0.8, 1.0, 1, None)]
+LUT = ((1.0 - np.cos(np.pi * (np.arange(65536, dtype=np.float64) / 65535.0) ** 0.7)) / 2.0 * 65535.0).astype(np.float32)
+
+
+def params(xtrans=False):
+    p = capi.PipelineParams()
+    p.sensor = 1 if xtrans else 0
+    p.bayer_method = capi.BAYER_AMAZE; p.filters = synth.FILTERS_RGGB; p.initial_gain = 1.0
+    p.xtrans_passes = 3
+    p.xtrans[:] = [int(v) for v in synth.XTRANS_FUJI.reshape(36)]
+    p.rgb_cam[:] = [float(v) for v in synth.XTRANS_RGB_CAM.reshape(12)]
+    p.border = 7 if xtrans else 4
+    p.mul[:] = MUL; p.do_clip = 1; p.has_cam_to_work = 1
+    p.cam_to_work[:] = [float(v) for v in MAT.reshape(9)]
+    p.ws[:] = [float(v) for v in WS.reshape(9)]
+    p.iws[:] = [float(v) for v in IWS.reshape(9)]
+    p.denoise_enabled = 0
+    p.denoise = capi.DenoiseToolParams(capi.DenoiseParams(40.0, 50.0, 0, 15.0, 0.0, 0.0, 1.7, 0, 0, 0), 0, 3, 0, 80)
+    p.exposure_enabled = 1; p.expcomp = 0.3; p.black = 0.0
+    p.tone_enabled = 1; p.tone_mode = 0
+    p.tone_lut = LUT.ctypes.data_as(C.POINTER(C.c_float)); p.white_point = 1.0
+    p.to_out[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]; p.to_work[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+    p.scale = 1.0
+    return p
+
+
+def cases():
+    """(name, what is on): keys dehaze, sharpen ('fixed' / 'auto'), cc, sm, tb, lc ('planes' = the regions' own, all ones / 'gen' = the pipe
+    generates the masks / 'caller' = device planes of the caller), denoise, ca, xtrans, mismatch"""
+    yield "plain", {}
+    for tool in ("dehaze", "denoise", "ca", "xtrans"):
+        yield tool, {tool: True}
+    for kind in ("fixed", "auto"):
+        yield "sharpen-" + kind, dict(sharpen=kind)
+    for tool in ("cc", "sm", "tb", "lc"):
+        for kind in ("planes", "gen") + (("caller",) if tool in ("cc", "sm") else ()):
+            yield f"{tool}-{kind}", {tool: kind}
+    yield "all-tools", dict(dehaze=True, sharpen="fixed", cc="caller", sm="caller", tb="gen", lc="gen")
+    yield "all-tools-denoise-ca-auto", dict(dehaze=True, sharpen="auto", cc="caller", sm="caller", tb="gen", lc="gen", denoise=True, ca=True)
+    for cc, sm, tb in itertools.product((None, "planes"), (None, "planes", "gen"), (None, "planes", "gen")):
+        yield f"modes-cc:{cc}-sm:{sm}-tb:{tb}", dict(cc=cc, sm=sm, tb=tb)
+    yield "modes-cc:gen-sm:planes-tb:gen", dict(cc="gen", sm="planes", tb="gen")
+    yield "xtrans-sharpen-auto", dict(xtrans=True, sharpen="auto")
+    yield "xtrans-sharpen-fixed", dict(xtrans=True, sharpen="fixed")
+    yield "mismatch-tb", dict(tb="gen", mismatch=True)
+    yield "mismatch-lc", dict(lc="gen", tb="planes", mismatch=True)
+    for dn, dh in itertools.product((False, True), (False, True)):
+        yield f"denoise:{int(dn)}-dehaze:{int(dh)}", dict(denoise=dn, dehaze=dh)
+
+
+def run_case(ctx, W, H, on):
+    xtrans = bool(on.get("xtrans"))
+    p = params(xtrans)
+    b = p.border
+    w, h = W - 2 * b, H - 2 * b
+    raw = synth.xtrans_frame(W, H, seed=5, noise=1500) if xtrans else synth.bayer_frame(W, H, synth.FILTERS_RGGB, seed=81, noise=1500)
+    keep = []
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    ramp = torch.from_numpy((0.5 + 0.5 * np.sin(xx / 37.0) * np.cos(yy / 23.0)).astype(np.float32)).to("cuda:0")
+    keep.append(ramp)
+    caller = capi.device_plane(ramp)
+    if on.get("denoise"):
+        p.denoise_enabled = 1
+    if on.get("ca"):
+        p.ca_enabled = 1; p.ca = capi.CaParams(1, 2, 0.0, 0.0, 1)
+    if on.get("dehaze"):
+        dh, k = capi.dehaze_params(depth=50)
+        keep.append(k)
+        p.dehaze_enabled = 1; p.dehaze = dh
+    if on.get("sharpen"):
+        p.sharpening_enabled = 1; p.sharpening = capi.sharpening_params(deconvradius=0.9)
+        p.sharpening_auto_radius = 1 if on["sharpen"] == "auto" else 0; p.sharpening_clip_val = 65535.0
+    if on.get("cc"):
+        regs = [dict(r, lmask=caller, abmask=caller) for r in CC] if on["cc"] == "caller" else CC
+        ctx.set_pipeline_color_correction(regs, MASKS if on["cc"] == "gen" else None)
+    if on.get("sm"):
+        regs = [dict(r, mask=caller) for r in SM] if on["sm"] == "caller" else SM
+        ctx.set_pipeline_smoothing(regs, MASKS if on["sm"] == "gen" else None)
+    if on.get("tb"):
+        arr, k = capi.texture_boost_regions(TB)
+        keep += [arr, k]
+        p.texture_boost_enabled = 1; p.texture_boost_nregions = len(TB); p.texture_boost_regions = arr
+    if on.get("lc"):
+        arr, k = capi.local_contrast_regions([(60.0, None, None)])
+        keep += [arr, k]
+        p.local_contrast_enabled = 1; p.local_contrast_nregions = 1; p.local_contrast_regions = arr
+    lc_masks = MASKS[:1] if on.get("lc") == "gen" else None
+    tb_masks = MASKS if on.get("tb") == "gen" else None
+    if on.get("mismatch"):
+        lc_masks, tb_masks = (MASKS if lc_masks else None), (MASKS[:1] if tb_masks else None)
+    ctx.set_pipeline_masks(lc_masks, tb_masks)
+    d_raw = torch.from_numpy(raw).to("cuda:0")
+    d_img = [torch.full((h, w), 7.0, dtype=torch.float32, device="cuda:0") for _ in range(3)]
+    try:
+        ctx.pipeline_run(capi.device_plane(d_raw), p, capi.RGB(*[capi.device_plane(t) for t in d_img]))
+        ctx.synchronize()
+        sha = hashlib.sha256()
+        for t in d_img:
+            sha.update(t.cpu().numpy().tobytes())
+        return sha.hexdigest()
+    except capi.ArtGpuError as e:
+        ctx.synchronize()
+        untouched = all(bool((t == 7.0).all()) for t in d_img)
+        return f"refused ({'output untouched' if untouched else 'OUTPUT WRITTEN'}): {e}"
+    finally:
+        ctx.set_pipeline_masks(None, None)
+        ctx.set_pipeline_smoothing(None)
+        ctx.set_pipeline_color_correction(None)
+        del keep
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", help="also write the lines to this file")
+    ap.add_argument("--sizes", default="392x296,395x301")
+    ap.add_argument("--only", help="substring of the case names to run")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "pipe_digest.py needs a GPU"
+    ctx = capi.Context(0)
+    lines = []
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        for name, on in cases():
+            if args.only and args.only not in name:
+                continue
+            lines.append(f"{W}x{H} {name}: {run_case(ctx, W, H, on)}")
+            print(lines[-1], flush=True)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -281,3 +281,118 @@ def test_progress_callback_and_roctx_ranges(gpu_ctx):
     n = len(events)
     gpu_ctx.demosaic_bayer_host(capi.BAYER_RCD, raw, filt, 1.0, 4)
     assert len(events) == n                                       # removed
+
+
+def test_pipeline_all_tools_equal_the_tools_one_by_one(gpu_ctx):
+    """Dehaze, sharpening with a fixed radius, colour correction and smoothing (GUIDED and NLMEANS) with caller planes, texture boost with
+    pipe-generated masks (legal behind colour correction because smoothing sits in between), the standard tone curve and local contrast with
+    pipe-generated masks in ONE frame, against the same tools called through their own entry points, in pipe order, on what a run with all of
+    them off returns.  No other test has more than three of them on at once, which is where the walk over the colour modes and the mask slot
+    that texture boost and local contrast share can go wrong.  Both sides are this build's kernels in the same order: float32 bit patterns,
+    no tolerance."""
+    import lc_lib
+    import mk_lib
+    import sm_lib
+    import tb_lib
+    import test_gpu_colorcorrection as CC
+    import test_gpu_masks as MK
+    import test_gpu_smoothing as SM
+    W, H = 392, 296
+    w, h = W - 8, H - 8
+    WS, IWS = O.REC2020_WS_D, O.REC2020_IWS_D
+    raw = synth.bayer_frame(W, H, synth.FILTERS_RGGB, seed=71, noise=1500)
+    lut = _lut()
+    p = _params(lut, 0)
+    p.denoise_enabled = 0; p.exposure_enabled = 0; p.tone_enabled = 0
+    base = SM._pipeline(gpu_ctx, raw, p)                           # demosaic + getImage
+    dh, keep_dh = capi.dehaze_params(depth=50)
+    sp = capi.sharpening_params(deconvradius=0.9)
+    keep = []
+    mask = tb_lib.smooth_mask(w, h)
+    box = np.zeros((h, w), np.float32); box[40:140, 60:200] = 0.8
+    cc = CC._capi_regions([dict(CC.PIPE_REGIONS[0], lmask=mask, abmask=mask), dict(CC.PIPE_REGIONS[1])], True, w, h, keep)
+    sm = SM._capi_regions([dict(SM.PIPE_REGIONS[0], mask=sm_lib.mask("between", w, h)), dict(SM.PIPE_REGIONS[1], mask=box)], True, w, h, keep)
+    tb_masks, lc_masks = SM._capi_masks(MK.TB_MASKS), SM._capi_masks(MK.LC_MASKS)
+    lc_curve = lc_lib.curve_lut(lc_lib.BOOST_CURVE_POINTS)
+    tb_arr, keep_tb = capi.texture_boost_regions([r + (None,) for r in MK.TB_REGIONS])
+    lc_arr, keep_lc = capi.local_contrast_regions([(60.0, lc_curve, None)])
+    p.exposure_enabled = 1; p.tone_enabled = 1
+    p.dehaze_enabled = 1; p.dehaze = dh
+    p.sharpening_enabled = 1; p.sharpening = sp; p.sharpening_auto_radius = 0
+    p.texture_boost_enabled = 1; p.texture_boost_nregions = len(MK.TB_REGIONS); p.texture_boost_regions = tb_arr
+    p.local_contrast_enabled = 1; p.local_contrast_nregions = 1; p.local_contrast_regions = lc_arr
+    try:
+        gpu_ctx.set_pipeline_color_correction(cc)
+        gpu_ctx.set_pipeline_smoothing(sm)
+        gpu_ctx.set_pipeline_masks(lc_masks, tb_masks)
+        got = SM._pipeline(gpu_ctx, raw, p)
+    finally:
+        gpu_ctx.set_pipeline_masks(None, None)
+        gpu_ctx.set_pipeline_smoothing(None)
+        gpu_ctx.set_pipeline_color_correction(None)
+    d = [torch.from_numpy(np.array(a)).to("cuda:0") for a in base]
+    img = capi.RGB(*[capi.device_plane(t) for t in d])
+    gpu_ctx.dehaze(img, dh, WS, 1.0)
+    gpu_ctx.exposure(img, float(np.float32(2.0 ** 0.3)), 0.0)
+    gpu_ctx.sharpening(img, sp, WS, 1.0)
+    gpu_ctx.color_correction(img, cc, WS, IWS, True)
+    gpu_ctx.smoothing(img, sm, WS, 1.0)
+    t_tb, mp = MK._generated(gpu_ctx, img, mk_lib.MODE_RGB, tb_masks, w, h)
+    gpu_ctx.texture_boost(img, [r + (m,) for r, m in zip(MK.TB_REGIONS, mp)], WS, 1.0, True, True)
+    gpu_ctx.tone_curve(img, lut, 1.0, True)
+    gpu_ctx.rgb_to_lab(img, WS)
+    t_lc, mp = MK._generated(gpu_ctx, img, mk_lib.MODE_LAB, lc_masks, w, h)
+    gpu_ctx.local_contrast(img.g, [(60.0, lc_curve, mp[0])])
+    gpu_ctx.lab_to_rgb(img, IWS)
+    gpu_ctx.synchronize()
+    want = [t.cpu().numpy() for t in d]
+    assert all(np.isfinite(g).all() for g in got)
+    for name, g, wnt in zip("rgb", got, want):
+        nbad = int((g.view(np.uint32) != wnt.view(np.uint32)).sum())
+        print(f"all tools, plane {name}: {nbad} values differ")
+        assert nbad == 0, (name, nbad)
+    assert not np.array_equal(got[1], base[1])
+    del keep, keep_dh, keep_tb, keep_lc, t_tb, t_lc
+
+
+def test_batch_lanes_inherit_the_pipe_settings_and_an_option():
+    """What a lane inherits is one block of the context: an option (lut_lds 0), a curve tail and the colour-correction and smoothing settings
+    of the pipe together.  Five frames on one lane and on three lanes give the same bits, and the settings do show in these frames."""
+    import test_gpu_colorcorrection as CC
+    import test_gpu_smoothing as SM
+    w, h = 392, 296
+    lut = _lut()
+    p = _params(lut, 0)
+    p.denoise_enabled = 0
+    p.white_point = 1.6
+    raws = [np.minimum(synth.bayer_frame(w, h, synth.FILTERS_RGGB, seed=s, noise=1500) * np.float32(1.7), np.float32(65535.0)) for s in (51, 52, 53, 54, 55)]
+
+    def run(ctx):
+        outs = [[np.zeros((h - 8, w - 8), np.float32) for _ in range(3)] for _ in raws]
+        ctx.batch_run([capi.host_plane(r) for r in raws], p, [capi.host_rgb(o) for o in outs])
+        return outs
+    ctx = capi.Context(0)
+    try:
+        ctx.set_option("lut_lds", 0)
+        ctx.set_curve_tail(1, 0.93)
+        ctx.set_pipeline_color_correction(CC.PIPE_REGIONS[1:])
+        ctx.set_pipeline_smoothing(SM.PIPE_REGIONS[:1])
+        one = run(ctx)
+        ctx.set_batch_lanes(3)
+        three = run(ctx)
+        for o, r in zip(three, one):
+            for a, b in zip(o, r):
+                assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and a.max() > 0
+        # cleared (the tail: identity -- the default kind refuses white_point > 1): the lanes follow, and the frames differ
+        ctx.set_option("lut_lds", 1)
+        ctx.set_curve_tail(2, 1.0)
+        ctx.set_pipeline_color_correction(None)
+        ctx.set_pipeline_smoothing(None)
+        cleared = run(ctx)
+        ctx.set_batch_lanes(1)
+        for o, r in zip(cleared, run(ctx)):
+            for a, b in zip(o, r):
+                assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        assert all((o[1] != r[1]).any() for o, r in zip(cleared, one))
+    finally:
+        ctx.close()
