@@ -47,6 +47,8 @@ struct artgpu_ctx {
                                        // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
         int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
                                        // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
+        int opt_dn_mad_fold = 1;       // MadRgb -- 1: from the bins the analysis kernels count while they write the bands; 0: launch_mad's pass over the bands
+        int opt_dn_mad_fold_grid = 0;  // > 0: the counting analysis kernels with at most this many workgroups (tests: many steps per workgroup; timing of the grid cap)
         int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
         long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
         int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
@@ -87,6 +89,8 @@ struct artgpu_ctx {
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
     long long batch_px = 0;       // artgpu_batch_run: pixels of the largest frame this context's scratch was grown for since the last trim
+    // RGB_denoise's last call: the fold's flag block (96 words in the P_MAD slot behind the 96 medians) and which of its words the call's launch_mad_fold launches wrote (first, count)
+    const int *dn_fold_flags = nullptr; int dn_fold_ranges[8][2] = {}; int dn_fold_nranges = 0;
     int dn_form = -1, dn_form_streak = 0;   // RGB_denoise: the shrink passes' form of the last call (1 fused / 0 three kernels) and how many calls in a row used it
     // per-workgroup work arenas (demosaic)
     float *arena = nullptr;
@@ -507,6 +511,33 @@ int artgpu_get_option(artgpu_ctx *ctx, const char *name, long *value)
         *value = v;
         return ARTGPU_OK;
     }
+    if (n == "dn_mad_fold") { *value = ctx->shared.opt_dn_mad_fold; return ARTGPU_OK; }
+    if (n.rfind("dn_mad_bits", 0) == 0 && n.size() > 11) {
+        // the bit pattern of word k (0 .. 95) of the last RGB_denoise call's SQR(MadRgb) block: L at 0, a at 32, b at 64 -- or, with one MadRgb
+        // launch set for the three channels, all bands back to back from 0 (DESIGN 28 lists a frame's median bins from these)
+        const int k = std::atoi(n.c_str() + 11);
+        if (k < 0 || k > 95 || !ctx->dn_fold_flags) return fail(ctx, ARTGPU_EINVAL, "get_option: %s: word 0 .. 95 of a context that has denoised", name);
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        int v = 0;
+        HIPCHK(ctx, hipMemcpy(&v, ctx->dn_fold_flags - 96 + k, sizeof v, hipMemcpyDeviceToHost));
+        *value = v;
+        return ARTGPU_OK;
+    }
+    if (n == "dn_mad_fold_settled" || n == "dn_mad_fold_fallback") {
+        // the last RGB_denoise call on this context: bands whose median came from the analysis kernels' counts / bands the counts could not
+        // settle, which took the full histogram (both 0 when the call did not fold)
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        int flags[96] = {};
+        if (ctx->dn_fold_nranges) HIPCHK(ctx, hipMemcpy(flags, ctx->dn_fold_flags, sizeof flags, hipMemcpyDeviceToHost));
+        const int want = n == "dn_mad_fold_settled" ? 1 : 2;
+        long cnt = 0;
+        for (int r = 0; r < ctx->dn_fold_nranges; ++r)
+            for (int k = 0; k < ctx->dn_fold_ranges[r][1]; ++k) cnt += flags[ctx->dn_fold_ranges[r][0] + k] == want;
+        *value = cnt;
+        return ARTGPU_OK;
+    }
     return fail(ctx, ARTGPU_EINVAL, "get_option: unknown option '%s'", name);
 }
 
@@ -524,6 +555,8 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
     else if (n == "roctx") ctx->shared.opt_roctx = value != 0;
     else if (n == "dn_streams") ctx->shared.opt_dn_streams = value != 0;
     else if (n == "dn_fused") ctx->shared.opt_dn_fused = (int)value;
+    else if (n == "dn_mad_fold") ctx->shared.opt_dn_mad_fold = value != 0;
+    else if (n == "dn_mad_fold_grid") { if (value < 0 || value > 65536) return fail(ctx, ARTGPU_EINVAL, "dn_mad_fold_grid: 0 (default) .. 65536 workgroups"); ctx->shared.opt_dn_mad_fold_grid = (int)value; }
     else if (n == "dn_detail_plain") { if (value < 0 || value > 3) return fail(ctx, ARTGPU_EINVAL, "dn_detail_plain: 0 .. 3"); ctx->shared.opt_dn_detail_plain = (int)value; }
     else if (n == "dn_debug_stall") ctx->shared.opt_dn_debug_stall = (int)value;
     else if (n == "dn_wait_ms") ctx->shared.opt_dn_wait_ms = value < 0 ? 0 : value;
@@ -586,6 +619,7 @@ int artgpu_trim_scratch(artgpu_ctx *ctx)
     ctx->batch_px = 0;
     // host-side records of what pool slots held: the tables are gone with them
     ctx->gam_tab = nullptr;
+    ctx->dn_fold_flags = nullptr; ctx->dn_fold_nranges = 0;
     ctx->ncurve_host.clear();
     for (int k = 0; k < 3; ++k) ctx->rgbcurve_host[k].clear();
     int rc = ARTGPU_OK;
@@ -1166,6 +1200,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
        P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
        P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
+       P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 
@@ -1173,6 +1208,8 @@ struct DevDecomp {
     float *bands, *low[2];
     int cur, nlevels, w, h, w2, h2;
     size_t n;
+    int *cnt;                   // non-null: decompose with the counting kernels -- MadRgb's low bins of this channel's bands, [3 * nlevels][MAD_FOLD_NB]
+    int g0, g1;                 // ... their grids
     float *band(int l, int dir) const { return bands + ((size_t)l * 3 + (dir - 1)) * n; }
 };
 
@@ -1181,14 +1218,18 @@ int decompose_dev(artgpu_ctx *ctx, DevDecomp &d, const float *src, hipStream_t s
     if (!st) st = ctx->stream;
     WaveArgs a = {};
     a.w = d.w; a.h = d.h; a.w2 = d.w2; a.h2 = d.h2;
+    if (d.cnt) HIPCHK(ctx, hipMemsetAsync(d.cnt, 0, (size_t)3 * d.nlevels * MAD_FOLD_NB * sizeof(int), st));
     for (int l = 0; l < d.nlevels; ++l) {
+        a.cnt = d.cnt ? d.cnt + (size_t)l * 3 * MAD_FOLD_NB : nullptr;
         a.b1 = d.band(l, 1); a.b2 = d.band(l, 2); a.b3 = d.band(l, 3);
         if (l == 0) {
             a.src = src; a.src_stride = src_stride ? src_stride : (size_t)d.w; a.lo = d.low[0]; d.cur = 0;
-            HIPCHK(ctx, launch_wavelet_analysis0(a, st));
+            a.cnt_grid = d.g0;
+            HIPCHK(ctx, d.cnt ? launch_wavelet_analysis0_count(a, st) : launch_wavelet_analysis0(a, st));
         } else {
             a.src = d.low[d.cur]; a.lo = d.low[d.cur ^ 1]; a.skip = wavelet_skip(l);
-            HIPCHK(ctx, launch_wavelet_haar_analysis(a, st));
+            a.cnt_grid = d.g1;
+            HIPCHK(ctx, d.cnt ? launch_wavelet_haar_analysis_count(a, st) : launch_wavelet_haar_analysis(a, st));
             d.cur ^= 1;
         }
     }
@@ -1330,6 +1371,8 @@ struct DnPlan {
     bool too_small;                // the planes do not hold `levwav` levels on the device path: nothing below is filled
     int rad[10], maxrad;           // box radius of the shrink factors per level
     bool fork;                     // the DCT detail recovery of L on the side stream
+    bool mad_fold;                 // MadRgb of the decomposed bands from the analysis kernels' counts (launch_mad_fold)
+    int fold_g0, fold_g1;          // ... the grids of the counting level-0 / Haar analysis kernels
     bool fused, merged, merged_mad;   // ShrinkAll: one kernel per channel / one launch for all three / with one MadRgb launch set
     bool two_chroma;               // a and b keep their own decomposition (otherwise b reuses a's)
     int detail_plain;              // DetailArgs::plain
@@ -1339,7 +1382,7 @@ struct DnPlan {
 
 // Pure: no context, no HIP call.
 DnPlan dn_plan(int w, int h, const artgpu_denoise_params *p, double scale, double expcomp, uint32_t flags, bool want_resid, bool has_ccalc,
-               int opt_dn_streams, int opt_dn_fused, int opt_dn_detail_plain, long opt_dn_wait_ms, int opt_dn_debug_stall)
+               int opt_dn_streams, int opt_dn_fused, int opt_dn_detail_plain, long opt_dn_wait_ms, int opt_dn_debug_stall, int opt_dn_mad_fold, int opt_dn_mad_fold_grid)
 {
     DnPlan pl = {};
     const int w2 = (w + 1) / 2, h2 = (h + 1) / 2;
@@ -1415,6 +1458,9 @@ DnPlan dn_plan(int w, int h, const artgpu_denoise_params *p, double scale, doubl
                 (autoch || (noisevarab_r > 0.001f && noisevarab_b > 0.001f));
     pl.merged_mad = pl.merged && opt_dn_fused != 3;      // (3: test switch, MadRgb per channel)
     pl.two_chroma = pl.fork || pl.merged;
+    // (a frame whose workgroups would count more than their threads' 8-bit counters hold keeps launch_mad: 195 MP and up with the default grids)
+    pl.fold_g0 = mad_fold_grid_a0(w2, h2, opt_dn_mad_fold_grid); pl.fold_g1 = mad_fold_grid_haar(pl.n2, opt_dn_mad_fold_grid);
+    pl.mad_fold = opt_dn_mad_fold != 0 && mad_fold_a0_fits(w2, h2, pl.fold_g0) && mad_fold_haar_fits(pl.n2, pl.fold_g1);
     return pl;
 }
 
@@ -1424,6 +1470,8 @@ struct DnBuffers {
     float *sfc[3], *tmpc[3], *histo_fc[3];          // 0: L, 1: a, 2: b
     DevDecomp Ld, Cdd[2];
     float *fused_scratch, *Lbands2;
+    int *fold_cnt;                                  // mad_fold: the counting kernels' bins, [channel][band of the channel][MAD_FOLD_NB]
+    int *fold_flags;
 };
 
 // a context that changes between the two forms of the passes gives back what only the other form uses (everything else is shared)
@@ -1458,8 +1506,16 @@ int dn_buffers(artgpu_ctx *ctx, const DnPlan &pl, const artgpu_plane *ccalc, DnB
         (rc = pool_get(ctx, P_LBANDS, (merged_mad ? 3 : 1) * band_bytes, &Ld.bands)) || (rc = pool_get(ctx, P_LLOW0, n2 * 4, &Ld.low[0])) || (rc = pool_get(ctx, P_LLOW1, n2 * 4, &Ld.low[1])) ||
         (rc = merged_mad ? ARTGPU_OK : pool_get(ctx, P_CBANDS, (merged ? 2 : 1) * band_bytes, &Cdd[0].bands)) || (rc = pool_get(ctx, P_CLOW0, n2 * 4, &Cdd[0].low[0])) || (rc = pool_get(ctx, P_CLOW1, n2 * 4, &Cdd[0].low[1])) ||
         (rc = pool_get(ctx, P_HISTO, (merged_mad ? 3 : 1) * histo_bytes, &b.histo_fc[0])) ||
-        (rc = pool_get(ctx, P_MAD, 3 * 32 * 4, &b.mad)) || (rc = pool_get(ctx, P_GAM, 2 * 65536 * 4, &b.gamlut)))
+        (rc = pool_get(ctx, P_MAD, 2 * 3 * 32 * 4, &b.mad)) || (rc = pool_get(ctx, P_GAM, 2 * 65536 * 4, &b.gamlut)))
         return rc;
+    b.fold_flags = reinterpret_cast<int *>(b.mad) + 96;
+    if (pl.mad_fold) {
+        // the channels of one launch_mad_fold call lie behind each other (merged_mad: L, a, b); every other plan takes its MADs channel by
+        // channel, each right behind its decomposition on the one stream, so all channels share the first channel's words
+        float *pf;
+        if ((rc = pool_get(ctx, P_MADPART, (size_t)(merged_mad ? 3 : 1) * nsub * MAD_FOLD_NB * sizeof(int), &pf))) return rc;
+        b.fold_cnt = reinterpret_cast<int *>(pf);
+    }
     // What only the OTHER form of the shrink passes uses (band-sized slots) is given back, but not on every switch: `fused` depends on the
     // frame (w2, h2 >= 64, radii <= 15), so a context or a batch that alternates small and large frames would pay a stream drain and a band-sized
     // hipFree / hipMalloc per frame -- the allocation the pool exists to avoid.  The slots go after FOUR calls in a row in the same form
@@ -1491,6 +1547,12 @@ int dn_buffers(artgpu_ctx *ctx, const DnPlan &pl, const artgpu_plane *ccalc, DnB
         b.histo_fc[1] = b.histo_fc[2] = b.histo_fc[0];
         Cdd[1] = Cdd[0];
     }
+    if (pl.mad_fold)
+        for (int c = 0; c < 3; ++c) {        // 0: L, 1: a, 2: b
+            DevDecomp &d = c == 0 ? Ld : Cdd[c - 1];
+            d.g0 = pl.fold_g0; d.g1 = pl.fold_g1;
+            d.cnt = b.fold_cnt + (merged_mad ? (size_t)c * nsub * MAD_FOLD_NB : 0);
+        }
     if (pl.useNoiseCCurve) {
         if (!plane_ok(ccalc) || ccalc->w != w2 || ccalc->h != h2) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: ccalc must be %dx%d", w2, h2);
         if (ccalc->on_device && (size_t)ccalc->row_stride_bytes == (size_t)w2 * 4) {
@@ -1537,6 +1599,15 @@ struct DnRun {
         return fa;
     }
     int fused_pass(bool ab, const float *cin, float *cout, const float *cL, const float *mL, const float *mab, int lev0, int nb, float nv_const, float noisevar_ab);
+    // SQR(MadRgb) of bands that decompose_dev has just written and nothing has touched since (`nb` = one channel's bands, or all three channels')
+    int mad_decomposed(const float *bands, int nb, int *histo, float *out)
+    {
+        if (!pl.mad_fold) { HIPCHK(ctx, launch_mad(bands, pl.n2, nb, histo, out, sL)); return ARTGPU_OK; }
+        int *flags = b.fold_flags + (out - b.mad);
+        HIPCHK(ctx, launch_mad_fold(bands, pl.n2, nb, pl.nsub, b.fold_cnt, histo, out, flags, sL));
+        if (ctx->dn_fold_nranges < 8) { ctx->dn_fold_ranges[ctx->dn_fold_nranges][0] = (int)(out - b.mad); ctx->dn_fold_ranges[ctx->dn_fold_nranges][1] = nb; ++ctx->dn_fold_nranges; }
+        return ARTGPU_OK;
+    }
     int chroma_front(int ch);
     int chroma_back(int ch);
     int luma(hipStream_t sd);
@@ -1576,7 +1647,7 @@ int DnRun::chroma_front(int ch)
     if (pl.aggressive && noisevar_ab > 0.001f) {
         // WaveletDenoiseAll_BiShrinkAB (L976-1108): MAD of all untouched bands, ShrinkAllAB on the top level (same MAD),
         // point-wise shrink of the levels below
-        HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, madab, sL));
+        if ((rc2 = mad_decomposed(Cd.bands, nsub, histo, madab))) return rc2;
         ShrinkArgs sa = {};
         sa.n = n2; sa.noisevar = b.ccalc_dev; sa.noisevar_scale = pl.maxNoiseVarab; sa.noisevar_ab = noisevar_ab; sa.useNoiseCCurve = pl.useNoiseCCurve ? 1 : 0;
         const size_t top = (size_t)(nsub - 3) * n2;
@@ -1598,7 +1669,10 @@ int DnRun::chroma_front(int ch)
         }
     }
     if (noisevar_ab > 0.001f && !pl.merged_mad) {
-        HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, ch == 1 && pl.merged ? b.mad + 32 + nsub : madab, sL));
+        float *out = ch == 1 && pl.merged ? b.mad + 32 + nsub : madab;
+        // (the BiShrink branch above has shrunk these bands: they are no longer what the decomposition counted)
+        if (pl.aggressive) HIPCHK(ctx, launch_mad(Cd.bands, n2, nsub, histo, out, sL));
+        else if ((rc2 = mad_decomposed(Cd.bands, nsub, histo, out))) return rc2;
         if (!pl.fused) {
             ShrinkArgs sa = {};
             sa.coef = Cd.bands; sa.coefL = Ld.bands; sa.sfave = sf; sa.n = n2; sa.madL = madL; sa.madab = madab;
@@ -1769,7 +1843,7 @@ int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_param
     if (w > 32767 || h > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: the reference holds the size in short (FTblockDN.cc:1779)");
     if (p->luminance == 0 && p->chrominance == 0 && !ccalc) return ARTGPU_OK; // L1655-1668: nothing to do
     const DnPlan pl = dn_plan(w, h, p, scale, expcomp, flags, nresi || highresi, ccalc != nullptr,
-                              ctx->shared.opt_dn_streams, ctx->shared.opt_dn_fused, ctx->shared.opt_dn_detail_plain, ctx->shared.opt_dn_wait_ms, ctx->shared.opt_dn_debug_stall);
+                              ctx->shared.opt_dn_streams, ctx->shared.opt_dn_fused, ctx->shared.opt_dn_detail_plain, ctx->shared.opt_dn_wait_ms, ctx->shared.opt_dn_debug_stall, ctx->shared.opt_dn_mad_fold, ctx->shared.opt_dn_mad_fold_grid);
     if (pl.too_small) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: %dx%d too small for %d wavelet levels on the device path", w, h, pl.levwav);
     DnBuffers b;
     int rc = dn_buffers(ctx, pl, ccalc, &b);
@@ -1815,16 +1889,17 @@ int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_param
     HIPCHK(ctx, launch_rgb2yuv(px, sL));
 
     // ---- L decomposition and its MADs (L2296-2320)
+    ctx->dn_fold_nranges = 0; ctx->dn_fold_flags = b.fold_flags;
     if ((rc = decompose_dev(ctx, b.Ld, b.L, sL))) return rc;
-    if (!pl.merged_mad) HIPCHK(ctx, launch_mad(b.Ld.bands, pl.n2, pl.nsub, reinterpret_cast<int *>(b.histo_fc[0]), b.mad, sL));
-
     DnRun run = {ctx, pl, b, fu, p, scale, nresi, highresi, sL, {0.f, 0.f}, 0.f, 0.f, b.L};
+    if (!pl.merged_mad && (rc = run.mad_decomposed(b.Ld.bands, pl.nsub, reinterpret_cast<int *>(b.histo_fc[0]), b.mad))) return rc;
+
     if (pl.merged) {
         // decompositions and MADs of a and b, the three channels' ShrinkAll passes as one launch, then the reconstructions -- L first, so that
         // its DCT detail recovery (side stream) runs beside those of a and b
         if ((rc = run.chroma_front(0)) || (rc = run.chroma_front(1))) return rc;
         // MadRgb of all three channels' bands as one launch set (the bands are back to back: L, a, b; the medians land at mad + band)
-        if (pl.merged_mad) HIPCHK(ctx, launch_mad(b.Ld.bands, pl.n2, 3 * pl.nsub, reinterpret_cast<int *>(b.histo_fc[0]), b.mad, sL));
+        if (pl.merged_mad && (rc = run.mad_decomposed(b.Ld.bands, 3 * pl.nsub, reinterpret_cast<int *>(b.histo_fc[0]), b.mad))) return rc;
         if ((rc = run.merged_pass())) return rc;
         SideStreamJoin dn_join;
         if (pl.fork) dn_join.arm(ctx->dn_stream[0]);

@@ -471,6 +471,40 @@ __global__ void __launch_bounds__(256) mad_finish_kernel(const int *histo, int d
     }
 }
 
+// ---- MadRgb from the counts the analysis kernels took while they wrote the bands (wavelet.hip): no pass over the bands at all.
+// One workgroup per band: the reference's walk over the bins counted, [0, MAD_FOLD_NB0) of a level-0 band and [0, MAD_FOLD_NB) of the others.
+// The walk is the full histogram's exactly when it ends inside these bins, i.e. when they hold at least half of the band; otherwise `done`
+// stays 0 and mad_hist_kernel / mad_finish_kernel behind this kernel compute the band as ever.
+__global__ void __launch_bounds__(256) mad_count_finish_kernel(const int *cnt, int nsub_ch, int *scr, int datalen, float *out, int *flags)
+{
+    __shared__ int part[256];
+    const int band = blockIdx.x;
+    const int nb = band % nsub_ch < 3 ? MAD_FOLD_NB0 : MAD_FOLD_NB, per = nb / 256;
+    const int *h = cnt + (size_t)band * MAD_FOLD_NB;
+    int *s = scr + (size_t)band * MAD_WIN_STRIDE;
+    int p = 0;
+    for (int i = 0; i < per; ++i) p += h[threadIdx.x * per + i];
+    part[threadIdx.x] = p;
+    __syncthreads();
+    if (threadIdx.x) return;
+    if (datalen <= 1) { out[band] = 0.f; s[0] = 1; if (flags) flags[band] = 1; return; }
+    const int half = datalen / 2;
+    long long total = 0;
+    for (int i = 0; i < 256; ++i) total += part[i];
+    if (total < half) { if (flags) flags[band] = 2; return; }       // the median bin lies above the bins counted
+    int count = 0, chunk = 0;
+    // `while (count < half) { count += histo[median]; ++median; }` -- skip whole chunks first
+    while (chunk < 256 && count + part[chunk] < half) { count += part[chunk]; ++chunk; }
+    int median = chunk * per;
+    while (count < half) { count += h[median]; ++median; }
+    const int count_ = count - h[median - 1];
+    const float q = ((median - 1) + (half - count_) / ((float)(count - count_)));
+    const float r = (float)((double)q / 0.6745);
+    out[band] = r * r;
+    s[0] = 1;
+    if (flags) flags[band] = 1;
+}
+
 // ---------------------------------------------------------------- shrink factors
 __global__ void __launch_bounds__(256) shrink_sf_L_kernel(ShrinkArgs a)
 {
@@ -942,6 +976,17 @@ hipError_t launch_mad(const float *bands, size_t n, int nsub, int *histo, float 
     hipLaunchKernelGGL(mad_pick_kernel, dim3(nsub), dim3(256), 0, s, scr);
     hipLaunchKernelGGL(mad_window_kernel, dim3(flat_grid((long long)n, MAD_GRID), nsub), dim3(256), 0, s, bands, n, scr);
     hipLaunchKernelGGL(mad_window_finish_kernel, dim3(nsub), dim3(64), 0, s, scr, (int)n, out);
+    hipLaunchKernelGGL(mad_hist_kernel, dim3(flat_grid((long long)n, MAD_GRID), nsub), dim3(256), 0, s, bands, n, histo, (const int *)scr);
+    hipLaunchKernelGGL(mad_finish_kernel, dim3(nsub), dim3(256), 0, s, (const int *)histo, (int)n, out, (const int *)scr);
+    return hipGetLastError();
+}
+hipError_t launch_mad_fold(const float *bands, size_t n, int nsub, int nsub_ch, const int *cnt, int *histo, float *out, int *flags, hipStream_t s)
+{
+    // same buffers and the same tail as launch_mad: only what settles the bands in front of the full histogram differs
+    int *scr = histo + (size_t)nsub * 65536;
+    hipError_t e = hipMemsetAsync(histo, 0, ((size_t)nsub * 65536 + (size_t)nsub * MAD_SCRATCH_INTS_PER_BAND) * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mad_count_finish_kernel, dim3(nsub), dim3(256), 0, s, cnt, nsub_ch, scr, (int)n, out, flags);
     hipLaunchKernelGGL(mad_hist_kernel, dim3(flat_grid((long long)n, MAD_GRID), nsub), dim3(256), 0, s, bands, n, histo, (const int *)scr);
     hipLaunchKernelGGL(mad_finish_kernel, dim3(nsub), dim3(256), 0, s, (const int *)histo, (int)n, out, (const int *)scr);
     return hipGetLastError();

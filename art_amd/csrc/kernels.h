@@ -348,9 +348,50 @@ struct WaveArgs {
     int w, h, w2, h2;
     int skip;
     float blend;
+    int *cnt;              // counting analysis kernels: MadRgb's bins of b1 .. b3, [3 bands][MAD_FOLD_NB], zero before the decomposition's first launch
+    int cnt_grid;          // ... their grid (mad_fold_grid_a0 / mad_fold_grid_haar)
 };
 hipError_t launch_wavelet_analysis0(const WaveArgs &a, hipStream_t s);
 hipError_t launch_wavelet_haar_analysis(const WaveArgs &a, hipStream_t s);
+// MadRgb's histogram counted while the bands are written: the two analysis kernels with a bounded grid; every workgroup counts the
+// low bins of min(65535, abs((int)x)) of the three bands it writes -- [0, MAD_FOLD_NB0) in the level-0 kernel, whose LDS also holds its tile,
+// [0, MAD_FOLD_NB) in the Haar levels -- and adds them to the band's MAD_FOLD_NB words at its end
+constexpr int MAD_FOLD_NB = 4096, MAD_FOLD_NB0 = 1024;
+constexpr int MAD_FOLD_A0_TILE_W = 64, MAD_FOLD_A0_TILE_H = 32, MAD_FOLD_HAAR_THREADS = 1024;
+#ifndef MAD_FOLD_A0_GRID
+#define MAD_FOLD_A0_GRID 768
+#endif
+#ifndef MAD_FOLD_HAAR_GRID
+#define MAD_FOLD_HAAR_GRID 512
+#endif
+inline long long mad_fold_a0_tiles(int w2, int h2)
+{
+    return (long long)((w2 + MAD_FOLD_A0_TILE_W - 1) / MAD_FOLD_A0_TILE_W) * ((h2 + MAD_FOLD_A0_TILE_H - 1) / MAD_FOLD_A0_TILE_H);
+}
+// cap: 0 for the grids above, > 0 for at most that many workgroups (option "dn_mad_fold_grid": tests, timing)
+inline int mad_fold_grid_a0(int w2, int h2, int cap)
+{
+    const long long t = mad_fold_a0_tiles(w2, h2), c = cap > 0 ? cap : MAD_FOLD_A0_GRID;
+    return (int)(t < c ? t : c);
+}
+inline int mad_fold_grid_haar(size_t n2, int cap)
+{
+    const size_t g = (n2 + MAD_FOLD_HAAR_THREADS - 1) / MAD_FOLD_HAAR_THREADS, c = cap > 0 ? cap : MAD_FOLD_HAAR_GRID;
+    return (int)(g < c ? g : c);
+}
+// A thread keeps bins 0 .. 7 in 8-bit counters that it flushes once, at the kernel's end: it may count at most 255 values of a band (level 0:
+// 8 per tile, so 31 tiles per workgroup -- 195 MP with the default grid; a Haar level: one per step, 535 MP)
+inline bool mad_fold_a0_fits(int w2, int h2, int g0)
+{
+    return g0 > 0 && (mad_fold_a0_tiles(w2, h2) + g0 - 1) / g0 * (MAD_FOLD_A0_TILE_W * MAD_FOLD_A0_TILE_H / 256) <= 255;
+}
+inline bool mad_fold_haar_fits(size_t n2, int g1)
+{
+    const size_t per = (size_t)g1 * MAD_FOLD_HAAR_THREADS;
+    return g1 > 0 && n2 <= 0x7fffffff && (n2 + per - 1) / per <= 255;
+}
+hipError_t launch_wavelet_analysis0_count(const WaveArgs &a, hipStream_t s);
+hipError_t launch_wavelet_haar_analysis_count(const WaveArgs &a, hipStream_t s);
 hipError_t launch_wavelet_haar_synthesis(const WaveArgs &a, hipStream_t s);
 hipError_t launch_wavelet_synthesis0(const WaveArgs &a, hipStream_t s);
 
@@ -440,6 +481,10 @@ hipError_t launch_yuv2rgb(const DnPixArgs &a, hipStream_t s);
 hipError_t launch_bishrink_AB(const ShrinkArgs &a, int nsub, hipStream_t s);
 constexpr int MAD_SCRATCH_INTS_PER_BAND = 8 + 1024 + 4096 + 8;      // launch_mad: `histo` holds nsub * (65536 + this) ints
 hipError_t launch_mad(const float *bands, size_t n, int nsub, int *histo, float *out, hipStream_t s);
+// The same medians from the counts the analysis kernels left in `cnt` ([nsub][MAD_FOLD_NB]; nsub / nsub_ch channels of nsub_ch bands each,
+// level-major), then launch_mad's full histogram for every band whose median bin lies above the bins counted.  flags[band] (may be null):
+// 1 settled from the counts, 2 left to the full histogram.
+hipError_t launch_mad_fold(const float *bands, size_t n, int nsub, int nsub_ch, const int *cnt, int *histo, float *out, int *flags, hipStream_t s);
 hipError_t launch_shrink_sf(const ShrinkArgs &a, int nsub, bool ab, hipStream_t s);
 hipError_t launch_hblur(const BlurArgs &a, int nsub, hipStream_t s);
 hipError_t launch_vblur_combine(const BlurArgs &a, int nsub, hipStream_t s);

@@ -43,6 +43,48 @@ constexpr int A0_LW = 2 * A0_TW + 6;           // tmp columns kept in LDS
 #endif
 constexpr int S0_TW = S0_TW_, S0_TH = S0_TH_;   // output tile of the level-0 synthesis
 constexpr int S0_LH = S0_TH / 2 + 4;           // horizontally synthesised rows kept in LDS
+
+// ---- MadRgb's histogram, counted by the analysis kernels while they write the bands.  Bins 0 .. 7 of a band go to eight 8-bit
+// counters packed into one 64-bit register per thread (a peaked band's one hot bin never reaches LDS), bins 8 .. NB - 1 to the
+// workgroup's LDS histogram, anything above is counted nowhere: launch_mad_fold sees from the total whether the median bin was inside.
+template <int NB>
+__device__ __forceinline__ void mad_count_add(unsigned long long &packed, int *h, float x, bool valid)
+{
+    int v = (int)fminf(fabsf(x), 65535.f);                     // the bin of mad_hist_kernel (denoise.hip), NaN / Inf / >= 2^31 included
+    v = valid ? v : 0x10000;
+    packed += (unsigned)v < 8u ? 1ull << (8 * v) : 0ull;
+    if (v >= 8 && v < NB) atomicAdd(&h[v], 1);
+}
+// Called by whole waves, once, at the kernel's end (no byte has counted 256 by then: kernels.h, mad_fold_*_fits): the eight bytes as two sets of four 16-bit fields (64 lanes x 255 fits), summed over the
+// wave, one LDS atomic per wave and non-empty bin
+template <int NB>
+__device__ __forceinline__ void mad_count_flush(unsigned long long (&packed)[3], int (*h)[NB])
+{
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        unsigned long long e = packed[b] & 0x00ff00ff00ff00ffull, o = (packed[b] >> 8) & 0x00ff00ff00ff00ffull;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) { e += __shfl_down(e, s); o += __shfl_down(o, s); }
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ce = (int)((e >> (16 * k)) & 0xffffull), co = (int)((o >> (16 * k)) & 0xffffull);
+                if (ce) atomicAdd(&h[b][2 * k], ce);
+                if (co) atomicAdd(&h[b][2 * k + 1], co);
+            }
+        }
+        packed[b] = 0ull;
+    }
+}
+// the workgroup's counts into the bands' words, empty bins skipped
+template <int NB, int THREADS>
+__device__ __forceinline__ void mad_count_store(const WaveArgs &a, const int (*h)[NB])
+{
+    for (int i = threadIdx.x; i < 3 * NB; i += THREADS) {
+        const int b = i / NB, j = i - b * NB, v = h[b][j];
+        if (v) atomicAdd(&a.cnt[b * MAD_FOLD_NB + j], v);
+    }
+}
 } // namespace
 
 // ---- level 0 analysis: src (w x h) -> lo, b1, b2, b3 (w2 x h2) ----
@@ -96,11 +138,14 @@ __global__ void __launch_bounds__(256) wavelet_analysis0_kernel(WaveArgs a)
 #else
 constexpr int A0_WR = 16;
 static_assert(A0_TW == 64 && A0_TH * 128 == 256 * A0_WR, "the walkers' mapping: 128 tmp columns x A0_TH / A0_WR row groups = 256 threads");
-__global__ void __launch_bounds__(256) wavelet_analysis0_kernel(WaveArgs a)
+// One output tile (bx, by): the body of wavelet_analysis0_kernel and, with COUNT, of wavelet_analysis0_count_kernel, which also counts the
+// three high bands' MadRgb bins -- the same expressions in the same order for both, so both write the same bits.
+template <bool COUNT>
+__device__ __forceinline__ void analysis0_tile(const WaveArgs &a, int bx, int by, float (*tLo)[A0_LW], float (*tHi)[A0_LW],
+                                               unsigned long long (&packed)[3], int (*hc)[MAD_FOLD_NB0])
 {
-    __shared__ float tLo[A0_TH][A0_LW], tHi[A0_TH][A0_LW];
     const int w = a.w, h = a.h, w2 = a.w2;
-    const int c0 = blockIdx.x * A0_TW, r0 = blockIdx.y * A0_TH; // output coords
+    const int c0 = bx * A0_TW, r0 = by * A0_TH; // output coords
     const int icol0 = 2 * c0 - 3;                                // first tmp column held
     {
         // tmp columns 0 .. 127: thread = (row group, column)
@@ -160,26 +205,99 @@ __global__ void __launch_bounds__(256) wavelet_analysis0_kernel(WaveArgs a)
         }
         const size_t o = (size_t)orow * w2 + ocol;
         a.lo[o] = l0; a.b1[o] = h0; a.b2[o] = l1; a.b3[o] = h1;
+        if constexpr (COUNT) {
+            mad_count_add<MAD_FOLD_NB0>(packed[0], hc[0], h0, true);
+            mad_count_add<MAD_FOLD_NB0>(packed[1], hc[1], l1, true);
+            mad_count_add<MAD_FOLD_NB0>(packed[2], hc[2], h1, true);
+        }
     }
+}
+__global__ void __launch_bounds__(256) wavelet_analysis0_kernel(WaveArgs a)
+{
+    __shared__ float tLo[A0_TH][A0_LW], tHi[A0_TH][A0_LW];
+    unsigned long long none[3];
+    analysis0_tile<false>(a, blockIdx.x, blockIdx.y, tLo, tHi, none, nullptr);
+}
+// The same tiles walked by a bounded grid, every workgroup with its counts (kernels.h: mad_fold_grid_a0)
+static_assert(A0_TW == MAD_FOLD_A0_TILE_W && A0_TH == MAD_FOLD_A0_TILE_H, "mad_fold_grid_a0 counts these tiles");
+__global__ void __launch_bounds__(256) wavelet_analysis0_count_kernel(WaveArgs a)
+{
+    __shared__ float tLo[A0_TH][A0_LW], tHi[A0_TH][A0_LW];
+    __shared__ int hc[3][MAD_FOLD_NB0];
+    for (int i = threadIdx.x; i < 3 * MAD_FOLD_NB0; i += 256) (&hc[0][0])[i] = 0;
+    __syncthreads();
+    const int tx = (a.w2 + A0_TW - 1) / A0_TW, ntiles = tx * ((a.h2 + A0_TH - 1) / A0_TH);
+    unsigned long long packed[3] = {0ull, 0ull, 0ull};
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {            // (at most 31 tiles: launch_wavelet_analysis0_count)
+        analysis0_tile<true>(a, tile % tx, tile / tx, tLo, tHi, packed, hc);
+        __syncthreads();                                                        // (the next tile's column stage overwrites tLo / tHi)
+    }
+    mad_count_flush(packed, hc);
+    __syncthreads();
+    mad_count_store<MAD_FOLD_NB0, 256>(a, hc);
 }
 #endif
 
 // ---- levels >= 1 analysis: undecimated Haar (cplx_wavelet_level.h:206-238) ----
+// One output pixel in three steps -- its four inputs, the sums, the stores (c1 .. c3 go to b1 .. b3): the body of both Haar analysis kernels
+__device__ __forceinline__ void haar_analysis_load(const WaveArgs &a, int w, int h, int skip, long long t, float (&s)[4])
+{
+    const int row = (int)(t / w), i = (int)(t - (long long)row * w);
+    const int rp = row < h - skip ? row + skip : row - skip;
+    const int ip = i < w - skip ? i + skip : i - skip;
+    s[0] = a.src[(size_t)row * w + i]; s[1] = a.src[(size_t)row * w + ip];
+    s[2] = a.src[(size_t)rp * w + i]; s[3] = a.src[(size_t)rp * w + ip];
+}
+__device__ __forceinline__ void haar_analysis_sums(const float (&s)[4], float &lo, float &c1, float &c2, float &c3)
+{
+    const float s00 = s[0], s01 = s[1], s10 = s[2], s11 = s[3];
+    const float tl0 = 0.25f * (s00 + s10), tl1 = 0.25f * (s01 + s11);
+    const float th0 = 0.25f * (s00 - s10), th1 = 0.25f * (s01 - s11);
+    lo = tl0 + tl1; c1 = tl0 - tl1; c2 = th0 + th1; c3 = th0 - th1;
+}
+__device__ __forceinline__ void haar_analysis_store(const WaveArgs &a, long long t, float lo, float c1, float c2, float c3)
+{
+    a.lo[t] = lo; a.b1[t] = c1;
+    a.b2[t] = c2; a.b3[t] = c3;
+}
 __global__ void __launch_bounds__(256) wavelet_haar_analysis_kernel(WaveArgs a)
 {
     const int w = a.w2, h = a.h2, skip = a.skip;
     const long long n = (long long)w * h;
     for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
-        const int row = (int)(t / w), i = (int)(t - (long long)row * w);
-        const int rp = row < h - skip ? row + skip : row - skip;
-        const int ip = i < w - skip ? i + skip : i - skip;
-        const float s00 = a.src[(size_t)row * w + i], s01 = a.src[(size_t)row * w + ip];
-        const float s10 = a.src[(size_t)rp * w + i], s11 = a.src[(size_t)rp * w + ip];
-        const float tl0 = 0.25f * (s00 + s10), tl1 = 0.25f * (s01 + s11);
-        const float th0 = 0.25f * (s00 - s10), th1 = 0.25f * (s01 - s11);
-        a.lo[t] = tl0 + tl1; a.b1[t] = tl0 - tl1;
-        a.b2[t] = th0 + th1; a.b3[t] = th0 - th1;
+        float s[4], lo, c1, c2, c3;
+        haar_analysis_load(a, w, h, skip, t, s);
+        haar_analysis_sums(s, lo, c1, c2, c3);
+        haar_analysis_store(a, t, lo, c1, c2, c3);
     }
+}
+// ... with the counts: a bounded grid (kernels.h: mad_fold_grid_haar), whole workgroups per step; a lane past the end stores and counts nothing
+__global__ void __launch_bounds__(MAD_FOLD_HAAR_THREADS) wavelet_haar_analysis_count_kernel(WaveArgs a)
+{
+    constexpr int T = MAD_FOLD_HAAR_THREADS;
+    __shared__ int hc[3][MAD_FOLD_NB];
+    for (int i = threadIdx.x; i < 3 * MAD_FOLD_NB; i += T) (&hc[0][0])[i] = 0;
+    __syncthreads();
+    const int w = a.w2, h = a.h2, skip = a.skip;
+    const long long n = (long long)w * h;
+    unsigned long long packed[3] = {0ull, 0ull, 0ull};
+    for (long long base = blockIdx.x * (long long)T; base < n; base += (long long)gridDim.x * T) {      // (at most 255 steps: launch_wavelet_haar_analysis_count)
+        const long long t = base + threadIdx.x;
+        const bool valid = t < n;
+        float c1 = 0.f, c2 = 0.f, c3 = 0.f;
+        if (valid) {
+            float s[4], lo;
+            haar_analysis_load(a, w, h, skip, t, s);
+            haar_analysis_sums(s, lo, c1, c2, c3);
+            haar_analysis_store(a, t, lo, c1, c2, c3);
+        }
+        mad_count_add<MAD_FOLD_NB>(packed[0], hc[0], c1, valid);
+        mad_count_add<MAD_FOLD_NB>(packed[1], hc[1], c2, valid);
+        mad_count_add<MAD_FOLD_NB>(packed[2], hc[2], c3, valid);
+    }
+    mad_count_flush(packed, hc);
+    __syncthreads();
+    mad_count_store<MAD_FOLD_NB, T>(a, hc);
 }
 
 // ---- levels >= 1 synthesis, fused H then V (cplx_wavelet_level.h:243-298) ----
@@ -319,6 +437,22 @@ static int flat_grid(long long n) { long long g = (n + 255) / 256; return (int)(
 hipError_t launch_wavelet_haar_analysis(const WaveArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(wavelet_haar_analysis_kernel, dim3(flat_grid((long long)a.w2 * a.h2)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_wavelet_analysis0_count(const WaveArgs &a, hipStream_t s)
+{
+#ifdef A0_PLAIN
+    return hipErrorNotSupported;
+#else
+    if (!a.cnt || a.cnt_grid > mad_fold_a0_tiles(a.w2, a.h2) || !mad_fold_a0_fits(a.w2, a.h2, a.cnt_grid)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wavelet_analysis0_count_kernel, dim3(a.cnt_grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+#endif
+}
+hipError_t launch_wavelet_haar_analysis_count(const WaveArgs &a, hipStream_t s)
+{
+    if (!a.cnt || !mad_fold_haar_fits((size_t)a.w2 * a.h2, a.cnt_grid)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wavelet_haar_analysis_count_kernel, dim3(a.cnt_grid), dim3(MAD_FOLD_HAAR_THREADS), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_wavelet_haar_synthesis(const WaveArgs &a, hipStream_t s)

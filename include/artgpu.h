@@ -90,6 +90,11 @@ int artgpu_synchronize(artgpu_ctx *ctx);
  *   "dn_detail_plain"   0 (default): the DCT detail recovery's trimmed kernels (blocks inside the image on a path of their own, the gather by rows);
  *                       1: the kernels before them, same bits (what tests/test_gpu_detail_paths.py compares against); 2 / 3: only the block kernel /
  *                       only the gather kernel plain
+ *   "dn_mad_fold"       1 (default): MadRgb of the decomposed bands from the low bins the wavelet analysis kernels count while they write the bands
+ *                       (DESIGN.md section 28), the full histogram only for a band whose median lies above them; 0: a pass over the bands, as before.
+ *                       Same bits.  "dn_mad_fold_grid" n > 0: the counting kernels with at most n workgroups (tests, timing).  artgpu_get_option:
+ *                       "dn_mad_fold_settled" / "dn_mad_fold_fallback": bands of the context's last RGB_denoise settled from the counts / left to
+ *                       the full histogram; "dn_mad_bitsK": bit pattern of word K (0 .. 95) of its SQR(MadRgb) block
  *   "dn_streams"        0 (default since round 5): RGB_denoise's kernels one after the other on the context's stream; 1: the DCT detail recovery of L on a
  *                       side stream beside the reconstructions of a and b (the default of rounds 3 and 4); "lut_lds" 0: never the LUT-in-LDS shape
  *                       of the pixel passes; "rcd_rows" 4 | 8; "roctx" 1: roctx ranges named after the reference functions
