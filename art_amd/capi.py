@@ -720,15 +720,22 @@ class Context:
     def nlmeans(self, img: Plane, strength: int = 50, detail: int = 80, scale: float = 1.0, normcoeff: float = 65535.0):
         self._chk(LIB.artgpu_nlmeans(self._h, C.byref(img), normcoeff, strength, detail, scale))
 
-    def scale_colors(self, src: np.ndarray, filters: int, xtrans, cblacksom, scale_mul, dst: Plane):
-        """host uint16 / float32 sensor data -> scaled float CFA plane; returns chmax[4]"""
-        assert src.dtype in (np.uint16, np.float32) and src.flags.c_contiguous
-        h, w = src.shape
+    def scale_colors(self, src: np.ndarray, filters: int, xtrans, cblacksom, scale_mul, dst: Plane, device_src=None):
+        """host uint16 / float32 sensor data -> scaled float CFA plane; returns chmax[4].  device_src: the sensor data on the device instead
+        (`src` is then ignored): a 2-D torch tensor of 16-bit integers (read as uint16) or float32 with unit column stride and any row stride."""
         xt = None if xtrans is None else np.ascontiguousarray(xtrans, dtype=np.int32).reshape(36).ctypes.data_as(C.POINTER(C.c_int32))
         cb = (C.c_float * 4)(*[float(v) for v in cblacksom]); sm = (C.c_float * 4)(*[float(v) for v in scale_mul])
         mx = (C.c_float * 4)()
-        self._chk(LIB.artgpu_scale_colors(self._h, src.ctypes.data, w, h, src.strides[0], 1 if src.dtype == np.uint16 else 0, 0, filters, xt,
-                                          cb, sm, C.byref(dst), mx))
+        if device_src is None:
+            assert src.dtype in (np.uint16, np.float32) and src.flags.c_contiguous
+            h, w = src.shape
+            ptr, row_bytes, is_u16, on_device = src.ctypes.data, src.strides[0], src.dtype == np.uint16, 0
+        else:
+            t = device_src
+            assert t.dim() == 2 and t.stride(1) == 1 and t.element_size() in (2, 4) and (t.element_size() == 2 or t.is_floating_point())
+            h, w = t.shape
+            ptr, row_bytes, is_u16, on_device = t.data_ptr(), t.stride(0) * t.element_size(), t.element_size() == 2, 1
+        self._chk(LIB.artgpu_scale_colors(self._h, ptr, w, h, row_bytes, 1 if is_u16 else 0, on_device, filters, xt, cb, sm, C.byref(dst), mx))
         return [float(v) for v in mx]
 
     def raw_ca_correct(self, raw: Plane, filters: int, params: "CaParams", want_fit: bool = False):
@@ -918,8 +925,15 @@ class Context:
         self._chk(LIB.artgpu_rgb2out_matrix(self._h, C.byref(src), C.byref(dst), m, 1 if trc_linear else 0,
                                             None if la is None else la.ctypes.data_as(C.POINTER(C.c_float)), 0 if la is None else la.size))
 
-    def get_scanlines(self, image: RGB, bps: int, is_float: bool = False) -> np.ndarray:
-        """Imagefloat::getScanline for every row -> (h, w, 3) array of uint8 / uint16 / float16-bits (uint16) / float32"""
+    def get_scanlines(self, image: RGB, bps: int, is_float: bool = False, device_dst=None):
+        """Imagefloat::getScanline for every row -> (h, w, 3) array of uint8 / uint16 / float16-bits (uint16) / float32.  device_dst: the
+        scanlines go to the device instead and nothing is returned: a 2-D torch tensor of bytes, one row per scanline (at least
+        w * 3 * bps / 8 bytes each, unit column stride, any row stride)."""
+        if device_dst is not None:
+            t = device_dst
+            assert t.dim() == 2 and t.element_size() == 1 and t.stride(1) == 1 and t.shape[0] == image.r.h and t.shape[1] >= image.r.w * 3 * bps // 8
+            self._chk(LIB.artgpu_get_scanlines(self._h, C.byref(image), bps, 1 if is_float else 0, t.data_ptr(), t.stride(0), 1))
+            return None
         dt = np.float32 if (is_float and bps == 32) else (np.uint8 if bps == 8 else np.uint16)
         out = np.zeros((image.r.h, image.r.w, 3), dt)
         self._chk(LIB.artgpu_get_scanlines(self._h, C.byref(image), bps, 1 if is_float else 0, out.ctypes.data, out.strides[0], 0))
