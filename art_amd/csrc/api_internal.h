@@ -1,0 +1,351 @@
+// art_amd/csrc/api_internal.h -- what the host files of the C ABI share: the context, the staging and pool helpers, and per stage
+// exactly the plan structs and *_dev / *_check / *_plan functions that ANOTHER file calls: the frame driver (api_pipeline.hip) and
+// io_frame (api_batch.hip).  This header is the list of what a stage exposes to the driver; everything a stage uses only itself stays
+// static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api, declared with hidden visibility:
+// none of them is in the library's dynamic symbol table (a definition inherits nothing from its declaration here: every opening of
+// the namespace carries the attribute).  Each is defined once (the helpers and the stages in artgpu_api.hip); none is inline.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <dlfcn.h>
+#include <cmath>
+#include <cstdio>
+#include <cstdarg>
+#include <cstring>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+#include <algorithm>
+
+#include "../../include/artgpu.h"
+#include "kernels.h"
+#include "dehaze.h"
+#include "textureboost.h"
+#include "colorcorrection.h"
+#include "smoothing.h"
+#include "masks.h"
+#include "sharpen.h"
+
+struct artgpu_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t aux = nullptr;      // second stream (serial statistics of the AUTOMATIC chroma estimation run beside the decompositions)
+    hipEvent_t aux_ev[2] = {nullptr, nullptr};
+    // RGB_denoise: the DCT detail recovery of L runs on a side stream beside the chroma blurs / reconstructions
+    hipStream_t dn_stream[1] = {nullptr};
+    hipEvent_t dn_ev[2] = {nullptr, nullptr};
+    const float *gam_tab = nullptr; float gam_key[6] = {};   // RGB_denoise's gamma / inverse-gamma tables in pool[P_GAM]: what they were built from
+    // What a batch lane inherits from its parent context (batch_prepare_lanes copies the block as one value on every batch call).  A field
+    // belongs here exactly if a frame's result or its reporting must not depend on which lane ran it.  (cu_reserve is not one: io_frame sets it
+    // per lane; the *_own storage the pipe_* pointers point into stays with the parent.)
+    struct Shared {
+        // options (artgpu_set_option): test / profiling switches that used to be environment variables
+        int opt_sharpen_fused = 1;     // RL deconvolution, stencil regimes -- 1: one kernel per iteration (rl_iter_kernel); 0: DIV, MULT and check_stop as three launches (timing)
+        int opt_lut_lds = 1;           // 0: never the LUT-in-LDS shapes of the pixel passes (tests compare the two)
+        int opt_dn_streams = 0;        // 1: the DCT detail recovery of L on a side stream beside the reconstructions of a and b.  The default until round 5, when the
+                                       // stage waited on LDS round trips and left the chip half idle; since detail_blocks_kernel lost a fifth of its time (detail.hip) the
+                                       // two chains only get in each other's way: one kernel after the other is 0.1 - 0.15 ms per 45 MP frame faster (scripts/r5_ab9.sh)
+        int opt_dn_fused = 1;          // ShrinkAllL / ShrinkAllAB -- 0: three kernels per channel (factors, row sums, column sums + update); 2: one kernel per
+                                       // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
+        int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
+                                       // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
+        int opt_dn_mad_fold = 1;       // MadRgb -- 1: from the bins the analysis kernels count while they write the bands; 0: launch_mad's pass over the bands
+        int opt_dn_mad_fold_grid = 0;  // > 0: the counting analysis kernels with at most this many workgroups (tests: many steps per workgroup; timing of the grid cap)
+        int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
+        long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
+        int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
+                                       // hipMemcpy; -1 (default): 8 with two lanes, 0 otherwise (io_frame has the measurements)
+        int opt_amaze_path = 0;        // 0: LDS streaming kernel for full tiles + arena kernel for the rest; 1: arena kernel for every tile
+        int opt_amaze_split = 0;       // 1 (with path 1): one launch per phase
+        long opt_amaze_zero_mask = 0x81f0;
+        int opt_amaze_zero_frame = 16;
+        int opt_amaze_poison = -1;     // >= 0: byte pattern the arenas are filled with before the launch
+        int opt_roctx = 0;             // 1: roctx ranges named after the reference functions around the entry points (rocprofv3 --marker-trace)
+        int opt_amaze_overlap = 1;     // 0: the arena kernel's static tiles behind the stream kernel instead of beside it
+        int opt_amaze_grid = 0;        // > 0: at most this many stream workgroups (each owns a CU): with several frames in flight the CUs left over
+                                       // take the other frames' bandwidth-bound passes while this frame's issue-bound demosaic runs
+        int opt_rcd_rows = 8;          // rows per iteration of the streaming kernel (4 or 8)
+        int curve_tail_kind = ARTGPU_CURVE_TAIL_HOST;   // artgpu_set_curve_tail
+        double curve_tail_y = 1.0;
+        artgpu::ParamCurve curve_tail_pc = {};
+        artgpu_progress_fn progress_fn = nullptr;   // artgpu_set_progress_callback
+        void *progress_user = nullptr;
+        // artgpu_set_pipeline_masks / _color_correction / _smoothing: what the pipe reads (the parent's pipe_*_own hold the memory)
+        const artgpu_mask_params *pipe_lc = nullptr, *pipe_tb = nullptr;
+        int pipe_nlc = 0, pipe_ntb = 0;
+        const artgpu_color_correction_region *pipe_cc = nullptr;
+        const artgpu_mask_params *pipe_cc_masks = nullptr;
+        int pipe_ncc = 0;
+        const artgpu_smoothing_region *pipe_sm = nullptr;
+        const artgpu_mask_params *pipe_sm_masks = nullptr;
+        int pipe_nsm = 0;
+    } shared;
+    float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
+    hipEvent_t sh_ev = nullptr;
+    // artgpu_set_pipeline_masks: deep copies (entries, curves, area descriptors); batch lanes point at their parent's
+    struct PipeMasks { std::vector<artgpu_mask_params> m; std::vector<std::vector<double>> curves; std::vector<artgpu_plane> areas; } pipe_lc_own, pipe_tb_own;
+    // artgpu_set_pipeline_color_correction / artgpu_set_pipeline_smoothing: the regions, their mask planes' descriptors and the mask parameters
+    template <typename Region> struct PipeRegions { std::vector<Region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; };
+    PipeRegions<artgpu_color_correction_region> pipe_cc_own;
+    PipeRegions<artgpu_smoothing_region> pipe_sm_own;
+    std::string err;
+    int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
+    long long batch_px = 0;       // artgpu_batch_run: pixels of the largest frame this context's scratch was grown for since the last trim
+    // RGB_denoise's last call: the fold's flag block (96 words in the P_MAD slot behind the 96 medians) and which of its words the call's launch_mad_fold launches wrote (first, count)
+    const int *dn_fold_flags = nullptr; int dn_fold_ranges[8][2] = {}; int dn_fold_nranges = 0;
+    int dn_form = -1, dn_form_streak = 0;   // RGB_denoise: the shrink passes' form of the last call (1 fused / 0 three kernels) and how many calls in a row used it
+    // per-workgroup work arenas (demosaic)
+    float *arena = nullptr;
+    size_t arena_bytes = 0;
+    // staging for host-pointer calls: one CFA plane + three output planes
+    static constexpr int NSTAGE = 8;
+    float *stage[NSTAGE] = {};
+    size_t stage_bytes[NSTAGE] = {};
+    // grow-only scratch pool for the denoise path (planes, decompositions, shrink buffers)
+    static constexpr int NPOOL = 96;
+    float *pool[NPOOL] = {};
+    size_t pool_bytes[NPOOL] = {};
+    // artgpu_batch_run lanes: sibling contexts (own stream, arena, pools) that take every lanes-th frame on their own host thread
+    std::vector<artgpu_ctx *> lanes;
+    int batch_lanes = 1;
+    int frames_in_flight = 1;      // set by artgpu_batch_run on itself and its lanes while a batch with L > 1 lanes runs: the demosaic then takes 5/8 of the CUs (option amaze_grid)
+    bool owns_stream = false;
+    // artgpu_batch_run_io: a frame's upload and download run on streams of their own beside the kernels on `stream`.  Events, by staging slot
+    // (the parity of the frame's turn on this lane): [0,1] uploaded, [2,3] the upload slot has been read, [4,5] scanlines written, [6,7] downloaded
+    hipStream_t io_up = nullptr, io_down = nullptr;
+    hipEvent_t io_ev[8] = {};
+    int *io_host = nullptr;        // pinned, 8 words per frame of the lane: channel maxima (bit patterns) x 3, -, rgb2out's count of unsupported values
+    int io_host_cap = 0;
+    int cu_reserve = 0;            // set around a batch whose downloads run as a kernel of a few workgroups: the persistent one-workgroup-per-CU pixel passes leave those CUs alone
+    // (what artgpu_improc_denoise_fused fuses into the denoise tool's pixel passes is not state of the context: it travels as a DnFusion argument)
+    float *bbox = nullptr; // AMaZE: per-tile nyquist bounding boxes
+    size_t bbox_bytes = 0;
+    // AMaZE v2: tile lists on the device (ints).  [stream tiles | arena-tile template: count, tiles | working copy: count, tiles + room
+    // for every streamed tile the stream kernel hands back]
+    float *amz_lists = nullptr;
+    size_t amz_lists_bytes = 0;
+    int amz_w = 0, amz_h = 0, amz_nstream = 0, amz_narena = 0, amz_mode = -1;
+    int num_cus = 0;
+    hipStream_t amz_side = nullptr;
+    hipEvent_t amz_ev[2] = {nullptr, nullptr};
+    int *rcd_counter = nullptr;    // RCD streaming kernel: tile counter
+    float *lut = nullptr; // 65536-entry tone LUT on the device
+    size_t lut_bytes = 0;
+    std::vector<float> lut_host;           // what ctx->lut holds (a curve that comes back unchanged is not uploaded again)
+    std::vector<float> ncurve_host;        // likewise the 501-entry chroma noise curve behind the cachef table
+    char *tab_ring = nullptr;              // pinned staging ring of h2d_table (caller look-up tables)
+    size_t tab_ring_bytes = 0, tab_ring_off = 0;
+    bool tab_ring_busy = false;
+    hipEvent_t tab_ev = nullptr;
+    std::vector<float> rgbcurve_host[3];   // likewise the three rgbCurves tables (P_RGBCURVES: a slot nothing else writes)
+    // timing
+    bool timing = false;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    artgpu_timings last = {0.f, 0.f, 0.f};
+};
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+// ---------------------------------------------------------------------------------------------
+// context: errors, staging of host planes, the scratch pool
+// ---------------------------------------------------------------------------------------------
+int fail(artgpu_ctx *ctx, int code, const char *fmt, ...);
+
+#define HIPCHK(ctx, call)                                                                        \
+    do {                                                                                         \
+        hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(ctx, ARTGPU_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// A call that puts work on a side stream has to leave with the context's stream behind that work on EVERY path: an error return in between
+// would otherwise leave the side stream running on pool buffers the next call hands out again.  Armed when the fork happens, disarmed by the
+// regular join (an event wait, no host blocking); on any other exit the destructor drains the side stream.
+struct SideStreamJoin {
+    hipStream_t side = nullptr;
+    void arm(hipStream_t s) { side = s; }
+    void disarm() { side = nullptr; }
+    ~SideStreamJoin() { if (side) (void)hipStreamSynchronize(side); }
+};
+
+int ensure(artgpu_ctx *ctx, float **buf, size_t *cur, size_t need);
+int h2d_table(artgpu_ctx *ctx, void *dst, const void *src, size_t bytes);
+bool plane_ok(const artgpu_plane *p);
+
+struct DevImage {
+    const float *raw; size_t raw_stride;
+    float *r, *g, *b; size_t out_stride;
+    bool staged;
+};
+int bind_images(artgpu_ctx *ctx, const artgpu_plane *raw, artgpu_rgb *out, DevImage *d);
+int unbind_images(artgpu_ctx *ctx, artgpu_rgb *out, const DevImage *d);
+
+// Generic RGB image binding: device planes are used in place, host planes are staged through
+// ctx->stage[slot..slot+2] (copy_in: H2D now; the D2H happens in unbind_rgb).
+struct DevRGB {
+    float *p[3];
+    size_t stride; // floats
+    int w, h;
+    bool staged;
+};
+artgpu_plane mk_dev_plane(float *p, int w, int h);
+artgpu_rgb mk_dev_rgb(float *const p[3], int w, int h, size_t stride);
+int bind_rgb(artgpu_ctx *ctx, const artgpu_rgb *img, int slot, bool copy_in, DevRGB *d, const char *what);
+int unbind_rgb(artgpu_ctx *ctx, artgpu_rgb *img, const DevRGB *d);
+
+enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1, P_SF, P_TMP, P_HISTO, P_MAD, P_GAM, P_CCALC, P_LIN, P_BLOCKS, P_DTAB, P_CCMAP, P_CACHEF, P_PQ, P_XCBRT, P_GAUSS64, P_DMASK, P_LABTABS, P_PIPE_R, P_PIPE_G, P_PIPE_B, P_DNINFO, P_BATCH, P_DCTTAB, P_CBANDS2, P_CLOW0_2, P_CLOW1_2, P_SF_A, P_SF_B, P_HISTO_A, P_HISTO_B, P_RGBCURVES, P_FUSED, P_LBANDS2,
+       P_IO_IN0, P_IO_IN1, P_IO_CFA, P_IO_IMG0, P_IO_IMG1, P_IO_IMG2, P_IO_IMG3, P_IO_IMG4, P_IO_IMG5, P_IO_OUT0, P_IO_OUT1, P_IO_FLAGS,      // artgpu_batch_run_io: staging slots, the CFA plane, the working image, the frames' flag words
+       P_CA_HALF, P_CA_BLK, P_CA_GUARD, P_CA_RAW,                                                                       // artgpu_raw_ca_correct
+       P_LC_BANDS, P_LC_LOW0, P_LC_LOW1, P_LC_NEW, P_LC_STATS, P_LC_MASK, P_LC_L,                                       // artgpu_local_contrast
+       P_DH_STATE, P_DH_THUMB, P_DH_LOW, P_DH_TMP, P_DH_T, P_DH_DARK,                                                   // artgpu_dehaze
+       P_SH_PLANES, P_SH_BYTES, P_SH_STATE,                                                                             // artgpu_sharpening
+       P_TB_PLANES, P_TB_LOW, P_TB_TMP, P_TB_STATE, P_TB_MASK, P_TB_Y,                                                  // artgpu_texture_boost
+       P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
+       P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
+       P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
+       P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
+       P_NSLOTS };
+static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
+int pool_get(artgpu_ctx *ctx, int slot, size_t bytes, float **out);
+int plane_to_pool(artgpu_ctx *ctx, const artgpu_plane *pl, int slot, float **out);
+int pool_to_plane(artgpu_ctx *ctx, const float *src, artgpu_plane *pl);
+
+#ifndef ARTGPU_MAX_TILE_WG
+#define ARTGPU_MAX_TILE_WG 8192
+#endif
+constexpr int MAX_TILE_WORKGROUPS = ARTGPU_MAX_TILE_WG;
+
+int check_async_faults(artgpu_ctx *ctx);
+
+// Host-side milestones of an entry point: the reference's ProgressListener (rtengine.h:165; amaze_demosaic_RT.cc:1567-1580 reports
+// per-tile fractions, the device path reports 0 when the stage's work starts being queued and 1 when the entry point returns) and,
+// with the "roctx" option, a roctx range named after the reference function so that profiles read like the reference's call tree.
+struct StageScope {
+    artgpu_ctx *ctx;
+    const char *name;
+    bool range;
+    typedef int (*push_fn)(const char *);
+    typedef int (*pop_fn)();
+    static push_fn &push();
+    static pop_fn &pop();
+    StageScope(artgpu_ctx *c, const char *n);
+    ~StageScope();
+};
+
+// ---------------------------------------------------------------------------------------------
+// raw CA correction
+// ---------------------------------------------------------------------------------------------
+bool ca_cfa(uint32_t filters, unsigned *cfa);
+int ca_correct_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, unsigned cfa, const artgpu_ca_params *p, double *fit_out);
+
+// ---------------------------------------------------------------------------------------------
+// local contrast
+// ---------------------------------------------------------------------------------------------
+int local_contrast_check(artgpu_ctx *ctx, int w, int h, const artgpu_local_contrast_region *regions, int nregions, double scale, const char *who);
+int local_contrast_dev(artgpu_ctx *ctx, float *L, size_t stride, int w, int h, const artgpu_local_contrast_region *regions, int nregions,
+                       artgpu_local_contrast_info *info);
+
+// ---------------------------------------------------------------------------------------------
+// dehaze
+// ---------------------------------------------------------------------------------------------
+// the sizes the call derives from W, H and scale before it touches anything
+struct DehazePlan {
+    int ww, hh, brad;              // thumbnail, subtract_black's blur radius (L254-257, L268)
+    int w1, h1, rad1;              // extract_channels' statistics grid and box radius
+    int patch, npx, npy;           // L396
+    int w2, h2, rad2;              // the transmission map's guided filter (L438-445)
+};
+int dehaze_check(artgpu_ctx *ctx, int W, int H, const artgpu_dehaze_params *p, const double *ws, double scale, const char *who, DehazePlan *pl);
+int dehaze_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_dehaze_params *p, const double ws[9],
+               const DehazePlan &pl, artgpu_dehaze_info *info);
+
+// ---------------------------------------------------------------------------------------------
+// texture boost
+// ---------------------------------------------------------------------------------------------
+// what one texture_boost call derives from its region, the plane's size and scale before it touches anything (iptextureboost.cc:39-63)
+struct TbPlan {
+    int radius, isguided, rescaled, w, h, K;       // w x h: the size the call works at; K: the gaussian's size (0 when guided)
+    float strength, strength2;
+    float coef[TB_MAX_K * TB_MAX_K];
+    int w1, h1, rad1;                              // guidedFilter(mid, mid, mid, radius, 0.001f)'s statistics grid and box radius (guided only)
+    int w2, h2, rad2;                              // guidedFilter(mid, mid, base, radius * 4, 0.0001f)'s
+};
+int tb_check(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_region *regions, int nregions, const double *ws, double scale, int high_detail,
+             const char *who, std::vector<TbPlan> *plans);
+int texture_boost_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_texture_boost_region *regions, int nregions,
+                      const double ws[9], const std::vector<TbPlan> &plans, int to_rgb, artgpu_texture_boost_info *info, int already_yuv = 0);
+
+// ---------------------------------------------------------------------------------------------
+// region masks
+// ---------------------------------------------------------------------------------------------
+struct MkRegionPlan {
+    MkCurve curve[3];                 // offsets inside the region's own table
+    std::vector<double> tab;
+    float ldetail;
+    int blurred, r1, r2;
+    int cthr, cthr_neg, cw, ch; float cthr_thresh, cthr_blur;
+    float post_p; int smooth, smooth_r; float fillval;
+    int inverted, has_opacity; float opacity;
+};
+struct MkPlan {
+    int W, H, lab, want_L, want_ab, has_mask, need_ll, need_guide, ll_r_small, ll_r;
+    std::vector<MkRegionPlan> reg;
+};
+int mk_plan(artgpu_ctx *ctx, int W, int H, int mode, const double *ws, const artgpu_mask_params *masks, int n, int full_w, int full_h, double scale,
+            bool want_L, bool want_ab, const char *who, MkPlan *pl, artgpu_masks_info *info);
+int masks_dev(artgpu_ctx *ctx, float *const img[3], size_t stride, const double *ws, const artgpu_mask_params *masks, const MkPlan &pl,
+              float *Lout, float *about);
+
+// ---------------------------------------------------------------------------------------------
+// colour correction
+// ---------------------------------------------------------------------------------------------
+// what a call derives on the host before it touches anything (L88-141, L280-414), and every reason not to run
+struct CcPlan { std::vector<CcRegion> regs; float ws[9], iws[9], fR, fG, fB; bool any_jz; };
+int cc_check(artgpu_ctx *ctx, int W, int H, const artgpu_color_correction_region *regions, int nregions, const double *ws, const double *iws, bool read_masks,
+             const char *who, CcPlan *pl);
+int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_color_correction_region *regions,
+                         const CcPlan &pl, int from_yuv, int to_rgb, artgpu_color_correction_info *info);
+
+// ---------------------------------------------------------------------------------------------
+// smoothing
+// ---------------------------------------------------------------------------------------------
+// what a call derives per region on the host before any kernel writes the image (ipsmoothing.cc:943-980, L348, L1040)
+struct SmRegionPlan {
+    int mode, channel, iterations, r, nlstrength, nldetail;
+    float epsilon;
+    int x0, y0, x1, y1, cropped, ww, hh;       // the box (max exclusive) and the working size
+    int sub, w, h, rad;                        // GUIDED: subsampling, statistics grid, f_mean's radius
+    int skipped;
+};
+int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regions, int nregions, const double *ws, double scale, bool read_masks, const char *who);
+int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl);
+int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
+                  artgpu_smoothing_info *info, const char *who);
+
+// ---------------------------------------------------------------------------------------------
+// capture sharpening
+// ---------------------------------------------------------------------------------------------
+// the stage's full-size planes in pool slot P_SH_PLANES; SHP_EST_A .. SHP_GTMP are what one deconvolution works in
+enum { SHP_Y = 0, SHP_BLEND, SHP_YY, SHP_EST_A, SHP_EST_B, SHP_RATIO, SHP_OUT, SHP_GTMP, SHP_YY2, SHP_NPLANES };
+// what the call derives from its parameters before it touches anything
+struct SharpenPlan {
+    int early;                     // artgpu_sharpening_info::early_out of doSharpening's own tests (L717)
+    float contrast, blur_radius, amount, delta;
+    double sigma;
+    int boost;
+};
+int sharpen_check(artgpu_ctx *ctx, int W, int H, const artgpu_sharpening_params *p, double scale, const char *who, SharpenPlan *pl);
+int sharpen_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_sharpening_params *p, const double ws[9],
+                const SharpenPlan &pl, artgpu_sharpening_info *info);
+int plane_into(artgpu_ctx *ctx, const artgpu_plane *pl, float *dst);
+int auto_radius_dev(artgpu_ctx *ctx, const float *raw, size_t stride, int W, int H, uint32_t filters, float lower, float upper, float **result);
+float auto_radius_of(float maxRatio);
+
+// ---------------------------------------------------------------------------------------------
+// api_pipeline.hip: what io_frame (api_batch.hip) takes from the frame driver
+// ---------------------------------------------------------------------------------------------
+bool pipeline_ca(const artgpu_pipeline_params *p);
+int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, const artgpu_pipeline_params *p);
+int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca);
+
+} } // namespace artgpu::api

@@ -1,148 +1,12 @@
-// art_amd/csrc/artgpu_api.hip -- the C ABI of libartgpu.so (include/artgpu.h): context,
+// art_amd/csrc/artgpu_api.hip -- the C ABI of libartgpu.so (include/artgpu.h) but for the frame driver and the batch lanes: context,
 // device buffers, staging for host-pointer calls, kernel launches, error reporting.
 // There is no CPU fallback here: every entry point either runs the HIP kernels or fails.
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <cmath>
-#include <cstdio>
-#include <cstdarg>
-#include <cstring>
-#include <new>
-#include <string>
-#include <thread>
-#include <vector>
-#include <algorithm>
-
-#include "../../include/artgpu.h"
-#include "kernels.h"
-#include "dehaze.h"
-#include "textureboost.h"
-#include "colorcorrection.h"
-#include "smoothing.h"
-#include "masks.h"
-#include "sharpen.h"
+#include "api_internal.h"
 
 using namespace artgpu;
+using namespace artgpu::api;
 
-struct artgpu_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t aux = nullptr;      // second stream (serial statistics of the AUTOMATIC chroma estimation run beside the decompositions)
-    hipEvent_t aux_ev[2] = {nullptr, nullptr};
-    // RGB_denoise: the DCT detail recovery of L runs on a side stream beside the chroma blurs / reconstructions
-    hipStream_t dn_stream[1] = {nullptr};
-    hipEvent_t dn_ev[2] = {nullptr, nullptr};
-    const float *gam_tab = nullptr; float gam_key[6] = {};   // RGB_denoise's gamma / inverse-gamma tables in pool[P_GAM]: what they were built from
-    // What a batch lane inherits from its parent context (batch_prepare_lanes copies the block as one value on every batch call).  A field
-    // belongs here exactly if a frame's result or its reporting must not depend on which lane ran it.  (cu_reserve is not one: io_frame sets it
-    // per lane; the *_own storage the pipe_* pointers point into stays with the parent.)
-    struct Shared {
-        // options (artgpu_set_option): test / profiling switches that used to be environment variables
-        int opt_sharpen_fused = 1;     // RL deconvolution, stencil regimes -- 1: one kernel per iteration (rl_iter_kernel); 0: DIV, MULT and check_stop as three launches (timing)
-        int opt_lut_lds = 1;           // 0: never the LUT-in-LDS shapes of the pixel passes (tests compare the two)
-        int opt_dn_streams = 0;        // 1: the DCT detail recovery of L on a side stream beside the reconstructions of a and b.  The default until round 5, when the
-                                       // stage waited on LDS round trips and left the chip half idle; since detail_blocks_kernel lost a fifth of its time (detail.hip) the
-                                       // two chains only get in each other's way: one kernel after the other is 0.1 - 0.15 ms per 45 MP frame faster (scripts/r5_ab9.sh)
-        int opt_dn_fused = 1;          // ShrinkAllL / ShrinkAllAB -- 0: three kernels per channel (factors, row sums, column sums + update); 2: one kernel per
-                                       // channel; 1: one kernel, and one launch for all three channels where nothing has to happen between them
-        int opt_dn_detail_plain = 0;   // DCT detail recovery -- 0: trimmed kernels; 1: the kernels before them (what the tests compare against);
-                                       // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
-        int opt_dn_mad_fold = 1;       // MadRgb -- 1: from the bins the analysis kernels count while they write the bands; 0: launch_mad's pass over the bands
-        int opt_dn_mad_fold_grid = 0;  // > 0: the counting analysis kernels with at most this many workgroups (tests: many steps per workgroup; timing of the grid cap)
-        int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
-        long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
-        int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
-                                       // hipMemcpy; -1 (default): 8 with two lanes, 0 otherwise (io_frame has the measurements)
-        int opt_amaze_path = 0;        // 0: LDS streaming kernel for full tiles + arena kernel for the rest; 1: arena kernel for every tile
-        int opt_amaze_split = 0;       // 1 (with path 1): one launch per phase
-        long opt_amaze_zero_mask = 0x81f0;
-        int opt_amaze_zero_frame = 16;
-        int opt_amaze_poison = -1;     // >= 0: byte pattern the arenas are filled with before the launch
-        int opt_roctx = 0;             // 1: roctx ranges named after the reference functions around the entry points (rocprofv3 --marker-trace)
-        int opt_amaze_overlap = 1;     // 0: the arena kernel's static tiles behind the stream kernel instead of beside it
-        int opt_amaze_grid = 0;        // > 0: at most this many stream workgroups (each owns a CU): with several frames in flight the CUs left over
-                                       // take the other frames' bandwidth-bound passes while this frame's issue-bound demosaic runs
-        int opt_rcd_rows = 8;          // rows per iteration of the streaming kernel (4 or 8)
-        int curve_tail_kind = ARTGPU_CURVE_TAIL_HOST;   // artgpu_set_curve_tail
-        double curve_tail_y = 1.0;
-        ParamCurve curve_tail_pc = {};
-        artgpu_progress_fn progress_fn = nullptr;   // artgpu_set_progress_callback
-        void *progress_user = nullptr;
-        // artgpu_set_pipeline_masks / _color_correction / _smoothing: what the pipe reads (the parent's pipe_*_own hold the memory)
-        const artgpu_mask_params *pipe_lc = nullptr, *pipe_tb = nullptr;
-        int pipe_nlc = 0, pipe_ntb = 0;
-        const artgpu_color_correction_region *pipe_cc = nullptr;
-        const artgpu_mask_params *pipe_cc_masks = nullptr;
-        int pipe_ncc = 0;
-        const artgpu_smoothing_region *pipe_sm = nullptr;
-        const artgpu_mask_params *pipe_sm_masks = nullptr;
-        int pipe_nsm = 0;
-    } shared;
-    float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
-    hipEvent_t sh_ev = nullptr;
-    // artgpu_set_pipeline_masks: deep copies (entries, curves, area descriptors); batch lanes point at their parent's
-    struct PipeMasks { std::vector<artgpu_mask_params> m; std::vector<std::vector<double>> curves; std::vector<artgpu_plane> areas; } pipe_lc_own, pipe_tb_own;
-    // artgpu_set_pipeline_color_correction / artgpu_set_pipeline_smoothing: the regions, their mask planes' descriptors and the mask parameters
-    template <typename Region> struct PipeRegions { std::vector<Region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; };
-    PipeRegions<artgpu_color_correction_region> pipe_cc_own;
-    PipeRegions<artgpu_smoothing_region> pipe_sm_own;
-    std::string err;
-    int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
-    long long batch_px = 0;       // artgpu_batch_run: pixels of the largest frame this context's scratch was grown for since the last trim
-    // RGB_denoise's last call: the fold's flag block (96 words in the P_MAD slot behind the 96 medians) and which of its words the call's launch_mad_fold launches wrote (first, count)
-    const int *dn_fold_flags = nullptr; int dn_fold_ranges[8][2] = {}; int dn_fold_nranges = 0;
-    int dn_form = -1, dn_form_streak = 0;   // RGB_denoise: the shrink passes' form of the last call (1 fused / 0 three kernels) and how many calls in a row used it
-    // per-workgroup work arenas (demosaic)
-    float *arena = nullptr;
-    size_t arena_bytes = 0;
-    // staging for host-pointer calls: one CFA plane + three output planes
-    static constexpr int NSTAGE = 8;
-    float *stage[NSTAGE] = {};
-    size_t stage_bytes[NSTAGE] = {};
-    // grow-only scratch pool for the denoise path (planes, decompositions, shrink buffers)
-    static constexpr int NPOOL = 96;
-    float *pool[NPOOL] = {};
-    size_t pool_bytes[NPOOL] = {};
-    // artgpu_batch_run lanes: sibling contexts (own stream, arena, pools) that take every lanes-th frame on their own host thread
-    std::vector<artgpu_ctx *> lanes;
-    int batch_lanes = 1;
-    int frames_in_flight = 1;      // set by artgpu_batch_run on itself and its lanes while a batch with L > 1 lanes runs: the demosaic then takes 5/8 of the CUs (option amaze_grid)
-    bool owns_stream = false;
-    // artgpu_batch_run_io: a frame's upload and download run on streams of their own beside the kernels on `stream`.  Events, by staging slot
-    // (the parity of the frame's turn on this lane): [0,1] uploaded, [2,3] the upload slot has been read, [4,5] scanlines written, [6,7] downloaded
-    hipStream_t io_up = nullptr, io_down = nullptr;
-    hipEvent_t io_ev[8] = {};
-    int *io_host = nullptr;        // pinned, 8 words per frame of the lane: channel maxima (bit patterns) x 3, -, rgb2out's count of unsupported values
-    int io_host_cap = 0;
-    int cu_reserve = 0;            // set around a batch whose downloads run as a kernel of a few workgroups: the persistent one-workgroup-per-CU pixel passes leave those CUs alone
-    // (what artgpu_improc_denoise_fused fuses into the denoise tool's pixel passes is not state of the context: it travels as a DnFusion argument)
-    float *bbox = nullptr; // AMaZE: per-tile nyquist bounding boxes
-    size_t bbox_bytes = 0;
-    // AMaZE v2: tile lists on the device (ints).  [stream tiles | arena-tile template: count, tiles | working copy: count, tiles + room
-    // for every streamed tile the stream kernel hands back]
-    float *amz_lists = nullptr;
-    size_t amz_lists_bytes = 0;
-    int amz_w = 0, amz_h = 0, amz_nstream = 0, amz_narena = 0, amz_mode = -1;
-    int num_cus = 0;
-    hipStream_t amz_side = nullptr;
-    hipEvent_t amz_ev[2] = {nullptr, nullptr};
-    int *rcd_counter = nullptr;    // RCD streaming kernel: tile counter
-    float *lut = nullptr; // 65536-entry tone LUT on the device
-    size_t lut_bytes = 0;
-    std::vector<float> lut_host;           // what ctx->lut holds (a curve that comes back unchanged is not uploaded again)
-    std::vector<float> ncurve_host;        // likewise the 501-entry chroma noise curve behind the cachef table
-    char *tab_ring = nullptr;              // pinned staging ring of h2d_table (caller look-up tables)
-    size_t tab_ring_bytes = 0, tab_ring_off = 0;
-    bool tab_ring_busy = false;
-    hipEvent_t tab_ev = nullptr;
-    std::vector<float> rgbcurve_host[3];   // likewise the three rgbCurves tables (P_RGBCURVES: a slot nothing else writes)
-    // timing
-    bool timing = false;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    artgpu_timings last = {0.f, 0.f, 0.f};
-};
-
-namespace {
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
 
 int fail(artgpu_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -165,23 +29,6 @@ int fail(artgpu_ctx *ctx, int code, const char *fmt, ...)
     }
     return code;
 }
-
-#define HIPCHK(ctx, call)                                                                        \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(ctx, ARTGPU_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-// A call that puts work on a side stream has to leave with the context's stream behind that work on EVERY path: an error return in between
-// would otherwise leave the side stream running on pool buffers the next call hands out again.  Armed when the fork happens, disarmed by the
-// regular join (an event wait, no host blocking); on any other exit the destructor drains the side stream.
-struct SideStreamJoin {
-    hipStream_t side = nullptr;
-    void arm(hipStream_t s) { side = s; }
-    void disarm() { side = nullptr; }
-    ~SideStreamJoin() { if (side) (void)hipStreamSynchronize(side); }
-};
 
 int ensure(artgpu_ctx *ctx, float **buf, size_t *cur, size_t need)
 {
@@ -236,12 +83,6 @@ bool plane_ok(const artgpu_plane *p)
     return p && p->p && p->w > 0 && p->h > 0 && p->row_stride_bytes >= (int64_t)p->w * 4 && (p->row_stride_bytes % 4) == 0;
 }
 
-struct DevImage {
-    const float *raw; size_t raw_stride;
-    float *r, *g, *b; size_t out_stride;
-    bool staged;
-};
-
 // Resolve device pointers for (raw, out); host planes are staged through ctx buffers.
 int bind_images(artgpu_ctx *ctx, const artgpu_plane *raw, artgpu_rgb *out, DevImage *d)
 {
@@ -290,6 +131,9 @@ int unbind_images(artgpu_ctx *ctx, artgpu_rgb *out, const DevImage *d)
     return ARTGPU_OK;
 }
 
+} } // namespace artgpu::api
+
+namespace {
 int launch_border(artgpu_ctx *ctx, const DevImage &d, int W, int H, unsigned filters, int bord)
 {
     if (bord <= 0) return ARTGPU_OK;
@@ -303,16 +147,9 @@ int launch_border(artgpu_ctx *ctx, const DevImage &d, int W, int H, unsigned fil
     HIPCHK(ctx, launch_border_interpolate2(b, grid, ctx->stream));
     return ARTGPU_OK;
 }
+} // namespace
 
-
-// Generic RGB image binding: device planes are used in place, host planes are staged through
-// ctx->stage[slot..slot+2] (copy_in: H2D now; the D2H happens in unbind_rgb).
-struct DevRGB {
-    float *p[3];
-    size_t stride; // floats
-    int w, h;
-    bool staged;
-};
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
 
 // descriptors of device memory: one dense w x h plane; three planes with rows of `stride` floats
 artgpu_plane mk_dev_plane(float *p, int w, int h) { return artgpu_plane{p, w, h, (int64_t)w * 4, 1}; }
@@ -362,12 +199,71 @@ int unbind_rgb(artgpu_ctx *ctx, artgpu_rgb *img, const DevRGB *d)
     return ARTGPU_OK;
 }
 
-#ifndef ARTGPU_MAX_TILE_WG
-#define ARTGPU_MAX_TILE_WG 8192
-#endif
-constexpr int MAX_TILE_WORKGROUPS = ARTGPU_MAX_TILE_WG;
+int pool_get(artgpu_ctx *ctx, int slot, size_t bytes, float **out)
+{
+    int rc = ensure(ctx, &ctx->pool[slot], &ctx->pool_bytes[slot], bytes);
+    *out = ctx->pool[slot];
+    return rc;
+}
 
-} // namespace
+// contiguous device working copy of one plane (host planes are staged, strided device planes copied)
+int plane_to_pool(artgpu_ctx *ctx, const artgpu_plane *pl, int slot, float **out)
+{
+    const size_t rowb = (size_t)pl->w * 4;
+    int rc = pool_get(ctx, slot, rowb * pl->h, out);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpy2DAsync(*out, rowb, pl->p, (size_t)pl->row_stride_bytes, rowb, pl->h,
+                                 pl->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    return ARTGPU_OK;
+}
+int pool_to_plane(artgpu_ctx *ctx, const float *src, artgpu_plane *pl)
+{
+    const size_t rowb = (size_t)pl->w * 4;
+    HIPCHK(ctx, hipMemcpy2DAsync(pl->p, (size_t)pl->row_stride_bytes, src, rowb, rowb, pl->h,
+                                 pl->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    if (!pl->on_device) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ARTGPU_OK;
+}
+
+// A kernel that gave up a bounded wait (the fused shrink pass: a strip whose predecessor did not hand down a block within five seconds) says so in
+// pinned host words and runs to its end with wrong coefficients instead of trapping -- a trap aborts the host process inside the runtime.  The
+// library reads the words wherever it has just waited for the stream and turns them into ARTGPU_EHIP with the band / strip / block in
+// artgpu_last_error (fail() appends them); the frame in flight is invalid, the context stays usable.
+int check_async_faults(artgpu_ctx *ctx)
+{
+    if (ctx->fs_diag && (unsigned)ctx->fs_diag[0] == 0xF5D1A600u) return fail(ctx, ARTGPU_EHIP, "a kernel gave up a bounded wait: the results of the calls since the last synchronisation are invalid");
+    return ARTGPU_OK;
+}
+
+StageScope::push_fn &StageScope::push() { static push_fn f = nullptr; return f; }
+StageScope::pop_fn &StageScope::pop() { static pop_fn f = nullptr; return f; }
+StageScope::StageScope(artgpu_ctx *c, const char *n) : ctx(c), name(n), range(false)
+{
+    if (!ctx) return;
+    if (ctx->shared.opt_roctx) {
+        static bool tried = false;
+        if (!tried) {
+            tried = true;
+            void *h = nullptr;
+            for (const char *lib : {"libroctx64.so.4", "libroctx64.so", "/opt/rocm/lib/libroctx64.so"})
+                if ((h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL))) break;
+            if (h) {
+                push() = reinterpret_cast<push_fn>(dlsym(h, "roctxRangePushA"));
+                pop() = reinterpret_cast<pop_fn>(dlsym(h, "roctxRangePop"));
+            }
+        }
+        if (push() && pop()) { push()(name); range = true; }
+    }
+    if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 0.0);
+}
+StageScope::~StageScope()
+{
+    if (!ctx) return;
+    if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 1.0);
+    if (range) pop()();
+}
+
+} } // namespace artgpu::api
 
 extern "C" {
 
@@ -453,16 +349,6 @@ int artgpu_set_stream(artgpu_ctx *ctx, void *hip_stream)
     }
     (void)hipGetLastError();
     ctx->stream = next;
-    return ARTGPU_OK;
-}
-
-// A kernel that gave up a bounded wait (the fused shrink pass: a strip whose predecessor did not hand down a block within five seconds) says so in
-// pinned host words and runs to its end with wrong coefficients instead of trapping -- a trap aborts the host process inside the runtime.  The
-// library reads the words wherever it has just waited for the stream and turns them into ARTGPU_EHIP with the band / strip / block in
-// artgpu_last_error (fail() appends them); the frame in flight is invalid, the context stays usable.
-static int check_async_faults(artgpu_ctx *ctx)
-{
-    if (ctx->fs_diag && (unsigned)ctx->fs_diag[0] == 0xF5D1A600u) return fail(ctx, ARTGPU_EHIP, "a kernel gave up a bounded wait: the results of the calls since the last synchronisation are invalid");
     return ARTGPU_OK;
 }
 
@@ -626,44 +512,6 @@ int artgpu_trim_scratch(artgpu_ctx *ctx)
     for (artgpu_ctx *l : ctx->lanes) { const int r = artgpu_trim_scratch(l); if (r && !rc) rc = r; }
     return rc;
 }
-
-// Host-side milestones of an entry point: the reference's ProgressListener (rtengine.h:165; amaze_demosaic_RT.cc:1567-1580 reports
-// per-tile fractions, the device path reports 0 when the stage's work starts being queued and 1 when the entry point returns) and,
-// with the "roctx" option, a roctx range named after the reference function so that profiles read like the reference's call tree.
-struct StageScope {
-    artgpu_ctx *ctx;
-    const char *name;
-    bool range;
-    typedef int (*push_fn)(const char *);
-    typedef int (*pop_fn)();
-    static push_fn &push() { static push_fn f = nullptr; return f; }
-    static pop_fn &pop() { static pop_fn f = nullptr; return f; }
-    StageScope(artgpu_ctx *c, const char *n) : ctx(c), name(n), range(false)
-    {
-        if (!ctx) return;
-        if (ctx->shared.opt_roctx) {
-            static bool tried = false;
-            if (!tried) {
-                tried = true;
-                void *h = nullptr;
-                for (const char *lib : {"libroctx64.so.4", "libroctx64.so", "/opt/rocm/lib/libroctx64.so"})
-                    if ((h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL))) break;
-                if (h) {
-                    push() = reinterpret_cast<push_fn>(dlsym(h, "roctxRangePushA"));
-                    pop() = reinterpret_cast<pop_fn>(dlsym(h, "roctxRangePop"));
-                }
-            }
-            if (push() && pop()) { push()(name); range = true; }
-        }
-        if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 0.0);
-    }
-    ~StageScope()
-    {
-        if (!ctx) return;
-        if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 1.0);
-        if (range) pop()();
-    }
-};
 
 struct DualReq { double *contrast; int auto_contrast; int second; };
 static int vng4_dev(artgpu_ctx *ctx, const float *raw, size_t raw_stride, float *r, float *g, float *b, size_t out_stride, int W, int H, uint32_t filters);
@@ -1190,20 +1038,6 @@ int artgpu_wavelet_free(artgpu_ctx *ctx, artgpu_wavelet *wv)
 
 namespace {
 
-enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1, P_SF, P_TMP, P_HISTO, P_MAD, P_GAM, P_CCALC, P_LIN, P_BLOCKS, P_DTAB, P_CCMAP, P_CACHEF, P_PQ, P_XCBRT, P_GAUSS64, P_DMASK, P_LABTABS, P_PIPE_R, P_PIPE_G, P_PIPE_B, P_DNINFO, P_BATCH, P_DCTTAB, P_CBANDS2, P_CLOW0_2, P_CLOW1_2, P_SF_A, P_SF_B, P_HISTO_A, P_HISTO_B, P_RGBCURVES, P_FUSED, P_LBANDS2,
-       P_IO_IN0, P_IO_IN1, P_IO_CFA, P_IO_IMG0, P_IO_IMG1, P_IO_IMG2, P_IO_IMG3, P_IO_IMG4, P_IO_IMG5, P_IO_OUT0, P_IO_OUT1, P_IO_FLAGS,      // artgpu_batch_run_io: staging slots, the CFA plane, the working image, the frames' flag words
-       P_CA_HALF, P_CA_BLK, P_CA_GUARD, P_CA_RAW,                                                                       // artgpu_raw_ca_correct
-       P_LC_BANDS, P_LC_LOW0, P_LC_LOW1, P_LC_NEW, P_LC_STATS, P_LC_MASK, P_LC_L,                                       // artgpu_local_contrast
-       P_DH_STATE, P_DH_THUMB, P_DH_LOW, P_DH_TMP, P_DH_T, P_DH_DARK,                                                   // artgpu_dehaze
-       P_SH_PLANES, P_SH_BYTES, P_SH_STATE,                                                                             // artgpu_sharpening
-       P_TB_PLANES, P_TB_LOW, P_TB_TMP, P_TB_STATE, P_TB_MASK, P_TB_Y,                                                  // artgpu_texture_boost
-       P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
-       P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
-       P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
-       P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
-       P_NSLOTS };
-static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
-
 struct DevDecomp {
     float *bands, *low[2];
     int cur, nlevels, w, h, w2, h2;
@@ -1254,21 +1088,14 @@ int reconstruct_dev(artgpu_ctx *ctx, DevDecomp &d, float *dst, hipStream_t st = 
     return ARTGPU_OK;
 }
 
-int pool_get(artgpu_ctx *ctx, int slot, size_t bytes, float **out)
-{
-    int rc = ensure(ctx, &ctx->pool[slot], &ctx->pool_bytes[slot], bytes);
-    *out = ctx->pool[slot];
-    return rc;
-}
-
 } // namespace
-
-extern "C" {
 
 namespace {
 int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float *mask, int W, int H,
                     float scaling, float threshold, float ceiling, float factor, float blur, float *scratch);
 }
+
+extern "C" {
 
 int artgpu_wavelet_mad(artgpu_ctx *ctx, const artgpu_wavelet *wv, float *mad_sqr)
 {
@@ -1953,6 +1780,7 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
 // ---------------------------------------------------------------------------------------------
 // guided chroma smoothing
 // ---------------------------------------------------------------------------------------------
+} // extern "C"
 namespace {
 int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter.cc:58-75)
 {
@@ -1964,6 +1792,7 @@ int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter
     return t < 2 ? 2 : (t > 4 ? 4 : t);
 }
 }
+extern "C" {
 
 int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const double ws[9], int guided_chroma_radius, double scale)
 {
@@ -2347,6 +2176,7 @@ int artgpu_hsl_equalizer(artgpu_ctx *ctx, artgpu_rgb *img, const double *hcurve,
 // ---------------------------------------------------------------------------------------------
 // gaussian blur, detail mask, NL-means
 // ---------------------------------------------------------------------------------------------
+} // extern "C"
 namespace {
 
 // calculateYvVFactors<double> + M rescaling (gauss.cc:94-126,556-562)
@@ -2382,25 +2212,6 @@ void yvv_factors(double sigma, GaussArgs &g, bool double_path = false)
     }
     g.b[0] = b1; g.b[1] = b2; g.b[2] = b3;
     g.Bf = (float)g.B; g.bf[0] = (float)b1; g.bf[1] = (float)b2; g.bf[2] = (float)b3;
-}
-
-// contiguous device working copy of one plane (host planes are staged, strided device planes copied)
-int plane_to_pool(artgpu_ctx *ctx, const artgpu_plane *pl, int slot, float **out)
-{
-    const size_t rowb = (size_t)pl->w * 4;
-    int rc = pool_get(ctx, slot, rowb * pl->h, out);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(*out, rowb, pl->p, (size_t)pl->row_stride_bytes, rowb, pl->h,
-                                 pl->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    return ARTGPU_OK;
-}
-int pool_to_plane(artgpu_ctx *ctx, const float *src, artgpu_plane *pl)
-{
-    const size_t rowb = (size_t)pl->w * 4;
-    HIPCHK(ctx, hipMemcpy2DAsync(pl->p, (size_t)pl->row_stride_bytes, src, rowb, rowb, pl->h,
-                                 pl->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    if (!pl->on_device) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ARTGPU_OK;
 }
 
 int gaussian_dev(artgpu_ctx *ctx, float *img, float *tmp, int W, int H, double sigma)
@@ -2444,6 +2255,7 @@ int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float 
 }
 
 } // namespace
+extern "C" {
 
 int artgpu_gaussian_blur(artgpu_ctx *ctx, artgpu_plane *img, double sigma)
 {
@@ -2475,6 +2287,7 @@ int artgpu_detail_mask(artgpu_ctx *ctx, const artgpu_plane *src, artgpu_plane *m
     return pool_to_plane(ctx, m, mask);
 }
 
+} // extern "C"
 namespace {
 // denoise::NLMeans (nlmeans.cc:44-320) on a contiguous device plane (rows of W floats), in place; enqueued on ctx->stream.  The caller has checked
 // strength != 0, W, H >= 32, (W + 14) * (H + 14) < 2^30 and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
@@ -2503,6 +2316,7 @@ int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, i
     return ARTGPU_OK;
 }
 } // namespace
+extern "C" {
 
 int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int strength, int detail_thresh, float scale)
 {
@@ -2638,7 +2452,9 @@ int artgpu_demosaic_xtrans(artgpu_ctx *ctx, int passes, int use_cielab, const ar
 // ---------------------------------------------------------------------------------------------
 // NEUTRAL tone curve
 // ---------------------------------------------------------------------------------------------
+} // extern "C"
 namespace { int pq_tables_dev(artgpu_ctx *ctx, float **out); }       // (defined with the colour correction, its other user)
+extern "C" {
 int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *lut65536, float whitecoeff, const artgpu_neutral_state *st)
 {
     StageScope scope_(ctx, "ImProcFunctions::toneCurve (NEUTRAL)");
@@ -3238,10 +3054,13 @@ int artgpu_scale_colors(artgpu_ctx *ctx, const void *src, int32_t w, int32_t h, 
     return ARTGPU_OK;
 }
 
-namespace {
+} // extern "C"
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
 // Bayer 2x2 colour map of `filters` for the CA correction: FC packed as CaArgs::cfa; false for X-Trans, a fourth colour or a
 // pattern without one green per row and column
-static bool ca_cfa(uint32_t filters, unsigned *cfa)
+bool ca_cfa(uint32_t filters, unsigned *cfa)
 {
     if (filters == 9) return false;
     unsigned f[2][2], packed = 0;
@@ -3258,7 +3077,7 @@ static bool ca_cfa(uint32_t filters, unsigned *cfa)
 }
 
 // CA_correct_RT on a contiguous-or-strided device CFA plane, enqueued on ctx->stream (no synchronisation unless fit_out)
-static int ca_correct_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, unsigned cfa, const artgpu_ca_params *p, double *fit_out)
+int ca_correct_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, unsigned cfa, const artgpu_ca_params *p, double *fit_out)
 {
     constexpr int ts = 128, border2 = 16, cb = 2;
     CaArgs a = {};
@@ -3309,7 +3128,10 @@ static int ca_correct_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int
     }
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_raw_ca_correct(artgpu_ctx *ctx, artgpu_plane *raw, uint32_t filters, const artgpu_ca_params *p, double fit_out[64])
 {
@@ -3328,9 +3150,14 @@ int artgpu_raw_ca_correct(artgpu_ctx *ctx, artgpu_plane *raw, uint32_t filters, 
     return pool_to_plane(ctx, work, raw);
 }
 
+} // extern "C"
+
 // ---------------------------------------------------------------------------------------------
 // ImProcFunctions::localContrast
 // ---------------------------------------------------------------------------------------------
+
+extern "C" {
+
 int artgpu_local_contrast_curve_lut(const double *points, int npoints, float lut[501], int *is_set)
 {
     if (!lut || !is_set || npoints < 0 || (npoints > 0 && !points)) return ARTGPU_EINVAL;
@@ -3338,9 +3165,12 @@ int artgpu_local_contrast_curve_lut(const double *points, int npoints, float lut
     return ARTGPU_OK;
 }
 
-namespace {
+} // extern "C"
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
 // what the call cannot do, before anything is touched: 0, or the code with the message set
-static int local_contrast_check(artgpu_ctx *ctx, int w, int h, const artgpu_local_contrast_region *regions, int nregions, double scale, const char *who)
+int local_contrast_check(artgpu_ctx *ctx, int w, int h, const artgpu_local_contrast_region *regions, int nregions, double scale, const char *who)
 {
     if (nregions < 0 || (nregions > 0 && !regions)) return fail(ctx, ARTGPU_EINVAL, "%s: bad region list", who);
     for (int r = 0; r < nregions; ++r) {
@@ -3358,7 +3188,7 @@ static int local_contrast_check(artgpu_ctx *ctx, int w, int h, const artgpu_loca
 
 // the regions of ImProcFunctions::localContrast (L463-481) on a device L plane (rows of `stride` floats), enqueued on ctx->stream; per
 // region the host waits once, for the statistics block it computes the constants of L372-380 from
-static int local_contrast_dev(artgpu_ctx *ctx, float *L, size_t stride, int w, int h, const artgpu_local_contrast_region *regions, int nregions,
+int local_contrast_dev(artgpu_ctx *ctx, float *L, size_t stride, int w, int h, const artgpu_local_contrast_region *regions, int nregions,
                               artgpu_local_contrast_info *info)
 {
     DevDecomp d = {};
@@ -3419,7 +3249,10 @@ static int local_contrast_dev(artgpu_ctx *ctx, float *L, size_t stride, int w, i
     }
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_local_contrast(artgpu_ctx *ctx, artgpu_plane *L, const artgpu_local_contrast_region *regions, int nregions, double scale,
                           artgpu_local_contrast_info *info)
@@ -3438,9 +3271,14 @@ int artgpu_local_contrast(artgpu_ctx *ctx, artgpu_plane *L, const artgpu_local_c
     return pool_to_plane(ctx, work, L);
 }
 
+} // extern "C"
+
 // ---------------------------------------------------------------------------------------------
 // ImProcFunctions::dehaze
 // ---------------------------------------------------------------------------------------------
+
+extern "C" {
+
 int artgpu_dehaze_strength_lut(const double *points, int npoints, float lut[65536])
 {
     if (!lut || npoints < 0 || (npoints > 0 && !points)) return ARTGPU_EINVAL;
@@ -3455,14 +3293,10 @@ int artgpu_dehaze_estimate_ambient(const float *R, const float *G, const float *
     return ARTGPU_OK;
 }
 
+} // extern "C"
+
 namespace {
-// the sizes the call derives from W, H and scale before it touches anything
-struct DehazePlan {
-    int ww, hh, brad;              // thumbnail, subtract_black's blur radius (L254-257, L268)
-    int w1, h1, rad1;              // extract_channels' statistics grid and box radius
-    int patch, npx, npy;           // L396
-    int w2, h2, rad2;              // the transmission map's guided filter (L438-445)
-};
+
 static void dehaze_gf_grid(int W, int H, int r, int *w, int *h, int *rad)
 {
     const int sub = gf_subsampling(W, H, r);
@@ -3471,26 +3305,6 @@ static void dehaze_gf_grid(int W, int H, int r, int *w, int *h, int *rad)
     int q = (int)(float(r) / sub);
     q = q < hi ? q : hi;
     *rad = q > 0 ? q : 0;
-}
-// what the call cannot do, before anything is touched: 0, or the code with the message set
-static int dehaze_check(artgpu_ctx *ctx, int W, int H, const artgpu_dehaze_params *p, const double *ws, double scale, const char *who, DehazePlan *pl)
-{
-    if (!p || !ws || !(scale > 0.0) || p->nstrength < 0 || (p->nstrength > 0 && !p->strength)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
-    dh_thumb_size(W, H, &pl->ww, &pl->hh);
-    const int lo = pl->ww < pl->hh ? pl->ww : pl->hh, hi = pl->ww < pl->hh ? pl->hh : pl->ww;
-    pl->brad = hi / 20 > 1 ? hi / 20 : 1;
-    if (p->blackpoint && lo < 2 * pl->brad + 1)
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: black point on a %dx%d frame: the %dx%d thumbnail is narrower than its box blur (radius %d)", who, W, H, pl->ww, pl->hh, pl->brad);
-    const int r1 = std::max((int)(5 / scale), 2);
-    dehaze_gf_grid(W, H, r1, &pl->w1, &pl->h1, &pl->rad1);
-    pl->patch = std::max(std::max(W, H) / 600, 2);
-    dehaze_gf_grid(W, H, pl->patch * 4, &pl->w2, &pl->h2, &pl->rad2);
-    if (pl->w1 < 1 || pl->h1 < 1 || pl->w2 < 1 || pl->h2 < 1)
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d frame has a side shorter than the guided filter's subsampling", who, W, H);
-    if (pl->patch > DH_MAX_PATCH || pl->rad1 > HBLUR_MAX_RADIUS || pl->rad2 > HBLUR_MAX_RADIUS || pl->brad > HBLUR_MAX_RADIUS)
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d frame is beyond the patch / box radius the kernels hold in LDS", who, W, H);
-    pl->npx = (W + pl->patch - 1) / pl->patch; pl->npy = (H + pl->patch - 1) / pl->patch;
-    return ARTGPU_OK;
 }
 
 // `count` planes of w x h floats, n apart: boxblur(float**, float**, radius, W, H) (boxblur.h:318) in place
@@ -3525,8 +3339,33 @@ static const float *dehaze_strength_cached(const artgpu_dehaze_params *p, std::v
     return out.data();
 }
 
+} // namespace
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+// what the call cannot do, before anything is touched: 0, or the code with the message set
+int dehaze_check(artgpu_ctx *ctx, int W, int H, const artgpu_dehaze_params *p, const double *ws, double scale, const char *who, DehazePlan *pl)
+{
+    if (!p || !ws || !(scale > 0.0) || p->nstrength < 0 || (p->nstrength > 0 && !p->strength)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
+    dh_thumb_size(W, H, &pl->ww, &pl->hh);
+    const int lo = pl->ww < pl->hh ? pl->ww : pl->hh, hi = pl->ww < pl->hh ? pl->hh : pl->ww;
+    pl->brad = hi / 20 > 1 ? hi / 20 : 1;
+    if (p->blackpoint && lo < 2 * pl->brad + 1)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: black point on a %dx%d frame: the %dx%d thumbnail is narrower than its box blur (radius %d)", who, W, H, pl->ww, pl->hh, pl->brad);
+    const int r1 = std::max((int)(5 / scale), 2);
+    dehaze_gf_grid(W, H, r1, &pl->w1, &pl->h1, &pl->rad1);
+    pl->patch = std::max(std::max(W, H) / 600, 2);
+    dehaze_gf_grid(W, H, pl->patch * 4, &pl->w2, &pl->h2, &pl->rad2);
+    if (pl->w1 < 1 || pl->h1 < 1 || pl->w2 < 1 || pl->h2 < 1)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d frame has a side shorter than the guided filter's subsampling", who, W, H);
+    if (pl->patch > DH_MAX_PATCH || pl->rad1 > HBLUR_MAX_RADIUS || pl->rad2 > HBLUR_MAX_RADIUS || pl->brad > HBLUR_MAX_RADIUS)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d frame is beyond the patch / box radius the kernels hold in LDS", who, W, H);
+    pl->npx = (W + pl->patch - 1) / pl->patch; pl->npy = (H + pl->patch - 1) / pl->patch;
+    return ARTGPU_OK;
+}
+
 // ImProcFunctions::dehaze on device planes (rows of `stride` floats), enqueued on ctx->stream; the host waits once, for the thumbnail
-static int dehaze_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_dehaze_params *p, const double ws[9],
+int dehaze_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_dehaze_params *p, const double ws[9],
                const DehazePlan &pl, artgpu_dehaze_info *info)
 {
     DhImage im = {{planes[0], planes[1], planes[2]}, stride, W, H};
@@ -3610,7 +3449,10 @@ static int dehaze_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, in
     HIPCHK(ctx, launch_dh_recover(ra, ctx->stream));
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_dehaze(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_dehaze_params *params, const double ws[9], double scale, artgpu_dehaze_info *info)
 {
@@ -3660,18 +3502,14 @@ int artgpu_dehaze_dark_channel(artgpu_ctx *ctx, const artgpu_rgb *rgb, int patch
     return dst->on_device ? ARTGPU_OK : pool_to_plane(ctx, out, dst);
 }
 
+} // extern "C"
+
 // ---------------------------------------------------------------------------------------------
 // ImProcFunctions::textureBoost
 // ---------------------------------------------------------------------------------------------
+
 namespace {
-// what one texture_boost call derives from its region, the plane's size and scale before it touches anything (iptextureboost.cc:39-63)
-struct TbPlan {
-    int radius, isguided, rescaled, w, h, K;       // w x h: the size the call works at; K: the gaussian's size (0 when guided)
-    float strength, strength2;
-    float coef[TB_MAX_K * TB_MAX_K];
-    int w1, h1, rad1;                              // guidedFilter(mid, mid, mid, radius, 0.001f)'s statistics grid and box radius (guided only)
-    int w2, h2, rad2;                              // guidedFilter(mid, mid, base, radius * 4, 0.0001f)'s
-};
+
 // 0, or the code with the message set
 static int tb_plan(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_region *r, double scale, int high_detail, const char *who, TbPlan *pl)
 {
@@ -3706,23 +3544,6 @@ static int tb_plan(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_reg
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d plane has a side shorter than the guided filter's subsampling", who, pl->w, pl->h);
     if (pl->rad1 > HBLUR_MAX_RADIUS || pl->rad2 > HBLUR_MAX_RADIUS)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: box radius %d is above the %d the blur kernels hold in LDS", who, std::max(pl->rad1, pl->rad2), HBLUR_MAX_RADIUS);
-    return ARTGPU_OK;
-}
-// the region list of the whole tool: a plan per region that runs (strength != 0, L227), in order
-static int tb_check(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_region *regions, int nregions, const double *ws, double scale, int high_detail,
-                    const char *who, std::vector<TbPlan> *plans)
-{
-    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !(scale > 0.0)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
-    plans->clear();
-    for (int r = 0; r < nregions; ++r) {
-        const artgpu_plane *m = regions[r].mask;
-        if (m && (!plane_ok(m) || m->w != W || m->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: the mask of region %d must be a %dx%d plane", who, r, W, H);
-        if (regions[r].strength == 0) continue;
-        TbPlan pl;
-        int rc;
-        if ((rc = tb_plan(ctx, W, H, &regions[r], scale, high_detail, who, &pl))) return rc;
-        plans->push_back(pl);
-    }
     return ARTGPU_OK;
 }
 
@@ -3802,10 +3623,32 @@ static int tb_fill_info(artgpu_ctx *ctx, const TbPlan &pl, const TbState *st, ar
     return ARTGPU_OK;
 }
 
+} // namespace
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+// the region list of the whole tool: a plan per region that runs (strength != 0, L227), in order
+int tb_check(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_region *regions, int nregions, const double *ws, double scale, int high_detail,
+                    const char *who, std::vector<TbPlan> *plans)
+{
+    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !(scale > 0.0)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
+    plans->clear();
+    for (int r = 0; r < nregions; ++r) {
+        const artgpu_plane *m = regions[r].mask;
+        if (m && (!plane_ok(m) || m->w != W || m->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: the mask of region %d must be a %dx%d plane", who, r, W, H);
+        if (regions[r].strength == 0) continue;
+        TbPlan pl;
+        int rc;
+        if ((rc = tb_plan(ctx, W, H, &regions[r], scale, high_detail, who, &pl))) return rc;
+        plans->push_back(pl);
+    }
+    return ARTGPU_OK;
+}
+
 // ImProcFunctions::textureBoost (L198-242) on device planes in RGB mode: setMode(YUV), the regions that run, setMode(RGB) when asked for.
 // already_yuv: the tool ahead (colorCorrection) left the image in YUV mode, where the reference's setMode(YUV) does nothing
-static int texture_boost_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_texture_boost_region *regions, int nregions,
-                             const double ws[9], const std::vector<TbPlan> &plans, int to_rgb, artgpu_texture_boost_info *info, int already_yuv = 0)
+int texture_boost_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_texture_boost_region *regions, int nregions,
+                             const double ws[9], const std::vector<TbPlan> &plans, int to_rgb, artgpu_texture_boost_info *info, int already_yuv)
 {
     PixArgs ya = {};                                                   // Imagefloat::setMode (yuv_mode_kernel: do_clip 0 = to YUV, 1 = to RGB)
     for (int k = 0; k < 3; ++k) { ya.dst[k] = planes[k]; ya.mul[k] = (float)ws[3 + k]; }
@@ -3826,7 +3669,10 @@ static int texture_boost_dev(artgpu_ctx *ctx, float *const planes[3], size_t str
     }
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_texture_boost_plane(artgpu_ctx *ctx, artgpu_plane *Y, const artgpu_texture_boost_region *region, double scale, int high_detail,
                                artgpu_texture_boost_info *info)
@@ -3868,25 +3714,16 @@ int artgpu_texture_boost(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_texture_
     return unbind_rgb(ctx, img, &d);
 }
 
+} // extern "C"
+
 // ---------------------------------------------------------------------------------------------
 // region masks: rtengine::generateMasks, parametric path (masks.cc:1037-1516)
 // ---------------------------------------------------------------------------------------------
+
 namespace {
+
 // one rtengine::guidedFilter call as artgpu_guided_filter will run it: decided in the plan, so that nothing starts before everything fits
 struct MkFilter { int on, r; };
-struct MkRegionPlan {
-    MkCurve curve[3];                 // offsets inside the region's own table
-    std::vector<double> tab;
-    float ldetail;
-    int blurred, r1, r2;
-    int cthr, cthr_neg, cw, ch; float cthr_thresh, cthr_blur;
-    float post_p; int smooth, smooth_r; float fillval;
-    int inverted, has_opacity; float opacity;
-};
-struct MkPlan {
-    int W, H, lab, want_L, want_ab, has_mask, need_ll, need_guide, ll_r_small, ll_r;
-    std::vector<MkRegionPlan> reg;
-};
 
 // ParametricMask's default curves (procparams.cc:1014-1053)
 const double MK_DEFAULT_HUE[9] = {1 /* FCT_MinMaxCPoints */, 0.166666667, 1., 0.35, 0.35, 0.8287775246, 1., 0.35, 0.35};
@@ -3907,6 +3744,10 @@ int mk_filter_check(artgpu_ctx *ctx, int W, int H, int r, const char *who, const
     if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %s: box radius %d (radius %d / subsampling %d) is above the %d the blur kernels hold in LDS", who, what, rad, r, sub, HBLUR_MAX_RADIUS);
     return ARTGPU_OK;
 }
+
+} // namespace
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
 
 // everything generateMasks decides before its first pixel loop, and every reason not to run
 int mk_plan(artgpu_ctx *ctx, int W, int H, int mode, const double *ws, const artgpu_mask_params *masks, int n, int full_w, int full_h, double scale,
@@ -4132,7 +3973,10 @@ int masks_dev(artgpu_ctx *ctx, float *const img[3], size_t stride, const double 
     }
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, const double ws[9], const artgpu_mask_params *masks, int n,
                           int full_w, int full_h, double scale, artgpu_plane *Lmask, artgpu_plane *abmask, artgpu_masks_info *info)
@@ -4162,53 +4006,13 @@ int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, cons
     return ARTGPU_OK;
 }
 
+} // extern "C"
+
 // ---------------------------------------------------------------------------------------------
 // colour correction: ImProcFunctions::colorCorrection (ipcolorcorrection.cc:39-866)
 // ---------------------------------------------------------------------------------------------
-namespace {
-// a deep copy of n mask entries (their curves and the area planes' descriptors) for a setting of the context
-const artgpu_mask_params *own_pipe_masks(artgpu_ctx::PipeMasks &o, const artgpu_mask_params *src, int n)
-{
-    o.m.assign(src, src + n);
-    o.curves.assign((size_t)3 * n, std::vector<double>());
-    o.areas.assign(n, artgpu_plane{});
-    for (int i = 0; i < n; ++i) {
-        artgpu_mask_params &m = o.m[i];
-        const double **pts[3] = {&m.hue, &m.chromaticity, &m.lightness};
-        int32_t *cnt[3] = {&m.nhue, &m.nchromaticity, &m.nlightness};
-        for (int k = 0; k < 3; ++k) {
-            if (*cnt[k] < 0) *cnt[k] = 0;
-            if (*pts[k] && *cnt[k] > 0) o.curves[3 * i + k].assign(*pts[k], *pts[k] + *cnt[k]);
-            *pts[k] = o.curves[3 * i + k].empty() ? nullptr : o.curves[3 * i + k].data();
-            if (!*pts[k]) *cnt[k] = 0;
-        }
-        if (m.area) { o.areas[i] = *m.area; m.area = &o.areas[i]; }
-    }
-    return n > 0 ? o.m.data() : nullptr;
-}
 
-// what artgpu_set_pipeline_color_correction and artgpu_set_pipeline_smoothing share: the regions are copied, the descriptors of their mask
-// planes (the members `fields` names) too -- the planes' memory stays the caller's --, the mask entries are owned or reset, and the pipe's
-// view of the setting (regions, entries, count) is written
-extern "C++" {
-template <typename Region>
-void own_pipe_regions(artgpu_ctx::PipeRegions<Region> &o, const Region *regions, int n, std::initializer_list<const artgpu_plane *Region::*> fields,
-                      const artgpu_mask_params *masks, const Region **regs, const artgpu_mask_params **entries, int *count)
-{
-    o.regs.assign(regions, regions + n);
-    o.planes.assign(fields.size() * n, artgpu_plane{});
-    artgpu_plane *next = o.planes.data();
-    for (Region &r : o.regs)
-        for (const auto f : fields) {
-            if (r.*f) { *next = *(r.*f); r.*f = next; }
-            ++next;
-        }
-    *entries = masks ? own_pipe_masks(o.masks, masks, n) : nullptr;
-    if (!masks) o.masks = artgpu_ctx::PipeMasks{};
-    *regs = n > 0 ? o.regs.data() : nullptr;
-    *count = n;
-}
-} // extern "C++"
+namespace {
 
 // the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)
 int pq_tables_dev(artgpu_ctx *ctx, float **out)
@@ -4230,9 +4034,11 @@ int pq_tables_dev(artgpu_ctx *ctx, float **out)
     return ARTGPU_OK;
 }
 
-// what a call derives on the host before it touches anything (L88-141, L280-414), and every reason not to run
-struct CcPlan { std::vector<CcRegion> regs; float ws[9], iws[9], fR, fG, fB; bool any_jz; };
-static int cc_check(artgpu_ctx *ctx, int W, int H, const artgpu_color_correction_region *regions, int nregions, const double *ws, const double *iws, bool read_masks,
+} // namespace
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+int cc_check(artgpu_ctx *ctx, int W, int H, const artgpu_color_correction_region *regions, int nregions, const double *ws, const double *iws, bool read_masks,
              const char *who, CcPlan *pl)
 {
     if (nregions < 0 || (nregions > 0 && !regions) || !ws || !iws) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
@@ -4264,7 +4070,7 @@ static int cc_check(artgpu_ctx *ctx, int W, int H, const artgpu_color_correction
 }
 
 // the tool on device planes (rows of `stride` floats) in RGB mode, or in YUV mode with `from_yuv`; enqueued on ctx->stream, one host wait with `info`
-static int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_color_correction_region *regions,
+int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_color_correction_region *regions,
                          const CcPlan &pl, int from_yuv, int to_rgb, artgpu_color_correction_info *info)
 {
     const int n = (int)pl.regs.size();
@@ -4344,7 +4150,10 @@ static int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t 
     }
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
                             const double iws[9], int to_rgb, artgpu_color_correction_info *info)
@@ -4362,81 +4171,13 @@ int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color
     return unbind_rgb(ctx, img, &d);
 }
 
-int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_correction_region *regions, int n, const artgpu_mask_params *masks)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_color_correction: bad arguments");
-    own_pipe_regions(ctx->pipe_cc_own, regions, n, {&artgpu_color_correction_region::lmask, &artgpu_color_correction_region::abmask}, masks,
-                     &ctx->shared.pipe_cc, &ctx->shared.pipe_cc_masks, &ctx->shared.pipe_ncc);
-    return ARTGPU_OK;
-}
+} // extern "C"
 
 // ---------------------------------------------------------------------------------------------
 // smoothing: ImProcFunctions::guidedSmoothing, modes GUIDED and NLMEANS
 // ---------------------------------------------------------------------------------------------
+
 namespace {
-// what a call derives per region on the host before any kernel writes the image (ipsmoothing.cc:943-980, L348, L1040)
-struct SmRegionPlan {
-    int mode, channel, iterations, r, nlstrength, nldetail;
-    float epsilon;
-    int x0, y0, x1, y1, cropped, ww, hh;       // the box (max exclusive) and the working size
-    int sub, w, h, rad;                        // GUIDED: subsampling, statistics grid, f_mean's radius
-    int skipped;
-};
-
-// everything that does not depend on a mask's box: what the pipe checks before any stage runs
-int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regions, int nregions, const double *ws, double scale, bool read_masks, const char *who)
-{
-    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !(scale > 0.0) || std::isinf(scale)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
-    for (int i = 0; i < nregions; ++i) {
-        const artgpu_smoothing_region &r = regions[i];
-        if (r.mode < ARTGPU_SMOOTHING_GUIDED || r.mode > ARTGPU_SMOOTHING_WAVELETS) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: mode %d", who, i, r.mode);
-        if (r.channel < ARTGPU_SMOOTHING_LUMINANCE || r.channel > ARTGPU_SMOOTHING_RGB) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: channel %d", who, i, r.channel);
-        if (r.mode != ARTGPU_SMOOTHING_GUIDED && r.mode != ARTGPU_SMOOTHING_NLMEANS)
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: mode %d is not on the device path (only GUIDED and NLMEANS are)", who, i, r.mode);
-        if (r.iterations < 1) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: iterations %d", who, i, r.iterations);
-        if (r.mode == ARTGPU_SMOOTHING_NLMEANS && r.nlstrength != 0 && !(scale >= 1.0))
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means at scale %g (below 1) is not on the device path", who, i, scale);
-        if (read_masks && r.mask && (!plane_ok(r.mask) || r.mask->w != W || r.mask->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: the mask must be a %dx%d plane", who, i, W, H);
-    }
-    return ARTGPU_OK;
-}
-
-// one region's plan from its box (inclusive maxima as the reduction leaves them; nullptr: a NULL mask, the frame)
-int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl)
-{
-    *pl = SmRegionPlan{};
-    pl->mode = r.mode; pl->channel = r.channel; pl->iterations = r.iterations; pl->nlstrength = r.nlstrength; pl->nldetail = r.nldetail;
-    if (box && box[2] < box[0]) { pl->skipped = ARTGPU_SMOOTHING_SKIP_EMPTY; return ARTGPU_OK; }
-    int min_x = box ? box[0] : 0, min_y = box ? box[1] : 0, max_x = box ? box[2] + 1 : W, max_y = box ? box[3] + 1 : H;
-    int ww = max_x - min_x, hh = max_y - min_y;
-    if (ww * hh < (W * H) / 2) pl->cropped = 1;                    // L957 (int arithmetic, as there)
-    else { min_x = 0; min_y = 0; max_x = W; max_y = H; ww = W; hh = H; }
-    pl->x0 = min_x; pl->y0 = min_y; pl->x1 = max_x; pl->y1 = max_y; pl->ww = ww; pl->hh = hh;
-    if (r.mode == ARTGPU_SMOOTHING_GUIDED) {
-        pl->epsilon = (float)std::max(0.001f * std::pow(2.0, (double)-r.epsilon), 1e-6);        // L1040: a double narrowed at the call
-        const int rr = (int)std::round(r.radius / scale);             // L348
-        pl->r = rr > 0 ? rr : 0;
-        if (pl->r == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_RADIUS; return ARTGPU_OK; }
-        pl->sub = gf_subsampling(ww, hh, pl->r);
-        pl->w = ww / pl->sub; pl->h = hh / pl->sub;
-        if (pl->w < ARTGPU_SMOOTHING_MIN_SIZE || pl->h < ARTGPU_SMOOTHING_MIN_SIZE)
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a %dx%d working plane leaves a %dx%d statistics grid, below %d", who, i, ww, hh, pl->w, pl->h, ARTGPU_SMOOTHING_MIN_SIZE);
-        const float r1 = float(pl->r) / pl->sub;                      // f_mean (guidedfilter.cc:160-167)
-        int rad = (int)r1;
-        const int hi = ((pl->w < pl->h ? pl->w : pl->h) - 1) / 2 - 1;
-        rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0;
-        pl->rad = rad;
-        if (rad > HBLUR_MAX_RADIUS)
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, i, rad, HBLUR_MAX_RADIUS);
-    } else {
-        if (r.nlstrength == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_STRENGTH; return ARTGPU_OK; }
-        if (ww < 32 || hh < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane, smaller than 32x32", who, i, ww, hh);
-        if ((unsigned long long)(ww + 14) * (unsigned long long)(hh + 14) >= (1ull << 30))
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane exceeds 2^30 pixels", who, i, ww, hh);
-    }
-    return ARTGPU_OK;
-}
 
 // floats of P_SM_PLANES a region needs
 size_t sm_region_floats(const SmRegionPlan &p)
@@ -4529,6 +4270,64 @@ int sm_region_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, const 
     return ARTGPU_OK;
 }
 
+} // namespace
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+// everything that does not depend on a mask's box: what the pipe checks before any stage runs
+int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regions, int nregions, const double *ws, double scale, bool read_masks, const char *who)
+{
+    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !(scale > 0.0) || std::isinf(scale)) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
+    for (int i = 0; i < nregions; ++i) {
+        const artgpu_smoothing_region &r = regions[i];
+        if (r.mode < ARTGPU_SMOOTHING_GUIDED || r.mode > ARTGPU_SMOOTHING_WAVELETS) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: mode %d", who, i, r.mode);
+        if (r.channel < ARTGPU_SMOOTHING_LUMINANCE || r.channel > ARTGPU_SMOOTHING_RGB) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: channel %d", who, i, r.channel);
+        if (r.mode != ARTGPU_SMOOTHING_GUIDED && r.mode != ARTGPU_SMOOTHING_NLMEANS)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: mode %d is not on the device path (only GUIDED and NLMEANS are)", who, i, r.mode);
+        if (r.iterations < 1) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: iterations %d", who, i, r.iterations);
+        if (r.mode == ARTGPU_SMOOTHING_NLMEANS && r.nlstrength != 0 && !(scale >= 1.0))
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means at scale %g (below 1) is not on the device path", who, i, scale);
+        if (read_masks && r.mask && (!plane_ok(r.mask) || r.mask->w != W || r.mask->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: the mask must be a %dx%d plane", who, i, W, H);
+    }
+    return ARTGPU_OK;
+}
+
+// one region's plan from its box (inclusive maxima as the reduction leaves them; nullptr: a NULL mask, the frame)
+int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl)
+{
+    *pl = SmRegionPlan{};
+    pl->mode = r.mode; pl->channel = r.channel; pl->iterations = r.iterations; pl->nlstrength = r.nlstrength; pl->nldetail = r.nldetail;
+    if (box && box[2] < box[0]) { pl->skipped = ARTGPU_SMOOTHING_SKIP_EMPTY; return ARTGPU_OK; }
+    int min_x = box ? box[0] : 0, min_y = box ? box[1] : 0, max_x = box ? box[2] + 1 : W, max_y = box ? box[3] + 1 : H;
+    int ww = max_x - min_x, hh = max_y - min_y;
+    if (ww * hh < (W * H) / 2) pl->cropped = 1;                    // L957 (int arithmetic, as there)
+    else { min_x = 0; min_y = 0; max_x = W; max_y = H; ww = W; hh = H; }
+    pl->x0 = min_x; pl->y0 = min_y; pl->x1 = max_x; pl->y1 = max_y; pl->ww = ww; pl->hh = hh;
+    if (r.mode == ARTGPU_SMOOTHING_GUIDED) {
+        pl->epsilon = (float)std::max(0.001f * std::pow(2.0, (double)-r.epsilon), 1e-6);        // L1040: a double narrowed at the call
+        const int rr = (int)std::round(r.radius / scale);             // L348
+        pl->r = rr > 0 ? rr : 0;
+        if (pl->r == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_RADIUS; return ARTGPU_OK; }
+        pl->sub = gf_subsampling(ww, hh, pl->r);
+        pl->w = ww / pl->sub; pl->h = hh / pl->sub;
+        if (pl->w < ARTGPU_SMOOTHING_MIN_SIZE || pl->h < ARTGPU_SMOOTHING_MIN_SIZE)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a %dx%d working plane leaves a %dx%d statistics grid, below %d", who, i, ww, hh, pl->w, pl->h, ARTGPU_SMOOTHING_MIN_SIZE);
+        const float r1 = float(pl->r) / pl->sub;                      // f_mean (guidedfilter.cc:160-167)
+        int rad = (int)r1;
+        const int hi = ((pl->w < pl->h ? pl->w : pl->h) - 1) / 2 - 1;
+        rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0;
+        pl->rad = rad;
+        if (rad > HBLUR_MAX_RADIUS)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, i, rad, HBLUR_MAX_RADIUS);
+    } else {
+        if (r.nlstrength == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_STRENGTH; return ARTGPU_OK; }
+        if (ww < 32 || hh < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane, smaller than 32x32", who, i, ww, hh);
+        if ((unsigned long long)(ww + 14) * (unsigned long long)(hh + 14) >= (1ull << 30))
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane exceeds 2^30 pixels", who, i, ww, hh);
+    }
+    return ARTGPU_OK;
+}
+
 // the tool on device planes (rows of `stride` floats) in RGB mode; enqueued on ctx->stream, one host wait when a region has a mask
 int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
                   artgpu_smoothing_info *info, const char *who)
@@ -4607,7 +4406,10 @@ int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W,
         }
     return ARTGPU_OK;
 }
-} // namespace
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_smoothing_region *regions, int nregions, const double ws[9], double scale,
                      artgpu_smoothing_info *info)
@@ -4624,52 +4426,17 @@ int artgpu_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_smoothing_re
     return unbind_rgb(ctx, img, &d);
 }
 
-int artgpu_set_pipeline_smoothing(artgpu_ctx *ctx, const artgpu_smoothing_region *regions, int n, const artgpu_mask_params *masks)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_smoothing: bad arguments");
-    own_pipe_regions(ctx->pipe_sm_own, regions, n, {&artgpu_smoothing_region::mask}, masks, &ctx->shared.pipe_sm, &ctx->shared.pipe_sm_masks, &ctx->shared.pipe_nsm);
-    return ARTGPU_OK;
-}
+} // extern "C"
 
 // ---------------------------------------------------------------------------------------------
 // capture sharpening: ImProcFunctions::doSharpening, method "rld"
 // ---------------------------------------------------------------------------------------------
+
 namespace {
-// the stage's full-size planes in pool slot P_SH_PLANES; SHP_EST_A .. SHP_GTMP are what one deconvolution works in
-enum { SHP_Y = 0, SHP_BLEND, SHP_YY, SHP_EST_A, SHP_EST_B, SHP_RATIO, SHP_OUT, SHP_GTMP, SHP_YY2, SHP_NPLANES };
+
 constexpr size_t SH_COUNTER_BYTES = 64;      // P_SH_BYTES: two 64-bit counters, then the impulse map
 
-// what the call derives from its parameters before it touches anything
-struct SharpenPlan {
-    int early;                     // artgpu_sharpening_info::early_out of doSharpening's own tests (L717)
-    float contrast, blur_radius, amount, delta;
-    double sigma;
-    int boost;
-};
-
 static bool sharpen_sigma_ok(double sigma) { return sigma == sigma && !std::isinf(sigma) && sigma < 25.0; }
-
-static int sharpen_check(artgpu_ctx *ctx, int W, int H, const artgpu_sharpening_params *p, double scale, const char *who, SharpenPlan *pl)
-{
-    *pl = SharpenPlan{};
-    if (!p->enabled) { pl->early = 1; return ARTGPU_OK; }
-    if (p->amount < 1) { pl->early = 2; return ARTGPU_OK; }
-    if (W < 8 || H < 8) { pl->early = 3; return ARTGPU_OK; }
-    if (p->method != ARTGPU_SHARPEN_RLD) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: only the rld method is on the device path (method %d)", who, p->method);
-    if (!(scale > 0.0) || std::isinf(scale)) return fail(ctx, ARTGPU_EINVAL, "%s: scale must be positive", who);
-    const float s_scale = std::sqrt(scale);                                          // L726-729
-    pl->contrast = sh_pow_F(p->contrast / 100.f, 1.2f) * s_scale;
-    pl->blur_radius = 2.f / s_scale;
-    if (!(pl->blur_radius >= 0.6)) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: mask blur radius %g (scale %g) below the shared gaussian's range", who, (double)pl->blur_radius, scale);
-    pl->sigma = p->deconvradius / scale;                                             // L756-759
-    pl->amount = p->deconvamount / 100.f;
-    pl->delta = p->deconvCornerBoost / scale;
-    pl->boost = pl->delta > 0.01f ? 1 : 0;
-    if (!sharpen_sigma_ok(pl->sigma) || (pl->boost && !sharpen_sigma_ok(pl->sigma + pl->delta)))
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: deconvolution radius %g (corner boost %g) is not finite or not below 25", who, pl->sigma, (double)pl->delta);
-    return ARTGPU_OK;
-}
 
 // deconvsharpening on a contiguous device plane; `work`: five planes (estimate x 2, ratio, out, the gaussian's forward buffer).
 // counters (device, zeroed; may be null): [1] += the pixels frozen before the last iteration.  *early / *regime for artgpu_sharpening_info.
@@ -4734,8 +4501,33 @@ static int sharpen_read_counters(artgpu_ctx *ctx, const unsigned long long *coun
     return ARTGPU_OK;
 }
 
+} // namespace
+
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+int sharpen_check(artgpu_ctx *ctx, int W, int H, const artgpu_sharpening_params *p, double scale, const char *who, SharpenPlan *pl)
+{
+    *pl = SharpenPlan{};
+    if (!p->enabled) { pl->early = 1; return ARTGPU_OK; }
+    if (p->amount < 1) { pl->early = 2; return ARTGPU_OK; }
+    if (W < 8 || H < 8) { pl->early = 3; return ARTGPU_OK; }
+    if (p->method != ARTGPU_SHARPEN_RLD) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: only the rld method is on the device path (method %d)", who, p->method);
+    if (!(scale > 0.0) || std::isinf(scale)) return fail(ctx, ARTGPU_EINVAL, "%s: scale must be positive", who);
+    const float s_scale = std::sqrt(scale);                                          // L726-729
+    pl->contrast = sh_pow_F(p->contrast / 100.f, 1.2f) * s_scale;
+    pl->blur_radius = 2.f / s_scale;
+    if (!(pl->blur_radius >= 0.6)) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: mask blur radius %g (scale %g) below the shared gaussian's range", who, (double)pl->blur_radius, scale);
+    pl->sigma = p->deconvradius / scale;                                             // L756-759
+    pl->amount = p->deconvamount / 100.f;
+    pl->delta = p->deconvCornerBoost / scale;
+    pl->boost = pl->delta > 0.01f ? 1 : 0;
+    if (!sharpen_sigma_ok(pl->sigma) || (pl->boost && !sharpen_sigma_ok(pl->sigma + pl->delta)))
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: deconvolution radius %g (corner boost %g) is not finite or not below 25", who, pl->sigma, (double)pl->delta);
+    return ARTGPU_OK;
+}
+
 // doSharpening on device planes (rows of `stride` floats), enqueued on ctx->stream; the host waits only to fill `info`
-static int sharpen_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_sharpening_params *p, const double ws[9],
+int sharpen_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_sharpening_params *p, const double ws[9],
                        const SharpenPlan &pl, artgpu_sharpening_info *info)
 {
     if (info) { info->early_out = pl.early; info->regime = -1; }
@@ -4788,7 +4580,7 @@ static int sharpen_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, i
     return ARTGPU_OK;
 }
 
-static int plane_into(artgpu_ctx *ctx, const artgpu_plane *pl, float *dst)
+int plane_into(artgpu_ctx *ctx, const artgpu_plane *pl, float *dst)
 {
     const size_t rowb = (size_t)pl->w * 4;
     HIPCHK(ctx, hipMemcpy2DAsync(dst, rowb, pl->p, (size_t)pl->row_stride_bytes, rowb, pl->h, pl->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
@@ -4796,7 +4588,7 @@ static int plane_into(artgpu_ctx *ctx, const artgpu_plane *pl, float *dst)
 }
 
 // calcRadiusBayer's maximum of a device CFA plane into result[0] (P_SH_STATE), enqueued; no wait
-static int auto_radius_dev(artgpu_ctx *ctx, const float *raw, size_t stride, int W, int H, uint32_t filters, float lower, float upper, float **result)
+int auto_radius_dev(artgpu_ctx *ctx, const float *raw, size_t stride, int W, int H, uint32_t filters, float lower, float upper, float **result)
 {
     float *st;
     int rc;
@@ -4807,8 +4599,12 @@ static int auto_radius_dev(artgpu_ctx *ctx, const float *raw, size_t stride, int
     *result = st;
     return ARTGPU_OK;
 }
-static float auto_radius_of(float maxRatio) { return std::sqrt((1.f / (std::log(1.f / maxRatio) / 2.f)) / -2.f); }   // L90
-} // namespace
+
+float auto_radius_of(float maxRatio) { return std::sqrt((1.f / (std::log(1.f / maxRatio) / 2.f)) / -2.f); }   // L90
+
+} } // namespace artgpu::api
+
+extern "C" {
 
 int artgpu_sharpening(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_sharpening_params *params, const double ws[9], double scale, artgpu_sharpening_info *info)
 {
@@ -4919,674 +4715,6 @@ int artgpu_deconv_auto_radius(artgpu_ctx *ctx, const artgpu_plane *raw, uint32_t
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (max_ratio) *max_ratio = mr;
     *radius = auto_radius_of(mr);
-    return ARTGPU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// one frame / one batch share through the whole path
-// ---------------------------------------------------------------------------------------------
-namespace {
-// the call site's condition (rawimagesource.cc:1827): CA correction enabled, auto or a manual shift, Bayer only (X-Trans skips it)
-static bool pipeline_ca(const artgpu_pipeline_params *p)
-{
-    return p->ca_enabled && (p->ca.autocorrect || fabs(p->ca.red) > 0.001 || fabs(p->ca.blue) > 0.001) && p->sensor == 0;
-}
-// CA correction of the CFA plane `raw` (device, rows of `stride` floats) in place, ahead of the demosaic
-static int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, const artgpu_pipeline_params *p)
-{
-    unsigned cfa;
-    if (!ca_cfa(p->filters, &cfa)) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on RGB Bayer patterns only (filters 0x%08x)", p->filters);
-    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on a frame smaller than 64x64");
-    return ca_correct_dev(ctx, raw, stride, W, H, cfa, &p->ca, nullptr);
-}
-
-enum PipeMode { PIPE_RGB, PIPE_YUV };
-// Everything a frame decides before its first launch (pipeline_plan).  The stages only read it, but for the `mask` pointers of lc_regs / tb_regs,
-// which pipe_stage3 aims at the planes it generates.
-struct PipePlan {
-    int W, H, b, w, h;             // the raw frame, its border, the image behind the demosaic (W - 2b x H - 2b)
-    double scale;
-    bool lc_on, lc_gen, tb_on, tb_gen, cc_on, cc_gen, sm_on, sm_gen;   // the local tools: on, and the pipe generates their masks (artgpu_set_pipeline_*)
-    bool cc_to_rgb, tb_in_yuv;     // the mode walk: colour correction ends with the switch back to RGB; texture boost finds the image in YUV mode
-    std::vector<artgpu_local_contrast_region> lc_regs;             // copies of the regions whose masks the pipe generates ...
-    std::vector<artgpu_texture_boost_region> tb_regs;
-    const artgpu_local_contrast_region *lc_regions;                // ... or the caller's
-    const artgpu_texture_boost_region *tb_regions;
-    MkPlan lc_mk, tb_mk, cc_mk, sm_mk;
-    CcPlan cc;
-    DehazePlan dehaze;
-    bool sh_on, sh_auto, sh_radius_pending;
-    artgpu_sharpening_params shpar;                                // (deconvradius: 0.75 stands in while the automatic radius is pending)
-    SharpenPlan sharpen;
-    std::vector<TbPlan> tb;
-};
-// What the stages hand on: the CFA plane the demosaic reads (the caller's, or its CA-corrected copy in the pool), the demosaiced W x H planes in the
-// pool, the w x h image the later stages work on (the caller's planes if they are on the device, else a staged copy) as launchers / entry points take it
-struct PipeFrame { artgpu_plane raw; artgpu_rgb dem; DevRGB d; artgpu_rgb img; };
-
-// the MkPlan of n regions whose masks the pipe generates on its own image (mode: ARTGPU_MASKS_MODE_LAB or _RGB; full size, no crop)
-static int pipe_plan_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, int mode, const artgpu_mask_params *masks, int n, bool want_ab, const char *who, MkPlan *mk)
-{
-    return mk_plan(ctx, pl.w, pl.h, mode, mode == ARTGPU_MASKS_MODE_LAB ? nullptr : p->ws, masks, n, pl.w, pl.h, pl.scale, true, want_ab, who, mk, nullptr);
-}
-
-// generateMasks(rgb, ., masks, 0, 0, full size, scale, ., -1, &Lmask, [&abmask]) on the device image: the planes go to pool slot `slot` and never
-// leave the device.  *planes: their descriptors, n L planes, then n ab planes when asked for
-static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const DevRGB &d, int slot, const artgpu_mask_params *masks, const MkPlan &mk, int n, bool want_ab,
-                          std::vector<artgpu_plane> *planes)
-{
-    const size_t np = (size_t)d.w * d.h, count = (size_t)n * (want_ab ? 2 : 1);
-    float *mo;
-    int rc;
-    if ((rc = pool_get(ctx, slot, count * np * 4, &mo)) || (rc = masks_dev(ctx, d.p, d.stride, p->ws, masks, mk, mo, want_ab ? mo + n * np : nullptr))) return rc;
-    planes->resize(count);
-    for (size_t i = 0; i < count; ++i) (*planes)[i] = mk_dev_plane(mo + i * np, d.w, d.h);
-    return ARTGPU_OK;
-}
-
-// Checks and derives everything; launches nothing and takes no pool slot, so a refused frame leaves the output planes alone.  The checks, in the
-// order they report (a frame that is wrong in two ways names the first):
-//   1. ctx, raw / p / out, the border, the output's size (then hipSetDevice, the one HIP call here)   2. artgpu_set_pipeline_masks' counts against the frame's
-//   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
-//   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
-//   8. dehaze_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
-static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, PipePlan *pl)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(raw_in) || !p || !out) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: null/bad argument");
-    const int b = p->border, w = raw_in->w - 2 * b, h = raw_in->h - 2 * b, nlc = p->local_contrast_nregions, ntb = p->texture_boost_nregions;
-    const double scale = p->scale > 0 ? p->scale : 1.0;
-    pl->W = raw_in->w; pl->H = raw_in->h; pl->b = b; pl->w = w; pl->h = h; pl->scale = scale;
-    if (b < 0 || w < 8 || h < 8) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: border %d leaves no image", b);
-    if (out->r.w != w || out->r.h != h) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", w, h);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const artgpu_ctx::Shared &s = ctx->shared;
-    pl->lc_on = p->local_contrast_enabled && nlc > 0; pl->lc_gen = pl->lc_on && s.pipe_lc;
-    pl->tb_on = p->texture_boost_enabled != 0;        pl->tb_gen = pl->tb_on && ntb > 0 && s.pipe_tb;
-    pl->cc_on = s.pipe_ncc > 0 && s.pipe_cc;          pl->cc_gen = pl->cc_on && s.pipe_cc_masks;
-    pl->sm_on = s.pipe_nsm > 0 && s.pipe_sm;          pl->sm_gen = pl->sm_on && s.pipe_sm_masks;
-    // The image's colour mode in front of each tool, in pipe order, as the reference has it: sharpening works on RGB; colorCorrection generates its masks
-    // on RGB and leaves YUV; guidedSmoothing generates its masks on what it finds, then setMode(RGB); textureBoost likewise, then setMode(YUV), and ends in
-    // RGB for the tone curve and localContrast (whose LAB, masks included, is its own switch).  The mask engine reads RGB only: masks to be generated
-    // on a YUV image fail the frame.  Colour correction ends with the next tool's setMode(RGB) (to_rgb) unless that tool is texture boost, which then skips
-    // its own switch (in_yuv).  '-': not read; the mask columns say what happens where the pipe generates that tool's masks
-    //   cc sm | in front of sm | in front of tb | cc to_rgb (tb off / on) | tb in_yuv | sm's masks | tb's masks
-    //    0  0 |       -        |      RGB       |           -             |     0     |     -      |    ok
-    //    0  1 |      RGB       |      RGB       |           -             |     0     |     ok     |    ok
-    //    1  0 |       -        |      YUV       |         1 / 0           |     1     |     -      |  refused
-    //    1  1 |      YUV       |      RGB       |         1 / 1           |     0     |  refused   |    ok
-    PipeMode mode = pl->cc_on ? PIPE_YUV : PIPE_RGB;           // (sharpening: RGB in, RGB out)
-    const bool sm_masks_from_yuv = pl->sm_gen && mode == PIPE_YUV;
-    if (pl->sm_on) mode = PIPE_RGB;
-    const bool tb_masks_from_yuv = pl->tb_gen && mode == PIPE_YUV;
-    pl->tb_in_yuv = pl->tb_on && mode == PIPE_YUV;
-    pl->cc_to_rgb = !pl->tb_in_yuv;
-    // regions whose blend planes the pipe generates itself (artgpu_set_pipeline_masks): the regions' own `mask` pointers are
-    // not read, the planes of artgpu_generate_masks take their place; what it does not support fails the frame here
-    if ((pl->lc_gen && s.pipe_nlc != nlc) || (pl->tb_gen && s.pipe_ntb != ntb))
-        return fail(ctx, ARTGPU_EINVAL, "pipeline_run: artgpu_set_pipeline_masks holds %d / %d entries, the frame has %d / %d regions", s.pipe_nlc, s.pipe_ntb, nlc, ntb);
-    const auto own = [](auto &regs, const auto *src, int n) { regs.assign(src, src + n); for (auto &r : regs) r.mask = nullptr; };
-    if (pl->lc_gen) {
-        if (!p->local_contrast_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(local contrast): bad region list");
-        own(pl->lc_regs, p->local_contrast_regions, nlc);
-        if ((rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_LAB, s.pipe_lc, nlc, false, "pipeline_run(local contrast masks)", &pl->lc_mk))) return rc;
-    }
-    if (pl->tb_gen) {
-        if (!p->texture_boost_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(texture boost): bad region list");
-        own(pl->tb_regs, p->texture_boost_regions, ntb);
-        if ((rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_tb, ntb, false, "pipeline_run(texture boost masks)", &pl->tb_mk))) return rc;
-    }
-    pl->lc_regions = pl->lc_gen ? pl->lc_regs.data() : p->local_contrast_regions;
-    pl->tb_regions = pl->tb_gen ? pl->tb_regs.data() : p->texture_boost_regions;
-    if (pl->cc_on) {      // ImProcFunctions::colorCorrection (artgpu_set_pipeline_color_correction)
-        if (tb_masks_from_yuv)
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate texture boost's masks from");
-        if ((rc = cc_check(ctx, w, h, s.pipe_cc, s.pipe_ncc, p->ws, p->iws, !pl->cc_gen, "pipeline_run(colour correction)", &pl->cc))) return rc;
-        if (pl->cc_gen && (rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_cc_masks, s.pipe_ncc, true, "pipeline_run(colour correction masks)", &pl->cc_mk))) return rc;
-    }
-    if (pl->sm_on) {      // ImProcFunctions::guidedSmoothing (artgpu_set_pipeline_smoothing): what does not depend on a mask's box is checked here
-        if (sm_masks_from_yuv)
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate smoothing's masks from");
-        if ((rc = sm_check(ctx, w, h, s.pipe_sm, s.pipe_nsm, p->ws, scale, !pl->sm_gen, "pipeline_run(smoothing)"))) return rc;
-        for (int i = 0; i < s.pipe_nsm && !pl->sm_gen; ++i) {       // a region without a mask is the frame: its limits are known now
-            SmRegionPlan sp;
-            if (!s.pipe_sm[i].mask && (rc = sm_plan_region(ctx, w, h, s.pipe_sm[i], nullptr, scale, "pipeline_run(smoothing)", i, &sp))) return rc;
-        }
-        if (pl->sm_gen && (rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_sm_masks, s.pipe_nsm, false, "pipeline_run(smoothing masks)", &pl->sm_mk))) return rc;
-    }
-    if (pl->lc_on && (rc = local_contrast_check(ctx, w, h, pl->lc_regions, nlc, scale, "pipeline_run(local contrast)"))) return rc;
-    if (p->dehaze_enabled && (rc = dehaze_check(ctx, w, h, &p->dehaze, p->ws, scale, "pipeline_run(dehaze)", &pl->dehaze))) return rc;
-    // sharpening (STAGE_2): method, scale and, with the automatic radius, the sensor are checked before any stage runs
-    pl->shpar = p->sharpening;
-    pl->sh_on = p->sharpening_enabled != 0;
-    pl->sh_auto = pl->sh_on && pl->shpar.enabled && p->sharpening_auto_radius;      // simpleprocess.cc:274
-    if (pl->sh_on) {
-        if (pl->sh_auto && p->sensor != 0) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run(sharpening): the automatic radius of X-Trans frames is not on the device path");
-        if (pl->sh_auto) pl->shpar.deconvradius = 0.75;                             // (replaced in pipe_stage2; the check is about everything else)
-        if ((rc = sharpen_check(ctx, w, h, &pl->shpar, scale, "pipeline_run(sharpening)", &pl->sharpen))) return rc;
-    }
-    pl->sh_radius_pending = pl->sh_auto && !pl->sharpen.early;
-    if (pl->tb_on && (rc = tb_check(ctx, w, h, pl->tb_regions, ntb, p->ws, scale, 1, "pipeline_run(texture boost)", &pl->tb))) return rc;
-    return ARTGPU_OK;
-}
-
-// The raw side: RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy (the caller's raw is never written), and
-// RawImageSource::getDeconvAutoRadius on the plane the demosaic reads (simpleprocess.cc:274-278 after preprocess): launched here, its one
-// number is waited for where the sharpening needs it
-static int pipe_raw_side(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, const artgpu_plane *raw_in, bool do_ca, PipeFrame *fr)
-{
-    const int W = pl.W, H = pl.H;
-    int rc;
-    float *cp, *res;
-    fr->raw = *raw_in;
-    if (do_ca && pipeline_ca(p)) {
-        if ((rc = plane_to_pool(ctx, raw_in, P_CA_RAW, &cp)) || (rc = pipeline_ca_dev(ctx, cp, W, W, H, p))) return rc;
-        fr->raw = mk_dev_plane(cp, W, H);
-    }
-    if (!pl.sh_radius_pending) return ARTGPU_OK;
-    const float *rp = fr->raw.p;
-    size_t rstride = (size_t)(fr->raw.row_stride_bytes / 4);
-    if (!fr->raw.on_device) {
-        const size_t need = std::max((size_t)W * H, (size_t)SHP_NPLANES * pl.w * pl.h) * 4;
-        if ((rc = pool_get(ctx, P_SH_PLANES, need, &cp)) || (rc = plane_into(ctx, &fr->raw, cp))) return rc;
-        rp = cp; rstride = W;
-    }
-    if ((rc = auto_radius_dev(ctx, rp, rstride, W, H, p->filters, 1000.f, p->sharpening_clip_val, &res))) return rc;
-    if (!ctx->sh_host) {
-        if (hipHostMalloc(reinterpret_cast<void **>(&ctx->sh_host), 64, hipHostMallocDefault) != hipSuccess) { ctx->sh_host = nullptr; return fail(ctx, ARTGPU_ENOMEM, "pipeline_run(sharpening): pinned word"); }
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sh_ev, hipEventDisableTiming));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->sh_host, res, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(ctx->sh_ev, ctx->stream));
-    return ARTGPU_OK;
-}
-
-// The demosaic into planes of the context pool (they never leave the device), and the image the remaining stages work on
-static int pipe_demosaic(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
-{
-    float *dp[3];
-    int rc;
-    for (int k = 0; k < 3; ++k)
-        if ((rc = pool_get(ctx, P_PIPE_R + k, (size_t)pl.W * pl.H * 4, &dp[k]))) return rc;
-    fr->dem = mk_dev_rgb(dp, pl.W, pl.H, pl.W);
-    if (p->sensor == 0) rc = artgpu_demosaic_bayer(ctx, p->bayer_method, &fr->raw, p->filters, p->initial_gain, pl.b, &fr->dem);
-    else rc = artgpu_demosaic_xtrans(ctx, p->xtrans_passes, p->xtrans_passes > 1 ? 1 : 0, &fr->raw, p->xtrans, p->rgb_cam, &fr->dem);
-    if (rc || (rc = bind_rgb(ctx, out, 4, false, &fr->d, "pipeline_run(out)"))) return rc;
-    fr->img = mk_dev_rgb(fr->d.p, fr->d.w, fr->d.h, fr->d.stride);
-    return ARTGPU_OK;
-}
-
-// From the demosaiced planes to the exposed image: denoiseComputeParams, getImage + convertColorSpace + the denoise tool, dehaze (STAGE_0), the exposure (STAGE_1)
-static int pipe_input(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, PipeFrame *fr)
-{
-    const double *cam_to_work = p->has_cam_to_work ? p->cam_to_work : nullptr;
-    const DevRGB &d = fr->d;
-    int rc;
-    artgpu_denoise_tool_params dnp = p->denoise;
-    if (p->denoise_enabled && dnp.dn.chrominance_method == 1) {
-        // ipf.denoiseComputeParams(imgsrc, currWB, dnstore, params.denoise) before getImage (simpleprocess.cc:254-256); a fresh store per frame
-        static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        artgpu_denoise_info_store store = {};
-        if ((rc = artgpu_denoise_compute_params(ctx, &fr->dem, pl.b, p->mul, p->do_clip, cam_to_work ? cam_to_work : ident, p->ws,
-                                                p->chrominance_auto_factor != 0.0 ? p->chrominance_auto_factor : 1.0, &store, &dnp.dn)))
-            return rc;
-    }
-    if (p->denoise_enabled) {
-        // getImage + convertColorSpace in front of the tool and the STAGE_1 exposure behind it live in the tool's own pixel passes where
-        // its parameters allow (artgpu_improc_denoise_fused: otherwise they run as the separate calls)
-        static const double curve_points[9] = {1 /*FCT_MinMaxCPoints*/, 0.05, 0.50, 0.35, 0.35, 0.35, 0.05, 0.35, 0.35};   // ipdenoise.cc:1139-1149
-        float curve[501];
-        (void)noise_curve_lut(curve_points, 9, curve);
-        const double ecomp = p->exposure_enabled ? p->expcomp : 0.0;       // ipdenoise.cc:1155
-        artgpu_denoise_fusion fu = {};
-        fu.demosaiced = &fr->dem; fu.sx1 = pl.b; fu.sy1 = pl.b;
-        for (int k = 0; k < 3; ++k) fu.mul[k] = p->mul[k];
-        fu.do_clip = p->do_clip; fu.cam_to_work = cam_to_work;
-        fu.exposure_enabled = p->exposure_enabled && !p->dehaze_enabled ? 1 : 0;      // (dehaze sits between the tool and the exposure)
-        fu.exp_scale = (float)std::pow(2.0, p->expcomp); fu.black = (float)(p->black * 2000.0);
-        if ((rc = artgpu_improc_denoise_fused(ctx, &fr->img, &fu, &dnp, p->ws, p->iws, ecomp, pl.scale, cam_to_work, curve, 0u))) return rc;
-    } else if ((rc = artgpu_get_image(ctx, &fr->dem, pl.b, pl.b, p->mul, p->do_clip, cam_to_work, &fr->img))) return rc;
-    // ImProcFunctions::dehaze, STAGE_0 of ImProcFunctions::process (improcfun.cc:577), ahead of the exposure (STAGE_1)
-    if (p->dehaze_enabled && (rc = dehaze_dev(ctx, d.p, d.stride, d.w, d.h, &p->dehaze, p->ws, pl.dehaze, nullptr))) return rc;
-    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled)) return artgpu_exposure(ctx, &fr->img, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0));
-    return ARTGPU_OK;
-}
-
-// STAGE_2 of ImProcFunctions::process: sharpening, colorCorrection, guidedSmoothing
-static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, PipeFrame *fr)
-{
-    const DevRGB &d = fr->d;
-    const artgpu_ctx::Shared &s = ctx->shared;
-    std::vector<artgpu_plane> gen;
-    int rc;
-    // ImProcFunctions::sharpening, the first step of STAGE_2 (improcfun.cc:595; simpleprocess.cc:395 between the exposure and the tone curve)
-    if (pl.sh_on) {
-        artgpu_sharpening_params shpar = pl.shpar;
-        SharpenPlan shp = pl.sharpen;
-        if (pl.sh_radius_pending) {
-            HIPCHK(ctx, hipEventSynchronize(ctx->sh_ev));
-            shpar.deconvradius = auto_radius_of(ctx->sh_host[0]);                    // params.sharpening.deconvradius = r
-            if ((rc = sharpen_check(ctx, d.w, d.h, &shpar, pl.scale, "pipeline_run(sharpening, automatic radius)", &shp))) return rc;
-        }
-        if ((rc = sharpen_dev(ctx, d.p, d.stride, d.w, d.h, &shpar, p->ws, shp, nullptr))) return rc;
-    }
-    // ImProcFunctions::colorCorrection, STAGE_2 behind the sharpening (improcfun.cc:601): generateMasks(rgb, ., &Lmask, &abmask) on the RGB image
-    // (ipcolorcorrection.cc:236), then the tool.  It leaves the image in YUV mode for textureBoost, whose setMode(YUV) is then a no-op
-    if (pl.cc_on) {
-        const int n = s.pipe_ncc;
-        std::vector<artgpu_color_correction_region> regs(s.pipe_cc, s.pipe_cc + n);
-        if (pl.cc_gen && (rc = pipe_gen_masks(ctx, p, d, P_CC_GEN, s.pipe_cc_masks, pl.cc_mk, n, true, &gen))) return rc;
-        for (int i = 0; i < n && pl.cc_gen; ++i) { regs[i].lmask = &gen[i]; regs[i].abmask = &gen[n + i]; }
-        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), pl.cc, 0, pl.cc_to_rgb, nullptr))) return rc;
-    }
-    // ImProcFunctions::guidedSmoothing, the last step of STAGE_2 (improcfun.cc:602): generateMasks on the image (ipsmoothing.cc:929), setMode(RGB)
-    // (colour correction ahead of it ends with that switch), the tool
-    if (pl.sm_on) {
-        const int n = s.pipe_nsm;
-        std::vector<artgpu_smoothing_region> regs(s.pipe_sm, s.pipe_sm + n);
-        if (pl.sm_gen && (rc = pipe_gen_masks(ctx, p, d, P_SM_GEN, s.pipe_sm_masks, pl.sm_mk, n, false, &gen))) return rc;
-        for (int i = 0; i < n && pl.sm_gen; ++i) regs[i].mask = &gen[i];
-        if ((rc = smoothing_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), n, p->ws, pl.scale, nullptr, "pipeline_run(smoothing)"))) return rc;
-    }
-    return ARTGPU_OK;
-}
-
-// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, the tone curve, localContrast; then the image goes back to the caller's planes
-static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
-{
-    const DevRGB &d = fr->d;
-    const int ntb = p->texture_boost_nregions, nlc = p->local_contrast_nregions;
-    std::vector<artgpu_plane> gen;
-    int rc;
-    // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
-    if (pl.tb_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_tb, pl.tb_mk, ntb, false, &gen))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
-    for (int i = 0; i < ntb && pl.tb_gen; ++i) pl.tb_regs[i].mask = &gen[i];
-    if (pl.tb_on && (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, pl.tb_regions, ntb, p->ws, pl.tb, 1, nullptr, pl.tb_in_yuv))) return rc;
-    if (p->tone_enabled && p->tone_mode == ARTGPU_TONE_NEUTRAL) {
-        artgpu_neutral_state st;
-        for (int k = 0; k < 9; ++k) { st.ws[k] = p->ws[k]; st.iws[k] = p->iws[k]; st.to_out[k] = p->to_out[k]; st.to_work[k] = p->to_work[k]; }
-        if ((rc = artgpu_tone_curve_neutral(ctx, &fr->img, p->tone_lut, p->white_point, &st))) return rc;
-    } else if (p->tone_enabled && (rc = artgpu_tone_curve(ctx, &fr->img, p->tone_mode, p->tone_lut, p->white_point, 1))) return rc;
-    // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
-    // L plane (Imagefloat::g), back to RGB
-    if (pl.lc_on) {
-        if ((rc = artgpu_rgb_to_lab(ctx, &fr->img, p->ws)) || (pl.lc_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_lc, pl.lc_mk, nlc, false, &gen)))) return rc;
-        for (int i = 0; i < nlc && pl.lc_gen; ++i) pl.lc_regs[i].mask = &gen[i];
-        if ((rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, pl.lc_regions, nlc, nullptr)) || (rc = artgpu_lab_to_rgb(ctx, &fr->img, p->iws))) return rc;
-    }
-    return unbind_rgb(ctx, out, &d);
-}
-
-// One frame: the plan, then the stages (do_ca: artgpu_pipeline_run; io_frame has corrected its staged CFA plane itself)
-static int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca)
-{
-    StageScope scope_(ctx, "ImageProcessor (stage_init .. stage_finish)");
-    PipePlan pl{};
-    PipeFrame fr;
-    int rc;
-    if ((rc = pipeline_plan(ctx, raw_in, p, out, &pl)) || (rc = pipe_raw_side(ctx, p, pl, raw_in, do_ca, &fr)) || (rc = pipe_demosaic(ctx, p, pl, out, &fr)) ||
-        (rc = pipe_input(ctx, p, pl, &fr)) || (rc = pipe_stage2(ctx, p, pl, &fr)))
-        return rc;
-    return pipe_stage3(ctx, p, pl, out, &fr);
-}
-} // namespace
-
-int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *lc, int nlc, const artgpu_mask_params *tb, int ntb)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (nlc < 0 || ntb < 0 || (nlc > 0 && !lc) || (ntb > 0 && !tb)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_masks: bad arguments");
-    ctx->shared.pipe_lc = own_pipe_masks(ctx->pipe_lc_own, lc, nlc); ctx->shared.pipe_nlc = nlc;
-    ctx->shared.pipe_tb = own_pipe_masks(ctx->pipe_tb_own, tb, ntb); ctx->shared.pipe_ntb = ntb;
-    return ARTGPU_OK;
-}
-
-int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_pipeline_params *p, artgpu_rgb *out)
-{
-    return pipeline_run_impl(ctx, raw, p, out, true);
-}
-
-int artgpu_set_batch_lanes(artgpu_ctx *ctx, int lanes)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (lanes < 1 || lanes > 8) return fail(ctx, ARTGPU_EINVAL, "set_batch_lanes: 1..8");
-    ctx->batch_lanes = lanes;
-    return ARTGPU_OK;
-}
-
-namespace {
-// The scratch of a context only grows (about 5 GB for a 45 MP frame through the whole tool).  A batch that goes on with much smaller frames
-// would keep the large frame's pools for nothing: when this frame AND the lane's next one have less than half the pixels the pools were
-// grown for, the lane gives them back first (artgpu_trim_scratch: a stream drain and a few hipFree, paid once per such transition; a
-// batch that alternates sizes keeps its pools).  Round-5 review, weak point 10.  `nxt` < 0: the lane's last frame has no successor to go
-// by -- it keeps the pools, a caller that is done calls artgpu_trim_scratch.
-int batch_settle_scratch(artgpu_ctx *c, long long px, long long nxt)
-{
-    if (nxt < 0) nxt = c->batch_px;
-    if (c->batch_px && 2 * px < c->batch_px && 2 * nxt < c->batch_px) {
-        std::vector<artgpu_ctx *> keep;
-        keep.swap(c->lanes);                       // (only this context's own pools: its lanes decide for themselves)
-        const int rc = artgpu_trim_scratch(c);
-        keep.swap(c->lanes);
-        if (rc) return rc;
-        c->batch_px = 0;
-    }
-    if (px > c->batch_px) c->batch_px = px;
-    return ARTGPU_OK;
-}
-
-// Frames are independent: lane k (its own context, stream and host thread) takes frames k, k+L, ...  The kernels of one frame
-// are a mix of latency-bound (AMaZE) and bandwidth-bound (wavelet passes) work, so frames in flight on different streams fill
-// each other's gaps (+11 % throughput with three lanes at 45 MP, scripts/overlap_time.py).
-int batch_prepare_lanes(artgpu_ctx *ctx, int L)
-{
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    while ((int)ctx->lanes.size() < L - 1) {
-        artgpu_ctx *peer = nullptr;
-        int rc = artgpu_create(ctx->device, &peer);
-        if (rc) return fail(ctx, rc, "batch_run: cannot create lane %d", (int)ctx->lanes.size() + 1);
-        if (hipStreamCreateWithFlags(&peer->stream, hipStreamNonBlocking) != hipSuccess) { (void)artgpu_destroy(peer); return fail(ctx, ARTGPU_EHIP, "batch_run: stream"); }
-        peer->owns_stream = true;
-        ctx->lanes.push_back(peer);
-    }
-    // the lanes are this context as far as the caller can tell: its options, curve tail and progress listener apply to every frame,
-    // whichever lane runs it (copied on every call -- they may change between calls)
-    for (artgpu_ctx *peer : ctx->lanes) {
-        peer->shared = ctx->shared;
-        peer->frames_in_flight = L;
-    }
-    ctx->frames_in_flight = L;
-    return ARTGPU_OK;
-}
-struct InFlightReset { artgpu_ctx *c; ~InFlightReset() { c->frames_in_flight = 1; for (artgpu_ctx *p : c->lanes) p->frames_in_flight = 1; } };
-
-// run `work(lane context, lane index)` on L lanes (lane 0 on the calling thread) and gather the status codes
-extern "C++" {
-template <typename F>
-int batch_on_lanes(artgpu_ctx *ctx, int L, F work)
-{
-    std::vector<int> rcs(L, ARTGPU_OK);
-    // (the lanes' contexts are looked up HERE: lane 0 may take ctx->lanes aside for a moment while it trims its own pools -- batch_settle_scratch --,
-    // and a thread that starts late must not index the vector then)
-    std::vector<artgpu_ctx *> cs(L, ctx);
-    for (int k = 1; k < L; ++k) cs[k] = ctx->lanes[k - 1];
-    std::vector<std::thread> threads;
-    for (int k = 1; k < L; ++k) threads.emplace_back([&rcs, &work, &cs, k]() { rcs[k] = work(cs[k], k); });
-    rcs[0] = work(ctx, 0);
-    for (std::thread &t : threads) t.join();
-    for (int k = 0; k < L; ++k)
-        if (rcs[k]) return fail(ctx, rcs[k], "batch_run: lane %d: %s", k, k == 0 ? ctx->err.c_str() : cs[k]->err.c_str());
-    return ARTGPU_OK;
-}
-} // extern "C++"
-} // namespace
-
-int artgpu_batch_run(artgpu_ctx *ctx, int nframes, const artgpu_plane *raws, const artgpu_pipeline_params *params, artgpu_rgb *outs)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (nframes < 0 || (nframes && (!raws || !params || !outs))) return fail(ctx, ARTGPU_EINVAL, "batch_run: null argument");
-    const int L = std::min(ctx->batch_lanes, nframes);
-    auto px_of = [&](int f) { return (long long)raws[f].w * raws[f].h; };
-    if (L <= 1) {
-        for (int f = 0; f < nframes; ++f) {
-            int rc = batch_settle_scratch(ctx, px_of(f), f + 1 < nframes ? px_of(f + 1) : -1);
-            if (!rc) rc = artgpu_pipeline_run(ctx, &raws[f], params, &outs[f]);
-            if (rc) return rc;
-        }
-        return ARTGPU_OK;
-    }
-    int rc = batch_prepare_lanes(ctx, L);
-    if (rc) return rc;
-    InFlightReset in_flight_reset{ctx};
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // inputs the caller produced on this context's stream
-    return batch_on_lanes(ctx, L, [&](artgpu_ctx *c, int k) -> int {
-        for (int f = k; f < nframes; f += L) {
-            int rc2 = batch_settle_scratch(c, px_of(f), f + L < nframes ? px_of(f + L) : -1);
-            if (!rc2) rc2 = artgpu_pipeline_run(c, &raws[f], params, &outs[f]);
-            if (rc2) return rc2;
-        }
-        if (k > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, ARTGPU_EHIP, "batch_run: lane %d: stream", k);
-        return ARTGPU_OK;
-    });
-}
-
-// ---------------------------------------------------------------------------------------------
-// the batch between the decoder's and the writers' formats, copies beside the kernels
-// ---------------------------------------------------------------------------------------------
-namespace {
-int io_setup(artgpu_ctx *c, int nfr)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->io_up) HIPCHK(c, hipStreamCreateWithFlags(&c->io_up, hipStreamNonBlocking));
-    if (!c->io_down) HIPCHK(c, hipStreamCreateWithFlags(&c->io_down, hipStreamNonBlocking));
-    for (int k = 0; k < 8; ++k)
-        if (!c->io_ev[k]) HIPCHK(c, hipEventCreateWithFlags(&c->io_ev[k], hipEventDisableTiming));
-    if (c->io_host_cap < nfr) {
-        if (c->io_host) { HIPCHK(c, hipHostFree(c->io_host)); c->io_host = nullptr; c->io_host_cap = 0; }
-        const int cap = nfr < 16 ? 16 : nfr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&c->io_host), (size_t)cap * 8 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-            c->io_host = nullptr;
-            return fail(c, ARTGPU_ENOMEM, "batch_run_io: pinned flag words for %d frames", cap);
-        }
-        c->io_host_cap = cap;
-    }
-    std::memset(c->io_host, 0, (size_t)c->io_host_cap * 8 * sizeof(int));
-    return ARTGPU_OK;
-}
-
-// pinned (hipHostMalloc / hipHostRegister) host memory?  Its device address if so.  Pageable memory is "invalid value" to the query: not an error here.
-void *pinned_device_address(const void *p)
-{
-    hipPointerAttribute_t at = {};
-    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) return at.devicePointer;
-    (void)hipGetLastError();
-    return nullptr;
-}
-
-// frame `i` of this lane: everything is queued, nothing is waited for (the staging slots of turn i - 2 are released through events)
-int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_pipeline_params *p, artgpu_scanline_frame *out)
-{
-    const int s = i & 1, W = in->w, H = in->h, b = p->border;
-    const int esz = in->is_u16 ? 2 : 4;
-    if (!in->data || W <= 0 || H <= 0 || in->row_stride_bytes < (int64_t)W * esz || in->row_stride_bytes % esz)
-        return fail(c, ARTGPU_EINVAL, "batch_run_io: sensor frame: bad pointer/size/stride");
-    if (b < 0 || W - 2 * b < 8 || H - 2 * b < 8) return fail(c, ARTGPU_EINVAL, "batch_run_io: border %d leaves no image", b);
-    const int iw = W - 2 * b, ih = H - 2 * b;
-    const bool okfmt = out->is_float ? (out->bps == 16 || out->bps == 32) : (out->bps == 8 || out->bps == 16);
-    if (!okfmt) return fail(c, ARTGPU_EINVAL, "batch_run_io: bps %d / is_float %d", out->bps, out->is_float);
-    const size_t rowb = (size_t)iw * 3 * (out->bps / 8);
-    if (!out->scanlines || out->row_stride_bytes < (int64_t)rowb) return fail(c, ARTGPU_EINVAL, "batch_run_io: scanlines: bad pointer / row stride < %zu", rowb);
-    if (out->rgb2out_enabled) {
-        if (!out->trc_linear && (!out->trc_lut || out->trc_lutsz < 2)) return fail(c, ARTGPU_EINVAL, "batch_run_io: a non-linear TRC needs its LUT");
-        if (out->trc_lut && (out->trc_lutsz < 2 || out->trc_lutsz > 65536)) return fail(c, ARTGPU_EINVAL, "batch_run_io: trc_lutsz %d", out->trc_lutsz);
-    }
-    int rc;
-    float *cfa, *img[3], *flags_f;
-    if ((rc = pool_get(c, P_IO_CFA, (size_t)W * H * 4, &cfa)) || (rc = pool_get(c, P_IO_FLAGS, 2 * 8 * sizeof(int), &flags_f))) return rc;
-    for (int k = 0; k < 3; ++k)
-        if ((rc = pool_get(c, P_IO_IMG0 + 3 * s + k, (size_t)iw * ih * 4, &img[k]))) return rc;      // (two sets: the download of turn i reads its set while turn i + 1 is computed)
-    int *flags = reinterpret_cast<int *>(flags_f) + 8 * s;
-    // Where do the scanlines go?  Pinned host memory is mapped into the device's address space: a few workgroups on the download stream write
-    // them there directly.  Anything else (pageable memory, rows that are not 16-byte aligned, option io_direct = 0) is staged and copied.
-    // Scanlines for PINNED memory can be written there by a kernel of the download stream (option io_direct = n workgroups) instead of being staged and
-    // copied.  Measured on 8192 x 5464 frames, 16-bit scanlines (scripts/pcie_batch.py, batches of 24 - 36 frames, seven runs): the runtime's copy -- itself a
-    // kernel, 268 MB in 4.9 ms -- 11.0 ms per frame with one lane, 10.6 - 13.8 with two (two modes: the lanes lock into step with the copy kernel in
-    // about half the runs), 10.7 - 11.3 with three; eight workgroups writing directly 11.7 - 12.6 / 11.2 - 11.8 / 11.7 - 12.9 (they hold eight CUs for
-    // 5 ms, and the one-workgroup-per-CU kernels of the next frame wait for a CU or run on fewer: cu_reserve).  So: the copy, except with two lanes.
-    const int direct_wgs = c->shared.opt_io_direct >= 0 ? c->shared.opt_io_direct : (c->frames_in_flight == 2 ? 8 : 0);
-    // A copy from / to PAGEABLE memory blocks the calling thread until it is done (the runtime stages it in pieces): nothing is gained by giving it a
-    // stream of its own, so it stays on the context's stream like the copies of the four separate entry points; lanes still overlap each other.
-    unsigned char *const out_pinned = out->on_device ? nullptr : static_cast<unsigned char *>(pinned_device_address(out->scanlines));
-    const hipStream_t s_up = (in->on_device || pinned_device_address(in->data)) ? c->io_up : c->stream;
-    const hipStream_t s_down = out_pinned ? c->io_down : c->stream;
-    unsigned char *host_dev = nullptr;
-    if (out_pinned && direct_wgs > 0 && (reinterpret_cast<uintptr_t>(out->scanlines) & 15) == 0 && (out->row_stride_bytes & 15) == 0) host_dev = out_pinned;
-    c->cu_reserve = host_dev ? direct_wgs * (c->frames_in_flight > 1 ? 2 : 1) : 0;      // (this lane's download and a neighbour's; reset when the lane is done)
-    // the working image of this slot is free again once the download of turn i - 2 has read it
-    if (i >= 2 && !out->on_device) HIPCHK(c, hipStreamWaitEvent(c->stream, c->io_ev[6 + s], 0));
-
-    // ---- upload (io_up) -> copyOriginalPixels + scaleColors (stream)
-    ScaleArgs a = {};
-    a.w = W; a.h = H; a.src_u16 = in->is_u16 ? 1 : 0;
-    if (in->on_device) { a.src = in->data; a.src_stride = (size_t)(in->row_stride_bytes / esz); }
-    else {
-        float *st;
-        if ((rc = pool_get(c, P_IO_IN0 + s, (size_t)W * H * esz, &st))) return rc;
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(s_up, c->io_ev[2 + s], 0));       // the kernel that read this slot two turns ago
-        // (always the pitched form: a LINEAR copy from or to pageable memory makes the runtime pin the caller's pages for the occasion, 25 ms for a frame's scanlines)
-        HIPCHK(c, hipMemcpy2DAsync(st, (size_t)W * esz, in->data, (size_t)in->row_stride_bytes, (size_t)W * esz, H, hipMemcpyHostToDevice, s_up));
-        HIPCHK(c, hipEventRecord(c->io_ev[s], s_up));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->io_ev[s], 0));
-        a.src = st; a.src_stride = W;
-    }
-    a.dst = cfa; a.dst_stride = W;
-    a.bayer = p->sensor == 0 ? 1 : 0;
-    for (int r = 0; r < 6; ++r)
-        for (int col = 0; col < 6; ++col) {
-            int v;
-            if (p->sensor != 0) v = p->xtrans[r * 6 + col];
-            else v = (p->filters >> ((((r << 1) & 14) + (col & 1)) << 1)) & 3;
-            if (v < 0 || v > 2) return fail(c, ARTGPU_EUNSUPPORTED, "batch_run_io: three-colour CFAs only");
-            a.cfa[r * 6 + col] = v;
-        }
-    for (int k = 0; k < 4; ++k) { a.cblacksom[k] = in->cblacksom[k]; a.scale_mul[k] = in->scale_mul[k]; }
-    a.chmax_bits = flags;
-    HIPCHK(c, hipMemsetAsync(flags, 0, 8 * sizeof(int), c->stream));
-    HIPCHK(c, launch_scale_colors(a, c->stream));
-    if (!in->on_device) HIPCHK(c, hipEventRecord(c->io_ev[2 + s], c->stream));
-
-    // ---- the path
-    artgpu_plane raw = {cfa, W, H, (int64_t)W * 4, 1};
-    // CA_correct_RT on the staged CFA plane itself, after scaleColors and before the demosaic (rawimagesource.cc:1666,1827)
-    if (pipeline_ca(p) && (rc = pipeline_ca_dev(c, cfa, W, W, H, p))) return rc;
-    artgpu_rgb image = mk_dev_rgb(img, iw, ih, iw);
-    // (the frame's plan -- pipeline_plan -- runs in here, behind the upload and scaleColors: a refused frame has done that work already.  Planning
-    // ahead of the upload would change what a refused frame leaves behind, so it stays)
-    if ((rc = pipeline_run_impl(c, &raw, p, &image, false))) return rc;
-
-    // ---- rgb2out (matrix + TRC, in place) and the writers' scanlines
-    OutArgs o = {};
-    for (int k = 0; k < 3; ++k) { o.src[k] = img[k]; o.dst[k] = img[k]; }
-    o.src_stride = iw; o.dst_stride = iw; o.w = iw; o.h = ih;
-    if (out->rgb2out_enabled) {
-        for (int k = 0; k < 9; ++k) o.m[k] = out->out_matrix[k];
-        o.linear = out->trc_linear ? 1 : 0;
-        o.unsupported = flags + 4;
-        if (out->trc_lut) {
-            float *tab;
-            if ((rc = pool_get(c, P_PIPE_R, (size_t)65536 * 4, &tab)) || (rc = h2d_table(c, tab, out->trc_lut, (size_t)out->trc_lutsz * 4))) return rc;   // (the demosaiced plane in this slot is done with)
-            o.lut = tab; o.lutsz = out->trc_lutsz;
-        }
-        HIPCHK(c, launch_rgb2out_matrix(o, c->stream));
-    }
-    o.bps = out->bps; o.is_float = out->is_float ? 1 : 0;
-    if (host_dev) {
-        // flags, then the scanlines on the download stream, straight into the caller's buffer
-        HIPCHK(c, hipMemcpyAsync(c->io_host + 8 * i, flags, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->io_ev[4 + s], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->io_down, c->io_ev[4 + s], 0));
-        o.out = host_dev; o.out_stride_bytes = (size_t)out->row_stride_bytes;
-        HIPCHK(c, launch_scanlines_host(o, direct_wgs, c->io_down));
-        HIPCHK(c, hipEventRecord(c->io_ev[6 + s], c->io_down));
-        return ARTGPU_OK;
-    }
-    if (out->on_device) { o.out = static_cast<unsigned char *>(out->scanlines); o.out_stride_bytes = (size_t)out->row_stride_bytes; }
-    else {
-        float *st;
-        if ((rc = pool_get(c, P_IO_OUT0 + s, rowb * ih + 16, &st))) return rc;
-        o.out = reinterpret_cast<unsigned char *>(st); o.out_stride_bytes = rowb;         // (free again: the wait for turn i - 2's download above)
-    }
-    HIPCHK(c, launch_scanlines(o, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->io_host + 8 * i, flags, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (!out->on_device) {
-        HIPCHK(c, hipEventRecord(c->io_ev[4 + s], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(s_down, c->io_ev[4 + s], 0));
-        HIPCHK(c, hipMemcpy2DAsync(out->scanlines, (size_t)out->row_stride_bytes, o.out, rowb, rowb, ih, hipMemcpyDeviceToHost, s_down));
-        HIPCHK(c, hipEventRecord(c->io_ev[6 + s], s_down));
-    }
-    return ARTGPU_OK;
-}
-} // namespace
-
-int artgpu_batch_run_io(artgpu_ctx *ctx, int nframes, const artgpu_sensor_frame *in, const artgpu_pipeline_params *params, artgpu_scanline_frame *out)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (nframes < 0 || (nframes && (!in || !params || !out))) return fail(ctx, ARTGPU_EINVAL, "batch_run_io: null argument");
-    if (nframes == 0) return ARTGPU_OK;
-    const int L = std::min(ctx->batch_lanes, nframes);
-    int rc = batch_prepare_lanes(ctx, L);          // (L == 1: no lanes, frames_in_flight = 1)
-    if (rc) return rc;
-    InFlightReset in_flight_reset{ctx};
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // inputs the caller produced on this context's stream
-    auto px_of = [&](int f) { return (long long)in[f].w * in[f].h; };
-    for (int f = 0; f < nframes; ++f) { out[f].status = ARTGPU_OK; out[f].chmax[0] = out[f].chmax[1] = out[f].chmax[2] = out[f].chmax[3] = 0.f; }
-    rc = batch_on_lanes(ctx, L, [&](artgpu_ctx *c, int k) -> int {
-        const int mine = (nframes - k + L - 1) / L;
-        int rc2 = io_setup(c, mine);
-        for (int f = k, i = 0; !rc2 && f < nframes; f += L, ++i) {
-            rc2 = batch_settle_scratch(c, px_of(f), f + L < nframes ? px_of(f + L) : -1);
-            if (!rc2) rc2 = io_frame(c, i, &in[f], params, &out[f]);
-        }
-        // the lane's copies and kernels, then what the frames left in the pinned words
-        c->cu_reserve = 0;
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (c->io_down) { const hipError_t e2 = hipStreamSynchronize(c->io_down); if (e == hipSuccess) e = e2; }
-        if (c->io_up) { const hipError_t e2 = hipStreamSynchronize(c->io_up); if (e == hipSuccess) e = e2; }
-        if (rc2) return rc2;
-        if (e != hipSuccess) return fail(c, ARTGPU_EHIP, "batch_run_io: lane %d: %s", k, hipGetErrorString(e));
-        if ((rc2 = check_async_faults(c))) return rc2;
-        for (int f = k, i = 0; f < nframes; f += L, ++i) {
-            const int *w = c->io_host + 8 * i;
-            for (int ch = 0; ch < 3; ++ch) std::memcpy(&out[f].chmax[ch], &w[ch], sizeof(float));
-            out[f].chmax[3] = out[f].chmax[1];
-            if (out[f].rgb2out_enabled && w[4]) {
-                out[f].status = ARTGPU_EUNSUPPORTED;
-                if (!rc2) rc2 = fail(c, ARTGPU_EUNSUPPORTED, "batch_run_io: frame %d: %d channel values above 1 need ARTOutputProfile::eval (lcms2/libm) on the host", f, w[4]);
-            }
-        }
-        return rc2;
-    });
-    return rc;
-}
-
-// The one collective of a multi-GPU batch: an all-gather of the ranks' completion records over the caller's RCCL communicator.
-// RCCL is bound at run time (dlopen), so the library has no link-time dependency on it and single-GPU users never load it.
-int artgpu_batch_complete(artgpu_ctx *ctx, void *rccl_comm, int nranks, const int64_t record[ARTGPU_BATCH_RECORD_WORDS], int64_t *all_records)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!record || !all_records || nranks < 1) return fail(ctx, ARTGPU_EINVAL, "batch_complete: bad argument");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the record describes work that has finished
-    if (!rccl_comm) {
-        if (nranks != 1) return fail(ctx, ARTGPU_EINVAL, "batch_complete: %d ranks need a communicator", nranks);
-        std::memcpy(all_records, record, sizeof(int64_t) * ARTGPU_BATCH_RECORD_WORDS);
-        return ARTGPU_OK;
-    }
-    // ncclResult_t ncclAllGather(const void *sendbuff, void *recvbuff, size_t sendcount, ncclDataType_t, ncclComm_t, hipStream_t)
-    typedef int (*allgather_fn)(const void *, void *, size_t, int, void *, hipStream_t);
-    typedef const char *(*errstr_fn)(int);
-    static allgather_fn allgather = nullptr;
-    static errstr_fn errstr = nullptr;
-    if (!allgather) {
-        void *h = nullptr;
-        for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-            if ((h = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-        if (!h) return fail(ctx, ARTGPU_EUNSUPPORTED, "batch_complete: cannot load librccl (%s)", dlerror());
-        allgather = reinterpret_cast<allgather_fn>(dlsym(h, "ncclAllGather"));
-        errstr = reinterpret_cast<errstr_fn>(dlsym(h, "ncclGetErrorString"));
-        if (!allgather) return fail(ctx, ARTGPU_EUNSUPPORTED, "batch_complete: librccl has no ncclAllGather");
-    }
-    constexpr int NCCL_INT64 = 4;       // ncclDataType_t (nccl.h): ncclInt8 0, ncclUint8 1, ncclInt32 2, ncclUint32 3, ncclInt64 4
-    const size_t words = ARTGPU_BATCH_RECORD_WORDS;
-    float *buf;
-    int rc = pool_get(ctx, P_BATCH, (size_t)(nranks + 1) * words * sizeof(int64_t), &buf);
-    if (rc) return rc;
-    int64_t *d_send = reinterpret_cast<int64_t *>(buf), *d_recv = d_send + words;
-    HIPCHK(ctx, hipMemcpyAsync(d_send, record, words * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    const int nrc = allgather(d_send, d_recv, words, NCCL_INT64, rccl_comm, ctx->stream);
-    if (nrc != 0) return fail(ctx, ARTGPU_EHIP, "batch_complete: ncclAllGather failed: %s", errstr ? errstr(nrc) : "?");
-    HIPCHK(ctx, hipMemcpyAsync(all_records, d_recv, (size_t)nranks * words * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return ARTGPU_OK;
 }
 

@@ -1,0 +1,36 @@
+"""CPU: the dynamic symbol table of the built libartgpu.so against include/artgpu.h, without loading the library.
+The C ABI is defined in several host files (artgpu_api.hip, api_pipeline.hip, api_batch.hip); an entry point that ends up outside
+`extern "C"` still links -- under its C++-mangled name -- and fails only at the first ctypes call.  Every function the header declares must be defined under its plain name, and nothing named
+artgpu_* may be exported that the header does not declare."""
+import os
+import re
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "art_amd", "libartgpu.so")
+HEADER = os.path.join(ROOT, "include", "artgpu.h")
+
+
+def _declared():
+    text = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)      # a comment may name a function with its parentheses
+    text = re.sub(r"//[^\n]*", " ", text)
+    return set(m.group(1) for m in re.finditer(r"\b(artgpu_\w+)\s*\(", text))
+
+
+def _defined():
+    out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
+    return set(line.split()[-1] for line in out.splitlines() if line.split())
+
+
+def test_header_and_dynamic_symbols_agree():
+    # the test pins what the build exports: a missing library or a missing nm is a failure, not a skip
+    assert os.path.exists(LIB), "art_amd/libartgpu.so is not built (python -c 'import __graft_entry__ as g; g.build()')"
+    assert shutil.which("nm") is not None, "no nm to read the dynamic symbol table"
+    declared, defined = _declared(), _defined()
+    assert len(declared) > 50, "the header's declarations were not found"
+    missing = sorted(declared - defined)
+    assert not missing, f"declared in include/artgpu.h, not defined (unmangled) in libartgpu.so: {missing}"
+    undeclared = sorted(n for n in defined - declared if n.startswith("artgpu_"))
+    assert not undeclared, f"exported by libartgpu.so, not declared in include/artgpu.h: {undeclared}"

@@ -1,4 +1,4 @@
-"""CPU: the stream / event protocol of artgpu_batch_run_io (art_amd/csrc/artgpu_api.hip io_frame) replayed as a discrete-event model.
+"""CPU: the stream / event protocol of artgpu_batch_run_io (art_amd/csrc/api_batch.hip io_frame) replayed as a discrete-event model.
 
 Per lane: an upload stream, the context's stream and a download stream; two staging slots on each side and two working images, picked by
 the parity of the frame's turn.  The model queues exactly the operations io_frame queues, in its order, with HIP's semantics -- a stream
