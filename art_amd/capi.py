@@ -194,6 +194,32 @@ def smoothing_regions(regions):
     return arr, keep
 
 
+class ToneEqualizerParams(C.Structure):
+    """artgpu_tone_equalizer_params: ToneEqualizerParams (defaults procparams.cc:2097-2104)"""
+    _fields_ = [("enabled", C.c_int32), ("bands", C.c_int32 * 5), ("regularization", C.c_int32), ("show_colormap", C.c_int32), ("pivot", C.c_double)]
+
+
+class ToneEqualizerInfo(C.Structure):
+    """artgpu_tone_equalizer_info: what the host derived"""
+    _fields_ = [("gain", C.c_float), ("w_sum", C.c_float), ("factors", C.c_float * 12), ("filters", C.c_int32), ("radius", C.c_int32 * 3),
+                ("subsampling", C.c_int32 * 3), ("box_radius", C.c_int32 * 3), ("epsilon", C.c_float * 3)]
+
+
+def tone_equalizer_params(bands=(0, 0, 0, 0, 0), regularization=4, pivot=0.0, enabled=True, show_colormap=False) -> ToneEqualizerParams:
+    assert len(bands) == 5
+    return ToneEqualizerParams(int(bool(enabled)), (C.c_int32 * 5)(*[int(b) for b in bands]), int(regularization), int(bool(show_colormap)), float(pivot))
+
+
+def tone_equalizer_lut(params: ToneEqualizerParams):
+    """the tool's correction table (65536 float32) and a ToneEqualizerInfo with gain, w_sum and factors, built on the host (no context)"""
+    lut = np.empty(65536, np.float32)
+    info = ToneEqualizerInfo()
+    rc = LIB.artgpu_tone_equalizer_lut(C.byref(params), lut.ctypes.data_as(C.POINTER(C.c_float)), C.byref(info))
+    if rc:
+        raise ArtGpuError(f"artgpu_tone_equalizer_lut: error {rc}")
+    return lut, info
+
+
 class MaskParams(C.Structure):
     """artgpu_mask_params: one rtengine::procparams::Mask as the parametric path of generateMasks reads it"""
     _fields_ = [("parametric_enabled", C.c_int32), ("lightness_detail", C.c_int32), ("hue", C.POINTER(C.c_double)),
@@ -492,6 +518,10 @@ def _load():
     lib.artgpu_smoothing.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(SmoothingRegion), C.c_int, C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(SmoothingInfo)]
     lib.artgpu_set_pipeline_smoothing.argtypes = [C.c_void_p, C.POINTER(SmoothingRegion), C.c_int, C.POINTER(MaskParams)]
+    lib.artgpu_tone_equalizer.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(ToneEqualizerParams), C.POINTER(C.c_double), C.c_double,
+                                          C.POINTER(ToneEqualizerInfo)]
+    lib.artgpu_tone_equalizer_lut.argtypes = [C.POINTER(ToneEqualizerParams), C.POINTER(C.c_float), C.POINTER(ToneEqualizerInfo)]
+    lib.artgpu_set_pipeline_tone_equalizer.argtypes = [C.c_void_p, C.POINTER(ToneEqualizerParams)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -573,7 +603,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
            "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
            "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks",
-           "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing"]
+           "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing",
+           "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -854,6 +885,20 @@ class Context:
         assert not masks or len(masks) == len(regions or [])
         self._chk(LIB.artgpu_set_pipeline_smoothing(self._h, arr if regions else None, len(regions or []), mk if masks else None))
         del k1, k2
+
+    def tone_equalizer(self, image: RGB, params: ToneEqualizerParams, ws, scale: float = 1.0, want_info: bool = False):
+        """ImProcFunctions::toneEqualizer in place on an RGB image (params from tone_equalizer_params()); returns the ToneEqualizerInfo when
+        want_info."""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        info = ToneEqualizerInfo() if want_info else None
+        self._chk(LIB.artgpu_tone_equalizer(self._h, C.byref(image), C.byref(params), wsd, float(scale), C.byref(info) if want_info else None))
+        return info
+
+    tone_equalizer_lut = staticmethod(tone_equalizer_lut)
+
+    def set_pipeline_tone_equalizer(self, params: ToneEqualizerParams = None):
+        """the tone equalizer pipeline_run / batch_run / batch_run_io run behind the exposure (None: off).  The library copies it."""
+        self._chk(LIB.artgpu_set_pipeline_tone_equalizer(self._h, C.byref(params) if params is not None else None))
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""

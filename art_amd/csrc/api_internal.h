@@ -3,7 +3,8 @@
 // io_frame (api_batch.hip).  This header is the list of what a stage exposes to the driver; everything a stage uses only itself stays
 // static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api, declared with hidden visibility:
 // none of them is in the library's dynamic symbol table (a definition inherits nothing from its declaration here: every opening of
-// the namespace carries the attribute).  Each is defined once (the helpers and the stages in artgpu_api.hip); none is inline.
+// the namespace carries the attribute).  Each is defined once (the helpers and the stages in artgpu_api.hip, the tone equalizer in
+// api_toneequalizer.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -23,6 +24,7 @@
 #include "textureboost.h"
 #include "colorcorrection.h"
 #include "smoothing.h"
+#include "toneequalizer.h"
 #include "masks.h"
 #include "sharpen.h"
 
@@ -41,6 +43,8 @@ struct artgpu_ctx {
     struct Shared {
         // options (artgpu_set_option): test / profiling switches that used to be environment variables
         int opt_sharpen_fused = 1;     // RL deconvolution, stencil regimes -- 1: one kernel per iteration (rl_iter_kernel); 0: DIV, MULT and check_stop as three launches (timing)
+        int opt_te_group_thread = 0;   // tone equalizer, the group-of-four rule -- 0: one pixel per lane, the decision from a ballot; 1: one thread per group (tests, timing)
+        int opt_te_fuse_upsample = 1;  // tone equalizer -- 1: the last regularising filter's up-sample happens in te_apply; 0: it writes Y, te_apply reads it (tests, timing)
         int opt_lut_lds = 1;           // 0: never the LUT-in-LDS shapes of the pixel passes (tests compare the two)
         int opt_dn_streams = 0;        // 1: the DCT detail recovery of L on a side stream beside the reconstructions of a and b.  The default until round 5, when the
                                        // stage waited on LDS round trips and left the chip half idle; since detail_blocks_kernel lost a fifth of its time (detail.hip) the
@@ -79,6 +83,8 @@ struct artgpu_ctx {
         const artgpu_smoothing_region *pipe_sm = nullptr;
         const artgpu_mask_params *pipe_sm_masks = nullptr;
         int pipe_nsm = 0;
+        int pipe_te_on = 0;            // artgpu_set_pipeline_tone_equalizer: a copy by value
+        artgpu_tone_equalizer_params pipe_te = {};
     } shared;
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
@@ -138,6 +144,9 @@ struct artgpu_ctx {
     bool tab_ring_busy = false;
     hipEvent_t tab_ev = nullptr;
     std::vector<float> rgbcurve_host[3];   // likewise the three rgbCurves tables (P_RGBCURVES: a slot nothing else writes)
+    std::vector<float> te_lut_host;        // the tone equalizer's correction table (65536 entries), the bands it was built from, and where in
+    int te_lut_bands[5] = {};              // P_TE_LUT (a slot nothing else writes) it was uploaded to: rebuilt when the bands change, uploaded
+    const float *te_lut_dev = nullptr;     // again when the slot moved (artgpu_trim_scratch)
     // timing
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -203,6 +212,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_MK_WORK, P_MK_TAB, P_MK_CTHR, P_MK_AREA, P_MK_OUT,                                                             // artgpu_generate_masks
        P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
        P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
+       P_TE_PLANES, P_TE_LUT,                                                                                           // artgpu_tone_equalizer
        P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
@@ -321,6 +331,22 @@ int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regio
 int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl);
 int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
                   artgpu_smoothing_info *info, const char *who);
+
+// ---------------------------------------------------------------------------------------------
+// guided filter (shared by the tools that call rtengine::guidedFilter)
+// ---------------------------------------------------------------------------------------------
+int gf_subsampling(int w, int h, int r);
+int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, int W, int H, int r, float epsilon, int subsampling, const char *who, GuidedArgs *g);
+int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
+                      const char *who);
+
+// ---------------------------------------------------------------------------------------------
+// tone equalizer
+// ---------------------------------------------------------------------------------------------
+// what a call derives on the host before any kernel runs: artgpu_tone_equalizer_info is the plan (filters, radii, grids' subsampling, box radii)
+int te_check(artgpu_ctx *ctx, int W, int H, const artgpu_tone_equalizer_params *p, const double *ws, double scale, const char *who, artgpu_tone_equalizer_info *pl);
+int tone_equalizer_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_tone_equalizer_params *p, const double ws[9],
+                       const artgpu_tone_equalizer_info &pl, const char *who);
 
 // ---------------------------------------------------------------------------------------------
 // capture sharpening

@@ -94,6 +94,8 @@ struct PipePlan {
     MkPlan lc_mk, tb_mk, cc_mk, sm_mk;
     CcPlan cc;
     DehazePlan dehaze;
+    bool te_on;                                                    // the tone equalizer (artgpu_set_pipeline_tone_equalizer, enabled)
+    artgpu_tone_equalizer_info te;
     bool sh_on, sh_auto, sh_radius_pending;
     artgpu_sharpening_params shpar;                                // (deconvradius: 0.75 stands in while the automatic radius is pending)
     SharpenPlan sharpen;
@@ -128,7 +130,7 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 //   1. ctx, raw / p / out, the border, the output's size (then hipSetDevice, the one HIP call here)   2. artgpu_set_pipeline_masks' counts against the frame's
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
-//   8. dehaze_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
+//   8. dehaze_check, te_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
 static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, PipePlan *pl)
 {
     if (!ctx) return ARTGPU_EINVAL;
@@ -196,6 +198,8 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     }
     if (pl->lc_on && (rc = local_contrast_check(ctx, w, h, pl->lc_regions, nlc, scale, "pipeline_run(local contrast)"))) return rc;
     if (p->dehaze_enabled && (rc = dehaze_check(ctx, w, h, &p->dehaze, p->ws, scale, "pipeline_run(dehaze)", &pl->dehaze))) return rc;
+    pl->te_on = s.pipe_te_on && s.pipe_te.enabled;
+    if (pl->te_on && (rc = te_check(ctx, w, h, &s.pipe_te, p->ws, scale, "pipeline_run(tone equalizer)", &pl->te))) return rc;
     // sharpening (STAGE_2): method, scale and, with the automatic radius, the sensor are checked before any stage runs
     pl->shpar = p->sharpening;
     pl->sh_on = p->sharpening_enabled != 0;
@@ -256,7 +260,8 @@ static int pipe_demosaic(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const
     return ARTGPU_OK;
 }
 
-// From the demosaiced planes to the exposed image: denoiseComputeParams, getImage + convertColorSpace + the denoise tool, dehaze (STAGE_0), the exposure (STAGE_1)
+// From the demosaiced planes to the exposed image: denoiseComputeParams, getImage + convertColorSpace + the denoise tool, dehaze (STAGE_0), the exposure and
+// the tone equalizer (STAGE_1)
 static int pipe_input(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, PipeFrame *fr)
 {
     const double *cam_to_work = p->has_cam_to_work ? p->cam_to_work : nullptr;
@@ -288,7 +293,9 @@ static int pipe_input(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const Pi
     } else if ((rc = artgpu_get_image(ctx, &fr->dem, pl.b, pl.b, p->mul, p->do_clip, cam_to_work, &fr->img))) return rc;
     // ImProcFunctions::dehaze, STAGE_0 of ImProcFunctions::process (improcfun.cc:577), ahead of the exposure (STAGE_1)
     if (p->dehaze_enabled && (rc = dehaze_dev(ctx, d.p, d.stride, d.w, d.h, &p->dehaze, p->ws, pl.dehaze, nullptr))) return rc;
-    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled)) return artgpu_exposure(ctx, &fr->img, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0));
+    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled) && (rc = artgpu_exposure(ctx, &fr->img, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0)))) return rc;
+    // ImProcFunctions::toneEqualizer, the last step of STAGE_1 (improcfun.cc:588), behind the exposure wherever that ran
+    if (pl.te_on) return tone_equalizer_dev(ctx, d.p, d.stride, d.w, d.h, &ctx->shared.pipe_te, p->ws, pl.te, "pipeline_run(tone equalizer)");
     return ARTGPU_OK;
 }
 

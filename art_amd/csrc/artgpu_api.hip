@@ -398,6 +398,8 @@ int artgpu_get_option(artgpu_ctx *ctx, const char *name, long *value)
         return ARTGPU_OK;
     }
     if (n == "dn_mad_fold") { *value = ctx->shared.opt_dn_mad_fold; return ARTGPU_OK; }
+    if (n == "te_group_thread") { *value = ctx->shared.opt_te_group_thread; return ARTGPU_OK; }
+    if (n == "te_fuse_upsample") { *value = ctx->shared.opt_te_fuse_upsample; return ARTGPU_OK; }
     if (n.rfind("dn_mad_bits", 0) == 0 && n.size() > 11) {
         // the bit pattern of word k (0 .. 95) of the last RGB_denoise call's SQR(MadRgb) block: L at 0, a at 32, b at 64 -- or, with one MadRgb
         // launch set for the three channels, all bands back to back from 0 (DESIGN 28 lists a frame's median bins from these)
@@ -447,6 +449,8 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
     else if (n == "dn_debug_stall") ctx->shared.opt_dn_debug_stall = (int)value;
     else if (n == "dn_wait_ms") ctx->shared.opt_dn_wait_ms = value < 0 ? 0 : value;
     else if (n == "lut_lds") ctx->shared.opt_lut_lds = value != 0;
+    else if (n == "te_group_thread") ctx->shared.opt_te_group_thread = value != 0;
+    else if (n == "te_fuse_upsample") ctx->shared.opt_te_fuse_upsample = value != 0;
     else if (n == "sharpen_fused") ctx->shared.opt_sharpen_fused = value != 0;
     else if (n == "cu_reserve") { if (value < 0 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "cu_reserve: 0 .. 4096"); ctx->cu_reserve = (int)value; }
     else if (n == "io_direct") { if (value < -1 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "io_direct: -1 (automatic), 0 .. 4096 workgroups"); ctx->shared.opt_io_direct = (int)value; }
@@ -508,6 +512,7 @@ int artgpu_trim_scratch(artgpu_ctx *ctx)
     ctx->dn_fold_flags = nullptr; ctx->dn_fold_nranges = 0;
     ctx->ncurve_host.clear();
     for (int k = 0; k < 3; ++k) ctx->rgbcurve_host[k].clear();
+    ctx->te_lut_dev = nullptr;
     int rc = ARTGPU_OK;
     for (artgpu_ctx *l : ctx->lanes) { const int r = artgpu_trim_scratch(l); if (r && !rc) rc = r; }
     return rc;
@@ -1781,7 +1786,7 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
 // guided chroma smoothing
 // ---------------------------------------------------------------------------------------------
 } // extern "C"
-namespace {
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
 int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter.cc:58-75)
 {
     if (r == 1) return 1;
@@ -1791,7 +1796,7 @@ int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter
     const int t = r / 2;
     return t < 2 ? 2 : (t > 4 ? 4 : t);
 }
-}
+} }
 extern "C" {
 
 int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const double ws[9], int guided_chroma_radius, double scale)
@@ -1843,21 +1848,28 @@ int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const doub
     return unbind_rgb(ctx, img, &d);
 }
 
-// rtengine::guidedFilter (guidedfilter.cc:80-241) on contiguous device planes (rows of W floats), q with rows of q_stride floats; q may be
-// `guide` or `src` (the last pass is pointwise).  Enqueued on ctx->stream; scratch: the statistics grid in P_TMP / P_LIN
-static int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
-                             const char *who)
+} // extern "C"
+namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+
+// rtengine::guidedFilter (guidedfilter.cc:80-241) on contiguous device planes (rows of W floats) up to mean a / mean b on the statistics grid
+// (g->low[2], g->low[5]): the caller runs the last, pointwise pass (launch_gf_finish_plain with g->q, or one of its own).  Enqueued on
+// ctx->stream; scratch: the statistics grid in P_TMP / P_LIN
+int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, int W, int H, int r, float epsilon, int subsampling, const char *who, GuidedArgs *gout)
 {
     const int sub = subsampling > 0 ? subsampling : gf_subsampling(W, H, r);
-    GuidedArgs g = {};
+    GuidedArgs &g = *gout;
+    g = GuidedArgs{};
     g.W = W; g.H = H; g.w = W / sub; g.h = H / sub; g.epsilon = epsilon; g.nch = 1;
     if (g.w < 1 || g.h < 1) return fail(ctx, ARTGPU_EINVAL, "%s: subsampling %d leaves no pixels", who, sub);
     const size_t nl = (size_t)g.w * g.h;
     float *low, *tmp;
     int rc;
     if ((rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
-    g.guide = const_cast<float *>(guide); g.chan[0] = const_cast<float *>(src); g.q = q; g.q_stride = q_stride;
-    for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
+    g.guide = const_cast<float *>(guide); g.chan[0] = const_cast<float *>(src);
+    // the four planes the single-channel statistics use lie next to each other, so that one blur launch takes them all (a grid plane of a
+    // subsampled frame is a few dozen workgroups: plane after plane the chip idles); the slots of channels 1 and 2 follow them, unused
+    static const int order[8] = {0, 1, 2, 5, 3, 4, 6, 7};
+    for (int k = 0; k < 8; ++k) g.low[order[k]] = low + k * nl;
     const float r1 = float(r) / sub;
     int rad = (int)r1;
     { const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }     // f_mean's LIM (L160-164)
@@ -1866,21 +1878,35 @@ static int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *s
     BlurArgs bl = {};
     bl.n = nl; bl.w = g.w; bl.h = g.h; bl.steady_div = 1; bl.plain = 1;
     for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    auto blur_plane = [&](float *plane) -> int {
+    auto blur_planes = [&](float *planes, int count) -> int {
         if (rad == 0) return ARTGPU_OK;
-        bl.src = plane; bl.dst = tmp;
-        HIPCHK(ctx, launch_hblur(bl, 1, ctx->stream));
-        bl.src = tmp; bl.dst = plane; bl.sfave = nullptr; bl.coef = nullptr;
-        HIPCHK(ctx, launch_vblur_combine(bl, 1, ctx->stream));
+        bl.src = planes; bl.dst = tmp;
+        HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
+        bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
+        HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
         return ARTGPU_OK;
     };
     // low[0] I1 -> meanI, low[1] I1*I1 -> corrI, low[2] p1 -> meanp, low[5] I1*p1 -> corrIp
-    if ((rc = blur_plane(g.low[0])) || (rc = blur_plane(g.low[1])) || (rc = blur_plane(g.low[2])) || (rc = blur_plane(g.low[5]))) return rc;
+    if ((rc = blur_planes(g.low[0], 4))) return rc;
     HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-    if ((rc = blur_plane(g.low[2])) || (rc = blur_plane(g.low[5]))) return rc;       // mean a, mean b
+    if ((rc = blur_planes(g.low[2], 2))) return rc;                                    // mean a, mean b
+    return ARTGPU_OK;
+}
+
+// ... and the whole filter: q with rows of q_stride floats; q may be `guide` or `src` (the last pass is pointwise)
+int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
+                      const char *who)
+{
+    GuidedArgs g;
+    int rc;
+    if ((rc = guided_filter_stats(ctx, guide, src, W, H, r, epsilon, subsampling, who, &g))) return rc;
+    g.q = q; g.q_stride = q_stride;
     HIPCHK(ctx, launch_gf_finish_plain(g, ctx->stream));
     return ARTGPU_OK;
 }
+
+} } // namespace artgpu::api
+extern "C" {
 
 int artgpu_guided_filter(artgpu_ctx *ctx, const artgpu_plane *guide, const artgpu_plane *src, artgpu_plane *dst, int r, float epsilon, int subsampling)
 {

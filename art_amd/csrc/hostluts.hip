@@ -3,9 +3,12 @@
 //   FlatCurve (FCT_MinMaxCPoints) polyline     rtengine/flatcurves.cc:27-77,124-360, rtengine/curves.cc:98-132
 //   NoiseCurve::Set -> 501-entry LUT + sum     rtengine/ipdenoise.cc:684-716
 //   Color::cachef                              rtengine/color.cc:178,202-217
+//   tone_eq's correction table                 rtengine/iptoneequalizer.cc:95-114,160-190,305-310 (scalar sleef forms, sleef.h)
 #include "kernels.h"
+#include "toneequalizer.h"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace artgpu {
@@ -309,6 +312,92 @@ void dninfo_reduce(const float info[9][16], bool aggressive, float ch_M[9], floa
         maxr = mean_dn_r + (low_r - mean_dn_r) * 0.66f;
     }
     out3[0] = chM / nr; out3[1] = maxr; out3[2] = maxb;
+}
+
+// ---------------------------------------------------------------- tone equalizer: the correction table
+// The scalar xlogf / xexpf / pow_F of rtengine/sleef.h:938-966,1198-1265,1296-1300 on the host, statement for statement the forms devsleef.h
+// holds for the device (this file is compiled with -ffp-contract=off as well).
+namespace {
+
+inline int hs_f2i(float f) { int i; std::memcpy(&i, &f, 4); return i; }
+inline float hs_i2f(int i) { float f; std::memcpy(&f, &i, 4); return f; }
+inline float hs_mla(float x, float y, float z) { return x * y + z; }
+inline int hs_ilogbp1f(float d)
+{
+    const bool m = d < 5.421010862427522E-20f;
+    d = m ? 1.8446744073709552E19f * d : d;
+    const int q = (hs_f2i(d) >> 23) & 0xff;
+    return m ? q - (64 + 0x7e) : q - 0x7e;
+}
+inline float hs_ldexpkf(float x, int q)
+{
+    int m = q >> 31;
+    m = (((m + q) >> 6) - m) << 4;
+    q = q - (m << 2);
+    float u = hs_i2f((m + 0x7f) << 23);
+    u = u * u;
+    x = x * u * u;
+    u = hs_i2f((q + 0x7f) << 23);
+    return x * u;
+}
+float hs_xexpf(float d)
+{
+    if (d <= -104.0f) return 0.0f;
+    const int q = (int)std::lrintf(d * 1.442695040888963407359924681001892137426645954152985934135449406931f);   // xrintf: to nearest even
+    float s = hs_mla((float)q, -0.693145751953125f, d);
+    s = hs_mla((float)q, -1.428606765330187045e-06f, s);
+    float u = 0.00136324646882712841033936f;
+    u = hs_mla(u, s, 0.00836596917361021041870117f);
+    u = hs_mla(u, s, 0.0416710823774337768554688f);
+    u = hs_mla(u, s, 0.166665524244308471679688f);
+    u = hs_mla(u, s, 0.499999850988388061523438f);
+    u = hs_mla(s, hs_mla(s, u, 1.f), 1.f);
+    return hs_ldexpkf(u, q);
+}
+float hs_xlogf(float d)
+{
+    const int e = hs_ilogbp1f(d * 0.7071f);
+    const float m = hs_ldexpkf(d, -e);
+    float x = (m - 1.0f) / (m + 1.0f);
+    const float x2 = x * x;
+    float t = 0.2371599674224853515625f;
+    t = hs_mla(t, x2, 0.285279005765914916992188f);
+    t = hs_mla(t, x2, 0.400005519390106201171875f);
+    t = hs_mla(t, x2, 0.666666567325592041015625f);
+    t = hs_mla(t, x2, 2.0f);
+    x = x * t + 0.693147180559945286226764f * (float)e;
+    if (d == INFINITY) x = INFINITY;
+    if (d < 0.f) x = NAN;
+    if (d == 0.f) x = -INFINITY;
+    return x;
+}
+inline float hs_pow_F(float a, float b) { return hs_xexpf(b * hs_xlogf(a)); }
+
+} // namespace
+
+// gain (iptoneequalizer.cc:354), factors (L95-114), w_sum (L167-170) and lut[i] = process_pixel(i / 65535.f) (L175-190, L305-310)
+void te_build_lut(const int bands[5], double pivot, float *lut, float *gain, float *w_sum, float factors[12])
+{
+    const float l2 = hs_xlogf(2.f);
+    const auto conv = [](int v, float lo, float hi) -> float { const float f = v < 0 ? lo : hi; return hs_pow_F(2.f, float(v) / 100.f * f); };
+    const auto gauss = [](float b, float x) -> float { return hs_xexpf(-((x - b) * (x - b)) / 4.0f); };
+    for (int c = 0; c < 12; ++c) {
+        const int band = c < 5 ? 0 : (c < 8 ? c - 4 : 4);
+        factors[c] = band < 2 ? conv(bands[band], 2.f, 3.f) : (band == 2 ? conv(bands[2], 2.5f, 2.5f) : conv(bands[band], 3.f, 2.f));
+    }
+    *gain = (float)(1.f / 65535.f * std::pow(2.f, -pivot));     // float * double, narrowed at the initialisation
+    float ws = 0.f;
+    for (int c = 0; c < 12; ++c) ws += gauss(-16.f + 2.f * c, 0.f);
+    *w_sum = ws;
+    if (!lut) return;
+    for (int i = 0; i < 65536; ++i) {
+        const float y = float(i) / 65535.f;
+        const float l = hs_xlogf(y < 0.f ? 0.f : y) / l2;
+        const float luma = std::max(-14.f, std::min(l, 4.f));
+        float corr = 0.f;
+        for (int c = 0; c < 12; ++c) corr += gauss(-16.f + 2.f * c, luma) * factors[c];
+        lut[i] = corr / ws;
+    }
 }
 
 } // namespace artgpu

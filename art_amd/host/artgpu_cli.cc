@@ -28,8 +28,10 @@
 //                                                      a value that starts with a digit is the denoiser's --smoothing radius,nlStrength,nlDetail)
 //              [--smoothing-mask lo,hi[,blur[,detail[,threshold[,opacity]]]]]   (a parametric mask on that region, in the form of
 //                                                      --color-correction-mask: generateMasks makes its Lmask on the device)
+//              [--tone-equalizer b0,b1,b2,b3,b4[,regularization[,pivot]]]   (ImProcFunctions::toneEqualizer, the last step of STAGE_1: the five bands
+//                                                      -100 .. 100, regularization 0 .. 4 (default 4), pivot in EV (default 0))
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
+//              [--tone-equalizer ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <cctype>
@@ -100,6 +102,9 @@ int main(int argc, char **argv)
     bool smm_enable = false;                                       // a parametric Mask on the smoothing region
     double smm_lo = 0.0, smm_hi = 1.0, smm_blur = 0.0;
     int smm_detail = 0, smm_threshold = 0, smm_opacity = 100;
+    bool te_enable = false;                                        // ToneEqualizerParams
+    int te_bands[5] = {0, 0, 0, 0, 0}, te_reg = 4;
+    double te_pivot = 0.0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -238,6 +243,12 @@ int main(int argc, char **argv)
             }
             smm_enable = true;
         }
+        else if (a == "--tone-equalizer") {
+            if (std::sscanf(next(), "%d,%d,%d,%d,%d,%d,%lf", &te_bands[0], &te_bands[1], &te_bands[2], &te_bands[3], &te_bands[4], &te_reg, &te_pivot) < 5) {
+                std::fprintf(stderr, "--tone-equalizer b0,b1,b2,b3,b4[,regularization[,pivot]]\n"); return 2;
+            }
+            te_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     ProcParams::Mask cc_mask;
@@ -271,6 +282,8 @@ int main(int argc, char **argv)
         if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
         params.colorcorrection.enabled = cc_enable; params.colorcorrection.regions = {cc_region};
         if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
+        params.toneEqualizer.enabled = te_enable; params.toneEqualizer.regularization = te_reg; params.toneEqualizer.pivot = te_pivot;
+        for (int k = 0; k < 5; ++k) params.toneEqualizer.bands[k] = te_bands[k];
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
             BatchQueue q(ctx, 16);
@@ -350,6 +363,8 @@ int main(int argc, char **argv)
         if (tbm_enable) params.textureBoost.masks = {ProcParams::TextureBoostMask{true, nullptr, &tb_mask}};
         params.colorcorrection.enabled = cc_enable; params.colorcorrection.regions = {cc_region};
         if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
+        params.toneEqualizer.enabled = te_enable; params.toneEqualizer.regularization = te_reg; params.toneEqualizer.pivot = te_pivot;
+        for (int k = 0; k < 5; ++k) params.toneEqualizer.bands[k] = te_bands[k];
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
         params.localContrast.enabled = lc_enable;

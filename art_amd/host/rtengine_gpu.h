@@ -219,6 +219,16 @@ struct ProcParams {
         }
         return regions;
     }
+    // ToneEqualizerParams (procparams.cc:2097-2104)
+    struct { bool enabled = false; int bands[5] = {0, 0, 0, 0, 0}; int regularization = 4; bool show_colormap = false; double pivot = 0; } toneEqualizer;
+    artgpu_tone_equalizer_params toneEqualizerParams() const
+    {
+        const auto &t = toneEqualizer;
+        artgpu_tone_equalizer_params q = {};
+        q.enabled = t.enabled ? 1 : 0; q.regularization = t.regularization; q.show_colormap = t.show_colormap ? 1 : 0; q.pivot = t.pivot;
+        for (int k = 0; k < 5; ++k) q.bands[k] = t.bands[k];
+        return q;
+    }
     // SmoothingParams (procparams.cc:2753-2775, procparams.h:1289-1347): regions with the reference's defaults (mode GUIDED, channel RGB);
     // masks[i].enabled and either the blend plane the application's generateMasks made of masks[i] (`blend`; nullptr = all ones) or the Mask itself
     struct SmoothingRegion {
@@ -376,14 +386,14 @@ public:
     ImProcFunctions(Context &c, const ProcParams *p, double scale = 1.0) : ctx(c), params(p), scale(scale) {}
 
     // ImProcFunctions::process (improcfun.cc:567-641): same step order; steps that are disabled / identity in the
-    // default ProcParams and not on the device path (DRC, toneEqualizer, impulse denoise, defringe, ... blackAndWhite) are
+    // default ProcParams and not on the device path (DRC, impulse denoise, defringe, ... blackAndWhite) are
     // skipped here exactly as their `enabled == false` early-outs skip them.  STAGE_2 holds capture sharpening, its first step.
     bool process(Pipeline pipeline, Stage stage, Imagefloat *img)
     {
         cur_pipeline = pipeline;
         switch (stage) {
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
-        case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); break;      // improcfun.cc:581-585
+        case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); toneEqualizer(img); break;   // improcfun.cc:581-588
         case Stage::STAGE_2: sharpening(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595, 601, 602
         case Stage::STAGE_3: textureBoost(img); logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:606-625 (the steps this library has)
         }
@@ -473,6 +483,17 @@ public:
         }
         artgpu_rgb i = img->view();
         ctx.check(artgpu_smoothing(ctx.get(), &i, regions.data(), (int)regions.size(), params->workingSpace, scale, nullptr));
+        return false;
+    }
+    // ImProcFunctions::toneEqualizer (iptoneequalizer.cc:345-371).  show_colormap only exists in the PREVIEW pipeline (L365) and is not on the device
+    // path: elsewhere the flag is dropped as the reference drops it, there the library refuses it
+    bool toneEqualizer(Imagefloat *img)
+    {
+        if (!params->toneEqualizer.enabled) return false;
+        artgpu_tone_equalizer_params tp = params->toneEqualizerParams();
+        tp.show_colormap = tp.show_colormap && cur_pipeline == Pipeline::PREVIEW;
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_tone_equalizer(ctx.get(), &i, &tp, params->workingSpace, scale, nullptr));
         return false;
     }
     // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
@@ -735,6 +756,10 @@ public:
         }
         ctx.check(artgpu_set_pipeline_smoothing(ctx.get(), sm_regions.empty() ? nullptr : sm_regions.data(), (int)sm_regions.size(),
                                                 sm_mp.empty() ? nullptr : sm_mp.data()));
+        // ImProcFunctions::toneEqualizer behind the exposure (the batch queue is the OUTPUT pipeline: no colour map)
+        artgpu_tone_equalizer_params te = p.toneEqualizerParams();
+        te.show_colormap = 0;
+        ctx.check(artgpu_set_pipeline_tone_equalizer(ctx.get(), p.toneEqualizer.enabled ? &te : nullptr));
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -750,6 +775,7 @@ public:
         (void)artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, nullptr, 0);
         (void)artgpu_set_pipeline_color_correction(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_smoothing(ctx.get(), nullptr, 0, nullptr);
+        (void)artgpu_set_pipeline_tone_equalizer(ctx.get(), nullptr);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

@@ -936,6 +936,42 @@ typedef struct artgpu_smoothing_info {    /* one per region: what the host deriv
 int artgpu_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_smoothing_region *regions, int nregions, const double ws[9], double scale,
                      artgpu_smoothing_info *info /* nregions entries or NULL */);
 
+/* ImProcFunctions::toneEqualizer (rtengine/iptoneequalizer.cc:345-371) and its tone_eq (L69-340), ART's shadows / midtones / highlights tool:
+ * the last step of STAGE_1, behind exposure and hslEqualizer (improcfun.cc:580-588).  `img`: RGB mode, 0..65535, host or device, any row
+ * stride or start alignment, in place.  enabled == 0 returns at once.  gain = (float)(1.f / 65535.f * pow(2.f, -pivot)); the image times
+ * gain, tone_eq, the image times 1.f / gain -- the two scaled images are never stored, ((R * gain) * corr) * (1.f / gain) has the same roundings.
+ *   Y = LIM(rgbLuminance(R, G, B, ws), 1e-5f, 32.f) with the double matrix;
+ *   regularization > 0: guidedFilterLog(10.f, Y, radius = int(5.f / scale + 0.5f), 0.014f) when radius > 0 (self-guided, in log form);
+ *   regularization > 1: Y2 = Y, Y = exp2(round(LIM(log2(max(Y, 1e-9f)), -16, 6) * 5.f) / 5.f), guidedFilter(Y2, Y, Y, r = int(350.f / scale),
+ *     0.004f) and, with reg = 5 - min(regularization, 4) > 1, guidedFilter(Y2, Y, Y, r * (reg - 1), 0.004f / 100);
+ *   corr: for the columns below 4 * (W / 4), in groups of four counted from column 0 of the row: vprocess_pixel (the 4-lane xlogf / xexpf)
+ *     for all four when any of their Y is above 1.f, else the vector LUTf lookup at Y * 65535.f; for the W % 4 columns behind them
+ *     Y > 1.f ? process_pixel(Y) : lut[Y * 65535.f] with the scalar forms (L315-339).  The table is artgpu_tone_equalizer_lut's.
+ * NaN-free input is the contract.
+ * ARTGPU_EUNSUPPORTED, image untouched, decided before any kernel runs: show_colormap (lcms2, PREVIEW pipeline only); regularization outside
+ * 0..4; scale < 1; a regularising guided filter that would run with radius 0 (scale above 350); a box radius (r / subsampling) above the blur
+ * kernels' 900; a filter whose statistics grid (size / subsampling) has a side below ARTGPU_SMOOTHING_MIN_SIZE -- the same reasoning as there:
+ * below 5 every box radius clamps to 0 and the shared blur kernels take no such grid.  With regularization == 0 no filter runs and every size
+ * from 1 x 1 is accepted.  (A detail filter whose radius comes out 0, scale >= 10, does not run, as in the reference.) */
+typedef struct artgpu_tone_equalizer_params {   /* ToneEqualizerParams, defaults procparams.cc:2097-2104 */
+    int32_t enabled;
+    int32_t bands[5];          /* -100 .. 100 */
+    int32_t regularization;    /* 0 .. 4, default 4 */
+    int32_t show_colormap;     /* != 0: ARTGPU_EUNSUPPORTED */
+    double pivot;              /* -12 .. 12 */
+} artgpu_tone_equalizer_params;
+typedef struct artgpu_tone_equalizer_info {     /* what the host derived */
+    float gain, w_sum, factors[12];
+    int32_t filters;                        /* 0 .. 3 guided filters that ran */
+    int32_t radius[3], subsampling[3], box_radius[3];   /* detail, regularise 1, regularise 2; zeros when not run */
+    float epsilon[3];
+} artgpu_tone_equalizer_info;
+int artgpu_tone_equalizer(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_tone_equalizer_params *params, const double ws[9], double scale,
+                          artgpu_tone_equalizer_info *info /* or NULL */);
+/* Host only, no context: gain, w_sum, factors (info; may be NULL) and the 65536-entry table lut[i] = process_pixel(i / 65535.f) (L305-310) with
+ * the host's scalar sleef forms.  This is the one table the device path reads. */
+int artgpu_tone_equalizer_lut(const artgpu_tone_equalizer_params *params, float *lut /* 65536, host */, artgpu_tone_equalizer_info *info);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -1033,6 +1069,11 @@ int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_cor
  * mask fail the frame before any stage runs; a limit that depends on a mask's box fails at the tool, before the tool writes. */
 int artgpu_set_pipeline_smoothing(artgpu_ctx *ctx, const artgpu_smoothing_region *regions, int n,
                                   const artgpu_mask_params *masks /* n entries or NULL */);
+/* The tone equalizer in the per-frame pipe, a setting of the context for the same reason (copied; batch lanes inherit it).  NULL = off, the
+ * default.  While set, the three pipe entries run artgpu_tone_equalizer's code with params->ws and params->scale after the exposure -- fused
+ * into the denoise tool's last pass or run on its own behind dehaze -- and before the sharpening (the last step of STAGE_1, improcfun.cc:588).
+ * What artgpu_tone_equalizer does not support fails the frame before any stage has run. */
+int artgpu_set_pipeline_tone_equalizer(artgpu_ctx *ctx, const artgpu_tone_equalizer_params *params);
 
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
