@@ -1057,16 +1057,20 @@ class Context:
         n = len(raws)
         self._chk(LIB.artgpu_batch_run(self._h, n, (Plane * n)(*raws), C.byref(params), (RGB * n)(*outs)))
 
-    def batch_run_io(self, sensor_frames, params: PipelineParams, scanline_frames):
+    def batch_run_io(self, sensor_frames, params: PipelineParams, scanline_frames, check: bool = True):
         """artgpu_batch_run_io: sensor data in, writers' scanlines out, copies beside the kernels.  `sensor_frames`: numpy arrays (uint16 /
         float32, host) or ready SensorFrame structures; `scanline_frames`: ScanlineFrame structures (scanline_frame() builds one around a
-        numpy array).  Returns the array of ScanlineFrame (chmax / status filled in)."""
+        numpy array).  Returns the array of ScanlineFrame (chmax / status filled in).  check=False: no exception for a non-zero return code;
+        returns (code, array) -- a frame whose status is 0 is complete whatever the code (artgpu.h)."""
         n = len(sensor_frames)
         ins = (SensorFrame * n)()
         for k, f in enumerate(sensor_frames):
             ins[k] = f if isinstance(f, SensorFrame) else sensor_frame(f)
         outs = (ScanlineFrame * n)(*scanline_frames)
-        self._chk(LIB.artgpu_batch_run_io(self._h, n, ins, C.byref(params), outs))
+        rc = LIB.artgpu_batch_run_io(self._h, n, ins, C.byref(params), outs)
+        if not check:
+            return rc, outs
+        self._chk(rc)
         return outs
 
     def demosaic_xtrans(self, passes: int, use_cielab: bool, raw: Plane, xtrans, rgb_cam, out: RGB):

@@ -189,9 +189,13 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
     const hipStream_t s_down = out_pinned ? c->io_down : c->stream;
     unsigned char *host_dev = nullptr;
     if (out_pinned && direct_wgs > 0 && (reinterpret_cast<uintptr_t>(out->scanlines) & 15) == 0 && (out->row_stride_bytes & 15) == 0) host_dev = out_pinned;
-    c->cu_reserve = host_dev ? direct_wgs * (c->frames_in_flight > 1 ? 2 : 1) : 0;      // (this lane's download and a neighbour's; reset when the lane is done)
-    // the working image of this slot is free again once the download of turn i - 2 has read it
-    if (i >= 2 && !out->on_device) HIPCHK(c, hipStreamWaitEvent(c->stream, c->io_ev[6 + s], 0));
+    // (this lane's download and a neighbour's; reset when the lane is done.  The caller's own "cu_reserve" is another field: cu_reserve_of())
+    c->io_cu_reserve = host_dev ? direct_wgs * (c->frames_in_flight > 1 ? 2 : 1) : 0;
+    // The working image of this slot is free again once the download of turn i - 2 has read it -- WHATEVER this frame's own output is: a direct
+    // download (launch_scanlines_host on io_down) reads the working image itself, and a frame with its scanlines on the device two turns later
+    // writes that image as any other does.  (The wait used to be left out for device outputs: DESIGN.md section 17.)  The event
+    // of a turn that had nothing to download holds an older record, long completed: no wait at all.
+    if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->io_ev[6 + s], 0));
 
     // ---- upload (io_up) -> copyOriginalPixels + scaleColors (stream)
     ScaleArgs a = {};
@@ -285,37 +289,49 @@ int artgpu_batch_run_io(artgpu_ctx *ctx, int nframes, const artgpu_sensor_frame 
     if (nframes < 0 || (nframes && (!in || !params || !out))) return fail(ctx, ARTGPU_EINVAL, "batch_run_io: null argument");
     if (nframes == 0) return ARTGPU_OK;
     const int L = std::min(ctx->batch_lanes, nframes);
+    // (a frame's `status` is ARTGPU_OK only where a lane vouches for it below: a call that ends before the lanes start says so on every frame)
+    auto all_frames = [&](int code) {
+        for (int f = 0; f < nframes; ++f) { out[f].status = code; out[f].chmax[0] = out[f].chmax[1] = out[f].chmax[2] = out[f].chmax[3] = 0.f; }
+        return code;
+    };
     int rc = batch_prepare_lanes(ctx, L);          // (L == 1: no lanes, frames_in_flight = 1)
-    if (rc) return rc;
+    if (rc) return all_frames(rc);
     InFlightReset in_flight_reset{ctx};
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // inputs the caller produced on this context's stream
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess)      // inputs the caller produced on this context's stream
+        return all_frames(fail(ctx, ARTGPU_EHIP, "batch_run_io: the context's stream"));
     auto px_of = [&](int f) { return (long long)in[f].w * in[f].h; };
-    for (int f = 0; f < nframes; ++f) { out[f].status = ARTGPU_OK; out[f].chmax[0] = out[f].chmax[1] = out[f].chmax[2] = out[f].chmax[3] = 0.f; }
+    all_frames(ARTGPU_OK);
     rc = batch_on_lanes(ctx, L, [&](artgpu_ctx *c, int k) -> int {
         const int mine = (nframes - k + L - 1) / L;
         int rc2 = io_setup(c, mine);
+        int queued = 0;        // turns of this lane that were queued to their end: the first one that was not is where the lane stopped
         for (int f = k, i = 0; !rc2 && f < nframes; f += L, ++i) {
             rc2 = batch_settle_scratch(c, px_of(f), f + L < nframes ? px_of(f + L) : -1);
             if (!rc2) rc2 = io_frame(c, i, &in[f], params, &out[f]);
+            if (!rc2) queued = i + 1;
         }
         // the lane's copies and kernels, then what the frames left in the pinned words
-        c->cu_reserve = 0;
+        c->io_cu_reserve = 0;
         hipError_t e = hipStreamSynchronize(c->stream);
         if (c->io_down) { const hipError_t e2 = hipStreamSynchronize(c->io_down); if (e == hipSuccess) e = e2; }
         if (c->io_up) { const hipError_t e2 = hipStreamSynchronize(c->io_up); if (e == hipSuccess) e = e2; }
-        if (rc2) return rc2;
-        if (e != hipSuccess) return fail(c, ARTGPU_EHIP, "batch_run_io: lane %d: %s", k, hipGetErrorString(e));
-        if ((rc2 = check_async_faults(c))) return rc2;
+        // A stream that failed or a kernel that gave up a bounded wait: the lane cannot vouch for any of its frames, the turns before a refused
+        // one included.  Otherwise those turns have run to their end, and their pinned words are what they are for any other frame.
+        if (e != hipSuccess) { rc2 = fail(c, ARTGPU_EHIP, "batch_run_io: lane %d: %s", k, hipGetErrorString(e)); queued = 0; }
+        else if (const int rf = check_async_faults(c)) { rc2 = rf; queued = 0; }
+        int unsupported = ARTGPU_OK;
         for (int f = k, i = 0; f < nframes; f += L, ++i) {
+            if (i >= queued) { out[f].status = rc2; continue; }      // the turn the lane stopped at and every later one: not run, chmax stays 0
             const int *w = c->io_host + 8 * i;
             for (int ch = 0; ch < 3; ++ch) std::memcpy(&out[f].chmax[ch], &w[ch], sizeof(float));
             out[f].chmax[3] = out[f].chmax[1];
             if (out[f].rgb2out_enabled && w[4]) {
                 out[f].status = ARTGPU_EUNSUPPORTED;
-                if (!rc2) rc2 = fail(c, ARTGPU_EUNSUPPORTED, "batch_run_io: frame %d: %d channel values above 1 need ARTOutputProfile::eval (lcms2/libm) on the host", f, w[4]);
+                // (the lane's own error, if it has one, keeps artgpu_last_error)
+                if (!rc2 && !unsupported) unsupported = fail(c, ARTGPU_EUNSUPPORTED, "batch_run_io: frame %d: %d channel values above 1 need ARTOutputProfile::eval (lcms2/libm) on the host", f, w[4]);
             }
         }
-        return rc2;
+        return rc2 ? rc2 : unsupported;
     });
     return rc;
 }

@@ -38,7 +38,7 @@ struct artgpu_ctx {
     hipEvent_t dn_ev[2] = {nullptr, nullptr};
     const float *gam_tab = nullptr; float gam_key[6] = {};   // RGB_denoise's gamma / inverse-gamma tables in pool[P_GAM]: what they were built from
     // What a batch lane inherits from its parent context (batch_prepare_lanes copies the block as one value on every batch call).  A field
-    // belongs here exactly if a frame's result or its reporting must not depend on which lane ran it.  (cu_reserve is not one: io_frame sets it
+    // belongs here exactly if a frame's result or its reporting must not depend on which lane ran it.  (io_cu_reserve is not one: io_frame sets it
     // per lane; the *_own storage the pipe_* pointers point into stays with the parent.)
     struct Shared {
         // options (artgpu_set_option): test / profiling switches that used to be environment variables
@@ -59,6 +59,8 @@ struct artgpu_ctx {
         long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
         int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
                                        // hipMemcpy; -1 (default): 8 with two lanes, 0 otherwise (io_frame has the measurements)
+        int opt_cu_reserve = 0;        // the caller's "cu_reserve": the persistent one-workgroup-per-CU pixel passes launch this many workgroups fewer.  Only
+                                       // artgpu_set_option writes it (a batch keeps its own figure in io_cu_reserve; the launchers take cu_reserve_of())
         int opt_amaze_path = 0;        // 0: LDS streaming kernel for full tiles + arena kernel for the rest; 1: arena kernel for every tile
         int opt_amaze_split = 0;       // 1 (with path 1): one launch per phase
         long opt_amaze_zero_mask = 0x81f0;
@@ -122,7 +124,7 @@ struct artgpu_ctx {
     hipEvent_t io_ev[8] = {};
     int *io_host = nullptr;        // pinned, 8 words per frame of the lane: channel maxima (bit patterns) x 3, -, rgb2out's count of unsupported values
     int io_host_cap = 0;
-    int cu_reserve = 0;            // set around a batch whose downloads run as a kernel of a few workgroups: the persistent one-workgroup-per-CU pixel passes leave those CUs alone
+    int io_cu_reserve = 0;         // set by io_frame while a batch's downloads run as a kernel of a few workgroups: the persistent one-workgroup-per-CU pixel passes leave those CUs alone
     // (what artgpu_improc_denoise_fused fuses into the denoise tool's pixel passes is not state of the context: it travels as a DnFusion argument)
     float *bbox = nullptr; // AMaZE: per-tile nyquist bounding boxes
     size_t bbox_bytes = 0;
@@ -226,6 +228,8 @@ int pool_to_plane(artgpu_ctx *ctx, const float *src, artgpu_plane *pl);
 constexpr int MAX_TILE_WORKGROUPS = ARTGPU_MAX_TILE_WG;
 
 int check_async_faults(artgpu_ctx *ctx);
+// CUs the persistent one-workgroup-per-CU passes of this context leave alone: the caller's option or what the batch in flight needs, whichever is more
+inline int cu_reserve_of(const artgpu_ctx *ctx) { return ctx->shared.opt_cu_reserve > ctx->io_cu_reserve ? ctx->shared.opt_cu_reserve : ctx->io_cu_reserve; }
 
 // Host-side milestones of an entry point: the reference's ProgressListener (rtengine.h:165; amaze_demosaic_RT.cc:1567-1580 reports
 // per-tile fractions, the device path reports 0 when the stage's work starts being queued and 1 when the entry point returns) and,

@@ -398,6 +398,8 @@ int artgpu_get_option(artgpu_ctx *ctx, const char *name, long *value)
         return ARTGPU_OK;
     }
     if (n == "dn_mad_fold") { *value = ctx->shared.opt_dn_mad_fold; return ARTGPU_OK; }
+    if (n == "cu_reserve") { *value = ctx->shared.opt_cu_reserve; return ARTGPU_OK; }     // (the caller's value: a batch never writes it)
+    if (n == "io_direct") { *value = ctx->shared.opt_io_direct; return ARTGPU_OK; }
     if (n == "te_group_thread") { *value = ctx->shared.opt_te_group_thread; return ARTGPU_OK; }
     if (n == "te_fuse_upsample") { *value = ctx->shared.opt_te_fuse_upsample; return ARTGPU_OK; }
     if (n.rfind("dn_mad_bits", 0) == 0 && n.size() > 11) {
@@ -452,7 +454,7 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
     else if (n == "te_group_thread") ctx->shared.opt_te_group_thread = value != 0;
     else if (n == "te_fuse_upsample") ctx->shared.opt_te_fuse_upsample = value != 0;
     else if (n == "sharpen_fused") ctx->shared.opt_sharpen_fused = value != 0;
-    else if (n == "cu_reserve") { if (value < 0 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "cu_reserve: 0 .. 4096"); ctx->cu_reserve = (int)value; }
+    else if (n == "cu_reserve") { if (value < 0 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "cu_reserve: 0 .. 4096"); ctx->shared.opt_cu_reserve = (int)value; }
     else if (n == "io_direct") { if (value < -1 || value > 4096) return fail(ctx, ARTGPU_EINVAL, "io_direct: -1 (automatic), 0 .. 4096 workgroups"); ctx->shared.opt_io_direct = (int)value; }
     else if (n == "rcd_rows") { if (value != 4 && value != 8) return fail(ctx, ARTGPU_EINVAL, "rcd_rows: 4 or 8"); ctx->shared.opt_rcd_rows = (int)value; }
     else return fail(ctx, ARTGPU_EINVAL, "set_option: unknown option '%s'", name);
@@ -877,7 +879,7 @@ int artgpu_tone_curve(artgpu_ctx *ctx, artgpu_rgb *image, int mode, const float 
         if ((rc = upload_curve(ctx, lut65536))) return rc;
         a.lut = ctx->lut;
     }
-    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
+    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
     HIPCHK(ctx, launch_tone_std(a, ctx->stream));
     return unbind_rgb(ctx, image, &d);
 }
@@ -1705,7 +1707,7 @@ int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_param
     px.gain = pl.gain; px.newGain = 1.f / pl.gain;
     px.gam = pl.gam; px.gamthresh = pl.gamthresh; px.gamslope = pl.gamslope; px.igam = pl.igam; px.igamthresh = pl.igamthresh; px.igamslope = pl.igamslope;
     px.gamcurve = b.gamlut; px.igamcurve = b.gamlut + 65536;
-    px.pre_scale = fu.pre_scale; px.post_scale = fu.post_scale; px.no_lds_lut = !ctx->shared.opt_lut_lds; px.cu_reserve = ctx->cu_reserve;
+    px.pre_scale = fu.pre_scale; px.post_scale = fu.post_scale; px.no_lds_lut = !ctx->shared.opt_lut_lds; px.cu_reserve = cu_reserve_of(ctx);
     px.gi = fu.gi; px.exp_on = fu.exp_on; px.exp_scale = fu.exp_scale; px.exp_black = fu.exp_black;
     // the inverse-gamma pass looks up gamma-encoded values: the mid-tones sit in the middle of the table, so the 40704 entries kept in LDS
     // start at 8000 (gamma 1.7: linear 0.03 .. 0.60 of white); the forward pass and the tone curve index with linear data and keep [0, 40704)
@@ -2499,7 +2501,7 @@ int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *l
     for (int k = 0; k < 9; ++k) { a.ws[k] = (float)st->ws[k]; a.iws[k] = (float)st->iws[k]; a.to_out[k] = st->to_out[k]; a.to_work[k] = st->to_work[k]; }
     a.whitecoeff = whitecoeff;
     a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
-    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
+    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
     HIPCHK(ctx, launch_tone_neutral(a, ctx->stream));
     return unbind_rgb(ctx, image, &d);
 }
@@ -2542,7 +2544,7 @@ static int chroma_map_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride
     a.stride = stride; a.wid = wid; a.hei = hei;
     a.has_mat = mat ? 1 : 0;
     for (int k = 0; k < 9; ++k) { a.mat[k] = mat ? mat[k] : 0.0; a.wpi[k] = (float)ws[k]; }
-    a.cachef = tab; a.curve = tab + 65536; a.out = map; a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = ctx->cu_reserve;
+    a.cachef = tab; a.curve = tab + 65536; a.out = map; a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
     HIPCHK(ctx, launch_chroma_map(a, ctx->stream));
     *out = map;
     return ARTGPU_OK;

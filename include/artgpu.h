@@ -101,7 +101,9 @@ int artgpu_synchronize(artgpu_ctx *ctx);
  *   "io_direct"         artgpu_batch_run_io, scanlines that go to PINNED host memory: n > 0: n persistent workgroups on the download stream write
  *                       them there directly (no staging plane, no copy); 0: staged on the device and copied by the runtime; -1 (default): 8 with
  *                       two lanes, 0 otherwise (measured: DESIGN.md section 17); "cu_reserve" n: the persistent one-workgroup-per-CU pixel passes launch
- *                       n workgroups fewer (experiments with kernels running beside a frame; artgpu_batch_run_io sets it for its direct downloads) */
+ *                       n workgroups fewer (experiments with kernels running beside a frame).  The value is the caller's: artgpu_batch_run_io
+ *                       reserves CUs for its direct downloads on its own account while it runs, the larger of the two applies, and the
+ *                       option reads back as it was set (artgpu_get_option: "cu_reserve", "io_direct") */
 int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value);
 /* read-only counterparts: "amaze_counter0" .. "amaze_counter7" = bookkeeping of the last AMaZE call (how many tiles were streamed a
  * second time, handed to the arena kernel, ...); synchronises the context's stream */
@@ -1096,9 +1098,19 @@ int artgpu_set_batch_lanes(artgpu_ctx *ctx, int lanes);
  * streams with two staging slots each, so the upload of frame f + 1 and the download of frame f - 1 run beside the kernels of frame f and
  * the host thread never waits for a copy before the batch ends.  Pinned host memory (hipHostMalloc / hipHostRegister) is what makes the
  * copies asynchronous; pageable memory works and is staged by the runtime, one blocking copy at a time.  Device pointers (on_device != 0)
- * skip the corresponding copy.  `status` of a frame: ARTGPU_OK, or ARTGPU_EUNSUPPORTED when rgb2out met values above 1 with a
- * non-linear TRC (artgpu_rgb2out_matrix's rule; the scanlines are complete for every other pixel); the call returns the first
- * non-zero status.  Same bits as artgpu_scale_colors -> artgpu_pipeline_run -> artgpu_rgb2out_matrix -> artgpu_get_scanlines. */
+ * skip the corresponding copy; frames of different residency may share a batch.  Same bits as artgpu_scale_colors -> artgpu_pipeline_run ->
+ * artgpu_rgb2out_matrix -> artgpu_get_scanlines.
+ * `status` of a frame, when the call returns -- WHATEVER it returns:
+ *   ARTGPU_OK            the frame's scanlines are complete and its `chmax` is valid;
+ *   ARTGPU_EUNSUPPORTED  with valid `chmax`: rgb2out met values above 1 with a non-linear TRC (artgpu_rgb2out_matrix's rule; the scanlines
+ *                        are complete for every other pixel);
+ *   any code, `chmax` 0  the frame was not run, or its lane cannot vouch for it.  A lane (frames k, k + lanes, ...) stops at the first of
+ *                        its frames that is refused (arguments, something the path does not support, memory): that frame and the lane's
+ *                        later ones carry the code and their buffers are not written, the frames before it run to their end and
+ *                        report as usual.  After a HIP error or a kernel that gave up a bounded wait on the lane, every frame of the
+ *                        lane carries the code.  Other lanes are not affected.
+ * The call returns non-zero if any frame's status is: a lane's own error before a frame's rgb2out report, the lowest lane first.  So: look
+ * at the return code to learn that something went wrong, at `status` to learn which frames can be written. */
 typedef struct {
     const void *data;               /* sensor values, row-major */
     int32_t w, h;
@@ -1118,7 +1130,7 @@ typedef struct {
     const float *trc_lut;           /* host, trc_lutsz entries (NULL with trc_linear) */
     int32_t trc_lutsz;
     float chmax[4];                 /* out: scaleColors' channel maxima (chmax[3] = chmax[1]) */
-    int32_t status;                 /* out */
+    int32_t status;                 /* out: ARTGPU_OK = scanlines complete and chmax valid, whatever the call returned (the contract above) */
 } artgpu_scanline_frame;
 int artgpu_batch_run_io(artgpu_ctx *ctx, int nframes, const artgpu_sensor_frame *in, const artgpu_pipeline_params *params,
                         artgpu_scanline_frame *out);
