@@ -220,6 +220,56 @@ def tone_equalizer_lut(params: ToneEqualizerParams):
     return lut, info
 
 
+class FilmSimulationParams(C.Structure):
+    """artgpu_film_simulation_params: strength (already divided by 100), same_profile, the four ICCStore matrices (row-major)"""
+    _fields_ = [("strength", C.c_float), ("same_profile", C.c_int32), ("work_to_xyz", C.c_double * 9), ("xyz_to_clut", C.c_double * 9),
+                ("clut_to_xyz", C.c_double * 9), ("xyz_to_work", C.c_double * 9)]
+
+
+def film_simulation_params(strength=1.0, work_to_xyz=None, xyz_to_clut=None, clut_to_xyz=None, xyz_to_work=None) -> FilmSimulationParams:
+    """same_profile unless the four matrices are given"""
+    mats = (work_to_xyz, xyz_to_clut, clut_to_xyz, xyz_to_work)
+    same = all(m is None for m in mats)
+    assert same or all(m is not None for m in mats)
+    p = FilmSimulationParams()
+    p.strength = float(strength); p.same_profile = int(same)
+    for name, m in zip(("work_to_xyz", "xyz_to_clut", "clut_to_xyz", "xyz_to_work"), mats):
+        if m is not None:
+            getattr(p, name)[:] = [float(v) for v in np.asarray(m, np.float64).reshape(9)]
+    return p
+
+
+def film_simulation_tables():
+    """the two 65536-entry float32 tables the film simulation reads (Color::gamma2curve, Color::igammatab_srgb), built on the host (no context)"""
+    g, ig = np.empty(65536, np.float32), np.empty(65536, np.float32)
+    rc = LIB.artgpu_film_simulation_tables(g.ctypes.data_as(C.POINTER(C.c_float)), ig.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise ArtGpuError(f"artgpu_film_simulation_tables: error {rc}")
+    return g, ig
+
+
+class Clut:
+    """artgpu_clut: a HaldCLUT on a context's device.  `table`: uint16 array of level^3 entries, red fastest, 3 or 4 values each."""
+
+    def __init__(self, ctx: "Context", table: np.ndarray, level: int):
+        table = np.ascontiguousarray(table)
+        assert table.dtype == np.uint16 and table.ndim == 2 and table.shape[1] in (3, 4)
+        assert int(level) not in [k * k for k in range(2, 17)] or table.shape[0] == int(level) ** 3   # (any other level: the library refuses it unread)
+        self._h = C.c_void_p()
+        ctx._chk(LIB.artgpu_clut_create(ctx._h, table.ctypes.data_as(C.POINTER(C.c_uint16)), int(level), int(table.shape[1]), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            LIB.artgpu_clut_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MaskParams(C.Structure):
     """artgpu_mask_params: one rtengine::procparams::Mask as the parametric path of generateMasks reads it"""
     _fields_ = [("parametric_enabled", C.c_int32), ("lightness_detail", C.c_int32), ("hue", C.POINTER(C.c_double)),
@@ -522,6 +572,12 @@ def _load():
                                           C.POINTER(ToneEqualizerInfo)]
     lib.artgpu_tone_equalizer_lut.argtypes = [C.POINTER(ToneEqualizerParams), C.POINTER(C.c_float), C.POINTER(ToneEqualizerInfo)]
     lib.artgpu_set_pipeline_tone_equalizer.argtypes = [C.c_void_p, C.POINTER(ToneEqualizerParams)]
+    lib.artgpu_clut_create.argtypes = [C.c_void_p, C.POINTER(C.c_uint16), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.artgpu_clut_destroy.argtypes = [C.c_void_p]
+    lib.artgpu_clut_destroy.restype = None
+    lib.artgpu_film_simulation.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_void_p, C.POINTER(FilmSimulationParams)]
+    lib.artgpu_film_simulation_tables.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.artgpu_set_pipeline_film_simulation.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FilmSimulationParams), C.c_int]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -604,7 +660,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
            "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks",
            "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing",
-           "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer"]
+           "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer",
+           "artgpu_clut_create", "artgpu_clut_destroy", "artgpu_film_simulation", "artgpu_film_simulation_tables", "artgpu_set_pipeline_film_simulation"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -899,6 +956,22 @@ class Context:
     def set_pipeline_tone_equalizer(self, params: ToneEqualizerParams = None):
         """the tone equalizer pipeline_run / batch_run / batch_run_io run behind the exposure (None: off).  The library copies it."""
         self._chk(LIB.artgpu_set_pipeline_tone_equalizer(self._h, C.byref(params) if params is not None else None))
+
+    def clut(self, table: np.ndarray, level: int) -> "Clut":
+        """a HaldCLUT on this context's device (artgpu_clut_create): level^3 x 3 or x 4 uint16, red fastest; level = entries per axis"""
+        return Clut(self, table, level)
+
+    def film_simulation(self, image: RGB, clut: "Clut", params: FilmSimulationParams):
+        """ImProcFunctions::filmSimulation with a HaldCLUT in place on an RGB image (params from film_simulation_params())"""
+        self._chk(LIB.artgpu_film_simulation(self._h, C.byref(image), clut._h, C.byref(params)))
+
+    film_simulation_tables = staticmethod(film_simulation_tables)
+
+    def set_pipeline_film_simulation(self, clut: "Clut" = None, params: FilmSimulationParams = None, after_tone_curve: bool = False):
+        """film simulation in pipeline_run / batch_run / batch_run_io: between texture boost and the tone curve, or right behind the tone curve
+        (None: off).  The library copies the parameters and keeps a reference to the CLUT."""
+        self._chk(LIB.artgpu_set_pipeline_film_simulation(self._h, clut._h if clut is not None else None, C.byref(params) if params is not None else None,
+                                                          int(bool(after_tone_curve))))
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""

@@ -4,7 +4,7 @@
 // static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api, declared with hidden visibility:
 // none of them is in the library's dynamic symbol table (a definition inherits nothing from its declaration here: every opening of
 // the namespace carries the attribute).  Each is defined once (the helpers and the stages in artgpu_api.hip, the tone equalizer in
-// api_toneequalizer.hip); none is inline.
+// api_toneequalizer.hip, film simulation in api_filmsim.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -25,6 +25,7 @@
 #include "colorcorrection.h"
 #include "smoothing.h"
 #include "toneequalizer.h"
+#include "filmsim.h"
 #include "masks.h"
 #include "sharpen.h"
 
@@ -87,6 +88,9 @@ struct artgpu_ctx {
         int pipe_nsm = 0;
         int pipe_te_on = 0;            // artgpu_set_pipeline_tone_equalizer: a copy by value
         artgpu_tone_equalizer_params pipe_te = {};
+        const artgpu_clut *pipe_fs = nullptr;      // artgpu_set_pipeline_film_simulation: the handle (the parent's pipe_fs_own holds the reference),
+        artgpu_film_simulation_params pipe_fs_par = {};   // a copy of the parameters, and the position
+        int pipe_fs_after = 0;
     } shared;
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
@@ -96,6 +100,7 @@ struct artgpu_ctx {
     template <typename Region> struct PipeRegions { std::vector<Region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; };
     PipeRegions<artgpu_color_correction_region> pipe_cc_own;
     PipeRegions<artgpu_smoothing_region> pipe_sm_own;
+    artgpu_clut *pipe_fs_own = nullptr;    // artgpu_set_pipeline_film_simulation: the reference this context holds (batch lanes hold none)
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
     long long batch_px = 0;       // artgpu_batch_run: pixels of the largest frame this context's scratch was grown for since the last trim
@@ -351,6 +356,15 @@ int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, flo
 int te_check(artgpu_ctx *ctx, int W, int H, const artgpu_tone_equalizer_params *p, const double *ws, double scale, const char *who, artgpu_tone_equalizer_info *pl);
 int tone_equalizer_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_tone_equalizer_params *p, const double ws[9],
                        const artgpu_tone_equalizer_info &pl, const char *who);
+
+// ---------------------------------------------------------------------------------------------
+// film simulation
+// ---------------------------------------------------------------------------------------------
+// every reason not to run (a bad handle, another device's, a strength that is not finite): nothing is launched
+int fs_check(artgpu_ctx *ctx, const artgpu_clut *clut, const artgpu_film_simulation_params *p, const char *who);
+// the tool on device planes (rows of `stride` floats) in RGB mode, after fs_check; enqueued on ctx->stream
+int film_simulation_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_clut *clut, const artgpu_film_simulation_params *p);
+void clut_release(artgpu_clut *clut);      // drops one reference; the last one frees the device copy
 
 // ---------------------------------------------------------------------------------------------
 // capture sharpening

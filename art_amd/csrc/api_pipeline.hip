@@ -96,6 +96,7 @@ struct PipePlan {
     DehazePlan dehaze;
     bool te_on;                                                    // the tone equalizer (artgpu_set_pipeline_tone_equalizer, enabled)
     artgpu_tone_equalizer_info te;
+    bool fs_on;                                                    // film simulation (artgpu_set_pipeline_film_simulation)
     bool sh_on, sh_auto, sh_radius_pending;
     artgpu_sharpening_params shpar;                                // (deconvradius: 0.75 stands in while the automatic radius is pending)
     SharpenPlan sharpen;
@@ -130,7 +131,7 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 //   1. ctx, raw / p / out, the border, the output's size (then hipSetDevice, the one HIP call here)   2. artgpu_set_pipeline_masks' counts against the frame's
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
-//   8. dehaze_check, te_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
+//   8. dehaze_check, te_check, fs_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
 static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, PipePlan *pl)
 {
     if (!ctx) return ARTGPU_EINVAL;
@@ -200,6 +201,8 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     if (p->dehaze_enabled && (rc = dehaze_check(ctx, w, h, &p->dehaze, p->ws, scale, "pipeline_run(dehaze)", &pl->dehaze))) return rc;
     pl->te_on = s.pipe_te_on && s.pipe_te.enabled;
     if (pl->te_on && (rc = te_check(ctx, w, h, &s.pipe_te, p->ws, scale, "pipeline_run(tone equalizer)", &pl->te))) return rc;
+    pl->fs_on = s.pipe_fs != nullptr;
+    if (pl->fs_on && (rc = fs_check(ctx, s.pipe_fs, &s.pipe_fs_par, "pipeline_run(film simulation)"))) return rc;
     // sharpening (STAGE_2): method, scale and, with the automatic radius, the sensor are checked before any stage runs
     pl->shpar = p->sharpening;
     pl->sh_on = p->sharpening_enabled != 0;
@@ -338,22 +341,27 @@ static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const P
     return ARTGPU_OK;
 }
 
-// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, the tone curve, localContrast; then the image goes back to the caller's planes
+// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, filmSimulation on either side of the tone curve, localContrast; then the image goes back to the caller's planes
 static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
 {
     const DevRGB &d = fr->d;
     const int ntb = p->texture_boost_nregions, nlc = p->local_contrast_nregions;
+    const artgpu_ctx::Shared &s = ctx->shared;
     std::vector<artgpu_plane> gen;
     int rc;
     // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
     if (pl.tb_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_tb, pl.tb_mk, ntb, false, &gen))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     for (int i = 0; i < ntb && pl.tb_gen; ++i) pl.tb_regs[i].mask = &gen[i];
     if (pl.tb_on && (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, pl.tb_regions, ntb, p->ws, pl.tb, 1, nullptr, pl.tb_in_yuv))) return rc;
+    // ImProcFunctions::filmSimulation ahead of the tone curve (improcfun.cc:614-616; the image is in RGB mode: texture boost ends with that switch)
+    if (pl.fs_on && !s.pipe_fs_after && (rc = film_simulation_dev(ctx, d.p, d.stride, d.w, d.h, s.pipe_fs, &s.pipe_fs_par))) return rc;
     if (p->tone_enabled && p->tone_mode == ARTGPU_TONE_NEUTRAL) {
         artgpu_neutral_state st;
         for (int k = 0; k < 9; ++k) { st.ws[k] = p->ws[k]; st.iws[k] = p->iws[k]; st.to_out[k] = p->to_out[k]; st.to_work[k] = p->to_work[k]; }
         if ((rc = artgpu_tone_curve_neutral(ctx, &fr->img, p->tone_lut, p->white_point, &st))) return rc;
     } else if (p->tone_enabled && (rc = artgpu_tone_curve(ctx, &fr->img, p->tone_mode, p->tone_lut, p->white_point, 1))) return rc;
+    // ... or right behind it (filmSimulation.after_tone_curve, L618-620)
+    if (pl.fs_on && s.pipe_fs_after && (rc = film_simulation_dev(ctx, d.p, d.stride, d.w, d.h, s.pipe_fs, &s.pipe_fs_par))) return rc;
     // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
     // L plane (Imagefloat::g), back to RGB
     if (pl.lc_on) {

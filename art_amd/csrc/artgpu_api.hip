@@ -312,6 +312,7 @@ int artgpu_destroy(artgpu_ctx *ctx)
         if (ctx->ev[k]) (void)hipEventDestroy(ctx->ev[k]);
     for (artgpu_ctx *l : ctx->lanes) (void)artgpu_destroy(l);
     ctx->lanes.clear();
+    clut_release(ctx->pipe_fs_own);
     if (ctx->io_up) { (void)hipStreamSynchronize(ctx->io_up); (void)hipStreamDestroy(ctx->io_up); }
     if (ctx->io_down) { (void)hipStreamSynchronize(ctx->io_down); (void)hipStreamDestroy(ctx->io_down); }
     for (int k = 0; k < 8; ++k)

@@ -348,19 +348,12 @@ void dh_thumb_size(int W, int H, int *ww, int *hh)
 }
 
 // strength[i] = (FlatCurve(points, false).getVal(gamma2curve[i] / 65535.f) - 0.5f) * 1.3f with identity value 0.5 (L419-424);
-// Color::gamma2curve = float(gamma2(i / 65535.0)) * 65535.f (color.cc:241-244, color.h:1122-1127)
+// Color::gamma2curve: build_gamma2curve (hostluts.hip)
 void dh_strength_lut(const double *pts, int npts, float lut[65536])
 {
     static std::once_flag once;
     static std::vector<float> gamma2curve;
-    std::call_once(once, [] {
-        gamma2curve.resize(65536);
-        for (int i = 0; i < 65536; ++i) {
-            const double x = i / 65535.0;
-            gamma2curve[i] = (float)(x <= 0.003040 ? x * 12.92310 : 1.055 * std::exp(std::log(x) / 2.4) - 0.055);
-        }
-        for (int i = 0; i < 65536; ++i) gamma2curve[i] *= 65535.f;
-    });
+    std::call_once(once, [] { gamma2curve.resize(65536); build_gamma2curve(gamma2curve.data()); });
     std::vector<double> x, y, slope;
     const bool curve = flat_curve_polyline(pts, npts, false, 1000, 0.5, x, y, slope);
     for (int i = 0; i < 65536; ++i) {

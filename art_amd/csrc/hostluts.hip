@@ -4,6 +4,7 @@
 //   NoiseCurve::Set -> 501-entry LUT + sum     rtengine/ipdenoise.cc:684-716
 //   Color::cachef                              rtengine/color.cc:178,202-217
 //   tone_eq's correction table                 rtengine/iptoneequalizer.cc:95-114,160-190,305-310 (scalar sleef forms, sleef.h)
+//   Color::gamma2curve, Color::igammatab_srgb  rtengine/color.cc:239-255, color.h:1122-1144
 #include "kernels.h"
 #include "toneequalizer.h"
 #include <algorithm>
@@ -200,6 +201,26 @@ void build_denoise_gamma_tabs(float *gtab, float *igtab)
         gtab[i] = (float)(65535.0 * (x <= 0.013189 ? x * 10.0 : 1.593503 * std::exp(std::log(x) / 5.5) - 0.593503));
         igtab[i] = (float)(65535.0 * (x <= 0.131889 ? x / 10.0 : std::exp(std::log((x + 0.593503) / 1.593503) * 5.5)));
     }
+}
+
+// Color::gammatab_srgb, which Color::gamma2curve shares (color.cc:241-244): gamma2(i / 65535.0) (color.h:1127) stored as float, then *= 65535.f
+void build_gamma2curve(float *lut)
+{
+    for (int i = 0; i < 65536; ++i) {
+        const double x = i / 65535.0;
+        lut[i] = (float)(x <= 0.003040 ? x * 12.92310 : 1.055 * std::exp(std::log(x) / 2.4) - 0.055);
+    }
+    for (int i = 0; i < 65536; ++i) lut[i] *= 65535.f;
+}
+
+// Color::igammatab_srgb (color.cc:252-255): igamma2(i / 65535.0) (color.h:1144) stored as float, then *= 65535.f
+void build_igammatab_srgb(float *lut)
+{
+    for (int i = 0; i < 65536; ++i) {
+        const double x = i / 65535.0;
+        lut[i] = (float)(x <= 0.039286 ? x / 12.92310 : std::exp(std::log((x + 0.055) / 1.055) * 2.4));
+    }
+    for (int i = 0; i < 65536; ++i) lut[i] *= 65535.f;
 }
 
 // Color::init jzazbz_pq_ / jzazbz_pq_inv_ (color.cc:323-326) with PQ / PQ_inv (color.cc:67-86): std::pow(float, float) is the

@@ -448,6 +448,8 @@ float noise_curve_lut(const double *pts, int npts, float lut[501]);
 void build_cachef(float *lut65536);
 void build_cachefy(float *lut65536);
 void build_denoise_gamma_tabs(float *gtab65536, float *igtab65536);
+void build_gamma2curve(float *lut65536);        // Color::gamma2curve's values (dehaze's strength table, film simulation)
+void build_igammatab_srgb(float *lut65536);     // Color::igammatab_srgb (film simulation)
 
 struct ShrinkArgs {
     float *coef;            // bands of the decomposition being shrunk: [nsub][n]

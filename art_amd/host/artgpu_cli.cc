@@ -30,8 +30,12 @@
 //                                                      --color-correction-mask: generateMasks makes its Lmask on the device)
 //              [--tone-equalizer b0,b1,b2,b3,b4[,regularization[,pivot]]]   (ImProcFunctions::toneEqualizer, the last step of STAGE_1: the five bands
 //                                                      -100 .. 100, regularization 0 .. 4 (default 4), pivot in EV (default 0))
+//              [--film-simulation file.u16,level[,strength[,after]]]   (ImProcFunctions::filmSimulation in STAGE_3: file.u16 = a HaldCLUT as raw
+//                                                      little-endian uint16 RGB triples, level^3 of them with red fastest; level = entries per axis
+//                                                      (64 for a level-8 file); strength in percent (default 100); after != 0: behind the tone
+//                                                      curve instead of ahead of it.  The CLUT's profile is taken to be the working profile)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--tone-equalizer ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
+//              [--tone-equalizer ..] [--film-simulation ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <cctype>
@@ -105,6 +109,8 @@ int main(int argc, char **argv)
     bool te_enable = false;                                        // ToneEqualizerParams
     int te_bands[5] = {0, 0, 0, 0, 0}, te_reg = 4;
     double te_pivot = 0.0;
+    std::string fs_file;                                           // FilmSimulationParams: the CLUT, strength, after_tone_curve
+    int fs_level = 0, fs_strength = 100, fs_after = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -249,6 +255,14 @@ int main(int argc, char **argv)
             }
             te_enable = true;
         }
+        else if (a == "--film-simulation") {
+            const std::string v = next();
+            const size_t c = v.find(',');
+            if (c == std::string::npos || std::sscanf(v.c_str() + c + 1, "%d,%d,%d", &fs_level, &fs_strength, &fs_after) < 1) {
+                std::fprintf(stderr, "--film-simulation file.u16,level[,strength[,after]]\n"); return 2;
+            }
+            fs_file = v.substr(0, c);
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     ProcParams::Mask cc_mask;
@@ -263,6 +277,20 @@ int main(int argc, char **argv)
     tb_mask.parametricMask.enabled = true; tb_mask.parametricMask.blur = tbm_blur; tb_mask.parametricMask.lightnessDetail = tbm_detail;
     tb_mask.parametricMask.contrastThreshold = tbm_threshold; tb_mask.opacity = tbm_opacity;
     tb_mask.parametricMask.lightness = {1 /*FCT_MinMaxCPoints*/, 0.0, 0.0, 0.35, 0.35, tbm_lo, 1.0, 0.35, 0.35, tbm_hi, 1.0, 0.35, 0.35, 1.0, 0.0, 0.35, 0.35};
+    // the CLUT file onto the context's device (what CLUTStore::getHaldClut hands to CLUTApplication); released when `clut` leaves scope
+    struct ClutHandle { artgpu_clut *h = nullptr; ~ClutHandle() { artgpu_clut_destroy(h); } } clut;
+    const auto film_simulation = [&](Context &ctx, ProcParams &params) {
+        if (fs_file.empty()) return;
+        const size_t n = fs_level > 0 && fs_level <= 256 ? (size_t)fs_level * fs_level * fs_level * 3 : 0;
+        std::vector<uint16_t> table(n);
+        std::ifstream f(fs_file, std::ios::binary);
+        if (!f) throw std::runtime_error("cannot open " + fs_file);
+        f.read(reinterpret_cast<char *>(table.data()), (std::streamsize)n * 2);
+        if (!f) throw std::runtime_error("short read on " + fs_file);
+        ctx.check(artgpu_clut_create(ctx.get(), table.data(), fs_level, 3, &clut.h));
+        params.filmSimulation.enabled = true; params.filmSimulation.clut = clut.h; params.filmSimulation.strength = fs_strength;
+        params.filmSimulation.after_tone_curve = fs_after != 0; params.filmSimulation.same_profile = true;
+    };
     if ((in.empty() && batch.empty()) || W <= 0 || H <= 0) { std::fprintf(stderr, "usage: artgpu-cli --in frame.f32 | --batch a.u16,b.u16,... --width W --height H [options]\n"); return 2; }
     if (!batch.empty()) {
         try {
@@ -284,6 +312,7 @@ int main(int argc, char **argv)
         if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
         params.toneEqualizer.enabled = te_enable; params.toneEqualizer.regularization = te_reg; params.toneEqualizer.pivot = te_pivot;
         for (int k = 0; k < 5; ++k) params.toneEqualizer.bands[k] = te_bands[k];
+        film_simulation(ctx, params);
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
             BatchQueue q(ctx, 16);
@@ -365,6 +394,7 @@ int main(int argc, char **argv)
         if (ccm_enable) params.colorcorrection.masks = {ProcParams::ColorCorrectionMask{true, nullptr, nullptr, &cc_mask}};
         params.toneEqualizer.enabled = te_enable; params.toneEqualizer.regularization = te_reg; params.toneEqualizer.pivot = te_pivot;
         for (int k = 0; k < 5; ++k) params.toneEqualizer.bands[k] = te_bands[k];
+        film_simulation(ctx, params);
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
         params.localContrast.enabled = lc_enable;

@@ -229,6 +229,24 @@ struct ProcParams {
         for (int k = 0; k < 5; ++k) q.bands[k] = t.bands[k];
         return q;
     }
+    // FilmSimulationParams (procparams.h: enabled, clutFilename, strength, after_tone_curve) as the device path takes them: the CLUT the application's
+    // CLUTStore loaded as a handle (artgpu_clut_create), strength in percent, and what CLUTApplication::init derives from the two profile names
+    // (clutstore.cc:1090-1097): same_profile, or the four ICCStore matrices
+    struct {
+        bool enabled = false; int strength = 100; bool after_tone_curve = false;
+        const artgpu_clut *clut = nullptr;
+        bool same_profile = true;
+        double work_to_xyz[9] = {}, xyz_to_clut[9] = {}, clut_to_xyz[9] = {}, xyz_to_work[9] = {};
+    } filmSimulation;
+    artgpu_film_simulation_params filmSimulationParams() const
+    {
+        const auto &f = filmSimulation;
+        artgpu_film_simulation_params q = {};
+        q.strength = float(f.strength) / 100.f;                           // ipfilmsim.cc:46
+        q.same_profile = f.same_profile ? 1 : 0;
+        for (int k = 0; k < 9; ++k) { q.work_to_xyz[k] = f.work_to_xyz[k]; q.xyz_to_clut[k] = f.xyz_to_clut[k]; q.clut_to_xyz[k] = f.clut_to_xyz[k]; q.xyz_to_work[k] = f.xyz_to_work[k]; }
+        return q;
+    }
     // SmoothingParams (procparams.cc:2753-2775, procparams.h:1289-1347): regions with the reference's defaults (mode GUIDED, channel RGB);
     // masks[i].enabled and either the blend plane the application's generateMasks made of masks[i] (`blend`; nullptr = all ones) or the Mask itself
     struct SmoothingRegion {
@@ -395,7 +413,13 @@ public:
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); toneEqualizer(img); break;   // improcfun.cc:581-588
         case Stage::STAGE_2: sharpening(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595, 601, 602
-        case Stage::STAGE_3: textureBoost(img); logEncoding(img); saturationVibrance(img); toneCurve(img); rgbCurves(img); labAdjustments(img); localContrast(img); break;  // improcfun.cc:606-625 (the steps this library has)
+        case Stage::STAGE_3:                                                                  // improcfun.cc:606-625 (the steps this library has)
+            textureBoost(img); logEncoding(img); saturationVibrance(img);
+            if (!params->filmSimulation.after_tone_curve) filmSimulation(img);                // L614-616
+            toneCurve(img);
+            if (params->filmSimulation.after_tone_curve) filmSimulation(img);                 // L618-620
+            rgbCurves(img); labAdjustments(img); localContrast(img);
+            break;
         }
         return false;
     }
@@ -495,6 +519,15 @@ public:
         artgpu_rgb i = img->view();
         ctx.check(artgpu_tone_equalizer(ctx.get(), &i, &tp, params->workingSpace, scale, nullptr));
         return false;
+    }
+    // ImProcFunctions::filmSimulation (ipfilmsim.cc:33-73) with a HaldCLUT; the image is in RGB mode at both of its positions.  A missing handle is the
+    // reference's "file could not be read": the step does nothing (its listener message stays with the application)
+    void filmSimulation(Imagefloat *img)
+    {
+        if (!params->filmSimulation.enabled || !params->filmSimulation.clut) return;
+        const artgpu_film_simulation_params fp = params->filmSimulationParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_film_simulation(ctx.get(), &i, params->filmSimulation.clut, &fp));
     }
     // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
     void dehaze(Imagefloat *img)
@@ -760,6 +793,10 @@ public:
         artgpu_tone_equalizer_params te = p.toneEqualizerParams();
         te.show_colormap = 0;
         ctx.check(artgpu_set_pipeline_tone_equalizer(ctx.get(), p.toneEqualizer.enabled ? &te : nullptr));
+        // ImProcFunctions::filmSimulation on either side of the tone curve
+        const artgpu_film_simulation_params fs = p.filmSimulationParams();
+        const bool fs_on = p.filmSimulation.enabled && p.filmSimulation.clut;
+        ctx.check(artgpu_set_pipeline_film_simulation(ctx.get(), fs_on ? p.filmSimulation.clut : nullptr, &fs, p.filmSimulation.after_tone_curve ? 1 : 0));
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -776,6 +813,7 @@ public:
         (void)artgpu_set_pipeline_color_correction(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_smoothing(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_tone_equalizer(ctx.get(), nullptr);
+        (void)artgpu_set_pipeline_film_simulation(ctx.get(), nullptr, nullptr, 0);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

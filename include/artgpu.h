@@ -974,6 +974,47 @@ int artgpu_tone_equalizer(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_tone_eq
  * the host's scalar sleef forms.  This is the one table the device path reads. */
 int artgpu_tone_equalizer_lut(const artgpu_tone_equalizer_params *params, float *lut /* 65536, host */, artgpu_tone_equalizer_info *info);
 
+/* ImProcFunctions::filmSimulation (rtengine/ipfilmsim.cc:33-73) with a HaldCLUT: CLUTApplication (clutstore.cc:1063-1112, 1464-1484,
+ * 1502-1615) over HaldCLUT::getRGB in its SSE2 form (clutstore.cc:178-288).  In STAGE_3 between texture boost and the tone curve, or, with
+ * filmSimulation.after_tone_curve, right behind the tone curve (improcfun.cc:614-620).
+ *
+ * A CLUT handle: `table` is the HaldCLUT as HaldCLUT::loadFile leaves it (clutstore.cc:83-96), level^3 entries with red fastest, each 3
+ * (channels == 3) or 4 (channels == 4, the fourth ignored) uint16 values, on the host.  `level` is the reference's clut_level after
+ * squaring (clutstore.cc:154), entries per axis: 64 for a level-8 file (512 x 512), 144 for a level-12 file (1728 x 1728).  Accepted: the
+ * squares of 2 .. 16; anything else is ARTGPU_EINVAL.  The device copy (RGBX, one padding entry behind the last as in the reference, and
+ * the two sRGB gamma tables beside it) is uploaded once to ctx's device and never changes; every context on that device may use the
+ * handle, from any thread.  Decoding the PNG / TIFF, the file cache and the profile name in the file name (StdImageSource, CLUTStore,
+ * CLUTStore::splitClutFilename) stay with the caller.  artgpu_clut_destroy releases the caller's reference; a pipe setting (below) holds
+ * one of its own, so destroying a handle that is still set is safe.  NULL is accepted. */
+typedef struct artgpu_clut artgpu_clut;
+int artgpu_clut_create(artgpu_ctx *ctx, const uint16_t *table, int level, int channels, artgpu_clut **out);
+void artgpu_clut_destroy(artgpu_clut *clut);
+
+/* `img`: RGB mode, 0..65535, host or device, any row stride or start alignment, in place; every size from 1 x 1.  Per pixel:
+ *   same_profile == 0: working -> CLUT space, Color::rgbxyz(work_to_xyz) then Color::xyz2rgb(xyz_to_clut): for the columns below
+ *     4 * (W / 4), in groups of four counted from column 0 of the row, the vfloat overloads with the matrices rounded to float
+ *     (L1518-1532), for the W % 4 columns behind them the scalar overloads with the double matrices (L1536-1544);
+ *   Color::gamma_srgbclipped: gamma2curve[x], clipped on both sides (L1557-1559);
+ *   HaldCLUT::getRGB: cell = unsigned(min(float(level - 2), x * (float(level - 1) / 65535.0f))) per channel, the position inside it
+ *     x * flevel_minus_one - float(cell) (exactly 1 at 65535), seven vintpf(a, b, c) = a * b + (1 - a) * c per channel over the eight
+ *     corners in the reference's order (red, green, red, green, blue), then vintpf(strength, out, gamma-encoded input);
+ *   Color::igamma_srgb: igammatab_srgb[x], a table without clipping: it extrapolates past either end (L1570-1572);
+ *   same_profile == 0: CLUT -> working space with clut_to_xyz and xyz_to_work, body and tail as above (L1581-1607).
+ * No product is contracted into an FMA.  NaN-free input is the contract.  ARTGPU_EINVAL: a bad handle, a handle of another device, a
+ * strength that is not finite. */
+typedef struct artgpu_film_simulation_params {
+    float strength;            /* float(params->filmSimulation.strength) / 100.f: the caller divides */
+    int32_t same_profile;      /* != 0: the CLUT's profile is the working profile; the matrices are not read */
+    double work_to_xyz[9];     /* ICCStore::workingSpaceMatrix(working profile), row-major (clutstore.cc:1093) */
+    double xyz_to_clut[9];     /* ICCStore::workingSpaceInverseMatrix(CLUT profile) (L1096) */
+    double clut_to_xyz[9];     /* ICCStore::workingSpaceMatrix(CLUT profile) (L1097) */
+    double xyz_to_work[9];     /* ICCStore::workingSpaceInverseMatrix(working profile) (L1094) */
+} artgpu_film_simulation_params;
+int artgpu_film_simulation(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_clut *clut, const artgpu_film_simulation_params *params);
+/* Host only, no context: the two 65536-entry tables the device path reads, as Color::init builds them (color.cc:239-255): gamma2curve
+ * (gammatab_srgb: float(gamma2(i / 65535.0)) * 65535.f) and igammatab_srgb.  Either may be NULL. */
+int artgpu_film_simulation_tables(float *gamma2curve /* 65536, host */, float *igammatab_srgb /* 65536, host */);
+
 /* The whole hot path for one frame in one call -- what ART's batch loop does per image between load and rgb2out
  * (simpleprocess.cc stage_init L215-259, stage_denoise L311-315, stage_finish L389-396):
  *   demosaic -> getImage (crop `border`, x mul, clip) + convertColorSpace matrix -> ImProcFunctions::denoise ->
@@ -1076,6 +1117,12 @@ int artgpu_set_pipeline_smoothing(artgpu_ctx *ctx, const artgpu_smoothing_region
  * into the denoise tool's last pass or run on its own behind dehaze -- and before the sharpening (the last step of STAGE_1, improcfun.cc:588).
  * What artgpu_tone_equalizer does not support fails the frame before any stage has run. */
 int artgpu_set_pipeline_tone_equalizer(artgpu_ctx *ctx, const artgpu_tone_equalizer_params *params);
+/* Film simulation in the per-frame pipe, a setting of the context for the same reason (params copied, a reference to the handle kept;
+ * batch lanes inherit it).  clut == NULL = off, the default.  While set, the three pipe entries run artgpu_film_simulation's code after
+ * texture boost and before the tone curve (improcfun.cc:614-616) or, with after_tone_curve != 0, right behind the tone curve (L618-620);
+ * the image is in RGB mode at both points, ahead of local contrast.  A bad handle or a handle of another device fails the frame before
+ * any stage has run.  With the setting off the pipe launches exactly what it launched without it. */
+int artgpu_set_pipeline_film_simulation(artgpu_ctx *ctx, const artgpu_clut *clut, const artgpu_film_simulation_params *params, int after_tone_curve);
 
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
