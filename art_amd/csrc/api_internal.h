@@ -1,9 +1,10 @@
 // art_amd/csrc/api_internal.h -- what the host files of the C ABI share: the context, the staging and pool helpers, and per stage
-// exactly the plan structs and *_dev / *_check / *_plan functions that ANOTHER file calls: the frame driver (api_pipeline.hip) and
-// io_frame (api_batch.hip).  This header is the list of what a stage exposes to the driver; everything a stage uses only itself stays
+// exactly the plan structs and *_dev / *_check / *_plan functions that ANOTHER file calls: the frame driver (api_pipeline.hip), io_frame
+// (api_batch.hip) or a sibling stage.  This header is the list of what a stage exposes; everything a stage uses only itself stays
 // static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api, declared with hidden visibility:
 // none of them is in the library's dynamic symbol table (a definition inherits nothing from its declaration here: every opening of
-// the namespace carries the attribute).  Each is defined once (the helpers and the stages in artgpu_api.hip, the tone equalizer in
+// the namespace carries the attribute).  Each is defined once (the helpers and most stages in artgpu_api.hip, the demosaicers in
+// api_demosaic.hip, the shared filters in api_filters.hip, colour correction in api_colorcorrection.hip, the tone equalizer in
 // api_toneequalizer.hip, film simulation in api_filmsim.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -348,6 +349,25 @@ int gf_subsampling(int w, int h, int r);
 int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, int W, int H, int r, float epsilon, int subsampling, const char *who, GuidedArgs *g);
 int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
                       const char *who);
+
+// ---------------------------------------------------------------------------------------------
+// what a stage exposes to its sibling stages, by the file that defines it
+// ---------------------------------------------------------------------------------------------
+// artgpu_api.hip
+// Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292), in P_LABTABS
+int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out);
+
+// api_filters.hip (with the guided filter above)
+int gaussian_dev(artgpu_ctx *ctx, float *img, float *tmp, int W, int H, double sigma);
+int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float *mask, int W, int H,
+                    float scaling, float threshold, float ceiling, float factor, float blur, float *scratch /* >= W*H + 2*(W/4)*(H/4) */);
+// denoise::NLMeans (nlmeans.cc:44-320) on a contiguous device plane (rows of W floats), in place; enqueued on ctx->stream.  The caller has checked
+// strength != 0, W, H >= 32, (W + 14) * (H + 14) < 2^30 and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
+int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, int strength, int detail_thresh, float scale);
+
+// api_colorcorrection.hip
+// the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)
+int pq_tables_dev(artgpu_ctx *ctx, float **out);
 
 // ---------------------------------------------------------------------------------------------
 // tone equalizer

@@ -1,10 +1,42 @@
-// art_amd/csrc/artgpu_api.hip -- the C ABI of libartgpu.so (include/artgpu.h) but for the frame driver and the batch lanes: context,
-// device buffers, staging for host-pointer calls, kernel launches, error reporting.
+// art_amd/csrc/artgpu_api.hip -- the C ABI of libartgpu.so (include/artgpu.h) but for the frame driver, the batch lanes, the demosaicers,
+// the shared filters and colour correction: context, device buffers, staging for host-pointer calls, kernel launches, error reporting.
 // There is no CPU fallback here: every entry point either runs the HIP kernels or fails.
 #include "api_internal.h"
 
 using namespace artgpu;
 using namespace artgpu::api;
+
+namespace {
+
+// A table of constants in a pool slot of its own, built on the host by `fill` (which gets `nfloats` zeroed floats) and uploaded once per
+// context.  The slot doubles as the "uploaded" flag.  The host waits for the copy because the host vector dies with this call -- a bubble in
+// the stream, which is why these tables have slots that nothing else grows -- and on a failed upload the slot is given back, or the next call
+// would skip the upload and read an empty table.
+int const_table_dev(artgpu_ctx *ctx, int slot, size_t nfloats, void (*fill)(float *), const char *what, float **out)
+{
+    const bool fresh = ctx->pool[slot] == nullptr;
+    const int rc = pool_get(ctx, slot, nfloats * 4, out);
+    if (rc || !fresh) return rc;
+    std::vector<float> host(nfloats);
+    fill(host.data());
+    hipError_t e = hipMemcpyAsync(*out, host.data(), nfloats * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(ctx->pool[slot]); ctx->pool[slot] = nullptr; ctx->pool_bytes[slot] = 0;
+        *out = nullptr;
+        return fail(ctx, ARTGPU_EHIP, "upload of the %s failed: %s", what, hipGetErrorString(e));
+    }
+    return ARTGPU_OK;
+}
+
+// Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292)
+void build_lab_tabs(float *host)
+{
+    build_cachef(host); build_cachefy(host + 65536);
+    build_denoise_gamma_tabs(host + 2 * 65536, host + 3 * 65536);
+}
+
+} // namespace
 
 namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
 
@@ -131,26 +163,6 @@ int unbind_images(artgpu_ctx *ctx, artgpu_rgb *out, const DevImage *d)
     return ARTGPU_OK;
 }
 
-} } // namespace artgpu::api
-
-namespace {
-int launch_border(artgpu_ctx *ctx, const DevImage &d, int W, int H, unsigned filters, int bord)
-{
-    if (bord <= 0) return ARTGPU_OK;
-    if (W <= 2 * bord || H <= 2 * bord) return fail(ctx, ARTGPU_EUNSUPPORTED, "border_interpolate2: image %dx%d too small for border %d", W, H, bord);
-    BorderArgs b;
-    b.raw = d.raw; b.raw_stride = d.raw_stride;
-    b.red = d.r; b.green = d.g; b.blue = d.b; b.out_stride = d.out_stride;
-    b.W = W; b.H = H; b.bord = bord; b.filters = filters;
-    const long long total = 2LL * bord * H + 2LL * bord * (W - 2 * bord);
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    HIPCHK(ctx, launch_border_interpolate2(b, grid, ctx->stream));
-    return ARTGPU_OK;
-}
-} // namespace
-
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
-
 // descriptors of device memory: one dense w x h plane; three planes with rows of `stride` floats
 artgpu_plane mk_dev_plane(float *p, int w, int h) { return artgpu_plane{p, w, h, (int64_t)w * 4, 1}; }
 artgpu_rgb mk_dev_rgb(float *const p[3], int w, int h, size_t stride)
@@ -261,6 +273,11 @@ StageScope::~StageScope()
     if (!ctx) return;
     if (ctx->shared.progress_fn) ctx->shared.progress_fn(ctx->shared.progress_user, name, 1.0);
     if (range) pop()();
+}
+
+int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out)
+{
+    return const_table_dev(ctx, P_LABTABS, 4 * 65536, build_lab_tabs, "Lab tables", tabs_out);
 }
 
 } } // namespace artgpu::api
@@ -519,257 +536,6 @@ int artgpu_trim_scratch(artgpu_ctx *ctx)
     int rc = ARTGPU_OK;
     for (artgpu_ctx *l : ctx->lanes) { const int r = artgpu_trim_scratch(l); if (r && !rc) rc = r; }
     return rc;
-}
-
-struct DualReq { double *contrast; int auto_contrast; int second; };
-static int vng4_dev(artgpu_ctx *ctx, const float *raw, size_t raw_stride, float *r, float *g, float *b, size_t out_stride, int W, int H, uint32_t filters);
-static int dual_blend_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, uint32_t filters, DualReq *req);
-static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *raw, uint32_t filters,
-                               double initial_gain, int border, artgpu_rgb *out, DualReq *dual)
-{
-    StageScope scope_(ctx, "RawImageSource::demosaic (Bayer)");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(raw) || !out) return fail(ctx, ARTGPU_EINVAL, "demosaic_bayer: bad raw plane or null output");
-    if (method != ARTGPU_BAYER_AMAZE && method != ARTGPU_BAYER_RCD && method != ARTGPU_BAYER_VNG4) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: method %d is not on the device path", method);
-    if (!(initial_gain > 0.0)) return fail(ctx, ARTGPU_EINVAL, "demosaic_bayer: initial_gain must be > 0");
-    // RGB Bayer only: the reference falls back to igv_interpolate for 4-colour CFAs (rcd_demosaic.cc:57-66)
-    for (unsigned r = 0; r < 2; ++r)
-        for (unsigned c = 0; c < 2; ++c)
-            if (((filters >> ((((r << 1) & 14) + (c & 1)) << 1)) & 3) == 3) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: 4-colour CFA");
-    const int W = raw->w, H = raw->h;
-    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: image %dx%d smaller than 64x64", W, H);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-
-    DevImage d;
-    int rc = bind_images(ctx, raw, out, &d);
-    if (rc) return rc;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-
-    int bord = 0;
-    if (method == ARTGPU_BAYER_AMAZE) {
-        const int nty = (H + 16 + AMAZE_STEP - 1) / AMAZE_STEP, ntx = (W + 16 + AMAZE_STEP - 1) / AMAZE_STEP;
-        const int ntiles = nty * ntx;
-        // Tile classes (amaze_demosaic_RT.cc:182-334).  Tiles that write no pixel (the clipped tile is at most 32 wide / high) are
-        // skipped.  Tiles that are 160 columns wide go to the LDS streaming kernel (amaze_stream.hip) unless their mirrored bottom /
-        // right border fill over-runs the tile row or the cfa plane in the reference (it always writes 16 rows / columns from the
-        // frame edge: exact only when a full-size tile ends 16 pixels past the frame); everything else -- narrower tiles, those
-        // over-run tiles and streamed tiles whose Nyquist sites do not fit the stream's assumption -- is done by the arena kernel
-        // (amaze.hip), which reproduces the reference's buffer layout literally.
-        const int mode = ctx->shared.opt_amaze_path;
-        if (ctx->amz_w != W || ctx->amz_h != H || ctx->amz_mode != mode) {
-            std::vector<int> st, ar;
-            for (int ty = 0; ty < nty; ++ty)
-                for (int tx = 0; tx < ntx; ++tx) {
-                    const int top = -16 + ty * AMAZE_STEP, left = -16 + tx * AMAZE_STEP;
-                    const int rr1 = std::min(top + AMAZE_TS, H + 16) - top, cc1 = std::min(left + AMAZE_TS, W + 16) - left;
-                    if (rr1 <= 32 || cc1 <= 32) continue;
-                    // streamable: 160 columns wide (any height), and the 16 mirrored rows / columns the reference appends at the
-                    // bottom / right frame edge end exactly at the tile's edge
-                    const bool wide = cc1 == AMAZE_TS && (left + AMAZE_TS <= W || left + AMAZE_TS == W + 16);
-                    const bool rows_ok = rr1 < AMAZE_TS || top + AMAZE_TS <= H || top + AMAZE_TS == H + 16;
-                    (mode == 0 && wide && rows_ok ? st : ar).push_back(ty * ntx + tx);
-                }
-            // ... + the redo queue: 4 header ints (reserved, taken, pad) and one 64-bit word per streamed tile, 16-byte aligned
-            const size_t nfixed = ((st.size() + (1 + ar.size()) + (1 + ar.size() + st.size()) + 3) / 4) * 4;
-            const size_t nints = nfixed + 4 + 2 * st.size() + 8;
-            if ((rc = ensure(ctx, &ctx->amz_lists, &ctx->amz_lists_bytes, nints * sizeof(int)))) return rc;
-            std::vector<int> hostbuf;
-            hostbuf.insert(hostbuf.end(), st.begin(), st.end());
-            hostbuf.push_back((int)ar.size());
-            hostbuf.insert(hostbuf.end(), ar.begin(), ar.end());
-            HIPCHK(ctx, hipMemcpyAsync(ctx->amz_lists, hostbuf.data(), hostbuf.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // hostbuf goes out of scope
-            ctx->amz_w = W; ctx->amz_h = H; ctx->amz_mode = mode;
-            ctx->amz_nstream = (int)st.size(); ctx->amz_narena = (int)ar.size();
-        }
-        int *const d_stream = reinterpret_cast<int *>(ctx->amz_lists);
-        int *const d_templ = d_stream + ctx->amz_nstream;
-        int *const d_work = d_templ + 1 + ctx->amz_narena;
-        const size_t nfixed = (((size_t)ctx->amz_nstream + (1 + ctx->amz_narena) + (1 + ctx->amz_narena + ctx->amz_nstream) + 3) / 4) * 4;
-        int *const d_queue = d_stream + nfixed;                                          // header (4 ints), then the 64-bit entries
-        unsigned long long *const d_qwords = reinterpret_cast<unsigned long long *>(d_queue + 4);
-        const float clip_pt = (float)(1.0 / initial_gain);   // amaze_demosaic_RT.cc:53-54
-        const float clip_pt8 = (float)(0.8 / initial_gain);
-        // The arena kernel runs twice.  EARLY, beside the stream kernel on a stream of its own: the tiles the stream cannot take (for a
-        // frame width that is not 32 + a multiple of 128 that is a whole column of narrow tiles: 43 of 2860 at 8256 x 5504) -- they are
-        // one workgroup each and a chain of twenty HBM round trips, 0.45 ms that used to follow the stream kernel; now they hold a few CUs
-        // back for that long while the stream workgroups on the other CUs take tiles from the shared counter.  LATE, behind both: whatever
-        // the stream handed back (tiles whose Nyquist sites did not fit its assumption and found no taker in the redo queue), normally nothing.
-        const bool split = mode == 1 && ctx->shared.opt_amaze_split;
-        const bool early = ctx->amz_nstream > 0 && ctx->amz_narena > 0 && ctx->shared.opt_amaze_overlap;
-        const int nlist_max = ctx->amz_narena + ctx->amz_nstream;
-        const int cap = split ? MAX_TILE_WORKGROUPS : 768;
-        // (the per-phase profiling path runs one arena per tile of the grid, the tiles that write nothing included)
-        const int grid = split ? std::min(ntiles, cap) : std::max(1, std::min(nlist_max, cap));
-        rc = ensure(ctx, &ctx->arena, &ctx->arena_bytes, (size_t)grid * AMAZE_ARENA_FLOATS * sizeof(float));
-        if (rc) return rc;
-        if ((rc = ensure(ctx, &ctx->bbox, &ctx->bbox_bytes, (size_t)grid * 4 * sizeof(int)))) return rc;
-        AmazeArgs a;
-        a.raw = d.raw; a.raw_stride = d.raw_stride;
-        a.red = d.r; a.green = d.g; a.blue = d.b; a.out_stride = d.out_stride;
-        a.arena = ctx->arena;
-        a.W = W; a.H = H; a.ntx = ntx; a.ntiles = ntiles;
-        a.filters = filters;
-        a.clip_pt = clip_pt;
-        a.clip_pt8 = clip_pt8;
-        a.bbox = reinterpret_cast<int *>(ctx->bbox);
-        // Arena regions that have read-before-write positions on full tiles and therefore must be cleared per tile: vcd, hcd,
-        // vcdalt, hcdalt, cddiffsq, nyquist (bits 4-8, 15): on a full tile every other position is written before it is read, for
-        // every CFA phase, because the phase loops cover fixed index ranges (derivation: DESIGN.md section 10).
-        // tests/test_gpu_demosaic.py re-checks it with poisoned arenas (artgpu_set_option "amaze_poison").  Partial tiles clear everything.
-        a.zero_mask = (unsigned)ctx->shared.opt_amaze_zero_mask;
-        // ... and of the five full-size planes among them only positions within a few pixels of the tile edge (plus the gap behind each
-        // plane): a frame of 4 already passes the poison test, 16 (the discarded tile border) is used.  0: whole planes.
-        a.zero_frame = ctx->shared.opt_amaze_zero_frame;
-        a.split = split ? 1 : 0;
-        a.queue_words = d_qwords;
-        a.queue_counters = reinterpret_cast<int *>(d_qwords + ctx->amz_nstream);
-        if (ctx->shared.opt_amaze_poison >= 0)   // test hook: fill the arenas with a byte pattern first
-            HIPCHK(ctx, hipMemsetAsync(ctx->arena, ctx->shared.opt_amaze_poison, (size_t)grid * AMAZE_ARENA_FLOATS * sizeof(float), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(d_queue, 0, (4 + 2 * (size_t)ctx->amz_nstream + 8) * sizeof(int), ctx->stream));   // + the 8 counters behind it
-        SideStreamJoin amz_join;
-        if (early) {
-            // the working list starts empty (the stream appends to it), the static tiles are taken from the template
-            HIPCHK(ctx, hipMemsetAsync(d_work, 0, sizeof(int), ctx->stream));
-            if (!ctx->amz_side) {
-                HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->amz_side, hipStreamNonBlocking));
-                for (int k = 0; k < 2; ++k) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->amz_ev[k], hipEventDisableTiming));
-            }
-            // the STREAM kernel goes to the side stream, behind an event: the arena kernel is then the one the hardware starts first (the
-            // other way round the persistent stream workgroups took every CU and the arena tiles waited for them to finish)
-            HIPCHK(ctx, hipEventRecord(ctx->amz_ev[0], ctx->stream));          // the CFA plane, the cleared queue
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->amz_side, ctx->amz_ev[0], 0));
-            amz_join.arm(ctx->amz_side);
-            a.tile_list = d_templ + 1; a.tile_count = d_templ;
-            a.queue_hdr = nullptr;
-            HIPCHK(ctx, launch_amaze(a, std::min(ctx->amz_narena, cap), ctx->stream));
-        } else {
-            HIPCHK(ctx, hipMemcpyAsync(d_work, d_templ, (size_t)(1 + ctx->amz_narena) * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        if (ctx->amz_nstream > 0) {
-            AmazeStreamArgs sa;
-            sa.raw = d.raw; sa.raw_stride = d.raw_stride;
-            sa.red = d.r; sa.green = d.g; sa.blue = d.b; sa.out_stride = d.out_stride;
-            sa.W = W; sa.H = H; sa.ntx = ntx;
-            sa.filters = filters;
-            sa.clip_pt = clip_pt; sa.clip_pt8 = clip_pt8;
-            const unsigned f00 = (filters >> 0) & 3, f01 = (filters >> 2) & 3;   // FC(0,0), FC(0,1)
-            sa.g00 = (int)(f00 & 1);
-            sa.ey = f00 == 1 ? (f01 == 0 ? 0 : 1) : (f00 == 0 ? 0 : 1);        // row of the red sites (L1381-1386: ey)
-            sa.tiles = d_stream; sa.ntiles = ctx->amz_nstream;
-            sa.fallback = d_work;
-            sa.queue_hdr = d_queue; sa.queue_words = d_qwords;
-            // persistent workgroups, one per CU (the kernel needs almost all of a CU's LDS): each streams tiles back to back
-            if (ctx->num_cus <= 0) {
-                hipDeviceProp_t prop;
-                HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
-                ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            }
-            // One stream workgroup owns a CU (156 KB of LDS, sixteen waves at 122 registers) and the kernel is bound by instruction issue; the
-            // FTblockDN passes of ANOTHER frame in flight are bound by memory and can do nothing with a CU the demosaic holds.  With frames in
-            // flight (artgpu_batch_run lanes) the stream kernel therefore leaves 3/8 of the CUs to them: measured 3881 -> 4006 .. 4056 MP/s with two
-            // frames in flight at 45 MP (scripts/r5_lanes.sh: 240 / 224 / 192 / 160 / 144 / 128 workgroups; one frame at a time: all CUs).
-            // Option "amaze_grid" overrides.
-            const int cu_auto = ctx->frames_in_flight > 1 ? std::max(1, ctx->num_cus * 5 / 8) : ctx->num_cus;
-            const int cu_cap = ctx->shared.opt_amaze_grid > 0 ? std::min(ctx->shared.opt_amaze_grid, ctx->num_cus) : cu_auto;
-            HIPCHK(ctx, launch_amaze_stream(sa, std::min(ctx->amz_nstream, cu_cap), early ? ctx->amz_side : ctx->stream));
-        }
-        if (early) {
-            HIPCHK(ctx, hipEventRecord(ctx->amz_ev[1], ctx->amz_side));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->amz_ev[1], 0));    // the streamed tiles are written, the hand-back list is final
-            amz_join.disarm();
-        }
-        // arena kernel over the listed tiles (the static ones unless they went early, plus whatever the stream handed back; the count is
-        // read on the device)
-        if (split) {               // one arena per tile, tiles 0..ntiles-1 (the empty ones write nothing)
-            a.tile_list = nullptr; a.tile_count = nullptr;
-            if (grid < ntiles) return fail(ctx, ARTGPU_EUNSUPPORTED, "amaze_split needs one arena per tile (%d tiles)", ntiles);
-        } else {
-            a.tile_list = d_work + 1; a.tile_count = d_work;
-        }
-        a.queue_hdr = (!split && ctx->amz_nstream > 0) ? d_queue : nullptr;
-        HIPCHK(ctx, launch_amaze(a, split ? ntiles : grid, ctx->stream));
-        bord = border < 4 ? 3 : 0; // amaze_demosaic_RT.cc:1587-1589
-    } else if (method == ARTGPU_BAYER_VNG4) {
-        if ((rc = vng4_dev(ctx, d.raw, d.raw_stride, d.r, d.g, d.b, d.out_stride, W, H, filters))) return rc;
-        bord = 3; // vng4_demosaic_RT.cc:384
-    } else {
-        const int tileSizeN = RCD_TS - 2 * RCD_BORDER;      // the reference's tile grid (rcd_demosaic.cc:82-87)
-        const int numTh = H / tileSizeN + ((H % tileSizeN) ? 1 : 0), numTw = W / tileSizeN + ((W % tileSizeN) ? 1 : 0);
-        const int ntiles = numTh * numTw;
-        {
-            // persistent workgroups take tiles from a counter; as many as the CUs hold at once
-            if (ctx->num_cus <= 0) {
-                hipDeviceProp_t prop;
-                HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
-                ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            }
-            if (!ctx->rcd_counter) HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->rcd_counter), 64));
-            HIPCHK(ctx, hipMemsetAsync(ctx->rcd_counter, 0, sizeof(int), ctx->stream));
-            RcdStreamArgs a;
-            a.raw = d.raw; a.raw_stride = d.raw_stride;
-            a.red = d.r; a.green = d.g; a.blue = d.b; a.out_stride = d.out_stride;
-            a.W = W; a.H = H; a.numTw = numTw; a.ntiles = ntiles;
-            a.filters = filters;
-            a.vec2 = d.out_stride % 2 == 0 && (reinterpret_cast<uintptr_t>(d.r) | reinterpret_cast<uintptr_t>(d.g) | reinterpret_cast<uintptr_t>(d.b)) % 8 == 0;
-            a.counter = ctx->rcd_counter;
-            const int R = ctx->shared.opt_rcd_rows;
-            HIPCHK(ctx, launch_rcd_stream(a, R, std::min(ntiles, ctx->num_cus * rcd_stream_workgroups_per_cu(R)), ctx->stream));
-        }
-        bord = RCD_BORDER; // rcd_demosaic.cc:342
-    }
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    rc = launch_border(ctx, d, W, H, filters, bord);
-    if (rc) return rc;
-    if (dual && (rc = dual_blend_dev(ctx, d, W, H, filters, dual))) return rc;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    rc = unbind_images(ctx, out, &d);
-    if (rc) return rc;
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev[2]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.demosaic_ms, ctx->ev[0], ctx->ev[1]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.border_ms, ctx->ev[1], ctx->ev[2]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.total_ms, ctx->ev[0], ctx->ev[2]));
-    }
-    return ARTGPU_OK;
-}
-int artgpu_demosaic_bayer(artgpu_ctx *ctx, int method, const artgpu_plane *raw, uint32_t filters,
-                          double initial_gain, int border, artgpu_rgb *out)
-{
-    return demosaic_bayer_impl(ctx, method, raw, filters, initial_gain, border, out, nullptr);
-}
-int artgpu_dual_demosaic_bayer(artgpu_ctx *ctx, int method, int second, const artgpu_plane *raw, uint32_t filters, double initial_gain, int border,
-                               double *contrast, int auto_contrast, artgpu_rgb *out)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (method == ARTGPU_BAYER_VNG4 || (second != ARTGPU_DUAL_BILINEAR && second != ARTGPU_DUAL_VNG4))
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "dual_demosaic_bayer: first demosaicer AMAZE or RCD, second BILINEAR or VNG4");
-    if (!contrast || !(*contrast >= 0.0)) return fail(ctx, ARTGPU_EINVAL, "dual_demosaic_bayer: contrast must be >= 0");
-    if (raw && (raw->w < 96 || raw->h < 96)) return fail(ctx, ARTGPU_EUNSUPPORTED, "dual_demosaic_bayer: image smaller than 96x96");
-    DualReq req = {contrast, auto_contrast, second};
-    // contrast == 0 without the automatic threshold: only the first demosaicer runs (dual_demosaic_RT.cc:43-71)
-    return demosaic_bayer_impl(ctx, method, raw, filters, initial_gain, border, out, (*contrast == 0.0 && !auto_contrast) ? nullptr : &req);
-}
-
-int artgpu_border_interpolate2(artgpu_ctx *ctx, const artgpu_plane *raw, uint32_t filters, int lborders, artgpu_rgb *out)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(raw) || !out || lborders < 0) return fail(ctx, ARTGPU_EINVAL, "border_interpolate2: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevImage d;
-    int rc = bind_images(ctx, raw, out, &d);
-    if (rc) return rc;
-    if (d.staged) {
-        // host outputs: start from the caller's current contents so that only the frame changes
-        const int W = raw->w, H = raw->h;
-        artgpu_plane *op[3] = {&out->r, &out->g, &out->b};
-        float *dst[3] = {d.r, d.g, d.b};
-        for (int k = 0; k < 3; ++k)
-            HIPCHK(ctx, hipMemcpy2DAsync(dst[k], (size_t)W * 4, op[k]->p, (size_t)op[k]->row_stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = launch_border(ctx, d, raw->w, raw->h, filters, lborders);
-    if (rc) return rc;
-    return unbind_images(ctx, out, &d);
 }
 
 int artgpu_get_image(artgpu_ctx *ctx, const artgpu_rgb *planes, int sx1, int sy1, const float mul[3],
@@ -1098,11 +864,6 @@ int reconstruct_dev(artgpu_ctx *ctx, DevDecomp &d, float *dst, hipStream_t st = 
 
 } // namespace
 
-namespace {
-int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float *mask, int W, int H,
-                    float scaling, float threshold, float ceiling, float factor, float blur, float *scratch);
-}
-
 extern "C" {
 
 int artgpu_wavelet_mad(artgpu_ctx *ctx, const artgpu_wavelet *wv, float *mad_sqr)
@@ -1136,39 +897,6 @@ struct DnFusion {
     float tail_scale, tail_black;
     int ccalc_nonneg;                 // the chroma noise map is the one chroma_map_kernel has just written (squares: no negative value)
 };
-
-// A table of constants in a pool slot of its own, built on the host by `fill` (which gets `nfloats` zeroed floats) and uploaded once per
-// context.  The slot doubles as the "uploaded" flag.  The host waits for the copy because the host vector dies with this call -- a bubble in
-// the stream, which is why these tables have slots that nothing else grows -- and on a failed upload the slot is given back, or the next call
-// would skip the upload and read an empty table.
-int const_table_dev(artgpu_ctx *ctx, int slot, size_t nfloats, void (*fill)(float *), const char *what, float **out)
-{
-    const bool fresh = ctx->pool[slot] == nullptr;
-    const int rc = pool_get(ctx, slot, nfloats * 4, out);
-    if (rc || !fresh) return rc;
-    std::vector<float> host(nfloats);
-    fill(host.data());
-    hipError_t e = hipMemcpyAsync(*out, host.data(), nfloats * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(ctx->pool[slot]); ctx->pool[slot] = nullptr; ctx->pool_bytes[slot] = 0;
-        *out = nullptr;
-        return fail(ctx, ARTGPU_EHIP, "upload of the %s failed: %s", what, hipGetErrorString(e));
-    }
-    return ARTGPU_OK;
-}
-
-// Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292)
-void build_lab_tabs(float *host)
-{
-    build_cachef(host); build_cachefy(host + 65536);
-    build_denoise_gamma_tabs(host + 2 * 65536, host + 3 * 65536);
-}
-
-int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out)
-{
-    return const_table_dev(ctx, P_LABTABS, 4 * 65536, build_lab_tabs, "Lab tables", tabs_out);
-}
 
 // detail_recovery's tile masks and the 64-point cosine table with its transpose (L1479-1635), exactly as the reference builds them:
 // [tilemask_in | tilemask_out | C | C^T], 64 x 64 each
@@ -1785,250 +1513,6 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     return unbind_rgb(ctx, img, &d);
 }
 
-// ---------------------------------------------------------------------------------------------
-// guided chroma smoothing
-// ---------------------------------------------------------------------------------------------
-} // extern "C"
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
-int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter.cc:58-75)
-{
-    if (r == 1) return 1;
-    if ((w > h ? w : h) <= 600) return 1;
-    for (int s = 5; s > 0; --s)
-        if (r % s == 0) return s;
-    const int t = r / 2;
-    return t < 2 ? 2 : (t > 4 ? 4 : t);
-}
-} }
-extern "C" {
-
-int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const double ws[9], int guided_chroma_radius, double scale)
-{
-    StageScope scope_(ctx, "denoise::denoiseGuidedSmoothing");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!img || !ws || !(scale >= 1.0)) return fail(ctx, ARTGPU_EINVAL, "denoise_guided_smoothing: bad arguments");
-    if (guided_chroma_radius == 0) return ARTGPU_OK;   // ipsmoothing.cc:877-879
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevRGB d;
-    int rc = bind_rgb(ctx, img, 4, true, &d, "denoise_guided_smoothing");
-    if (rc) return rc;
-    const int W = d.w, H = d.h;
-    int r = (int)std::round(guided_chroma_radius / scale);
-    r = r > 0 ? r : 0;
-    GuidedArgs g = {};
-    for (int k = 0; k < 3; ++k) { g.rgb[k] = d.p[k]; g.ws1[k] = ws[3 + k]; }
-    g.stride = d.stride; g.W = W; g.H = H; g.epsilon = 0.001f;
-    const int sub = gf_subsampling(W, H, r);
-    g.w = W / sub; g.h = H / sub;
-    if (r == 0 || g.w < 8 || g.h < 8) return fail(ctx, ARTGPU_EUNSUPPORTED, "denoise_guided_smoothing: radius/scale combination not on the device path");
-    const size_t n = (size_t)W * H, nl = (size_t)g.w * g.h;
-    float *big, *low, *tmp;
-    if ((rc = pool_get(ctx, P_SF, 7 * n * 4, &big)) || (rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
-    for (int k = 0; k < 3; ++k) { g.in[k] = big + k * n; g.chan[k] = big + (3 + k) * n; }
-    g.guide = big + 6 * n;
-    for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
-    HIPCHK(ctx, launch_gf_prepare(g, ctx->stream));
-    HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
-    // f_mean (guidedfilter.cc:160-167): rad = LIM(int(r1), 0, (min(w,h)-1)/2 - 1); boxblur.h:318 variant
-    const float r1 = float(r) / sub;
-    int rad = (int)r1;
-    { const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }
-    BlurArgs bl = {};
-    bl.n = nl; bl.w = g.w; bl.h = g.h; bl.steady_div = 1; bl.plain = 1;
-    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    auto blur_planes = [&](float *planes, int count) -> int {
-        if (rad == 0) return ARTGPU_OK;
-        bl.src = planes; bl.dst = tmp;
-        HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
-        bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
-        HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
-        return ARTGPU_OK;
-    };
-    if ((rc = blur_planes(low, 8))) return rc;                 // meanI, corrI, meanp[3], corrIp[3]
-    HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-    if ((rc = blur_planes(low + 2 * nl, 6))) return rc;        // mean a[3], mean b[3]
-    HIPCHK(ctx, launch_gf_finish(g, ctx->stream));
-    return unbind_rgb(ctx, img, &d);
-}
-
-} // extern "C"
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
-
-// rtengine::guidedFilter (guidedfilter.cc:80-241) on contiguous device planes (rows of W floats) up to mean a / mean b on the statistics grid
-// (g->low[2], g->low[5]): the caller runs the last, pointwise pass (launch_gf_finish_plain with g->q, or one of its own).  Enqueued on
-// ctx->stream; scratch: the statistics grid in P_TMP / P_LIN
-int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, int W, int H, int r, float epsilon, int subsampling, const char *who, GuidedArgs *gout)
-{
-    const int sub = subsampling > 0 ? subsampling : gf_subsampling(W, H, r);
-    GuidedArgs &g = *gout;
-    g = GuidedArgs{};
-    g.W = W; g.H = H; g.w = W / sub; g.h = H / sub; g.epsilon = epsilon; g.nch = 1;
-    if (g.w < 1 || g.h < 1) return fail(ctx, ARTGPU_EINVAL, "%s: subsampling %d leaves no pixels", who, sub);
-    const size_t nl = (size_t)g.w * g.h;
-    float *low, *tmp;
-    int rc;
-    if ((rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
-    g.guide = const_cast<float *>(guide); g.chan[0] = const_cast<float *>(src);
-    // the four planes the single-channel statistics use lie next to each other, so that one blur launch takes them all (a grid plane of a
-    // subsampled frame is a few dozen workgroups: plane after plane the chip idles); the slots of channels 1 and 2 follow them, unused
-    static const int order[8] = {0, 1, 2, 5, 3, 4, 6, 7};
-    for (int k = 0; k < 8; ++k) g.low[order[k]] = low + k * nl;
-    const float r1 = float(r) / sub;
-    int rad = (int)r1;
-    { const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }     // f_mean's LIM (L160-164)
-    if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, rad, HBLUR_MAX_RADIUS);
-    HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
-    BlurArgs bl = {};
-    bl.n = nl; bl.w = g.w; bl.h = g.h; bl.steady_div = 1; bl.plain = 1;
-    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    auto blur_planes = [&](float *planes, int count) -> int {
-        if (rad == 0) return ARTGPU_OK;
-        bl.src = planes; bl.dst = tmp;
-        HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
-        bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
-        HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
-        return ARTGPU_OK;
-    };
-    // low[0] I1 -> meanI, low[1] I1*I1 -> corrI, low[2] p1 -> meanp, low[5] I1*p1 -> corrIp
-    if ((rc = blur_planes(g.low[0], 4))) return rc;
-    HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-    if ((rc = blur_planes(g.low[2], 2))) return rc;                                    // mean a, mean b
-    return ARTGPU_OK;
-}
-
-// ... and the whole filter: q with rows of q_stride floats; q may be `guide` or `src` (the last pass is pointwise)
-int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
-                      const char *who)
-{
-    GuidedArgs g;
-    int rc;
-    if ((rc = guided_filter_stats(ctx, guide, src, W, H, r, epsilon, subsampling, who, &g))) return rc;
-    g.q = q; g.q_stride = q_stride;
-    HIPCHK(ctx, launch_gf_finish_plain(g, ctx->stream));
-    return ARTGPU_OK;
-}
-
-} } // namespace artgpu::api
-extern "C" {
-
-int artgpu_guided_filter(artgpu_ctx *ctx, const artgpu_plane *guide, const artgpu_plane *src, artgpu_plane *dst, int r, float epsilon, int subsampling)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!guide || !src || !dst || !plane_ok(guide) || !plane_ok(src) || !plane_ok(dst)) return fail(ctx, ARTGPU_EINVAL, "guided_filter: bad plane");
-    const int W = src->w, H = src->h;
-    if (guide->w != W || guide->h != H || dst->w != W || dst->h != H || r < 0) return fail(ctx, ARTGPU_EINVAL, "guided_filter: size mismatch / negative radius");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H;
-    float *big;
-    int rc;
-    if ((rc = pool_get(ctx, P_SF, 3 * n * 4, &big))) return rc;
-    const size_t rowb = (size_t)W * 4;
-    HIPCHK(ctx, hipMemcpy2DAsync(big, rowb, guide->p, (size_t)guide->row_stride_bytes, rowb, H, guide->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpy2DAsync(big + n, rowb, src->p, (size_t)src->row_stride_bytes, rowb, H, src->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = guided_filter_dev(ctx, big, big + n, big + 2 * n, (size_t)W, W, H, r, epsilon, subsampling, "guided_filter"))) return rc;
-    HIPCHK(ctx, hipMemcpy2DAsync(dst->p, (size_t)dst->row_stride_bytes, big + 2 * n, rowb, rowb, H, dst->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    if (!dst->on_device) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ARTGPU_OK;
-}
-
-// RawImageSource::vng4_demosaic on device planes (vng4_demosaic_RT.cc:62-397)
-static int vng4_dev(artgpu_ctx *ctx, const float *raw, size_t raw_stride, float *r, float *g, float *b, size_t out_stride, int W, int H, uint32_t filters)
-{
-    if (W < 16 || H < 16) return fail(ctx, ARTGPU_EUNSUPPORTED, "vng4: image %dx%d smaller than 16x16", W, H);
-    float *image, *codef;
-    int rc;
-    if ((rc = pool_get(ctx, P_BLOCKS, (size_t)W * H * 16, &image)) || (rc = pool_get(ctx, P_DTAB, 16 * VNG4_CODE_INTS * 4, &codef))) return rc;
-    Vng4Args a = {};
-    a.raw = raw; a.raw_stride = raw_stride; a.red = r; a.green = g; a.blue = b; a.out_stride = out_stride;
-    a.image = image; a.code = reinterpret_cast<const int *>(codef); a.w = W; a.h = H; a.filters = filters; a.prefilters = vng4_prefilters(filters);
-    std::vector<int> codes(16 * VNG4_CODE_INTS, 0);
-    vng4_build_code(a.prefilters, W, codes.data());
-    HIPCHK(ctx, hipMemcpyAsync(codef, codes.data(), codes.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));     // `codes` goes out of scope
-    HIPCHK(ctx, launch_vng4(a, ctx->stream));
-    return ARTGPU_OK;
-}
-// dual_demosaic_RT.cc:99-152 after the first demosaicer: L, buildBlendMask (rt_algo.cc:315-498), bilinear blend
-static int dual_blend_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, uint32_t filters, DualReq *req)
-{
-    const size_t n = (size_t)W * H;
-    float *tabs, *L, *blend, *var;
-    int rc;
-    if ((rc = lab_tabs_dev(ctx, &tabs)) || (rc = pool_get(ctx, P_DMASK, n * 4, &L)) || (rc = pool_get(ctx, P_CCMAP, n * 4, &blend))) return rc;
-    DualArgs a = {};
-    a.rgb[0] = d.r; a.rgb[1] = d.g; a.rgb[2] = d.b; a.stride = d.out_stride;
-    a.raw = d.raw; a.raw_stride = d.raw_stride; a.w = W; a.h = H; a.filters = filters;
-    a.cachefy = tabs + 65536; a.L = L; a.blend = blend;
-    HIPCHK(ctx, launch_rgb2l(a, ctx->stream));
-    float thr = (float)(*req->contrast / 100.0);
-    if (req->auto_contrast) {
-        // the reference's two-pass search for the flattest tile (rt_algo.cc:317-432): tile statistics on the device, the serial
-        // first-minimum scan over them on the host
-        std::vector<float> host;
-        float *res;
-        auto stats = [&](int nH, int nW, int y0, int x0, int step, int ts, int *mi, int *mj, float *minvar) -> int {
-            *mi = *mj = 0; *minvar = INFINITY;
-            if (nH <= 0 || nW <= 0) return ARTGPU_OK;
-            const size_t cnt = (size_t)nH * nW;
-            int rc2 = pool_get(ctx, P_TMP, cnt * 4, &var);
-            if (rc2) return rc2;
-            HIPCHK(ctx, launch_tile_stats(a, nH, nW, y0, x0, step, ts, var, ctx->stream));
-            host.resize(cnt);
-            HIPCHK(ctx, hipMemcpyAsync(host.data(), var, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            for (int i = 0; i < nH; ++i)
-                for (int j = 0; j < nW; ++j)
-                    if (host[(size_t)i * nW + j] < *minvar) { *minvar = host[(size_t)i * nW + j]; *mi = i; *mj = j; }
-            return ARTGPU_OK;
-        };
-        auto threshold_of = [&](int ty, int tx, int ts, float *out_thr) -> int {
-            int rc2 = pool_get(ctx, P_MAD, 64, &res);
-            if (rc2) return rc2;
-            HIPCHK(ctx, launch_contrast_threshold(a, ty, tx, ts, res, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(out_thr, res, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            return ARTGPU_OK;
-        };
-        for (int pass = 0; pass < 2; ++pass) {
-            const int ts = 80 / (pass + 1), skip = pass == 0 ? ts : ts / 4;
-            const int nW = W / skip - 3 * pass, nH = H / skip - 3 * pass;
-            int mi, mj; float minvar;
-            if ((rc = stats(nH, nW, 0, 0, skip, ts, &mi, &mj, &minvar))) return rc;
-            if (minvar <= 1.f || pass == 1) {
-                const int minY = skip * mi, minX = skip * mj;
-                if (pass == 0) {
-                    if ((rc = threshold_of(minY, minX, ts, &thr))) return rc;
-                    break;
-                }
-                const int y0 = std::max(minY - skip, 0), x0 = std::max(minX - skip, 0);
-                const int y1 = std::min(minY + skip, H - ts), x1 = std::min(minX + skip, W - ts);
-                int mi2, mj2; float minvar2;
-                if ((rc = stats(y1 - y0 + 1, x1 - x0 + 1, y0, x0, 1, ts, &mi2, &mj2, &minvar2))) return rc;
-                if (minvar2 <= 8.f) { if ((rc = threshold_of(y0 + mi2, x0 + mj2, ts, &thr))) return rc; }
-                else thr = 0.f;
-            }
-        }
-    }
-    *req->contrast = thr * 100.f;
-    a.threshold = thr;
-    HIPCHK(ctx, launch_blend_mask(a, ctx->stream));
-    if (thr != 0.f) {
-        artgpu_plane bp = {blend, W, H, (int64_t)W * 4, 1};
-        if ((rc = artgpu_gaussian_blur(ctx, &bp, 2.0))) return rc;      // rt_algo.cc:492
-    }
-    if (req->second == ARTGPU_DUAL_VNG4) {
-        // vng4_demosaic into temporaries, then all three channels of every pixel (dual_demosaic_RT.cc:128-148)
-        float *t;
-        if ((rc = pool_get(ctx, P_SF, 3 * n * 4, &t))) return rc;
-        if ((rc = vng4_dev(ctx, d.raw, d.raw_stride, t, t + n, t + 2 * n, (size_t)W, W, H, filters))) return rc;
-        DevImage tmp = {d.raw, d.raw_stride, t, t + n, t + 2 * n, (size_t)W, false};
-        if ((rc = launch_border(ctx, tmp, W, H, filters, 3))) return rc;
-        HIPCHK(ctx, launch_dual_blend_planes(a, t, t + n, t + 2 * n, (size_t)W, ctx->stream));
-        return ARTGPU_OK;
-    }
-    HIPCHK(ctx, launch_bilinear_blend(a, ctx->stream));
-    return ARTGPU_OK;
-}
 static int lab_mode_switch(artgpu_ctx *ctx, artgpu_rgb *img, const double m[9], bool to_lab, const char *who)
 {
     if (!ctx) return ARTGPU_EINVAL;
@@ -2203,286 +1687,9 @@ int artgpu_hsl_equalizer(artgpu_ctx *ctx, artgpu_rgb *img, const double *hcurve,
 }
 
 // ---------------------------------------------------------------------------------------------
-// gaussian blur, detail mask, NL-means
-// ---------------------------------------------------------------------------------------------
-} // extern "C"
-namespace {
-
-// calculateYvVFactors<double> + M rescaling (gauss.cc:94-126,556-562)
-void yvv_factors(double sigma, GaussArgs &g, bool double_path = false)
-{
-    double q;
-    if (sigma < 2.5) q = 3.97156 - 4.14554 * std::sqrt(1.0 - 0.26891 * sigma);
-    else q = 0.98711 * sigma - 0.96330;
-    const double b0 = 1.57825 + 2.44413 * q + 1.4281 * q * q + 0.422205 * q * q * q;
-    double b1 = 2.44413 * q + 2.85619 * q * q + 1.26661 * q * q * q;
-    double b2 = -1.4281 * q * q - 1.26661 * q * q * q;
-    double b3 = 0.422205 * q * q * q;
-    g.B = 1.0 - (b1 + b2 + b3) / b0;
-    b1 /= b0; b2 /= b0; b3 /= b0;
-    double *M = g.M;
-    M[0] = -b3 * b1 + 1.0 - b3 * b3 - b2;
-    M[1] = (b3 + b1) * (b2 + b3 * b1);
-    M[2] = b3 * (b1 + b3 * b2);
-    M[3] = b1 + b3 * b2;
-    M[4] = -(b2 - 1.0) * (b2 + b3 * b1);
-    M[5] = -(b3 * b1 + b3 * b3 + b2 - 1.0) * b3;
-    M[6] = b3 * b1 + b2 + b1 * b1 - b2 * b2;
-    M[7] = b1 * b2 + b3 * b2 * b2 - b1 * b3 * b3 - b3 * b3 * b3 - b3 * b2 + b3;
-    M[8] = b3 * (b1 + b3 * b2);
-    for (int i = 0; i < 9; ++i) {
-        if (double_path) {           // gaussHorizontal<T> / gaussVertical<T> normalise differently (gauss.cc:674-677 vs 559-563)
-            M[i] /= (1.0 + b1 - b2 + b3) * (1.0 + b2 + (b1 - b3) * b3);
-        } else {
-            M[i] *= (1.0 + b2 + (b1 - b3) * b3);
-            M[i] /= (1.0 + b1 - b2 + b3) * (1.0 - b1 - b2 - b3);
-        }
-        g.Mf[i] = (float)M[i];
-    }
-    g.b[0] = b1; g.b[1] = b2; g.b[2] = b3;
-    g.Bf = (float)g.B; g.bf[0] = (float)b1; g.bf[1] = (float)b2; g.bf[2] = (float)b3;
-}
-
-int gaussian_dev(artgpu_ctx *ctx, float *img, float *tmp, int W, int H, double sigma)
-{
-    // gaussianBlur's dispatch for src == dst (gauss.cc:1436-1523; the box-blur approximation above it is only taken for
-    // sigma > 2 of the frame width, far off this path)
-    if (!(sigma == sigma) || W < 8 || H < 8) return fail(ctx, ARTGPU_EUNSUPPORTED, "gaussian_blur: sigma %g / size %dx%d not on the device path", sigma, W, H);
-    if (sigma < 0.25) return ARTGPU_OK;                 // GAUSS_SKIP: no filtering
-    if (sigma < 0.6) {                                  // GAUSS_3X3_LIMIT: separated 3-tap kernel, coefficients in double, passed as float
-        double c1 = exp(-1.0 / (2.0 * sigma * sigma));
-        const double csum = 2.0 * c1 + 1.0;
-        c1 /= csum;
-        const double c0 = 1.0 / csum;
-        HIPCHK(ctx, launch_gaussian3(img, tmp, W, H, (float)c0, (float)c1, ctx->stream));
-        return ARTGPU_OK;
-    }
-    GaussArgs g = {};
-    g.img = img; g.tmp = tmp; g.W = W; g.H = H;
-    if (sigma >= 25.0) {                    // GAUSS_DOUBLE (gauss.cc:1393,1520-1523): all-double recursion
-        float *t64;
-        int rc = pool_get(ctx, P_GAUSS64, (size_t)W * H * sizeof(double), &t64);
-        if (rc) return rc;
-        g.tmp64 = reinterpret_cast<double *>(t64);
-        yvv_factors(sigma, g, true);
-    } else {
-        yvv_factors((double)(float)sigma, g);   // the Sse functions take `const float sigma`
-    }
-    HIPCHK(ctx, launch_gaussian(g, ctx->stream));
-    return ARTGPU_OK;
-}
-
-int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float *mask, int W, int H,
-                    float scaling, float threshold, float ceiling, float factor, float blur, float *scratch /* >= W*H + 2*(W/4)*(H/4) */)
-{
-    MaskArgs m = {};
-    m.src = src; m.src_stride = src_stride; m.mask = mask; m.W = W; m.H = H; m.w4 = W / 4; m.h4 = H / 4;
-    m.L2 = scratch + (size_t)W * H; m.m2 = m.L2 + (size_t)m.w4 * m.h4;
-    m.scaling = scaling; m.threshold = threshold; m.ceiling = ceiling; m.factor = factor;
-    HIPCHK(ctx, launch_detail_mask(m, ctx->stream));
-    return gaussian_dev(ctx, mask, scratch, W, H, blur);
-}
-
-} // namespace
-extern "C" {
-
-int artgpu_gaussian_blur(artgpu_ctx *ctx, artgpu_plane *img, double sigma)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(img)) return fail(ctx, ARTGPU_EINVAL, "gaussian_blur: bad plane");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    float *work, *tmp;
-    int rc = plane_to_pool(ctx, img, P_SF, &work);
-    if (rc) return rc;
-    if ((rc = pool_get(ctx, P_TMP, (size_t)img->w * img->h * 4, &tmp))) return rc;
-    if ((rc = gaussian_dev(ctx, work, tmp, img->w, img->h, sigma))) return rc;
-    return pool_to_plane(ctx, work, img);
-}
-
-int artgpu_detail_mask(artgpu_ctx *ctx, const artgpu_plane *src, artgpu_plane *mask, float scaling, float threshold,
-                       float ceiling, float factor, float blur)
-{
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(src) || !plane_ok(mask) || mask->w != src->w || mask->h != src->h) return fail(ctx, ARTGPU_EINVAL, "detail_mask: bad planes");
-    if (src->w < 32 || src->h < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "detail_mask: image smaller than 32x32");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int W = src->w, H = src->h;
-    float *in, *m, *scratch;
-    int rc = plane_to_pool(ctx, src, P_SF, &in);
-    if (rc) return rc;
-    if ((rc = pool_get(ctx, P_TMP, (size_t)W * H * 4, &m))) return rc;
-    if ((rc = pool_get(ctx, P_LIN, ((size_t)W * H + 2 * (size_t)(W / 4) * (H / 4)) * 4, &scratch))) return rc;
-    if ((rc = detail_mask_dev(ctx, in, W, m, W, H, scaling, threshold, ceiling, factor, blur, scratch))) return rc;
-    return pool_to_plane(ctx, m, mask);
-}
-
-} // extern "C"
-namespace {
-// denoise::NLMeans (nlmeans.cc:44-320) on a contiguous device plane (rows of W floats), in place; enqueued on ctx->stream.  The caller has checked
-// strength != 0, W, H >= 32, (W + 14) * (H + 14) < 2^30 and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
-int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, int strength, int detail_thresh, float scale)
-{
-    NlmArgs a = {};
-    a.search_radius = int(std::ceil(5.f / scale));
-    a.patch_radius = int(std::ceil(2.f / scale));
-    const float t = std::pow(float(strength) / 100.f, 0.9f) / 10.f / scale;
-    a.h2 = t * t;
-    float amount = float(detail_thresh) / 100.f;
-    amount = amount < 0.f ? 0.f : (amount > 0.99f ? 0.99f : amount);   // LIM(x, 0, 0.99)
-    a.border = a.search_radius + a.patch_radius;
-    a.W = W; a.H = H; a.WW = W + 2 * a.border; a.HH = H + 2 * a.border; a.factor = normcoeff;
-    a.ntiles_x = int(std::ceil(float(a.WW) / (150 - 2 * a.border)));
-    a.ntiles_y = int(std::ceil(float(a.HH) / (150 - 2 * a.border)));
-    float *scratch, *pad;
-    int rc = ARTGPU_OK;
-    if ((rc = pool_get(ctx, P_TMP, (size_t)W * H * 4 * 2 + 8192 * 4, &a.mask))) return rc;
-    a.SW = a.mask + (size_t)W * H; a.explut = a.SW + (size_t)W * H;
-    if ((rc = pool_get(ctx, P_LIN, ((size_t)W * H + 2 * (size_t)(W / 4) * (H / 4)) * 4, &scratch))) return rc;
-    if ((rc = pool_get(ctx, P_BLOCKS, (size_t)a.WW * a.HH * 4, &pad))) return rc;
-    if ((rc = detail_mask_dev(ctx, work, W, a.mask, W, H, normcoeff, 1e-3f * normcoeff, normcoeff, amount, 2.f / scale, scratch))) return rc;
-    a.img = work; a.img_stride = W; a.src = pad;
-    HIPCHK(ctx, launch_nlm(a, ctx->stream));
-    return ARTGPU_OK;
-}
-} // namespace
-extern "C" {
-
-int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int strength, int detail_thresh, float scale)
-{
-    StageScope scope_(ctx, "denoise::NLMeans");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(img) || !(scale >= 1.f)) return fail(ctx, ARTGPU_EINVAL, "nlmeans: bad arguments");
-    if (!strength) return ARTGPU_OK;                       // nlmeans.cc:52-54
-    if (img->w < 32 || img->h < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image smaller than 32x32");
-    // (the tile kernel addresses a plane through 32-bit byte offsets)
-    if ((unsigned long long)(img->w + 14) * (unsigned long long)(img->h + 14) >= (1ull << 30)) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image of %dx%d exceeds 2^30 pixels", img->w, img->h);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int W = img->w, H = img->h;
-    float *work;
-    // a contiguous device plane is worked on where it lies (the kernels read the padded copy `pad` and the mask, and write the plane): two plane
-    // copies less per call, 0.16 ms of a 45 MP frame; anything else goes through a contiguous working copy
-    const bool in_place = img->on_device && img->row_stride_bytes == (int64_t)W * 4;
-    int rc = ARTGPU_OK;
-    if (in_place) work = img->p;
-    else if ((rc = plane_to_pool(ctx, img, P_SF, &work))) return rc;
-    if ((rc = nlm_plane_dev(ctx, work, W, H, normcoeff, strength, detail_thresh, scale))) return rc;
-    return in_place ? ARTGPU_OK : pool_to_plane(ctx, work, img);
-}
-
-// ---------------------------------------------------------------------------------------------
-// X-Trans demosaic
-// ---------------------------------------------------------------------------------------------
-int artgpu_demosaic_xtrans(artgpu_ctx *ctx, int passes, int use_cielab, const artgpu_plane *raw, const int32_t xtrans[36],
-                           const float rgb_cam[12], artgpu_rgb *out)
-{
-    StageScope scope_(ctx, "RawImageSource::xtrans_interpolate");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(raw) || !out || !xtrans || !rgb_cam) return fail(ctx, ARTGPU_EINVAL, "demosaic_xtrans: bad raw plane or null argument");
-    if (passes < 1 || passes > 4) return fail(ctx, ARTGPU_EINVAL, "demosaic_xtrans: passes must be 1..4");
-    const int W = raw->w, H = raw->h;
-    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: image %dx%d smaller than 64x64", W, H);
-    int ngreen = 0;
-    for (int i = 0; i < 36; ++i) {
-        if (xtrans[i] < 0 || xtrans[i] > 2) return fail(ctx, ARTGPU_EINVAL, "demosaic_xtrans: colour map entries must be 0..2");
-        ngreen += xtrans[i] == 1;
-    }
-    if (ngreen != 20) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: not an X-Trans colour map (%d green of 36)", ngreen);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevImage d;
-    int rc = bind_images(ctx, raw, out, &d);
-    if (rc) return rc;
-    // the reference keeps the hexagon offsets in `short` (xtrans_demosaic.cc:233): same range limit here
-    if (2 * (long long)d.raw_stride + 2 > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: row stride %zu exceeds the reference's short offsets", d.raw_stride);
-
-    XtransArgs a = {};
-    a.raw = d.raw; a.raw_stride = d.raw_stride;
-    a.red = d.r; a.green = d.g; a.blue = d.b; a.out_stride = d.out_stride;
-    a.W = W; a.H = H; a.passes = passes; a.ndir = 4 << (passes > 1); a.use_cielab = use_cielab ? 1 : 0;
-    for (int i = 0; i < 36; ++i) a.xtrans[i] = xtrans[i];
-    auto isgreen = [&](int row, int col) { return a.xtrans[(row % 3) * 6 + col % 3] & 1; };
-    {   // xyz_cam (L219-230)
-        static const float xyz_rgb[3][3] = {{0.412453, 0.357580, 0.180423}, {0.212671, 0.715160, 0.072169}, {0.019334, 0.119193, 0.950227}};
-        static const float d65_white[3] = {0.950456, 1, 1.088754};
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) {
-                float acc = 0;
-                for (int k = 0; k < 3; k++) acc += xyz_rgb[i][k] * rgb_cam[k * 4 + j] / d65_white[i];
-                a.xyz_cam[i * 3 + j] = acc;
-            }
-    }
-    {   // green hexagons around each site class and the solitary-green phase (L232-267)
-        static const int orth[12] = {1, 0, 0, 1, -1, 0, 0, -1, 1, 0, 0, 1};
-        static const int patt[2][16] = {{0, 1, 0, -1, 2, 0, -1, 0, 1, 1, 1, -1, 0, 0, 0, 0}, {0, 1, 0, -2, 1, 0, -2, 0, 1, 1, -2, -2, 1, -1, -1, 1}};
-        for (int row = 0; row < 3; row++)
-            for (int col = 0; col < 3; col++) {
-                const int gint = isgreen(row, col);
-                for (int ng = 0, dd = 0; dd < 10; dd += 2) {
-                    if (isgreen(row + orth[dd] + 6, col + orth[dd + 2] + 6)) ng = 0; else ng++;
-                    if (ng == 4) { a.sgrow = row; a.sgcol = col; }
-                    if (ng == gint + 1)
-                        for (int c = 0; c < 8; c++) {
-                            const int v = orth[dd] * patt[gint][c * 2] + orth[dd + 1] * patt[gint][c * 2 + 1];
-                            const int h = orth[dd + 2] * patt[gint][c * 2] + orth[dd + 3] * patt[gint][c * 2 + 1];
-                            a.allhex0[row][col][c ^ (gint * 2 & dd)] = h + v * (int)d.raw_stride;
-                            a.allhex1[row][col][c ^ (gint * 2 & dd)] = h + v * XTRANS_TS;
-                        }
-                }
-            }
-        for (int row = 0; row < 3; row++) {
-            int greencount = 0;
-            for (int col = 0; col < 3; col++) greencount += isgreen(row, col);
-            a.right_shift[row] = greencount == 2;
-        }
-    }
-    float *lut;
-    const bool fresh = ctx->pool[P_XCBRT] == nullptr;
-    if ((rc = pool_get(ctx, P_XCBRT, 0x14000 * 4, &lut))) return rc;
-    if (fresh) {   // cielab's LUT (L43-57), built on the host like the reference's
-        std::vector<float> host(0x14000);
-        const double eps = 216.0 / 24389.0, kappa = 24389.0 / 27.0;
-        for (int i = 0; i < 0x14000; i++) {
-            const double r = i / 65535.0;
-            host[i] = (float)(r > eps ? std::cbrt(r) : (kappa * r + 16.0) / 116.0);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(lut, host.data(), host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    a.cbrt_lut = lut;
-    a.ntx = (W - 22 + (XTRANS_TS - 16) - 1) / (XTRANS_TS - 16);
-    const int nty = (H - 22 + (XTRANS_TS - 16) - 1) / (XTRANS_TS - 16);
-    a.ntiles = a.ntx * nty;
-    // one 1024-thread workgroup is resident per CU: one persistent workgroup per CU, tiles from a shared counter (the arena is 0.45 GB)
-    if (ctx->num_cus <= 0) {
-        hipDeviceProp_t prop;
-        HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    const int grid = a.ntiles < ctx->num_cus ? a.ntiles : ctx->num_cus;
-    if (!ctx->rcd_counter) HIPCHK(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->rcd_counter), 64));
-    a.counter = ctx->rcd_counter + 4;           // (the RCD kernel's counter is word 0 of the same 64 bytes)
-    HIPCHK(ctx, hipMemsetAsync(a.counter, 0, sizeof(int), ctx->stream));
-    a.arena_floats = (size_t)XTRANS_TS * XTRANS_TS * (a.ndir * 4 + 3) + 128;
-    rc = ensure(ctx, &ctx->arena, &ctx->arena_bytes, (size_t)grid * a.arena_floats * sizeof(float));
-    if (rc) return rc;
-    a.arena = ctx->arena;
-    if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    HIPCHK(ctx, launch_xtrans(a, grid, ctx->stream));
-    if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream)); }
-    rc = unbind_images(ctx, out, &d);
-    if (rc) return rc;
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev[2]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.demosaic_ms, ctx->ev[0], ctx->ev[1]));
-        ctx->last.border_ms = 0.f; ctx->last.total_ms = ctx->last.demosaic_ms;
-    }
-    return ARTGPU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
 // NEUTRAL tone curve
 // ---------------------------------------------------------------------------------------------
 } // extern "C"
-namespace { int pq_tables_dev(artgpu_ctx *ctx, float **out); }       // (defined with the colour correction, its other user)
 extern "C" {
 int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *lut65536, float whitecoeff, const artgpu_neutral_state *st)
 {
@@ -4033,171 +3240,6 @@ int artgpu_generate_masks(artgpu_ctx *ctx, const artgpu_rgb *img, int mode, cons
         if (abmask && (rc = pool_to_plane(ctx, about + (size_t)i * np, &abmask[i]))) return rc;
     }
     return ARTGPU_OK;
-}
-
-} // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// colour correction: ImProcFunctions::colorCorrection (ipcolorcorrection.cc:39-866)
-// ---------------------------------------------------------------------------------------------
-
-namespace {
-
-// the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)
-int pq_tables_dev(artgpu_ctx *ctx, float **out)
-{
-    float *pq;
-    int rc;
-    const bool fresh = ctx->pool[P_PQ] == nullptr;
-    if ((rc = pool_get(ctx, P_PQ, (2 * 65536 + 64) * 4, &pq))) return rc;
-    if (fresh) {
-        std::vector<float> host(2 * 65536);
-        build_pq_luts(host.data(), host.data() + 65536);
-        HIPCHK(ctx, hipMemcpyAsync(pq, host.data(), host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        NeutralArgs a = {};
-        a.pq = pq; a.pq_inv = pq + 65536; a.hues = pq + 2 * 65536;
-        HIPCHK(ctx, launch_neutral_hues(a, ctx->stream));
-    }
-    *out = pq;
-    return ARTGPU_OK;
-}
-
-} // namespace
-
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
-
-int cc_check(artgpu_ctx *ctx, int W, int H, const artgpu_color_correction_region *regions, int nregions, const double *ws, const double *iws, bool read_masks,
-             const char *who, CcPlan *pl)
-{
-    if (nregions < 0 || (nregions > 0 && !regions) || !ws || !iws) return fail(ctx, ARTGPU_EINVAL, "%s: bad arguments", who);
-    for (int k = 0; k < 9; ++k) { pl->ws[k] = (float)ws[k]; pl->iws[k] = (float)iws[k]; }      // TMatrix -> float ws[3][3], once (L94-108)
-    cc_luminance_factors(pl->ws, &pl->fR, &pl->fG, &pl->fB);
-    pl->regs.assign(nregions, CcRegion{});
-    pl->any_jz = false;
-    for (int i = 0; i < nregions; ++i) {
-        const artgpu_color_correction_region &r = regions[i];
-        if (r.mode == ARTGPU_CC_LUT) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: LUT mode (CLUT files) is not on the device path", who, i);
-        if (r.mode < ARTGPU_CC_YUV || r.mode > ARTGPU_CC_LUT) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: mode %d", who, i, r.mode);
-        if (r.mode == ARTGPU_CC_HSL && !(r.hsl_gamma > 0.0)) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: hsl_gamma %g", who, i, r.hsl_gamma);
-        CcRegionParams p;
-        p.mode = r.mode; p.rgbluminance = r.rgbluminance;
-        p.a = r.a; p.b = r.b; p.in_saturation = r.in_saturation; p.out_saturation = r.out_saturation; p.hueshift = r.hueshift; p.hsl_gamma = r.hsl_gamma;
-        for (int c = 0; c < 3; ++c) {
-            p.slope[c] = r.slope[c]; p.offset[c] = r.offset[c]; p.power[c] = r.power[c]; p.pivot[c] = r.pivot[c]; p.compression[c] = r.compression[c];
-            p.hue[c] = r.hue[c]; p.sat[c] = r.sat[c]; p.factor[c] = r.factor[c];
-        }
-        cc_derive_region(p, pl->ws, &pl->regs[i]);
-        if (!cc_region_finite(pl->regs[i]))
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a derived scalar is not finite (power 0, pivot 0 or a value out of range)", who, i);
-        pl->any_jz = pl->any_jz || pl->regs[i].jzazbz;
-        for (const artgpu_plane *m : {r.lmask, r.abmask})
-            if (read_masks && m && (!plane_ok(m) || m->w != W || m->h != H)) return fail(ctx, ARTGPU_EINVAL, "%s: region %d: a mask must be a %dx%d plane", who, i, W, H);
-    }
-    if (!std::isfinite(pl->fR) || !std::isfinite(pl->fG) || !std::isfinite(pl->fB)) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: the working space's luminance row", who);
-    return ARTGPU_OK;
-}
-
-// the tool on device planes (rows of `stride` floats) in RGB mode, or in YUV mode with `from_yuv`; enqueued on ctx->stream, one host wait with `info`
-int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_color_correction_region *regions,
-                         const CcPlan &pl, int from_yuv, int to_rgb, artgpu_color_correction_info *info)
-{
-    const int n = (int)pl.regs.size();
-    const size_t np = (size_t)W * H;
-    int rc;
-    std::vector<CcRegion> regs = pl.regs;
-    // host planes are staged once each (one plane may serve as both masks, and several regions may share one)
-    std::vector<const artgpu_plane *> host;
-    for (int i = 0; i < n; ++i)
-        for (const artgpu_plane *m : {regions[i].lmask, regions[i].abmask})
-            if (m && !m->on_device && std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) == host.end()) host.push_back(m);
-    float *staged = nullptr;
-    if (!host.empty()) {
-        if ((rc = pool_get(ctx, P_CC_MASK, host.size() * np * 4, &staged))) return rc;
-        for (size_t k = 0; k < host.size(); ++k)
-            HIPCHK(ctx, hipMemcpy2DAsync(staged + k * np, (size_t)W * 4, host[k]->p, (size_t)host[k]->row_stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const auto bind = [&](const artgpu_plane *m, const float **p, size_t *s) {
-        *p = nullptr; *s = 0;
-        if (!m) return;
-        if (m->on_device) { *p = m->p; *s = (size_t)(m->row_stride_bytes / 4); return; }
-        const size_t k = std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) - host.begin();
-        *p = staged + k * np; *s = W;
-    };
-    for (int i = 0; i < n; ++i) { bind(regions[i].lmask, &regs[i].lmask, &regs[i].l_stride); bind(regions[i].abmask, &regs[i].abmask, &regs[i].ab_stride); }
-    CcArgs a = {};
-    for (int k = 0; k < 3; ++k) a.img[k] = planes[k];
-    a.stride = stride; a.w = W; a.h = H;
-    for (int k = 0; k < 9; ++k) { a.ws[k] = pl.ws[k]; a.iws[k] = pl.iws[k]; }
-    a.fR = pl.fR; a.fG = pl.fG; a.fB = pl.fB;
-    if (pl.any_jz) {
-        float *pq;
-        if ((rc = pq_tables_dev(ctx, &pq))) return rc;
-        a.pq = pq; a.pq_inv = pq + 65536;
-        cc_pq_low(&a.pq_low, &a.pq_inv_low);
-    }
-    unsigned long long *count = nullptr;
-    if (info && pl.any_jz) {
-        float *buf;
-        if ((rc = pool_get(ctx, P_CC_OOR, 64 + np, &buf))) return rc;
-        HIPCHK(ctx, hipMemsetAsync(buf, 0, 64 + np, ctx->stream));
-        count = reinterpret_cast<unsigned long long *>(buf);
-        a.oor = reinterpret_cast<unsigned char *>(buf) + 64;
-    }
-    // launches: up to CC_MAX_REGIONS regions each, cut earlier where Jzazbz and the HSL hue shift would meet (they share no instantiation).
-    // The tool is in place and pointwise, so the launches compose: the first does setMode(YUV), the last setMode(RGB)
-    int first = 0;
-    do {
-        int cnt = 0, need = 0;
-        while (first + cnt < n && cnt < CC_MAX_REGIONS && cc_need_fits(need | cc_region_need(regs[first + cnt]))) need |= cc_region_need(regs[first + cnt++]);
-        for (int k = 0; k < cnt; ++k) a.r[k] = regs[first + k];
-        a.nregions = cnt;
-        a.from_yuv = first > 0 ? 1 : from_yuv;
-        a.to_rgb = first + cnt == n ? to_rgb : 0;
-        HIPCHK(ctx, launch_cc(a, need, ctx->stream));
-        first += cnt;
-    } while (first < n);
-    if (info) {
-        long long oor = 0;
-        if (count) {
-            HIPCHK(ctx, launch_cc_count(a.oor, np, count, ctx->stream));
-            unsigned long long c = 0;
-            HIPCHK(ctx, hipMemcpyAsync(&c, count, 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            oor = (long long)c;
-        }
-        for (int i = 0; i < n; ++i) {
-            const CcRegion &r = pl.regs[i];
-            artgpu_color_correction_info &o = info[i];
-            o = artgpu_color_correction_info{};
-            o.abca = r.abca; o.abcb = r.abcb; o.enabled = r.enabled; o.rgbmode = r.rgbmode; o.rhs = r.rhs; o.oor_pixels = oor;
-            for (int c = 0; c < 3; ++c) {
-                o.slope[c] = r.slope[c]; o.offset[c] = r.offset[c]; o.power[c] = r.power[c]; o.pivot[c] = r.pivot[c];
-                o.compression[c][0] = r.comp[c][0]; o.compression[c][1] = r.comp[c][1];
-            }
-        }
-    }
-    return ARTGPU_OK;
-}
-
-} } // namespace artgpu::api
-
-extern "C" {
-
-int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
-                            const double iws[9], int to_rgb, artgpu_color_correction_info *info)
-{
-    StageScope scope_(ctx, "ImProcFunctions::colorCorrection");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!img || !plane_ok(&img->r)) return fail(ctx, ARTGPU_EINVAL, "color_correction: bad image");
-    CcPlan pl;
-    int rc;
-    if ((rc = cc_check(ctx, img->r.w, img->r.h, regions, nregions, ws, iws, true, "color_correction", &pl))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevRGB d;
-    if ((rc = bind_rgb(ctx, img, 4, true, &d, "color_correction"))) return rc;
-    if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regions, pl, 0, to_rgb, info))) return rc;
-    return unbind_rgb(ctx, img, &d);
 }
 
 } // extern "C"

@@ -32,7 +32,7 @@ def emul():
 
 
 def _streamable(top, left, w, h):
-    """Same classification as artgpu_api.hip: tiles that are 160 wide (any height that writes a pixel) whose mirrored bottom /
+    """Same classification as api_demosaic.hip: tiles that are 160 wide (any height that writes a pixel) whose mirrored bottom /
     right border fill does not over-run the row / the cfa plane in the reference."""
     rr1 = min(top + 160, h + 16) - top
     cc1 = min(left + 160, w + 16) - left

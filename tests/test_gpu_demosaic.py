@@ -108,7 +108,7 @@ def amaze_options(gpu_ctx):
 
 @pytest.mark.parametrize("filt", [synth.FILTERS_RGGB, synth.FILTERS_BGGR, synth.FILTERS_GRBG, synth.FILTERS_GBRG])
 def test_amaze_selective_arena_clear_is_exact(gpu_ctx, amaze_options, filt):
-    """Arena kernel: only six of the 17 arena regions are cleared per full tile (artgpu_api.hip: zero_mask), and of the five full-size
+    """Arena kernel: only six of the 17 arena regions are cleared per full tile (api_demosaic.hip: zero_mask), and of the five full-size
     planes among them only a 16-pixel frame (zero_frame).  With the arenas pre-filled with different byte patterns (0xFF.. = NaN) the
     result must not move, for every CFA phase and with partial and full tiles: nothing else is read before it is written."""
     from art_amd import capi
