@@ -5,7 +5,7 @@
 using namespace artgpu;
 using namespace artgpu::api;
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)
 int pq_tables_dev(artgpu_ctx *ctx, float **out)

@@ -29,7 +29,7 @@ bool clut_level_ok(int level)
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 void clut_release(artgpu_clut *clut)
 {

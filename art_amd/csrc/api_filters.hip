@@ -45,7 +45,7 @@ void yvv_factors(double sigma, GaussArgs &g, bool double_path = false)
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter.cc:58-75)
 {
@@ -57,16 +57,45 @@ int gf_subsampling(int w, int h, int r)   // calculate_subsampling (guidedfilter
     return t < 2 ? 2 : (t > 4 ? 4 : t);
 }
 
+// the statistics grid of one rtengine::guidedFilter call on a W x H plane and f_mean's box radius on it (guidedfilter.cc:160-167):
+// rad = LIM(int(float(r) / sub), 0, (min(w, h) - 1) / 2 - 1), which is 0 for a grid without pixels.  Checks nothing: every caller has
+// its own size limits, its HBLUR_MAX_RADIUS check and its message
+GfGrid gf_grid(int W, int H, int r, int subsampling)
+{
+    GfGrid g;
+    g.sub = subsampling > 0 ? subsampling : gf_subsampling(W, H, r);
+    g.w = W / g.sub; g.h = H / g.sub;
+    const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1;
+    int rad = (int)(float(r) / g.sub);
+    rad = rad < hi ? rad : hi;
+    g.rad = rad > 0 ? rad : 0;
+    return g;
+}
+
+// `count` planes of w x h floats, n apart: boxblur(float**, float**, radius, W, H) (boxblur.h:318) in place through `tmp`, enqueued on ctx->stream
+int box_blur_planes(artgpu_ctx *ctx, float *planes, float *tmp, int count, size_t n, int w, int h, int rad)
+{
+    if (rad == 0) return ARTGPU_OK;
+    BlurArgs bl = {};
+    bl.n = n; bl.w = w; bl.h = h; bl.steady_div = 1; bl.plain = 1;
+    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
+    bl.src = planes; bl.dst = tmp;
+    HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
+    bl.src = tmp; bl.dst = planes;
+    HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
+    return ARTGPU_OK;
+}
+
 // rtengine::guidedFilter (guidedfilter.cc:80-241) on contiguous device planes (rows of W floats) up to mean a / mean b on the statistics grid
 // (g->low[2], g->low[5]): the caller runs the last, pointwise pass (launch_gf_finish_plain with g->q, or one of its own).  Enqueued on
 // ctx->stream; scratch: the statistics grid in P_TMP / P_LIN
 int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, int W, int H, int r, float epsilon, int subsampling, const char *who, GuidedArgs *gout)
 {
-    const int sub = subsampling > 0 ? subsampling : gf_subsampling(W, H, r);
+    const GfGrid grid = gf_grid(W, H, r, subsampling);
     GuidedArgs &g = *gout;
     g = GuidedArgs{};
-    g.W = W; g.H = H; g.w = W / sub; g.h = H / sub; g.epsilon = epsilon; g.nch = 1;
-    if (g.w < 1 || g.h < 1) return fail(ctx, ARTGPU_EINVAL, "%s: subsampling %d leaves no pixels", who, sub);
+    g.W = W; g.H = H; g.w = grid.w; g.h = grid.h; g.epsilon = epsilon; g.nch = 1;
+    if (g.w < 1 || g.h < 1) return fail(ctx, ARTGPU_EINVAL, "%s: subsampling %d leaves no pixels", who, grid.sub);
     const size_t nl = (size_t)g.w * g.h;
     float *low, *tmp;
     int rc;
@@ -76,26 +105,13 @@ int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, i
     // subsampled frame is a few dozen workgroups: plane after plane the chip idles); the slots of channels 1 and 2 follow them, unused
     static const int order[8] = {0, 1, 2, 5, 3, 4, 6, 7};
     for (int k = 0; k < 8; ++k) g.low[order[k]] = low + k * nl;
-    const float r1 = float(r) / sub;
-    int rad = (int)r1;
-    { const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }     // f_mean's LIM (L160-164)
+    const int rad = grid.rad;
     if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, rad, HBLUR_MAX_RADIUS);
     HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
-    BlurArgs bl = {};
-    bl.n = nl; bl.w = g.w; bl.h = g.h; bl.steady_div = 1; bl.plain = 1;
-    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    auto blur_planes = [&](float *planes, int count) -> int {
-        if (rad == 0) return ARTGPU_OK;
-        bl.src = planes; bl.dst = tmp;
-        HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
-        bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
-        HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
-        return ARTGPU_OK;
-    };
     // low[0] I1 -> meanI, low[1] I1*I1 -> corrI, low[2] p1 -> meanp, low[5] I1*p1 -> corrIp
-    if ((rc = blur_planes(g.low[0], 4))) return rc;
+    if ((rc = box_blur_planes(ctx, g.low[0], tmp, 4, nl, g.w, g.h, rad))) return rc;
     HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-    if ((rc = blur_planes(g.low[2], 2))) return rc;                                    // mean a, mean b
+    if ((rc = box_blur_planes(ctx, g.low[2], tmp, 2, nl, g.w, g.h, rad))) return rc;   // mean a, mean b
     return ARTGPU_OK;
 }
 
@@ -201,8 +217,8 @@ int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const doub
     GuidedArgs g = {};
     for (int k = 0; k < 3; ++k) { g.rgb[k] = d.p[k]; g.ws1[k] = ws[3 + k]; }
     g.stride = d.stride; g.W = W; g.H = H; g.epsilon = 0.001f;
-    const int sub = gf_subsampling(W, H, r);
-    g.w = W / sub; g.h = H / sub;
+    const GfGrid grid = gf_grid(W, H, r);
+    g.w = grid.w; g.h = grid.h;
     if (r == 0 || g.w < 8 || g.h < 8) return fail(ctx, ARTGPU_EUNSUPPORTED, "denoise_guided_smoothing: radius/scale combination not on the device path");
     const size_t n = (size_t)W * H, nl = (size_t)g.w * g.h;
     float *big, *low, *tmp;
@@ -212,24 +228,9 @@ int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const doub
     for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
     HIPCHK(ctx, launch_gf_prepare(g, ctx->stream));
     HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
-    // f_mean (guidedfilter.cc:160-167): rad = LIM(int(r1), 0, (min(w,h)-1)/2 - 1); boxblur.h:318 variant
-    const float r1 = float(r) / sub;
-    int rad = (int)r1;
-    { const int hi = ((g.w < g.h ? g.w : g.h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }
-    BlurArgs bl = {};
-    bl.n = nl; bl.w = g.w; bl.h = g.h; bl.steady_div = 1; bl.plain = 1;
-    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    auto blur_planes = [&](float *planes, int count) -> int {
-        if (rad == 0) return ARTGPU_OK;
-        bl.src = planes; bl.dst = tmp;
-        HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
-        bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
-        HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
-        return ARTGPU_OK;
-    };
-    if ((rc = blur_planes(low, 8))) return rc;                 // meanI, corrI, meanp[3], corrIp[3]
+    if ((rc = box_blur_planes(ctx, low, tmp, 8, nl, g.w, g.h, grid.rad))) return rc;              // meanI, corrI, meanp[3], corrIp[3]
     HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-    if ((rc = blur_planes(low + 2 * nl, 6))) return rc;        // mean a[3], mean b[3]
+    if ((rc = box_blur_planes(ctx, low + 2 * nl, tmp, 6, nl, g.w, g.h, grid.rad))) return rc;     // mean a[3], mean b[3]
     HIPCHK(ctx, launch_gf_finish(g, ctx->stream));
     return unbind_rgb(ctx, img, &d);
 }

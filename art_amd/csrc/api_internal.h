@@ -1,9 +1,9 @@
 // art_amd/csrc/api_internal.h -- what the host files of the C ABI share: the context, the staging and pool helpers, and per stage
 // exactly the plan structs and *_dev / *_check / *_plan functions that ANOTHER file calls: the frame driver (api_pipeline.hip), io_frame
 // (api_batch.hip) or a sibling stage.  This header is the list of what a stage exposes; everything a stage uses only itself stays
-// static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api, declared with hidden visibility:
-// none of them is in the library's dynamic symbol table (a definition inherits nothing from its declaration here: every opening of
-// the namespace carries the attribute).  Each is defined once (the helpers and most stages in artgpu_api.hip, the demosaicers in
+// static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api.  None of them is in the library's
+// dynamic symbol table, and no namespace opening has to say so: every translation unit is compiled with hidden visibility, and
+// nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers and most stages in artgpu_api.hip, the demosaicers in
 // api_demosaic.hip, the shared filters in api_filters.hip, colour correction in api_colorcorrection.hip, the tone equalizer in
 // api_toneequalizer.hip, film simulation in api_filmsim.hip); none is inline.
 #pragma once
@@ -161,7 +161,7 @@ struct artgpu_ctx {
     artgpu_timings last = {0.f, 0.f, 0.f};
 };
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // ---------------------------------------------------------------------------------------------
 // context: errors, staging of host planes, the scratch pool
@@ -346,6 +346,11 @@ int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W,
 // guided filter (shared by the tools that call rtengine::guidedFilter)
 // ---------------------------------------------------------------------------------------------
 int gf_subsampling(int w, int h, int r);
+// one call's statistics grid: subsampling (calculate_subsampling unless the caller names one), size, f_mean's box radius (0 for an empty grid)
+struct GfGrid { int sub, w, h, rad; };
+GfGrid gf_grid(int W, int H, int r, int subsampling = 0);
+// the plain box blur f_mean runs (boxblur.h:318), `count` planes n floats apart, in place through `tmp`; nothing for rad == 0
+int box_blur_planes(artgpu_ctx *ctx, float *planes, float *tmp, int count, size_t n, int w, int h, int rad);
 int guided_filter_stats(artgpu_ctx *ctx, const float *guide, const float *src, int W, int H, int r, float epsilon, int subsampling, const char *who, GuidedArgs *g);
 int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, float *q, size_t q_stride, int W, int H, int r, float epsilon, int subsampling,
                       const char *who);

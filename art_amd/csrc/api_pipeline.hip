@@ -59,7 +59,7 @@ void own_pipe_regions(artgpu_ctx::PipeRegions<Region> &o, const Region *regions,
 // one frame / one batch share through the whole path
 // ---------------------------------------------------------------------------------------------
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // the call site's condition (rawimagesource.cc:1827): CA correction enabled, auto or a manual shift, Bayer only (X-Trans skips it)
 bool pipeline_ca(const artgpu_pipeline_params *p)
@@ -374,7 +374,7 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // One frame: the plan, then the stages (do_ca: artgpu_pipeline_run; io_frame has corrected its staged CFA plane itself)
 int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca)

@@ -12,12 +12,10 @@ int te_plan_filter(artgpu_ctx *ctx, int W, int H, int k, int r, float epsilon, c
 {
     static const char *const name[3] = {"detail filter", "first regularising filter", "second regularising filter"};
     if (r <= 0) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: the %s would run with radius %d", who, name[k], r);
-    const int sub = gf_subsampling(W, H, r), w = W / sub, h = H / sub;
+    const GfGrid grid = gf_grid(W, H, r);
+    const int sub = grid.sub, w = grid.w, h = grid.h, rad = grid.rad;
     if (w < ARTGPU_SMOOTHING_MIN_SIZE || h < ARTGPU_SMOOTHING_MIN_SIZE)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: the %s of a %dx%d image has a %dx%d statistics grid, below %d", who, name[k], W, H, w, h, ARTGPU_SMOOTHING_MIN_SIZE);
-    int rad = (int)(float(r) / sub);                                    // f_mean (guidedfilter.cc:160-167)
-    const int hi = ((w < h ? w : h) - 1) / 2 - 1;
-    rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0;
     if (rad > HBLUR_MAX_RADIUS)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: the %s: box radius %d (radius %d / subsampling %d) is above the %d the blur kernels hold in LDS", who, name[k], rad, r, sub, HBLUR_MAX_RADIUS);
     pl->radius[k] = r; pl->subsampling[k] = sub; pl->box_radius[k] = rad; pl->epsilon[k] = epsilon;
@@ -49,7 +47,7 @@ int te_table(artgpu_ctx *ctx, const artgpu_tone_equalizer_params *p, const float
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // every reason not to run, and what the call derives (L127-129, L150-157, L354): nothing is launched
 int te_check(artgpu_ctx *ctx, int W, int H, const artgpu_tone_equalizer_params *p, const double *ws, double scale, const char *who, artgpu_tone_equalizer_info *pl)

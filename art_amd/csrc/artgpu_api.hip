@@ -38,7 +38,7 @@ void build_lab_tabs(float *host)
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 int fail(artgpu_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -2292,7 +2292,7 @@ int artgpu_scale_colors(artgpu_ctx *ctx, const void *src, int32_t w, int32_t h, 
 
 } // extern "C"
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // Bayer 2x2 colour map of `filters` for the CA correction: FC packed as CaArgs::cfa; false for X-Trans, a fourth colour or a
 // pattern without one green per row and column
@@ -2403,7 +2403,7 @@ int artgpu_local_contrast_curve_lut(const double *points, int npoints, float lut
 
 } // extern "C"
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // what the call cannot do, before anything is touched: 0, or the code with the message set
 int local_contrast_check(artgpu_ctx *ctx, int w, int h, const artgpu_local_contrast_region *regions, int nregions, double scale, const char *who)
@@ -2533,30 +2533,6 @@ int artgpu_dehaze_estimate_ambient(const float *R, const float *G, const float *
 
 namespace {
 
-static void dehaze_gf_grid(int W, int H, int r, int *w, int *h, int *rad)
-{
-    const int sub = gf_subsampling(W, H, r);
-    *w = W / sub; *h = H / sub;
-    const int hi = ((*w < *h ? *w : *h) - 1) / 2 - 1;                  // f_mean's LIM (guidedfilter.cc:160-164)
-    int q = (int)(float(r) / sub);
-    q = q < hi ? q : hi;
-    *rad = q > 0 ? q : 0;
-}
-
-// `count` planes of w x h floats, n apart: boxblur(float**, float**, radius, W, H) (boxblur.h:318) in place
-static int dehaze_blur(artgpu_ctx *ctx, float *planes, int count, size_t n, int w, int h, int rad, float *tmp)
-{
-    if (rad == 0) return ARTGPU_OK;
-    BlurArgs bl = {};
-    bl.n = n; bl.w = w; bl.h = h; bl.steady_div = 1; bl.plain = 1;
-    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    bl.src = planes; bl.dst = tmp;
-    HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
-    bl.src = tmp; bl.dst = planes;
-    HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
-    return ARTGPU_OK;
-}
-
 // the strength table of the last curve seen: a batch passes the same curve for every frame, and 65536 curve evaluations on the host
 // would otherwise be the longest step of the call
 static const float *dehaze_strength_cached(const artgpu_dehaze_params *p, std::vector<float> &out)
@@ -2577,7 +2553,7 @@ static const float *dehaze_strength_cached(const artgpu_dehaze_params *p, std::v
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // what the call cannot do, before anything is touched: 0, or the code with the message set
 int dehaze_check(artgpu_ctx *ctx, int W, int H, const artgpu_dehaze_params *p, const double *ws, double scale, const char *who, DehazePlan *pl)
@@ -2589,9 +2565,9 @@ int dehaze_check(artgpu_ctx *ctx, int W, int H, const artgpu_dehaze_params *p, c
     if (p->blackpoint && lo < 2 * pl->brad + 1)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: black point on a %dx%d frame: the %dx%d thumbnail is narrower than its box blur (radius %d)", who, W, H, pl->ww, pl->hh, pl->brad);
     const int r1 = std::max((int)(5 / scale), 2);
-    dehaze_gf_grid(W, H, r1, &pl->w1, &pl->h1, &pl->rad1);
+    { const GfGrid g = gf_grid(W, H, r1); pl->w1 = g.w; pl->h1 = g.h; pl->rad1 = g.rad; }
     pl->patch = std::max(std::max(W, H) / 600, 2);
-    dehaze_gf_grid(W, H, pl->patch * 4, &pl->w2, &pl->h2, &pl->rad2);
+    { const GfGrid g = gf_grid(W, H, pl->patch * 4); pl->w2 = g.w; pl->h2 = g.h; pl->rad2 = g.rad; }
     if (pl->w1 < 1 || pl->h1 < 1 || pl->w2 < 1 || pl->h2 < 1)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d frame has a side shorter than the guided filter's subsampling", who, W, H);
     if (pl->patch > DH_MAX_PATCH || pl->rad1 > HBLUR_MAX_RADIUS || pl->rad2 > HBLUR_MAX_RADIUS || pl->brad > HBLUR_MAX_RADIUS)
@@ -2622,16 +2598,16 @@ int dehaze_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, in
     ta.im = im; ta.st = st; ta.thumb = thumb; ta.ww = pl.ww; ta.hh = pl.hh;
     if (p->blackpoint) {
         HIPCHK(ctx, launch_dh_thumb(ta, ctx->stream));
-        if ((rc = dehaze_blur(ctx, thumb, 3, nt, pl.ww, pl.hh, pl.brad, thumb + 3 * nt))) return rc;
+        if ((rc = box_blur_planes(ctx, thumb, thumb + 3 * nt, 3, nt, pl.ww, pl.hh, pl.brad))) return rc;
         HIPCHK(ctx, launch_dh_black(thumb, (int)nt, float(p->blackpoint) / 100.f, st, ctx->stream));
     }
     HIPCHK(ctx, launch_dh_normalize(im, st, p->blackpoint ? 1 : 0, ctx->stream));
     // extract_channels (L369): the statistics of the three self-guided filters; their outputs are evaluated where they are read
     DhGuided g1 = {low, nl1, pl.w1, pl.h1, 1e-1f};
     HIPCHK(ctx, launch_dh_gf_subsample(im, nullptr, 0, g1, ctx->stream));
-    if ((rc = dehaze_blur(ctx, low, 6, nl1, pl.w1, pl.h1, pl.rad1, tmp))) return rc;
+    if ((rc = box_blur_planes(ctx, low, tmp, 6, nl1, pl.w1, pl.h1, pl.rad1))) return rc;
     HIPCHK(ctx, launch_dh_gf_ab(g1, 1, ctx->stream));
-    if ((rc = dehaze_blur(ctx, low, 6, nl1, pl.w1, pl.h1, pl.rad1, tmp))) return rc;
+    if ((rc = box_blur_planes(ctx, low, tmp, 6, nl1, pl.w1, pl.h1, pl.rad1))) return rc;
     // the thumbnail (L372-381) and the state block come to the host: the call's one wait
     std::vector<float> host(3 * nt + 8);
     if (nt) {
@@ -2674,9 +2650,9 @@ int dehaze_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, in
     // guidedFilter(B, t~, t, 4 * patchsize, 1e-5f) (L438-445): its last step is the first of the recovery pass
     DhGuided g2 = {low, nl2, pl.w2, pl.h2, 1e-5f};
     HIPCHK(ctx, launch_dh_gf_subsample(im, T, (size_t)W, g2, ctx->stream));
-    if ((rc = dehaze_blur(ctx, low, 4, nl2, pl.w2, pl.h2, pl.rad2, tmp))) return rc;
+    if ((rc = box_blur_planes(ctx, low, tmp, 4, nl2, pl.w2, pl.h2, pl.rad2))) return rc;
     HIPCHK(ctx, launch_dh_gf_ab(g2, 0, ctx->stream));
-    if ((rc = dehaze_blur(ctx, low + 2 * nl2, 2, nl2, pl.w2, pl.h2, pl.rad2, tmp))) return rc;
+    if ((rc = box_blur_planes(ctx, low + 2 * nl2, tmp, 2, nl2, pl.w2, pl.h2, pl.rad2))) return rc;
     DhRecoverArgs ra = {};
     ra.im = im; ra.st = st; ra.gf = g2; ra.lut = lut_dev; ra.t0 = t0;
     for (int k = 0; k < 3; ++k) { ra.ws1[k] = ws[3 + k]; ra.ambient[k] = ambient[k]; }
@@ -2773,9 +2749,9 @@ static int tb_plan(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_reg
         pl->K = tb_gaussian_kernel(fradius, pl->coef);
         if (pl->K > TB_MAX_K) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: sigma %g needs a %dx%d gaussian, the kernels hold %dx%d", who, fradius, pl->K, pl->K, TB_MAX_K, TB_MAX_K);
     } else {
-        dehaze_gf_grid(pl->w, pl->h, radius, &pl->w1, &pl->h1, &pl->rad1);
+        { const GfGrid g = gf_grid(pl->w, pl->h, radius); pl->w1 = g.w; pl->h1 = g.h; pl->rad1 = g.rad; }
     }
-    dehaze_gf_grid(pl->w, pl->h, radius * 4, &pl->w2, &pl->h2, &pl->rad2);
+    { const GfGrid g = gf_grid(pl->w, pl->h, radius * 4); pl->w2 = g.w; pl->h2 = g.h; pl->rad2 = g.rad; }
     if ((pl->isguided && (pl->w1 < 1 || pl->h1 < 1)) || pl->w2 < 1 || pl->h2 < 1)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: a %dx%d plane has a side shorter than the guided filter's subsampling", who, pl->w, pl->h);
     if (pl->rad1 > HBLUR_MAX_RADIUS || pl->rad2 > HBLUR_MAX_RADIUS)
@@ -2788,9 +2764,9 @@ static int tb_guided_stats(artgpu_ctx *ctx, const float *mid, int w, int h, cons
 {
     int rc;
     HIPCHK(ctx, launch_tb_gf_subsample(mid, w, h, gf, ctx->stream));
-    if ((rc = dehaze_blur(ctx, gf.low, 2, gf.nl, gf.w, gf.h, rad, tmp))) return rc;
+    if ((rc = box_blur_planes(ctx, gf.low, tmp, 2, gf.nl, gf.w, gf.h, rad))) return rc;
     HIPCHK(ctx, launch_tb_gf_ab(gf, ctx->stream));
-    return dehaze_blur(ctx, gf.low, 2, gf.nl, gf.w, gf.h, rad, tmp);
+    return box_blur_planes(ctx, gf.low, tmp, 2, gf.nl, gf.w, gf.h, rad);
 }
 
 // texture_boost (iptextureboost.cc:37-178) on a device Y plane (rows of `stride` floats), enqueued on ctx->stream without a host wait;
@@ -2861,7 +2837,7 @@ static int tb_fill_info(artgpu_ctx *ctx, const TbPlan &pl, const TbState *st, ar
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // the region list of the whole tool: a plan per region that runs (strength != 0, L227), in order
 int tb_check(artgpu_ctx *ctx, int W, int H, const artgpu_texture_boost_region *regions, int nregions, const double *ws, double scale, int high_detail,
@@ -2973,17 +2949,16 @@ bool mk_curve_present(const artgpu_mask_params &m, const double *pts, int n, con
 }
 int mk_filter_check(artgpu_ctx *ctx, int W, int H, int r, const char *who, const char *what)
 {
-    const int sub = gf_subsampling(W, H, r), w = W / sub, h = H / sub;
+    const GfGrid grid = gf_grid(W, H, r);
+    const int sub = grid.sub, w = grid.w, h = grid.h, rad = grid.rad;
     if (w < 1 || h < 1) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %s: a %dx%d image has a side shorter than the guided filter's subsampling %d", who, what, W, H, sub);
-    int rad = (int)(float(r) / sub);
-    { const int hi = ((w < h ? w : h) - 1) / 2 - 1; rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0; }
     if (rad > HBLUR_MAX_RADIUS) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: %s: box radius %d (radius %d / subsampling %d) is above the %d the blur kernels hold in LDS", who, what, rad, r, sub, HBLUR_MAX_RADIUS);
     return ARTGPU_OK;
 }
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // everything generateMasks decides before its first pixel loop, and every reason not to run
 int mk_plan(artgpu_ctx *ctx, int W, int H, int mode, const double *ws, const artgpu_mask_params *masks, int n, int full_w, int full_h, double scale,
@@ -3259,19 +3234,6 @@ size_t sm_region_floats(const SmRegionPlan &p)
     return (p.channel == SM_CH_L ? 1 : p.channel == SM_CH_LC ? (p.skipped ? 0 : 3) : 4) * nw;
 }
 
-int sm_blur_planes(artgpu_ctx *ctx, float *planes, float *tmp, int count, int w, int h, int rad)
-{
-    if (rad == 0) return ARTGPU_OK;
-    BlurArgs bl = {};
-    bl.n = (size_t)w * h; bl.w = w; bl.h = h; bl.steady_div = 1; bl.plain = 1;      // boxblur.h:318 variant, as artgpu_denoise_guided_smoothing runs it
-    for (int l = 0; l < 10; ++l) bl.rad[l] = rad;
-    bl.src = planes; bl.dst = tmp;
-    HIPCHK(ctx, launch_hblur(bl, count, ctx->stream));
-    bl.src = tmp; bl.dst = planes; bl.sfave = nullptr; bl.coef = nullptr;
-    HIPCHK(ctx, launch_vblur_combine(bl, count, ctx->stream));
-    return ARTGPU_OK;
-}
-
 // one region on the normalised device image; `mask`: the region's blend plane on the device (rows of mstride floats) or nullptr
 // norm_in: the image is not normalised yet and this (full-frame) region does it; denorm_out: this (full-frame) region stores * 65535.f
 int sm_region_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, const SmRegionPlan &p, const float *mask, size_t mstride, const double *ws, double scale, float *big,
@@ -3312,14 +3274,14 @@ int sm_region_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, const 
             HIPCHK(ctx, launch_sm_prepare(a, ctx->stream));
             if (self) {
                 HIPCHK(ctx, launch_sm_subsample_self(a, ctx->stream));
-                if ((rc = sm_blur_planes(ctx, low, tmp, 6, p.w, p.h, p.rad))) return rc;        // mean I, corr I per channel
+                if ((rc = box_blur_planes(ctx, low, tmp, 6, nl, p.w, p.h, p.rad))) return rc;        // mean I, corr I per channel
                 HIPCHK(ctx, launch_sm_ab_self(a, ctx->stream));
-                if ((rc = sm_blur_planes(ctx, low, tmp, 6, p.w, p.h, p.rad))) return rc;        // mean a, mean b per channel
+                if ((rc = box_blur_planes(ctx, low, tmp, 6, nl, p.w, p.h, p.rad))) return rc;        // mean a, mean b per channel
             } else {
                 HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
-                if ((rc = sm_blur_planes(ctx, low, tmp, 8, p.w, p.h, p.rad))) return rc;        // meanI, corrI, meanp[3], corrIp[3]
+                if ((rc = box_blur_planes(ctx, low, tmp, 8, nl, p.w, p.h, p.rad))) return rc;        // meanI, corrI, meanp[3], corrIp[3]
                 HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-                if ((rc = sm_blur_planes(ctx, low + 2 * nl, tmp, 6, p.w, p.h, p.rad))) return rc;   // mean a[3], mean b[3]
+                if ((rc = box_blur_planes(ctx, low + 2 * nl, tmp, 6, nl, p.w, p.h, p.rad))) return rc;   // mean a[3], mean b[3]
             }
             HIPCHK(ctx, launch_sm_finish(a, ctx->stream));
         }
@@ -3343,7 +3305,7 @@ int sm_region_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, const 
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 // everything that does not depend on a mask's box: what the pipe checks before any stage runs
 int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regions, int nregions, const double *ws, double scale, bool read_masks, const char *who)
@@ -3379,17 +3341,13 @@ int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region 
         const int rr = (int)std::round(r.radius / scale);             // L348
         pl->r = rr > 0 ? rr : 0;
         if (pl->r == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_RADIUS; return ARTGPU_OK; }
-        pl->sub = gf_subsampling(ww, hh, pl->r);
-        pl->w = ww / pl->sub; pl->h = hh / pl->sub;
+        const GfGrid grid = gf_grid(ww, hh, pl->r);                   // calculate_subsampling, f_mean (guidedfilter.cc:58-75, 160-167)
+        pl->sub = grid.sub; pl->w = grid.w; pl->h = grid.h;
         if (pl->w < ARTGPU_SMOOTHING_MIN_SIZE || pl->h < ARTGPU_SMOOTHING_MIN_SIZE)
             return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: a %dx%d working plane leaves a %dx%d statistics grid, below %d", who, i, ww, hh, pl->w, pl->h, ARTGPU_SMOOTHING_MIN_SIZE);
-        const float r1 = float(pl->r) / pl->sub;                      // f_mean (guidedfilter.cc:160-167)
-        int rad = (int)r1;
-        const int hi = ((pl->w < pl->h ? pl->w : pl->h) - 1) / 2 - 1;
-        rad = rad < hi ? rad : hi; rad = rad > 0 ? rad : 0;
-        pl->rad = rad;
-        if (rad > HBLUR_MAX_RADIUS)
-            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, i, rad, HBLUR_MAX_RADIUS);
+        pl->rad = grid.rad;
+        if (pl->rad > HBLUR_MAX_RADIUS)
+            return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: box radius %d (r / subsampling) is above the %d the blur kernels hold in LDS", who, i, pl->rad, HBLUR_MAX_RADIUS);
     } else {
         if (r.nlstrength == 0) { pl->skipped = ARTGPU_SMOOTHING_SKIP_STRENGTH; return ARTGPU_OK; }
         if (ww < 32 || hh < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: region %d: NL-means on a %dx%d working plane, smaller than 32x32", who, i, ww, hh);
@@ -3574,7 +3532,7 @@ static int sharpen_read_counters(artgpu_ctx *ctx, const unsigned long long *coun
 
 } // namespace
 
-namespace artgpu { namespace api __attribute__((visibility("hidden"))) {
+namespace artgpu { namespace api {
 
 int sharpen_check(artgpu_ctx *ctx, int W, int H, const artgpu_sharpening_params *p, double scale, const char *who, SharpenPlan *pl)
 {

@@ -29,6 +29,10 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* libartgpu.so is built with hidden visibility: what this header declares is what the library exports */
+#if defined(__GNUC__)
+#pragma GCC visibility push(default)
+#endif
 
 #define ARTGPU_OK            0
 #define ARTGPU_EINVAL       -1  /* bad argument */
@@ -1203,6 +1207,9 @@ size_t artgpu_scratch_bytes(const artgpu_ctx *ctx);
  * a batch is over, a much smaller frame size follows, or several contexts / ranks have to share one GPU's memory. */
 int artgpu_trim_scratch(artgpu_ctx *ctx);
 
+#if defined(__GNUC__)
+#pragma GCC visibility pop
+#endif
 #ifdef __cplusplus
 }
 #endif

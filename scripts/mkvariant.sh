@@ -13,7 +13,7 @@ case $B in
   nlmeans) EXTRA="-fno-slp-vectorize";;
   shrinkblur) EXTRA="-mllvm -amdgpu-sched-strategy=max-memory-clause";;
 esac
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function $EXTRA $X -c $F -o /tmp/var_$N.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -ffp-contract=off -fno-fast-math -Wno-unused-function $EXTRA $X -c $F -o /tmp/var_$N.o
 OBJS=$(ls *.o | grep -v "^$B.o$")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../variants/lib$N.so $OBJS /tmp/var_$N.o
 echo variants/lib$N.so
