@@ -248,6 +248,28 @@ def film_simulation_tables():
     return g, ig
 
 
+RESIZE_PLANES, RESIZE_RGB = 0, 1
+
+
+class ResizeParams(C.Structure):
+    """artgpu_resize_params: ResizeParams as ImProcFunctions::resizeScale reads them (dataspec: 0 scale, 1 width, 2 height, 3 fit box)"""
+    _fields_ = [("enabled", C.c_int32), ("dataspec", C.c_int32), ("scale", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
+                ("allow_upscaling", C.c_int32)]
+
+
+def resize_params(dataspec=0, scale=1.0, width=900, height=900, allow_upscaling=False, enabled=True) -> ResizeParams:
+    return ResizeParams(int(bool(enabled)), int(dataspec), float(scale), int(width), int(height), int(bool(allow_upscaling)))
+
+
+def resize_scale(params, fw: int, fh: int):
+    """ImProcFunctions::resizeScale on the host (no context): (imw, imh, scale)"""
+    imw, imh, sc = C.c_int(), C.c_int(), C.c_float()
+    rc = LIB.artgpu_resize_scale(C.byref(params) if params is not None else None, int(fw), int(fh), C.byref(imw), C.byref(imh), C.byref(sc))
+    if rc:
+        raise ArtGpuError(f"artgpu_resize_scale: error {rc}")
+    return imw.value, imh.value, np.float32(sc.value)
+
+
 class Clut:
     """artgpu_clut: a HaldCLUT on a context's device.  `table`: uint16 array of level^3 entries, red fastest, 3 or 4 values each."""
 
@@ -578,6 +600,9 @@ def _load():
     lib.artgpu_film_simulation.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_void_p, C.POINTER(FilmSimulationParams)]
     lib.artgpu_film_simulation_tables.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.artgpu_set_pipeline_film_simulation.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FilmSimulationParams), C.c_int]
+    lib.artgpu_resize_lanczos.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(RGB), C.c_float, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.artgpu_resize_scale.argtypes = [C.POINTER(ResizeParams), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    lib.artgpu_set_pipeline_resize.argtypes = [C.c_void_p, C.POINTER(ResizeParams)]
     lib.artgpu_local_contrast.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(LocalContrastRegion), C.c_int, C.c_double, C.POINTER(LocalContrastInfo)]
     lib.artgpu_scale_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Plane), C.POINTER(C.c_float)]
@@ -661,7 +686,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks",
            "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing",
            "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer",
-           "artgpu_clut_create", "artgpu_clut_destroy", "artgpu_film_simulation", "artgpu_film_simulation_tables", "artgpu_set_pipeline_film_simulation"]
+           "artgpu_clut_create", "artgpu_clut_destroy", "artgpu_film_simulation", "artgpu_film_simulation_tables", "artgpu_set_pipeline_film_simulation",
+           "artgpu_resize_lanczos", "artgpu_resize_scale", "artgpu_set_pipeline_resize"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -972,6 +998,19 @@ class Context:
         (None: off).  The library copies the parameters and keeps a reference to the CLUT."""
         self._chk(LIB.artgpu_set_pipeline_film_simulation(self._h, clut._h if clut is not None else None, C.byref(params) if params is not None else None,
                                                           int(bool(after_tone_curve))))
+
+    def resize_lanczos(self, src: RGB, dst: RGB, scale: float, mode: int = RESIZE_PLANES, ws=None, iws=None):
+        """ImProcFunctions::Lanczos from src into dst (the caller's size).  RESIZE_RGB: setMode(LAB) on src (whose contents are unspecified
+        afterwards), the resampler, setMode(RGB) on dst; needs ws and iws"""
+        def mat(m):
+            return None if m is None else (C.c_double * 9)(*[float(v) for v in np.asarray(m, dtype=np.float64).reshape(9)])
+        self._chk(LIB.artgpu_resize_lanczos(self._h, C.byref(src), C.byref(dst), C.c_float(float(scale)), int(mode), mat(ws), mat(iws)))
+
+    resize_scale = staticmethod(resize_scale)
+
+    def set_pipeline_resize(self, params: ResizeParams = None):
+        """the Resize tool behind STAGE_3 of the per-frame pipe (None: off): outputs are then imw x imh of resize_scale on the bordered frame"""
+        self._chk(LIB.artgpu_set_pipeline_resize(self._h, C.byref(params) if params is not None else None))
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""

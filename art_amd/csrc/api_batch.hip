@@ -159,7 +159,11 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
     if (!in->data || W <= 0 || H <= 0 || in->row_stride_bytes < (int64_t)W * esz || in->row_stride_bytes % esz)
         return fail(c, ARTGPU_EINVAL, "batch_run_io: sensor frame: bad pointer/size/stride");
     if (b < 0 || W - 2 * b < 8 || H - 2 * b < 8) return fail(c, ARTGPU_EINVAL, "batch_run_io: border %d leaves no image", b);
-    const int iw = W - 2 * b, ih = H - 2 * b;
+    // the size the frame leaves at: the image behind the border, or what the Resize tool makes of it (artgpu_set_pipeline_resize)
+    int iw, ih;
+    float rs_scale;
+    (void)pipeline_resize(c, W - 2 * b, H - 2 * b, &iw, &ih, &rs_scale);
+    if (iw < 1 || ih < 1) return fail(c, ARTGPU_EINVAL, "batch_run_io: the Resize tool leaves no image (%dx%d)", iw, ih);
     const bool okfmt = out->is_float ? (out->bps == 16 || out->bps == 32) : (out->bps == 8 || out->bps == 16);
     if (!okfmt) return fail(c, ARTGPU_EINVAL, "batch_run_io: bps %d / is_float %d", out->bps, out->is_float);
     const size_t rowb = (size_t)iw * 3 * (out->bps / 8);

@@ -5,7 +5,7 @@
 // dynamic symbol table, and no namespace opening has to say so: every translation unit is compiled with hidden visibility, and
 // nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers and most stages in artgpu_api.hip, the demosaicers in
 // api_demosaic.hip, the shared filters in api_filters.hip, colour correction in api_colorcorrection.hip, the tone equalizer in
-// api_toneequalizer.hip, film simulation in api_filmsim.hip); none is inline.
+// api_toneequalizer.hip, film simulation in api_filmsim.hip, resize in api_resize.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -27,6 +27,7 @@
 #include "smoothing.h"
 #include "toneequalizer.h"
 #include "filmsim.h"
+#include "resize.h"
 #include "masks.h"
 #include "sharpen.h"
 
@@ -92,6 +93,8 @@ struct artgpu_ctx {
         const artgpu_clut *pipe_fs = nullptr;      // artgpu_set_pipeline_film_simulation: the handle (the parent's pipe_fs_own holds the reference),
         artgpu_film_simulation_params pipe_fs_par = {};   // a copy of the parameters, and the position
         int pipe_fs_after = 0;
+        int pipe_rs_on = 0;            // artgpu_set_pipeline_resize: a copy by value
+        artgpu_resize_params pipe_rs = {};
     } shared;
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
@@ -116,7 +119,7 @@ struct artgpu_ctx {
     float *stage[NSTAGE] = {};
     size_t stage_bytes[NSTAGE] = {};
     // grow-only scratch pool for the denoise path (planes, decompositions, shrink buffers)
-    static constexpr int NPOOL = 96;
+    static constexpr int NPOOL = 104;
     float *pool[NPOOL] = {};
     size_t pool_bytes[NPOOL] = {};
     // artgpu_batch_run lanes: sibling contexts (own stream, arena, pools) that take every lanes-th frame on their own host thread
@@ -155,6 +158,12 @@ struct artgpu_ctx {
     std::vector<float> te_lut_host;        // the tone equalizer's correction table (65536 entries), the bands it was built from, and where in
     int te_lut_bands[5] = {};              // P_TE_LUT (a slot nothing else writes) it was uploaded to: rebuilt when the bands change, uploaded
     const float *te_lut_dev = nullptr;     // again when the slot moved (artgpu_trim_scratch)
+    // the resampler's tables (api_resize.hip): what the host copy was built for, the copy, and where in P_RS_TAB (a slot nothing else writes) it
+    // was uploaded to: rebuilt when the key changes, uploaded again when the slot moved
+    int rs_key[4] = {}; float rs_key_scale = 0.f;
+    int rs_support = 0, rs_tile_w = 0;
+    std::vector<int> rs_host;
+    const float *rs_dev = nullptr;
     // timing
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -221,6 +230,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_CC_MASK, P_CC_OOR, P_CC_GEN,                                                                                   // artgpu_color_correction
        P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
        P_TE_PLANES, P_TE_LUT,                                                                                           // artgpu_tone_equalizer
+       P_RS_TAB, P_RS_IMG0, P_RS_IMG1, P_RS_IMG2,                                                                       // artgpu_resize_lanczos: the tables; the pipe's full-size working image
        P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
@@ -390,6 +400,19 @@ int fs_check(artgpu_ctx *ctx, const artgpu_clut *clut, const artgpu_film_simulat
 // the tool on device planes (rows of `stride` floats) in RGB mode, after fs_check; enqueued on ctx->stream
 int film_simulation_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_clut *clut, const artgpu_film_simulation_params *p);
 void clut_release(artgpu_clut *clut);      // drops one reference; the last one frees the device copy
+
+// ---------------------------------------------------------------------------------------------
+// resize
+// ---------------------------------------------------------------------------------------------
+// every reason not to run, and the tables (built on the host and kept by the context; nothing is uploaded or launched)
+int rs_check(artgpu_ctx *ctx, int sW, int sH, int dW, int dH, float scale, const char *who);
+// ImProcFunctions::Lanczos on device planes, after rs_check with the same sizes and scale; enqueued on ctx->stream.  m_in / m_out: ws / iws of the
+// mode switches in front (on src, in place) and behind (on dst), or null for none
+int resize_dev(artgpu_ctx *ctx, const DevRGB &src, const DevRGB &dst, float scale, const double *m_in, const double *m_out);
+// the pipe's decision (simpleprocess.cc:402-407): does a frame of w x h leave at another size, and which
+bool pipeline_resize(const artgpu_ctx *ctx, int w, int h, int *imw, int *imh, float *scale);
+// Imagefloat::setMode(LAB) / (RGB) on device planes
+int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab);
 
 // ---------------------------------------------------------------------------------------------
 // capture sharpening

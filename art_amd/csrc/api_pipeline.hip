@@ -97,6 +97,9 @@ struct PipePlan {
     bool te_on;                                                    // the tone equalizer (artgpu_set_pipeline_tone_equalizer, enabled)
     artgpu_tone_equalizer_info te;
     bool fs_on;                                                    // film simulation (artgpu_set_pipeline_film_simulation)
+    bool rs_on;                                                    // the Resize tool (artgpu_set_pipeline_resize) changes this frame's size: to imw x imh
+    int imw, imh;
+    float rs_scale;
     bool sh_on, sh_auto, sh_radius_pending;
     artgpu_sharpening_params shpar;                                // (deconvradius: 0.75 stands in while the automatic radius is pending)
     SharpenPlan sharpen;
@@ -104,7 +107,8 @@ struct PipePlan {
 };
 // What the stages hand on: the CFA plane the demosaic reads (the caller's, or its CA-corrected copy in the pool), the demosaiced W x H planes in the
 // pool, the w x h image the later stages work on (the caller's planes if they are on the device, else a staged copy) as launchers / entry points take it
-struct PipeFrame { artgpu_plane raw; artgpu_rgb dem; DevRGB d; artgpu_rgb img; };
+// (with the Resize tool: planes of the pool, and `small` is the caller's imw x imh image the resampler writes)
+struct PipeFrame { artgpu_plane raw; artgpu_rgb dem; DevRGB d; artgpu_rgb img; DevRGB small; };
 
 // the MkPlan of n regions whose masks the pipe generates on its own image (mode: ARTGPU_MASKS_MODE_LAB or _RGB; full size, no crop)
 static int pipe_plan_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, int mode, const artgpu_mask_params *masks, int n, bool want_ab, const char *who, MkPlan *mk)
@@ -128,7 +132,7 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 
 // Checks and derives everything; launches nothing and takes no pool slot, so a refused frame leaves the output planes alone.  The checks, in the
 // order they report (a frame that is wrong in two ways names the first):
-//   1. ctx, raw / p / out, the border, the output's size (then hipSetDevice, the one HIP call here)   2. artgpu_set_pipeline_masks' counts against the frame's
+//   1. ctx, raw / p / out, the border, the Resize tool's result, the output's size (then hipSetDevice, the one HIP call here; then rs_check)   2. artgpu_set_pipeline_masks' counts against the frame's
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
 //   8. dehaze_check, te_check, fs_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
@@ -140,9 +144,13 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     const double scale = p->scale > 0 ? p->scale : 1.0;
     pl->W = raw_in->w; pl->H = raw_in->h; pl->b = b; pl->w = w; pl->h = h; pl->scale = scale;
     if (b < 0 || w < 8 || h < 8) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: border %d leaves no image", b);
-    if (out->r.w != w || out->r.h != h) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", w, h);
+    // ImProcFunctions::resizeScale on the image behind the border, and simpleprocess.cc:406-407's decision
+    pl->rs_on = pipeline_resize(ctx, w, h, &pl->imw, &pl->imh, &pl->rs_scale);
+    if (pl->imw < 1 || pl->imh < 1) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: the Resize tool leaves no image (%dx%d)", pl->imw, pl->imh);
+    if (out->r.w != pl->imw || out->r.h != pl->imh) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: output must be %dx%d", pl->imw, pl->imh);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
+    if (pl->rs_on && (rc = rs_check(ctx, w, h, pl->imw, pl->imh, pl->rs_scale, "pipeline_run(resize)"))) return rc;
     const artgpu_ctx::Shared &s = ctx->shared;
     pl->lc_on = p->local_contrast_enabled && nlc > 0; pl->lc_gen = pl->lc_on && s.pipe_lc;
     pl->tb_on = p->texture_boost_enabled != 0;        pl->tb_gen = pl->tb_on && ntb > 0 && s.pipe_tb;
@@ -258,7 +266,14 @@ static int pipe_demosaic(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const
     fr->dem = mk_dev_rgb(dp, pl.W, pl.H, pl.W);
     if (p->sensor == 0) rc = artgpu_demosaic_bayer(ctx, p->bayer_method, &fr->raw, p->filters, p->initial_gain, pl.b, &fr->dem);
     else rc = artgpu_demosaic_xtrans(ctx, p->xtrans_passes, p->xtrans_passes > 1 ? 1 : 0, &fr->raw, p->xtrans, p->rgb_cam, &fr->dem);
-    if (rc || (rc = bind_rgb(ctx, out, 4, false, &fr->d, "pipeline_run(out)"))) return rc;
+    if (rc) return rc;
+    if (pl.rs_on) {
+        // the full-size working image cannot be the caller's planes: they have the size the resampler writes
+        if ((rc = bind_rgb(ctx, out, 4, false, &fr->small, "pipeline_run(out)"))) return rc;
+        for (int k = 0; k < 3; ++k)
+            if ((rc = pool_get(ctx, P_RS_IMG0 + k, (size_t)pl.w * pl.h * 4, &fr->d.p[k]))) return rc;
+        fr->d.stride = pl.w; fr->d.w = pl.w; fr->d.h = pl.h; fr->d.staged = false;
+    } else if ((rc = bind_rgb(ctx, out, 4, false, &fr->d, "pipeline_run(out)"))) return rc;
     fr->img = mk_dev_rgb(fr->d.p, fr->d.w, fr->d.h, fr->d.stride);
     return ARTGPU_OK;
 }
@@ -341,7 +356,8 @@ static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const P
     return ARTGPU_OK;
 }
 
-// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, filmSimulation on either side of the tone curve, localContrast; then the image goes back to the caller's planes
+// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, filmSimulation on either side of the tone curve, localContrast, [the Resize
+// tool]; then the image goes back to the caller's planes
 static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
 {
     const DevRGB &d = fr->d;
@@ -367,9 +383,15 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
     if (pl.lc_on) {
         if ((rc = artgpu_rgb_to_lab(ctx, &fr->img, p->ws)) || (pl.lc_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_lc, pl.lc_mk, nlc, false, &gen)))) return rc;
         for (int i = 0; i < nlc && pl.lc_gen; ++i) pl.lc_regs[i].mask = &gen[i];
-        if ((rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, pl.lc_regions, nlc, nullptr)) || (rc = artgpu_lab_to_rgb(ctx, &fr->img, p->iws))) return rc;
+        if ((rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, pl.lc_regions, nlc, nullptr))) return rc;
+        // (with the Resize tool the image stays in LAB mode, as in the reference: iplocalcontrast.cc:441 does not switch back)
+        if (!pl.rs_on && (rc = artgpu_lab_to_rgb(ctx, &fr->img, p->iws))) return rc;
     }
-    return unbind_rgb(ctx, out, &d);
+    if (!pl.rs_on) return unbind_rgb(ctx, out, &d);
+    // ImProcFunctions::resize (simpleprocess.cc:402-414): Lanczos' setMode(LAB) is a no-op behind localContrast; the switch to RGB happens on the
+    // small image (iprgb2out.cc:455)
+    if ((rc = resize_dev(ctx, d, fr->small, pl.rs_scale, pl.lc_on ? nullptr : p->ws, p->iws))) return rc;
+    return unbind_rgb(ctx, out, &fr->small);
 }
 
 } // namespace

@@ -34,8 +34,10 @@
 //                                                      little-endian uint16 RGB triples, level^3 of them with red fastest; level = entries per axis
 //                                                      (64 for a level-8 file); strength in percent (default 100); after != 0: behind the tone
 //                                                      curve instead of ahead of it.  The CLUT's profile is taken to be the working profile)
+//              [--resize-scale S | --resize-fit WxH]   (the Resize tool behind STAGE_3, simpleprocess.cc:402-414: ImProcFunctions::resizeScale with
+//                                                      dataspec 0 (scale S) or 3 (fit the W x H box; never upscales), then ImProcFunctions::resize)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--tone-equalizer ..] [--film-simulation ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
+//              [--tone-equalizer ..] [--film-simulation ..] [--resize-scale ..] [--resize-fit ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <cctype>
@@ -111,6 +113,9 @@ int main(int argc, char **argv)
     double te_pivot = 0.0;
     std::string fs_file;                                           // FilmSimulationParams: the CLUT, strength, after_tone_curve
     int fs_level = 0, fs_strength = 100, fs_after = 0;
+    bool rs_enable = false;                                        // ResizeParams
+    int rs_dataspec = 0, rs_width = 900, rs_height = 900;
+    double rs_scale = 1.0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -263,6 +268,11 @@ int main(int argc, char **argv)
             }
             fs_file = v.substr(0, c);
         }
+        else if (a == "--resize-scale") { rs_scale = std::atof(next()); rs_dataspec = 0; rs_enable = true; }
+        else if (a == "--resize-fit") {
+            if (std::sscanf(next(), "%dx%d", &rs_width, &rs_height) != 2 || rs_width < 1 || rs_height < 1) { std::fprintf(stderr, "--resize-fit WxH\n"); return 2; }
+            rs_dataspec = 3; rs_enable = true;
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     ProcParams::Mask cc_mask;
@@ -315,6 +325,7 @@ int main(int argc, char **argv)
         film_simulation(ctx, params);
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
+        params.resize.enabled = rs_enable; params.resize.dataspec = rs_dataspec; params.resize.scale = rs_scale; params.resize.width = rs_width; params.resize.height = rs_height;
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
             for (size_t pos = 0; pos <= batch.size();) {
@@ -324,7 +335,7 @@ int main(int argc, char **argv)
                 pos = e + 1;
             }
             for (const std::string &n : names) {
-                BatchQueue::Job &j = q.addJob(W, H, border);
+                BatchQueue::Job &j = q.addJob(W, H, border, &params);
                 std::ifstream f(n, std::ios::binary);
                 if (!f) throw std::runtime_error("cannot open " + n);
                 f.read(reinterpret_cast<char *>(j.sensor), (std::streamsize)W * H * 2);
@@ -336,7 +347,7 @@ int main(int argc, char **argv)
             auto t0 = std::chrono::steady_clock::now();
             q.process(params, filters, mul, mat, lanes, cblack, smul);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            const int fw = W - 2 * border, fh = H - 2 * border;
+            const int fw = q.jobs[0].outW, fh = q.jobs[0].outH;
             for (size_t k = 0; k < q.jobs.size(); ++k) {
                 if (out.empty()) break;
                 std::ofstream o(out + "." + std::to_string(k) + ".ppm", std::ios::binary);
@@ -397,6 +408,7 @@ int main(int argc, char **argv)
         film_simulation(ctx, params);
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
+        params.resize.enabled = rs_enable; params.resize.dataspec = rs_dataspec; params.resize.scale = rs_scale; params.resize.width = rs_width; params.resize.height = rs_height;
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {
             ProcParams::LocalContrastRegion region;
@@ -425,7 +437,8 @@ int main(int argc, char **argv)
         imgsrc.demosaic(params);
         int fw, fh;
         imgsrc.getFullSize(fw, fh);
-        Imagefloat img(fw, fh);
+        Imagefloat full(fw, fh);
+        Imagefloat &img = full;
         const float mul[3] = {2.1374f, 1.0f, 1.5918f};
         const double mat[9] = {0.6325, 0.2312, 0.0921, 0.2198, 0.7712, 0.0090, 0.0166, 0.0713, 0.7514};
         ImProcFunctions ipf(ctx, &params, 1.0);
@@ -453,11 +466,23 @@ int main(int argc, char **argv)
         ipf.process(ImProcFunctions::Pipeline::OUTPUT, ImProcFunctions::Stage::STAGE_1, &img);
         ipf.process(ImProcFunctions::Pipeline::OUTPUT, ImProcFunctions::Stage::STAGE_2, &img);
         ipf.process(ImProcFunctions::Pipeline::OUTPUT, ImProcFunctions::Stage::STAGE_3, &img);
+        // the Resize tool (simpleprocess.cc:402-414)
+        std::unique_ptr<Imagefloat> resized;
+        if (params.resize.enabled) {
+            int imw, imh;
+            const float rscale = ImProcFunctions::resizeScale(&params, fw, fh, imw, imh);
+            if (rscale < 1.f || (rscale > 1.f && (params.resize.allowUpscaling || params.resize.dataspec == 0))) {
+                resized.reset(new Imagefloat(imw, imh));
+                ipf.resize(&full, resized.get(), rscale);
+                fw = imw; fh = imh;
+            }
+        }
+        Imagefloat &result = resized ? *resized : full;
         ctx.synchronize();
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 
         std::vector<float> r((size_t)fw * fh), g(r.size()), b(r.size());
-        img.r.download(r.data()); img.g.download(g.data()); img.b.download(b.data());
+        result.r.download(r.data()); result.g.download(g.data()); result.b.download(b.data());
         double sum = 0;
         for (size_t k = 0; k < r.size(); ++k) sum += r[k] + g[k] + b[k];
         if (!out.empty()) {

@@ -296,6 +296,16 @@ struct ProcParams {
         }
         return any;
     }
+    // ResizeParams (procparams.h) as ImProcFunctions::resizeScale reads them: dataspec 0 scale, 1 width, 2 height, 3 fit box; width / height are
+    // get_width() / get_height(), in pixels.  The mirror has no crop, so appliesTo is not here
+    struct { bool enabled = false; int dataspec = 3; double scale = 1.0; int width = 900, height = 900; bool allowUpscaling = false; } resize;
+    artgpu_resize_params resizeParams() const
+    {
+        artgpu_resize_params q = {};
+        q.enabled = resize.enabled ? 1 : 0; q.dataspec = resize.dataspec; q.scale = resize.scale; q.width = resize.width; q.height = resize.height;
+        q.allow_upscaling = resize.allowUpscaling ? 1 : 0;
+        return q;
+    }
     struct { bool enabled = false; std::vector<float> rlut, glut, blut; } rgbCurves;                                             // RGBCurvesParams, as outCurve LUTs
     struct { bool enabled = true; int curveMode = ARTGPU_TONE_STD; std::vector<float> lut; float whitePoint = 1.f; bool basecurveLinear = true; } toneCurve;
     // toneCurve.curveMode: ARTGPU_TONE_STD or ARTGPU_TONE_NEUTRAL (ART's default, procparams.cc:1585)
@@ -529,6 +539,23 @@ public:
         artgpu_rgb i = img->view();
         ctx.check(artgpu_film_simulation(ctx.get(), &i, params->filmSimulation.clut, &fp));
     }
+    // ImProcFunctions::resizeScale (ipresize.cc:226-297) without a crop
+    static float resizeScale(const ProcParams *params, int fw, int fh, int &imw, int &imh)
+    {
+        float s = 1.f;
+        const artgpu_resize_params rp = params ? params->resizeParams() : artgpu_resize_params{};
+        (void)artgpu_resize_scale(params ? &rp : nullptr, fw, fh, &imw, &imh, &s);
+        return s;
+    }
+    // ImProcFunctions::Lanczos (ipresize.cc:53-223).  The mirror's images are in RGB mode between calls (localContrast switches back), so this is
+    // always the reference's setMode(LAB) / resample / setMode(RGB); src is left as the reference leaves it, in LAB mode.  The pipe
+    // (artgpu_set_pipeline_resize) keeps the reference's lazy mode behind localContrast instead
+    void Lanczos(Imagefloat *src, Imagefloat *dst, float scale_)
+    {
+        artgpu_rgb s = src->view(), d = dst->view();
+        ctx.check(artgpu_resize_lanczos(ctx.get(), &s, &d, scale_, ARTGPU_RESIZE_RGB, params->workingSpace, params->workingSpaceInverse));
+    }
+    void resize(Imagefloat *src, Imagefloat *dst, float dScale) { Lanczos(src, dst, dScale); }
     // ImProcFunctions::dehaze (ipdehaze.cc:306-512)
     void dehaze(Imagefloat *img)
     {
@@ -717,8 +744,9 @@ class BatchQueue {
 public:
     struct Job {
         uint16_t *sensor = nullptr;      // W x H, pinned
-        unsigned char *scanlines = nullptr;   // (H - 2 border) x (W - 2 border) x 3 x bps / 8, pinned
+        unsigned char *scanlines = nullptr;   // outH x outW x 3 x bps / 8, pinned
         int W = 0, H = 0;
+        int outW = 0, outH = 0;               // (W - 2 border) x (H - 2 border), or what the Resize tool makes of it
         float chmax[4] = {0, 0, 0, 0};
         int status = 0;
     };
@@ -726,12 +754,18 @@ public:
     ~BatchQueue() { for (Job &j : jobs) { if (j.sensor) (void)hipHostFree(j.sensor); if (j.scanlines) (void)hipHostFree(j.scanlines); } }
     BatchQueue(const BatchQueue &) = delete;
     BatchQueue &operator=(const BatchQueue &) = delete;
-    // a job's buffers; the caller fills `sensor` (the decoder's output)
-    Job &addJob(int W, int H, int border)
+    // a job's buffers; the caller fills `sensor` (the decoder's output).  p: the parameters process() will get, for the Resize tool's output size
+    // (simpleprocess.cc:402-407)
+    Job &addJob(int W, int H, int border, const ProcParams *p = nullptr)
     {
-        Job j; j.W = W; j.H = H;
+        Job j; j.W = W; j.H = H; j.outW = W - 2 * border; j.outH = H - 2 * border;
+        if (p && p->resize.enabled) {
+            int imw, imh;
+            const float s = ImProcFunctions::resizeScale(p, j.outW, j.outH, imw, imh);
+            if (s < 1.f || (s > 1.f && (p->resize.allowUpscaling || p->resize.dataspec == 0))) { j.outW = imw; j.outH = imh; }
+        }
         hipcheck(hipHostMalloc(reinterpret_cast<void **>(&j.sensor), (size_t)W * H * 2, hipHostMallocDefault), "hipHostMalloc(sensor)");
-        hipcheck(hipHostMalloc(reinterpret_cast<void **>(&j.scanlines), rowBytes(W, border) * (size_t)(H - 2 * border), hipHostMallocDefault), "hipHostMalloc(scanlines)");
+        hipcheck(hipHostMalloc(reinterpret_cast<void **>(&j.scanlines), (size_t)j.outW * 3 * (bps / 8) * (size_t)j.outH, hipHostMallocDefault), "hipHostMalloc(scanlines)");
         jobs.push_back(j);
         return jobs.back();
     }
@@ -797,6 +831,9 @@ public:
         const artgpu_film_simulation_params fs = p.filmSimulationParams();
         const bool fs_on = p.filmSimulation.enabled && p.filmSimulation.clut;
         ctx.check(artgpu_set_pipeline_film_simulation(ctx.get(), fs_on ? p.filmSimulation.clut : nullptr, &fs, p.filmSimulation.after_tone_curve ? 1 : 0));
+        // ImProcFunctions::resize behind STAGE_3 (the jobs' scanline buffers have the size addJob derived from the same parameters)
+        const artgpu_resize_params rs = p.resizeParams();
+        ctx.check(artgpu_set_pipeline_resize(ctx.get(), p.resize.enabled ? &rs : nullptr));
         std::vector<artgpu_sensor_frame> in(jobs.size());
         std::vector<artgpu_scanline_frame> out(jobs.size());
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -804,7 +841,7 @@ public:
             in[k] = artgpu_sensor_frame{j.sensor, j.W, j.H, (int64_t)j.W * 2, 1, 0, {cblacksom[0], cblacksom[1], cblacksom[2], cblacksom[3]},
                                         {scale_mul[0], scale_mul[1], scale_mul[2], scale_mul[3]}};
             out[k] = artgpu_scanline_frame{};
-            out[k].scanlines = j.scanlines; out[k].row_stride_bytes = (int64_t)rowBytes(j.W, pp.border); out[k].bps = bps; out[k].is_float = 0;
+            out[k].scanlines = j.scanlines; out[k].row_stride_bytes = (int64_t)j.outW * 3 * (bps / 8); out[k].bps = bps; out[k].is_float = 0;
             out[k].rgb2out_enabled = 0; out[k].trc_linear = 1;
         }
         ctx.check(artgpu_set_batch_lanes(ctx.get(), lanes));
@@ -814,6 +851,7 @@ public:
         (void)artgpu_set_pipeline_smoothing(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_tone_equalizer(ctx.get(), nullptr);
         (void)artgpu_set_pipeline_film_simulation(ctx.get(), nullptr, nullptr, 0);
+        (void)artgpu_set_pipeline_resize(ctx.get(), nullptr);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

@@ -1128,6 +1128,50 @@ int artgpu_set_pipeline_tone_equalizer(artgpu_ctx *ctx, const artgpu_tone_equali
  * any stage has run.  With the setting off the pipe launches exactly what it launched without it. */
 int artgpu_set_pipeline_film_simulation(artgpu_ctx *ctx, const artgpu_clut *clut, const artgpu_film_simulation_params *params, int after_tone_curve);
 
+/* ImProcFunctions::Lanczos (rtengine/ipresize.cc:53-223), the Resize tool's resampler: Lanczos-3 from `src` into `dst`, whose size is the
+ * caller's (imw x imh of artgpu_resize_scale; as in the reference it is not derived from `scale`).  src and dst are different images,
+ * each on the host or on the device, with any row stride.
+ *   weights: per destination column and row, on the host with the reference's float expressions: x0 = (j + 0.5f) * delta - 0.5f with
+ *     delta = 1.0f / scale, sc = min(scale, 1.0f), support = int(2.0f * 3.0f / sc) + 1, taps max(0, int(floorf(x0 - 3.0f / sc)) + 1) ..
+ *     min(sW, int(floorf(x0 + 3.0f / sc)) + 1) - 1, Lanc(sc * (x0 - jj), 3.0f) with the scalar xsinf (sleef.h:993-1016), divided by their
+ *     float sum.  The tables are uploaded once per (source size, destination size, scale) and kept by the context;
+ *   arithmetic: the vertical pass over ascending source rows (L181-195; its 4-wide body is the same arithmetic), then the horizontal pass
+ *     over ascending source columns (L198-215), acc += w * value with the product rounded before the sum.  A row or column without taps --
+ *     a dst larger than scale implies -- is 0.0f.  The vertically interpolated rows live on chip; one kernel, all three planes.
+ *   mode: the reference resamples the image's LAB representation (src->setMode(LAB), L56; dst->setMode(mode), L222).
+ *     ARTGPU_RESIZE_PLANES  the three planes as they are: Lanczos() on an image that is already in LAB mode (or any three planes);
+ *     ARTGPU_RESIZE_RGB     Lanczos() on an image in RGB mode: artgpu_rgb_to_lab(ws) on src, the resampler, artgpu_lab_to_rgb(iws) on dst.
+ *                           What src holds afterwards is unspecified (the reference leaves it in LAB mode and deletes it).
+ * ARTGPU_EINVAL: scale == 1 (the caller's artgpu_resize_scale returns 1 for "no resize"), not finite or <= 0; an unknown mode; RGB mode
+ * without ws / iws.  ARTGPU_EUNSUPPORTED: a scale so small that the horizontal taps of eight neighbouring destination columns do not lie
+ * within 256 source columns (about scale < 1/17; every 1/16 <= scale is supported, upscales of any factor).  Neither writes dst. */
+#define ARTGPU_RESIZE_PLANES 0
+#define ARTGPU_RESIZE_RGB    1
+int artgpu_resize_lanczos(artgpu_ctx *ctx, artgpu_rgb *src, artgpu_rgb *dst, float scale, int mode,
+                          const double ws[9], const double iws[9] /* RGB mode only */);
+/* ResizeParams as ImProcFunctions::resizeScale reads them (ipresize.cc:226-297).  The pipe has no crop, so the crop branches of resizeScale
+ * (crop.enabled with appliesTo "Cropped area" / "Full image") are not restated: the values apply to the full image. */
+typedef struct artgpu_resize_params {
+    int32_t enabled;
+    int32_t dataspec;          /* 0 scale, 1 width, 2 height, 3 fit box */
+    double scale;
+    int32_t width, height;     /* ResizeParams::get_width() / get_height(): pixels */
+    int32_t allow_upscaling;
+} artgpu_resize_params;
+/* Host only, no context: ImProcFunctions::resizeScale(params, fw, fh, imw, imh).  *scale is what it returns: 1.0f with *imw = fw, *imh = fh
+ * for a NULL or disabled tool and for |dScale - 1| <= 1e-5; otherwise float(dScale) with *imw = int(fw * dScale + 0.5), likewise *imh. */
+int artgpu_resize_scale(const artgpu_resize_params *params, int fw, int fh, int *imw, int *imh, float *scale);
+/* The Resize tool in the per-frame pipe, a setting of the context for the same reason (copied; batch lanes inherit it).  NULL = off, the
+ * default.  While set, the three pipe entries call artgpu_resize_scale on the frame's size behind the border, and where the reference
+ * resizes (simpleprocess.cc:406-407: scale < 1, or scale > 1 with allow_upscaling or dataspec 0) the output is imw x imh: artgpu_pipeline_run
+ * and artgpu_batch_run take `out` of that size, artgpu_batch_run_io writes imh rows of imw pixels.  Every stage in front sees the full size
+ * (the working image then lives in the context's scratch); ImProcFunctions::resize follows STAGE_3.  With local contrast on, the image is
+ * still in LAB mode there (iplocalcontrast.cc:441), so the LAB planes are resampled as they are and the switch to RGB happens on the small
+ * image; otherwise it is the ARTGPU_RESIZE_RGB path.  Where the reference does not resize, the frame goes through at full size with the same
+ * bits as with the setting off.  An unsupported scale, a result smaller than one pixel or an `out` of another size fail the frame before any
+ * stage has run.  With the setting off the pipe allocates and launches exactly what it did without it. */
+int artgpu_set_pipeline_resize(artgpu_ctx *ctx, const artgpu_resize_params *params);
+
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
  * barrier / gather lives in the host driver (bench.py, art_amd/batch.py), not in the data path. */
