@@ -3,9 +3,10 @@
 // (api_batch.hip) or a sibling stage.  This header is the list of what a stage exposes; everything a stage uses only itself stays
 // static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api.  None of them is in the library's
 // dynamic symbol table, and no namespace opening has to say so: every translation unit is compiled with hidden visibility, and
-// nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers and most stages in artgpu_api.hip, the demosaicers in
-// api_demosaic.hip, the shared filters in api_filters.hip, colour correction in api_colorcorrection.hip, the tone equalizer in
-// api_toneequalizer.hip, film simulation in api_filmsim.hip, resize in api_resize.hip); none is inline.
+// nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers and the seven tools from raw CA correction to
+// capture sharpening in artgpu_api.hip, the demosaicers in api_demosaic.hip, the shared filters in api_filters.hip, the pixel passes in
+// api_pixelops.hip, the wavelet decomposition in api_wavelet.hip, the denoiser in api_denoise.hip (it exposes nothing), colour correction in
+// api_colorcorrection.hip, the tone equalizer in api_toneequalizer.hip, film simulation in api_filmsim.hip, resize in api_resize.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -369,8 +370,28 @@ int guided_filter_dev(artgpu_ctx *ctx, const float *guide, const float *src, flo
 // what a stage exposes to its sibling stages, by the file that defines it
 // ---------------------------------------------------------------------------------------------
 // artgpu_api.hip
+// A table of constants in a pool slot of its own, built on the host by `fill` (which gets `nfloats` zeroed floats) and uploaded once per context
+int const_table_dev(artgpu_ctx *ctx, int slot, size_t nfloats, void (*fill)(float *), const char *what, float **out);
 // Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292), in P_LABTABS
 int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out);
+
+// api_pixelops.hip
+// Imagefloat::setMode(LAB) / (RGB) on device planes
+int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab);
+
+// api_wavelet.hip
+int wavelet_skip(int level);
+// one plane's decomposition in pool buffers the caller has fetched (RGB_denoise, local contrast); st: the context's stream unless named
+struct DevDecomp {
+    float *bands, *low[2];
+    int cur, nlevels, w, h, w2, h2;
+    size_t n;
+    int *cnt;                   // non-null: decompose with the counting kernels -- MadRgb's low bins of this channel's bands, [3 * nlevels][MAD_FOLD_NB]
+    int g0, g1;                 // ... their grids
+    float *band(int l, int dir) const { return bands + ((size_t)l * 3 + (dir - 1)) * n; }
+};
+int decompose_dev(artgpu_ctx *ctx, DevDecomp &d, const float *src, hipStream_t st = nullptr, size_t src_stride = 0);
+int reconstruct_dev(artgpu_ctx *ctx, DevDecomp &d, float *dst, hipStream_t st = nullptr);
 
 // api_filters.hip (with the guided filter above)
 int gaussian_dev(artgpu_ctx *ctx, float *img, float *tmp, int W, int H, double sigma);
@@ -411,8 +432,6 @@ int rs_check(artgpu_ctx *ctx, int sW, int sH, int dW, int dH, float scale, const
 int resize_dev(artgpu_ctx *ctx, const DevRGB &src, const DevRGB &dst, float scale, const double *m_in, const double *m_out);
 // the pipe's decision (simpleprocess.cc:402-407): does a frame of w x h leave at another size, and which
 bool pipeline_resize(const artgpu_ctx *ctx, int w, int h, int *imw, int *imh, float *scale);
-// Imagefloat::setMode(LAB) / (RGB) on device planes
-int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab);
 
 // ---------------------------------------------------------------------------------------------
 // capture sharpening

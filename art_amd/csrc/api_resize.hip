@@ -79,20 +79,6 @@ bool rs_scale_ok(float scale) { return std::isfinite(scale) && scale > 0.f && sc
 
 namespace artgpu { namespace api {
 
-int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab)
-{
-    float *tabs;
-    int rc = lab_tabs_dev(ctx, &tabs);
-    if (rc) return rc;
-    LabArgs a = {};
-    for (int k = 0; k < 3; ++k) a.img[k] = d.p[k];
-    a.stride = d.stride; a.w = d.w; a.h = d.h;
-    for (int k = 0; k < 9; ++k) { a.ws[k] = (float)m[k]; a.iws[k] = (float)m[k]; }
-    a.cachef = tabs; a.cachefy = tabs + 65536;
-    HIPCHK(ctx, to_lab ? launch_rgb_to_lab(a, ctx->stream) : launch_lab_to_rgb(a, ctx->stream));
-    return ARTGPU_OK;
-}
-
 // The host copy of the tables, as 4-byte words: [ii0 dH | ii1 dH | jj0 dW | jj1 dW | wv dH x support | wh dW x support]
 int rs_check(artgpu_ctx *ctx, int sW, int sH, int dW, int dH, float scale, const char *who)
 {
