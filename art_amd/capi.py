@@ -248,6 +248,47 @@ def film_simulation_tables():
     return g, ig
 
 
+FILM_GRAIN_MAX_REGIONS, GRAIN_TABLE_SIZE = 4, 5233
+
+
+class FilmGrainParams(C.Structure):
+    """artgpu_film_grain_params: GrainParams (enabled 0, iso 400, strength 50, color 0)"""
+    _fields_ = [("enabled", C.c_int32), ("iso", C.c_int32), ("strength", C.c_int32), ("color", C.c_int32)]
+
+
+class FilmGrainRegionInfo(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("strength", C.c_int32), ("coarseness", C.c_int32), ("seed", C.c_int32), ("sz", C.c_int32), ("sf", C.c_float)]
+
+    def as_tuple(self):
+        return (self.channel, self.strength, self.coarseness, self.seed, self.sz, np.float32(self.sf))
+
+
+class FilmGrainInfo(C.Structure):
+    _fields_ = [("nregions", C.c_int32), ("region", FilmGrainRegionInfo * FILM_GRAIN_MAX_REGIONS)]
+
+    def regions(self):
+        return [self.region[i].as_tuple() for i in range(self.nregions)]
+
+
+def film_grain_params(iso=400, strength=50, color=False, enabled=True) -> FilmGrainParams:
+    return FilmGrainParams(int(bool(enabled)), int(iso), int(strength), int(bool(color)))
+
+
+def grain_table(seed: int, radius: float = None):
+    """what add_noise builds before it reads a pixel, on the host (no context): (normd[5233], state) of a generator seeded `seed`, and with
+    `radius` also (the sz x sz normalised cone, sz)"""
+    normd = np.empty(GRAIN_TABLE_SIZE, np.float32)
+    taps = np.zeros(49, np.float32)
+    sz, state = C.c_int(0), C.c_uint64(0)
+    rc = LIB.artgpu_grain_table(int(seed), normd.ctypes.data_as(C.POINTER(C.c_float)), taps.ctypes.data_as(C.POINTER(C.c_float)) if radius is not None else None,
+                                C.byref(sz), C.c_float(0.0 if radius is None else float(radius)), C.byref(state))
+    if rc:
+        raise ArtGpuError(f"artgpu_grain_table: error {rc}")
+    if radius is None:
+        return normd, int(state.value)
+    return normd, int(state.value), taps[:sz.value * sz.value].reshape(sz.value, sz.value).copy(), sz.value
+
+
 RESIZE_PLANES, RESIZE_RGB = 0, 1
 
 
@@ -600,6 +641,11 @@ def _load():
     lib.artgpu_film_simulation.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_void_p, C.POINTER(FilmSimulationParams)]
     lib.artgpu_film_simulation_tables.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.artgpu_set_pipeline_film_simulation.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FilmSimulationParams), C.c_int]
+    lib.artgpu_film_grain.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(FilmGrainParams), C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(FilmGrainInfo)]
+    lib.artgpu_add_noise.argtypes = [C.c_void_p, C.POINTER(RGB), C.c_int, C.c_int, C.c_int, C.POINTER(Plane), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int]
+    lib.artgpu_grain_table.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_uint64)]
+    lib.artgpu_grain_indices.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]
+    lib.artgpu_set_pipeline_film_grain.argtypes = [C.c_void_p, C.POINTER(FilmGrainParams)]
     lib.artgpu_resize_lanczos.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(RGB), C.c_float, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.artgpu_resize_scale.argtypes = [C.POINTER(ResizeParams), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
     lib.artgpu_set_pipeline_resize.argtypes = [C.c_void_p, C.POINTER(ResizeParams)]
@@ -687,7 +733,8 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing",
            "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer",
            "artgpu_clut_create", "artgpu_clut_destroy", "artgpu_film_simulation", "artgpu_film_simulation_tables", "artgpu_set_pipeline_film_simulation",
-           "artgpu_resize_lanczos", "artgpu_resize_scale", "artgpu_set_pipeline_resize"]
+           "artgpu_resize_lanczos", "artgpu_resize_scale", "artgpu_set_pipeline_resize",
+           "artgpu_film_grain", "artgpu_add_noise", "artgpu_grain_table", "artgpu_grain_indices", "artgpu_set_pipeline_film_grain"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -998,6 +1045,33 @@ class Context:
         (None: off).  The library copies the parameters and keeps a reference to the CLUT."""
         self._chk(LIB.artgpu_set_pipeline_film_simulation(self._h, clut._h if clut is not None else None, C.byref(params) if params is not None else None,
                                                           int(bool(after_tone_curve))))
+
+    def film_grain(self, image: RGB, params: FilmGrainParams, ws, scale: float = 1.0, output_pipeline: bool = True, want_info: bool = False):
+        """ImProcFunctions::filmGrain in place on an RGB image (params from film_grain_params()); returns the FilmGrainInfo when want_info"""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel()) if ws is not None else None
+        info = FilmGrainInfo() if want_info else None
+        self._chk(LIB.artgpu_film_grain(self._h, C.byref(image), C.byref(params) if params is not None else None, wsd, float(scale), int(bool(output_pipeline)),
+                                        C.byref(info) if want_info else None))
+        return info
+
+    def add_noise(self, image: RGB, strength: int, coarseness: int, channel: int, ws, scale: float = 1.0, mask: Plane = None, first: bool = True, last: bool = True):
+        """one NOISE region of guidedSmoothing in place on an RGB image: add_noise on the mask's working area and the blend; first / last: this
+        call normalises the image ahead of the region / scales it back behind it"""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel()) if ws is not None else None
+        self._chk(LIB.artgpu_add_noise(self._h, C.byref(image), int(strength), int(coarseness), int(channel), C.byref(mask) if mask is not None else None, wsd,
+                                       float(scale), int(bool(first)), int(bool(last))))
+
+    grain_table = staticmethod(grain_table)
+
+    def grain_indices(self, state: int, first: int, n: int) -> np.ndarray:
+        """the table indices of draws first .. first + n - 1 counted from `state`, through the device's jump-ahead (a diagnostic)"""
+        out = np.zeros(max(int(n), 1), np.uint32)
+        self._chk(LIB.artgpu_grain_indices(self._h, int(state), int(first), int(n), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:n]
+
+    def set_pipeline_film_grain(self, params: FilmGrainParams = None):
+        """film grain in pipeline_run / batch_run / batch_run_io: behind texture boost, ahead of film simulation (None: off).  The library copies it."""
+        self._chk(LIB.artgpu_set_pipeline_film_grain(self._h, C.byref(params) if params is not None else None))
 
     def resize_lanczos(self, src: RGB, dst: RGB, scale: float, mode: int = RESIZE_PLANES, ws=None, iws=None):
         """ImProcFunctions::Lanczos from src into dst (the caller's size).  RESIZE_RGB: setMode(LAB) on src (whose contents are unspecified

@@ -6,7 +6,7 @@
 // nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers and the seven tools from raw CA correction to
 // capture sharpening in artgpu_api.hip, the demosaicers in api_demosaic.hip, the shared filters in api_filters.hip, the pixel passes in
 // api_pixelops.hip, the wavelet decomposition in api_wavelet.hip, the denoiser in api_denoise.hip (it exposes nothing), colour correction in
-// api_colorcorrection.hip, the tone equalizer in api_toneequalizer.hip, film simulation in api_filmsim.hip, resize in api_resize.hip); none is inline.
+// api_colorcorrection.hip, the tone equalizer in api_toneequalizer.hip, film simulation in api_filmsim.hip, film grain in api_filmgrain.hip, resize in api_resize.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -28,6 +28,7 @@
 #include "smoothing.h"
 #include "toneequalizer.h"
 #include "filmsim.h"
+#include "filmgrain.h"
 #include "resize.h"
 #include "masks.h"
 #include "sharpen.h"
@@ -59,6 +60,7 @@ struct artgpu_ctx {
                                        // 2: only detail_blocks_kernel plain; 3: only detail_gather_kernel plain (timing of the two halves)
         int opt_dn_mad_fold = 1;       // MadRgb -- 1: from the bins the analysis kernels count while they write the bands; 0: launch_mad's pass over the bands
         int opt_dn_mad_fold_grid = 0;  // > 0: the counting analysis kernels with at most this many workgroups (tests: many steps per workgroup; timing of the grid cap)
+        int opt_fg_grid = 0;           // film grain: > 0: the region kernel with at most this many workgroups (tests: a workgroup walks many tiles; timing)
         int opt_dn_debug_stall = -1;   // test hook: band << 16 | strip of the fused shrink pass that never publishes its progress (-1: none)
         long opt_dn_wait_ms = 0;       // how long a strip of the fused shrink pass waits for the strip above before it gives up (0: five seconds)
         int opt_io_direct = -1;        // artgpu_batch_run_io, scanlines into pinned host memory: n > 0: written there by n persistent workgroups (no staging, no copy); 0: staged +
@@ -94,6 +96,8 @@ struct artgpu_ctx {
         const artgpu_clut *pipe_fs = nullptr;      // artgpu_set_pipeline_film_simulation: the handle (the parent's pipe_fs_own holds the reference),
         artgpu_film_simulation_params pipe_fs_par = {};   // a copy of the parameters, and the position
         int pipe_fs_after = 0;
+        int pipe_fg_on = 0;            // artgpu_set_pipeline_film_grain: a copy by value
+        artgpu_film_grain_params pipe_fg = {};
         int pipe_rs_on = 0;            // artgpu_set_pipeline_resize: a copy by value
         artgpu_resize_params pipe_rs = {};
     } shared;
@@ -232,6 +236,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_SM_PLANES, P_SM_MASK, P_SM_BOX, P_SM_GEN,                                                                      // artgpu_smoothing
        P_TE_PLANES, P_TE_LUT,                                                                                           // artgpu_tone_equalizer
        P_RS_TAB, P_RS_IMG0, P_RS_IMG1, P_RS_IMG2,                                                                       // artgpu_resize_lanczos: the tables; the pipe's full-size working image
+       P_FG_WORK, P_FG_TAB, P_FG_IDX,                                                                                   // artgpu_film_grain: the planes a region writes, its tables; artgpu_grain_indices
        P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
@@ -349,7 +354,10 @@ struct SmRegionPlan {
     int skipped;
 };
 int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regions, int nregions, const double *ws, double scale, bool read_masks, const char *who);
+bool sm_working_area(int W, int H, const int *box, SmRegionPlan *pl);       // the crop rule alone (what film grain's NOISE regions share with the modes above)
 int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl);
+// the regions' blend planes on the device and the box of each (find_region): see the definition
+int sm_mask_boxes(artgpu_ctx *ctx, int W, int H, const artgpu_plane *const *masks, int n, std::vector<const float *> *mp, std::vector<size_t> *ms, std::vector<int> *boxes);
 int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
                   artgpu_smoothing_info *info, const char *who);
 
@@ -421,6 +429,16 @@ int fs_check(artgpu_ctx *ctx, const artgpu_clut *clut, const artgpu_film_simulat
 // the tool on device planes (rows of `stride` floats) in RGB mode, after fs_check; enqueued on ctx->stream
 int film_simulation_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_clut *clut, const artgpu_film_simulation_params *p);
 void clut_release(artgpu_clut *clut);      // drops one reference; the last one frees the device copy
+
+// ---------------------------------------------------------------------------------------------
+// film grain
+// ---------------------------------------------------------------------------------------------
+// what filmGrain derives from its parameters (ipgrain.cc:40-69) and add_noise from each region (ipsmoothing.cc:572-597), before anything runs
+struct FgPlan { artgpu_film_grain_info info; double scale; };
+// every reason not to run; nothing is uploaded or launched
+int fg_check(artgpu_ctx *ctx, int W, int H, const artgpu_film_grain_params *p, const double *ws, double scale, int output_pipeline, const char *who, FgPlan *pl);
+// the tool on device planes (rows of `stride` floats) in RGB mode, after fg_check; enqueued on ctx->stream
+int film_grain_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const double ws[9], const FgPlan &pl);
 
 // ---------------------------------------------------------------------------------------------
 // resize

@@ -97,6 +97,7 @@ struct PipePlan {
     bool te_on;                                                    // the tone equalizer (artgpu_set_pipeline_tone_equalizer, enabled)
     artgpu_tone_equalizer_info te;
     bool fs_on;                                                    // film simulation (artgpu_set_pipeline_film_simulation)
+    FgPlan fg;                                                     // film grain (artgpu_set_pipeline_film_grain): the derived regions, none when off
     bool rs_on;                                                    // the Resize tool (artgpu_set_pipeline_resize) changes this frame's size: to imw x imh
     int imw, imh;
     float rs_scale;
@@ -135,7 +136,7 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 //   1. ctx, raw / p / out, the border, the Resize tool's result, the output's size (then hipSetDevice, the one HIP call here; then rs_check)   2. artgpu_set_pipeline_masks' counts against the frame's
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
-//   8. dehaze_check, te_check, fs_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
+//   8. dehaze_check, te_check, fs_check, fg_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
 static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, PipePlan *pl)
 {
     if (!ctx) return ARTGPU_EINVAL;
@@ -211,6 +212,7 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     if (pl->te_on && (rc = te_check(ctx, w, h, &s.pipe_te, p->ws, scale, "pipeline_run(tone equalizer)", &pl->te))) return rc;
     pl->fs_on = s.pipe_fs != nullptr;
     if (pl->fs_on && (rc = fs_check(ctx, s.pipe_fs, &s.pipe_fs_par, "pipeline_run(film simulation)"))) return rc;
+    if (s.pipe_fg_on && (rc = fg_check(ctx, w, h, &s.pipe_fg, p->ws, scale, 1, "pipeline_run(film grain)", &pl->fg))) return rc;      // (the batch pipe is the OUTPUT pipeline)
     // sharpening (STAGE_2): method, scale and, with the automatic radius, the sensor are checked before any stage runs
     pl->shpar = p->sharpening;
     pl->sh_on = p->sharpening_enabled != 0;
@@ -356,7 +358,7 @@ static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const P
     return ARTGPU_OK;
 }
 
-// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, filmSimulation on either side of the tone curve, localContrast, [the Resize
+// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, filmGrain, filmSimulation on either side of the tone curve, localContrast, [the Resize
 // tool]; then the image goes back to the caller's planes
 static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
 {
@@ -369,6 +371,8 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
     if (pl.tb_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_tb, pl.tb_mk, ntb, false, &gen))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     for (int i = 0; i < ntb && pl.tb_gen; ++i) pl.tb_regs[i].mask = &gen[i];
     if (pl.tb_on && (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, pl.tb_regions, ntb, p->ws, pl.tb, 1, nullptr, pl.tb_in_yuv))) return rc;
+    // ImProcFunctions::filmGrain, right behind texture boost (improcfun.cc:608): its guidedSmoothing starts with setMode(RGB), which texture boost ended with
+    if (pl.fg.info.nregions > 0 && (rc = film_grain_dev(ctx, d.p, d.stride, d.w, d.h, p->ws, pl.fg))) return rc;
     // ImProcFunctions::filmSimulation ahead of the tone curve (improcfun.cc:614-616; the image is in RGB mode: texture boost ends with that switch)
     if (pl.fs_on && !s.pipe_fs_after && (rc = film_simulation_dev(ctx, d.p, d.stride, d.w, d.h, s.pipe_fs, &s.pipe_fs_par))) return rc;
     if (p->tone_enabled && p->tone_mode == ARTGPU_TONE_NEUTRAL) {

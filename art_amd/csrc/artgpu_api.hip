@@ -467,6 +467,7 @@ int artgpu_set_option(artgpu_ctx *ctx, const char *name, long value)
     else if (n == "dn_fused") ctx->shared.opt_dn_fused = (int)value;
     else if (n == "dn_mad_fold") ctx->shared.opt_dn_mad_fold = value != 0;
     else if (n == "dn_mad_fold_grid") { if (value < 0 || value > 65536) return fail(ctx, ARTGPU_EINVAL, "dn_mad_fold_grid: 0 (default) .. 65536 workgroups"); ctx->shared.opt_dn_mad_fold_grid = (int)value; }
+    else if (n == "fg_grid") { if (value < 0 || value > 65536) return fail(ctx, ARTGPU_EINVAL, "fg_grid: 0 (default) .. 65536 workgroups"); ctx->shared.opt_fg_grid = (int)value; }
     else if (n == "dn_detail_plain") { if (value < 0 || value > 3) return fail(ctx, ARTGPU_EINVAL, "dn_detail_plain: 0 .. 3"); ctx->shared.opt_dn_detail_plain = (int)value; }
     else if (n == "dn_debug_stall") ctx->shared.opt_dn_debug_stall = (int)value;
     else if (n == "dn_wait_ms") ctx->shared.opt_dn_wait_ms = value < 0 ? 0 : value;
@@ -1629,17 +1630,26 @@ int sm_check(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region *regio
     return ARTGPU_OK;
 }
 
-// one region's plan from its box (inclusive maxima as the reduction leaves them; nullptr: a NULL mask, the frame)
-int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl)
+// the working area of a region from its box (inclusive maxima as the reduction leaves them; nullptr: a NULL mask, the frame), L948-980: the
+// box, or the frame unless the box is under half of it.  false: no mask pixel above zero, skipped = ARTGPU_SMOOTHING_SKIP_EMPTY
+bool sm_working_area(int W, int H, const int *box, SmRegionPlan *pl)
 {
-    *pl = SmRegionPlan{};
-    pl->mode = r.mode; pl->channel = r.channel; pl->iterations = r.iterations; pl->nlstrength = r.nlstrength; pl->nldetail = r.nldetail;
-    if (box && box[2] < box[0]) { pl->skipped = ARTGPU_SMOOTHING_SKIP_EMPTY; return ARTGPU_OK; }
+    if (box && box[2] < box[0]) { pl->skipped = ARTGPU_SMOOTHING_SKIP_EMPTY; return false; }
     int min_x = box ? box[0] : 0, min_y = box ? box[1] : 0, max_x = box ? box[2] + 1 : W, max_y = box ? box[3] + 1 : H;
     int ww = max_x - min_x, hh = max_y - min_y;
     if (ww * hh < (W * H) / 2) pl->cropped = 1;                    // L957 (int arithmetic, as there)
     else { min_x = 0; min_y = 0; max_x = W; max_y = H; ww = W; hh = H; }
     pl->x0 = min_x; pl->y0 = min_y; pl->x1 = max_x; pl->y1 = max_y; pl->ww = ww; pl->hh = hh;
+    return true;
+}
+
+// one region's plan from its box
+int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region &r, const int *box, double scale, const char *who, int i, SmRegionPlan *pl)
+{
+    *pl = SmRegionPlan{};
+    pl->mode = r.mode; pl->channel = r.channel; pl->iterations = r.iterations; pl->nlstrength = r.nlstrength; pl->nldetail = r.nldetail;
+    if (!sm_working_area(W, H, box, pl)) return ARTGPU_OK;
+    const int ww = pl->ww, hh = pl->hh;
     if (r.mode == ARTGPU_SMOOTHING_GUIDED) {
         pl->epsilon = (float)std::max(0.001f * std::pow(2.0, (double)-r.epsilon), 1e-6);        // L1040: a double narrowed at the call
         const int rr = (int)std::round(r.radius / scale);             // L348
@@ -1661,16 +1671,18 @@ int sm_plan_region(artgpu_ctx *ctx, int W, int H, const artgpu_smoothing_region 
     return ARTGPU_OK;
 }
 
-// the tool on device planes (rows of `stride` floats) in RGB mode; enqueued on ctx->stream, one host wait when a region has a mask
-int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
-                  artgpu_smoothing_info *info, const char *who)
+// The blend planes of a call's regions on the device and find_region (L411-434) of each: host planes are staged (P_SM_MASK), every mask's box
+// comes from one pass (SM_MAX_BOX_REGIONS planes per launch) and one host wait for 4 ints per mask.  mp / ms: per region the plane and its row
+// stride in floats (nullptr: all ones); boxes: 4 ints per region that has a mask, in region order
+int sm_mask_boxes(artgpu_ctx *ctx, int W, int H, const artgpu_plane *const *masks, int n, std::vector<const float *> *mp_out, std::vector<size_t> *ms_out,
+                  std::vector<int> *boxes_out)
 {
     int rc;
     const size_t np = (size_t)W * H;
     // host planes are staged once each (several regions may share one)
     std::vector<const artgpu_plane *> host;
     for (int i = 0; i < n; ++i) {
-        const artgpu_plane *m = regions[i].mask;
+        const artgpu_plane *m = masks[i];
         if (m && !m->on_device && std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) == host.end()) host.push_back(m);
     }
     float *staged = nullptr;
@@ -1679,18 +1691,20 @@ int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W,
         for (size_t k = 0; k < host.size(); ++k)
             HIPCHK(ctx, hipMemcpy2DAsync(staged + k * np, (size_t)W * 4, host[k]->p, (size_t)host[k]->row_stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, ctx->stream));
     }
-    std::vector<const float *> mp(n, nullptr);
-    std::vector<size_t> ms(n, 0);
+    std::vector<const float *> &mp = *mp_out;
+    std::vector<size_t> &ms = *ms_out;
+    std::vector<int> &boxes = *boxes_out;
+    mp.assign(n, nullptr); ms.assign(n, 0);
     std::vector<int> masked;
     for (int i = 0; i < n; ++i) {
-        const artgpu_plane *m = regions[i].mask;
+        const artgpu_plane *m = masks[i];
         if (!m) continue;
         if (m->on_device) { mp[i] = m->p; ms[i] = (size_t)(m->row_stride_bytes / 4); }
         else { mp[i] = staged + (std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) - host.begin()) * np; ms[i] = W; }
         masked.push_back(i);
     }
     // find_region of every mask: one pass (SM_MAX_BOX_REGIONS planes per launch), one wait for 4 ints per mask
-    std::vector<int> boxes(4 * masked.size());
+    boxes.assign(4 * masked.size(), 0);
     if (!masked.empty()) {
         for (size_t k = 0; k < masked.size(); ++k) { boxes[4 * k] = W; boxes[4 * k + 1] = H; boxes[4 * k + 2] = -1; boxes[4 * k + 3] = -1; }
         float *bx;
@@ -1705,6 +1719,20 @@ int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W,
         HIPCHK(ctx, hipMemcpyAsync(boxes.data(), bx, boxes.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return ARTGPU_OK;
+}
+
+// the tool on device planes (rows of `stride` floats) in RGB mode; enqueued on ctx->stream, one host wait when a region has a mask
+int smoothing_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const artgpu_smoothing_region *regions, int n, const double *ws, double scale,
+                  artgpu_smoothing_info *info, const char *who)
+{
+    int rc;
+    std::vector<const artgpu_plane *> masks(n);
+    for (int i = 0; i < n; ++i) masks[i] = regions[i].mask;
+    std::vector<const float *> mp;
+    std::vector<size_t> ms;
+    std::vector<int> boxes;
+    if ((rc = sm_mask_boxes(ctx, W, H, masks.data(), n, &mp, &ms, &boxes))) return rc;
     // the whole plan, before any kernel writes the image
     std::vector<SmRegionPlan> plans(n);
     size_t need = 0;

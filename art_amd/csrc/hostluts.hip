@@ -7,6 +7,7 @@
 //   Color::gamma2curve, Color::igammatab_srgb  rtengine/color.cc:239-255, color.h:1122-1144
 #include "kernels.h"
 #include "toneequalizer.h"
+#include "filmgrain.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -418,6 +419,72 @@ void te_build_lut(const int bands[5], double pivot, float *lut, float *gain, flo
         float corr = 0.f;
         for (int c = 0; c < 12; ++c) corr += gauss(-16.f + 2.f * c, luma) * factors[c];
         lut[i] = corr / ws;
+    }
+}
+
+// ---------------------------------------------------------------- film grain: the normal table, the cone, the jump maps
+// RandomNumberGenerator (rng.h:31-57) stepped serially through NormalDistribution (rng.h:61-90), every conversion as written there.  Only
+// bits 16..47 of the state are ever read and bit k of the next state depends on bits <= k, so the low 48 bits are the whole generator.
+void build_grain_table(int seed, float *normd, uint64_t *state48)
+{
+    uint64_t st = (uint64_t)(uint32_t)seed & FG_MASK48;
+    const auto randint = [&st](uint32_t upper_bound) -> uint32_t {
+        st = (st * FG_LCG_A + FG_LCG_C) & FG_MASK48;
+        return uint32_t(st >> 16U) % upper_bound;
+    };
+    const auto randfloat = [&randint]() -> float {
+        const uint32_t ub = 2147483647u;                    // std::numeric_limits<int>::max()
+        return float(randint(ub)) / float(ub);
+    };
+    const float mean = 0.f, std_dev = 1.f;
+    float spare = 0.f;
+    bool has_spare = false;
+    for (int i = 0; i < FG_NORMD; ++i) {
+        if (has_spare) {
+            has_spare = false;
+            normd[i] = spare * std_dev + mean;
+        } else {
+            double u, v, s;
+            do {
+                u = randfloat() * 2.f - 1.f;
+                v = randfloat() * 2.f - 1.f;
+                s = u * u + v * v;
+            } while (s >= 1.f || s == 0.f);
+            s = sqrtf(float(-2.f * hs_xlogf(float(s)) / s));     // xlogf takes a float; the quotient is double, sqrtf narrows it
+            spare = float(v * s);
+            has_spare = true;
+            normd[i] = float(mean + std_dev * u * s);
+        }
+    }
+    *state48 = st;
+}
+
+// the cone of ipsmoothing.cc:577-597
+int build_grain_kernel(float radius, float *taps)
+{
+    if (!(radius > 0.f) || std::isinf(radius) || std::ceil(radius) > (float)FG_MAX_R) return 0;
+    const int sz = int(std::ceil(radius)) * 2 + 1;
+    const int c = sz / 2;
+    double totd = 0.0;
+    for (int i = 0; i < sz; ++i)
+        for (int j = 0; j < sz; ++j) {
+            const float r = (float)std::sqrt((double)((i - c) * (i - c) + (j - c) * (j - c)));       // std::sqrt(int): double, narrowed
+            const float d = r - radius;
+            taps[i * sz + j] = d < 0.f ? 1.f : std::max(1.f - d, 0.f);
+            totd += taps[i * sz + j];
+        }
+    const float tot = (float)totd;
+    for (int k = 0; k < sz * sz; ++k) taps[k] /= tot;
+    return sz;
+}
+
+// 2^j steps as one affine map: the square of the map of 2^(j-1) steps
+void build_grain_jump(FgJump *j)
+{
+    j->A[0] = FG_LCG_A; j->C[0] = FG_LCG_C;
+    for (int b = 1; b < FG_JUMP_BITS; ++b) {
+        j->A[b] = (j->A[b - 1] * j->A[b - 1]) & FG_MASK48;
+        j->C[b] = (j->A[b - 1] * j->C[b - 1] + j->C[b - 1]) & FG_MASK48;
     }
 }
 

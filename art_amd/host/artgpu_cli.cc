@@ -34,10 +34,12 @@
 //                                                      little-endian uint16 RGB triples, level^3 of them with red fastest; level = entries per axis
 //                                                      (64 for a level-8 file); strength in percent (default 100); after != 0: behind the tone
 //                                                      curve instead of ahead of it.  The CLUT's profile is taken to be the working profile)
+//              [--film-grain iso,strength[,color]]   (ImProcFunctions::filmGrain in STAGE_3, behind texture boost: iso 100 .. 6400, strength 0 .. 100,
+//                                                      color != 0 adds the chrominance region)
 //              [--resize-scale S | --resize-fit WxH]   (the Resize tool behind STAGE_3, simpleprocess.cc:402-414: ImProcFunctions::resizeScale with
 //                                                      dataspec 0 (scale S) or 3 (fit the W x H box; never upscales), then ImProcFunctions::resize)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--tone-equalizer ..] [--film-simulation ..] [--resize-scale ..] [--resize-fit ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
+//              [--tone-equalizer ..] [--film-simulation ..] [--film-grain ..] [--resize-scale ..] [--resize-fit ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <cctype>
@@ -113,6 +115,8 @@ int main(int argc, char **argv)
     double te_pivot = 0.0;
     std::string fs_file;                                           // FilmSimulationParams: the CLUT, strength, after_tone_curve
     int fs_level = 0, fs_strength = 100, fs_after = 0;
+    bool fg_enable = false;                                        // GrainParams
+    int fg_iso = 400, fg_strength = 50, fg_color = 0;
     bool rs_enable = false;                                        // ResizeParams
     int rs_dataspec = 0, rs_width = 900, rs_height = 900;
     double rs_scale = 1.0;
@@ -268,6 +272,10 @@ int main(int argc, char **argv)
             }
             fs_file = v.substr(0, c);
         }
+        else if (a == "--film-grain") {
+            if (std::sscanf(next(), "%d,%d,%d", &fg_iso, &fg_strength, &fg_color) < 2) { std::fprintf(stderr, "--film-grain iso,strength[,color]\n"); return 2; }
+            fg_enable = true;
+        }
         else if (a == "--resize-scale") { rs_scale = std::atof(next()); rs_dataspec = 0; rs_enable = true; }
         else if (a == "--resize-fit") {
             if (std::sscanf(next(), "%dx%d", &rs_width, &rs_height) != 2 || rs_width < 1 || rs_height < 1) { std::fprintf(stderr, "--resize-fit WxH\n"); return 2; }
@@ -323,6 +331,7 @@ int main(int argc, char **argv)
         params.toneEqualizer.enabled = te_enable; params.toneEqualizer.regularization = te_reg; params.toneEqualizer.pivot = te_pivot;
         for (int k = 0; k < 5; ++k) params.toneEqualizer.bands[k] = te_bands[k];
         film_simulation(ctx, params);
+        params.grain.enabled = fg_enable; params.grain.iso = fg_iso; params.grain.strength = fg_strength; params.grain.color = fg_color != 0;
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
         params.resize.enabled = rs_enable; params.resize.dataspec = rs_dataspec; params.resize.scale = rs_scale; params.resize.width = rs_width; params.resize.height = rs_height;
@@ -406,6 +415,7 @@ int main(int argc, char **argv)
         params.toneEqualizer.enabled = te_enable; params.toneEqualizer.regularization = te_reg; params.toneEqualizer.pivot = te_pivot;
         for (int k = 0; k < 5; ++k) params.toneEqualizer.bands[k] = te_bands[k];
         film_simulation(ctx, params);
+        params.grain.enabled = fg_enable; params.grain.iso = fg_iso; params.grain.strength = fg_strength; params.grain.color = fg_color != 0;
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
         params.resize.enabled = rs_enable; params.resize.dataspec = rs_dataspec; params.resize.scale = rs_scale; params.resize.width = rs_width; params.resize.height = rs_height;

@@ -247,6 +247,9 @@ struct ProcParams {
         for (int k = 0; k < 9; ++k) { q.work_to_xyz[k] = f.work_to_xyz[k]; q.xyz_to_clut[k] = f.xyz_to_clut[k]; q.clut_to_xyz[k] = f.clut_to_xyz[k]; q.xyz_to_work[k] = f.xyz_to_work[k]; }
         return q;
     }
+    // GrainParams (procparams.cc:2731-2737)
+    struct { bool enabled = false; int iso = 400; int strength = 50; bool color = false; } grain;
+    artgpu_film_grain_params grainParams() const { return artgpu_film_grain_params{grain.enabled ? 1 : 0, grain.iso, grain.strength, grain.color ? 1 : 0}; }
     // SmoothingParams (procparams.cc:2753-2775, procparams.h:1289-1347): regions with the reference's defaults (mode GUIDED, channel RGB);
     // masks[i].enabled and either the blend plane the application's generateMasks made of masks[i] (`blend`; nullptr = all ones) or the Mask itself
     struct SmoothingRegion {
@@ -424,7 +427,7 @@ public:
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); toneEqualizer(img); break;   // improcfun.cc:581-588
         case Stage::STAGE_2: sharpening(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595, 601, 602
         case Stage::STAGE_3:                                                                  // improcfun.cc:606-625 (the steps this library has)
-            textureBoost(img); logEncoding(img); saturationVibrance(img);
+            textureBoost(img); filmGrain(img); logEncoding(img); saturationVibrance(img);       // L606-611
             if (!params->filmSimulation.after_tone_curve) filmSimulation(img);                // L614-616
             toneCurve(img);
             if (params->filmSimulation.after_tone_curve) filmSimulation(img);                 // L618-620
@@ -538,6 +541,15 @@ public:
         const artgpu_film_simulation_params fp = params->filmSimulationParams();
         artgpu_rgb i = img->view();
         ctx.check(artgpu_film_simulation(ctx.get(), &i, params->filmSimulation.clut, &fp));
+    }
+    // ImProcFunctions::filmGrain (ipgrain.cc:88-98): guidedSmoothing over the NOISE regions it derives; the reference adds noise in the OUTPUT and
+    // PREVIEW pipelines only (ipsmoothing.cc:990), elsewhere the regions' blend and the normalise round trip is all that happens -- not on the device path
+    void filmGrain(Imagefloat *img)
+    {
+        if (!params->grain.enabled || (cur_pipeline != Pipeline::OUTPUT && cur_pipeline != Pipeline::PREVIEW)) return;
+        const artgpu_film_grain_params gp = params->grainParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_film_grain(ctx.get(), &i, &gp, params->workingSpace, scale, cur_pipeline == Pipeline::OUTPUT ? 1 : 0, nullptr));
     }
     // ImProcFunctions::resizeScale (ipresize.cc:226-297) without a crop
     static float resizeScale(const ProcParams *params, int fw, int fh, int &imw, int &imh)
@@ -831,6 +843,9 @@ public:
         const artgpu_film_simulation_params fs = p.filmSimulationParams();
         const bool fs_on = p.filmSimulation.enabled && p.filmSimulation.clut;
         ctx.check(artgpu_set_pipeline_film_simulation(ctx.get(), fs_on ? p.filmSimulation.clut : nullptr, &fs, p.filmSimulation.after_tone_curve ? 1 : 0));
+        // ImProcFunctions::filmGrain behind texture boost
+        const artgpu_film_grain_params fg = p.grainParams();
+        ctx.check(artgpu_set_pipeline_film_grain(ctx.get(), p.grain.enabled ? &fg : nullptr));
         // ImProcFunctions::resize behind STAGE_3 (the jobs' scanline buffers have the size addJob derived from the same parameters)
         const artgpu_resize_params rs = p.resizeParams();
         ctx.check(artgpu_set_pipeline_resize(ctx.get(), p.resize.enabled ? &rs : nullptr));
@@ -851,6 +866,7 @@ public:
         (void)artgpu_set_pipeline_smoothing(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_tone_equalizer(ctx.get(), nullptr);
         (void)artgpu_set_pipeline_film_simulation(ctx.get(), nullptr, nullptr, 0);
+        (void)artgpu_set_pipeline_film_grain(ctx.get(), nullptr);
         (void)artgpu_set_pipeline_resize(ctx.get(), nullptr);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);

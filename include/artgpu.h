@@ -99,6 +99,8 @@ int artgpu_synchronize(artgpu_ctx *ctx);
  *                       Same bits.  "dn_mad_fold_grid" n > 0: the counting kernels with at most n workgroups (tests, timing).  artgpu_get_option:
  *                       "dn_mad_fold_settled" / "dn_mad_fold_fallback": bands of the context's last RGB_denoise settled from the counts / left to
  *                       the full histogram; "dn_mad_bitsK": bit pattern of word K (0 .. 95) of its SQR(MadRgb) block
+ *   "fg_grid"           n > 0: the film grain region kernel with at most n workgroups, each walking a longer chunk of tiles (tests, timing); 0 (default):
+ *                       four per CU.  Same bits.
  *   "dn_streams"        0 (default since round 5): RGB_denoise's kernels one after the other on the context's stream; 1: the DCT detail recovery of L on a
  *                       side stream beside the reconstructions of a and b (the default of rounds 3 and 4); "lut_lds" 0: never the LUT-in-LDS shape
  *                       of the pixel passes; "rcd_rows" 4 | 8; "roctx" 1: roctx ranges named after the reference functions
@@ -883,7 +885,7 @@ int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color
  * region: nothing of it runs, skipped = ARTGPU_SMOOTHING_SKIP_EMPTY.  nregions == 0: the normalise round trip.  NaN-free input is the
  * contract.
  * ARTGPU_EUNSUPPORTED, image untouched: the modes GAUSSIAN, GAUSSIAN_GLOW, MOTION, LENS, NOISE, HALATION (Convolution is an FFTW product;
- * inpaint; the reference's RNG stream) and WAVELETS; iterations < 1; a GUIDED region (r > 0) whose statistics grid (working size /
+ * inpaint; NOISE regions are not taken here but by artgpu_add_noise / artgpu_film_grain below) and WAVELETS; iterations < 1; a GUIDED region (r > 0) whose statistics grid (working size /
  * subsampling) has a side below ARTGPU_SMOOTHING_MIN_SIZE, or whose box radius is above the blur kernels' 900; an NLMEANS region
  * (nlstrength != 0) with a working plane below 32 x 32, (ww + 14) * (hh + 14) >= 2^30, or scale < 1.  Not built: show_mask, the pipette
  * buffers. */
@@ -1127,6 +1129,75 @@ int artgpu_set_pipeline_tone_equalizer(artgpu_ctx *ctx, const artgpu_tone_equali
  * the image is in RGB mode at both points, ahead of local contrast.  A bad handle or a handle of another device fails the frame before
  * any stage has run.  With the setting off the pipe launches exactly what it launched without it. */
 int artgpu_set_pipeline_film_simulation(artgpu_ctx *ctx, const artgpu_clut *clut, const artgpu_film_simulation_params *params, int after_tone_curve);
+
+/* ImProcFunctions::filmGrain (rtengine/ipgrain.cc:33-98), ART's "Film grain" tool: the second step of STAGE_3, behind textureBoost and ahead of
+ * logEncoding / filmSimulation (improcfun.cc:606-616).  `img`: RGB mode, 0..65535, host or device, any row stride or start offset, in place.
+ * enabled == 0 returns at once.  The tool is guidedSmoothing (ipsmoothing.cc:933-1067) over NOISE regions it derives itself (ipgrain.cc:40-69):
+ *   coarseness = int(LIM01(float(iso - 19) / 6380.f) * 100.f + 0.5f); nlevels = 3 in the OUTPUT pipeline, int(ceil(3 / scale)) otherwise;
+ *   with `color` first one CHROMINANCE region (strength / 2, coarseness / 2); then LUMINANCE regions i = 0 .. nlevels - 1 with
+ *   strength / (nlevels - i) and coarseness / (i + 1), all int divisions.  Their masks are default-constructed: generateMasks finds nothing
+ *   that makes a mask (masks.cc:1053-1084) and fills the planes with 1.f (L1296-1308), which is what mask == NULL means here.
+ * Around the regions: setMode(RGB), x * (1.f / 65535.f) (normalizeFloatTo1), per region the working area (the crop rule of artgpu_smoothing,
+ * L948-980), add_noise on the working copy, rgb = intp(mask, working, rgb) over the area (L1050-1064: with an all-ones mask still
+ * 1.f * w + (1.f - 1.f) * r), and x * 65535.f behind the last region.
+ * add_noise (L565-695) of (strength, coarseness, channel) at `scale`:
+ *   sf = LIM01(float(strength) / (L ? 200.f : 100.f)) / scale; radius = (0.5f + 1.75f * float(coarseness) / 100.f) / scale (both double
+ *   quotients narrowed to float); the kernel is the sz x sz cone, sz = 2 * ceil(radius) + 1: k = d < 0 ? 1 : max(1 - d, 0) with
+ *   d = float(sqrt(di^2 + dj^2)) - radius, its total summed in double, every tap divided by float(total);
+ *   the generator (rng.h:31-57) is seeded 42 + int(channel) + coarseness and first fills normd[5233] through NormalDistribution (rng.h:61-90:
+ *   Marsaglia's polar method, u, v, s double, xlogf of s narrowed to float, sqrtf, the spare value kept as float);
+ *   per plane a, in raster order: mu = max(a, 0.f) * c, r = normd[randint(5233)] * sd, m = mu + sqrtf(mu) * r, noise = m / c - a with
+ *   c = 655.35f / (20.f + powf(coarseness / 100.f, 0.5f) * 80.f) and sd = 1 for Y, 0.7 / 1 / 1.3 for R / G / B; the noise plane convolved
+ *   with the kernel (replicate padding); a = max(a + sf * conv, 0.f).
+ *   LUMINANCE runs on Y of rgb2yuv and keeps u, v; RGB on R, G, B; CHROMINANCE as RGB, then the input's Y under the noisy u, v.
+ * Two things the reference leaves open are defined here:
+ *   draw order -- the reference draws from one generator inside an OpenMP loop, a race; the single-threaded raster order is the definition:
+ *     pixel (y, x) of plane p of a ww x hh working area reads draw number p * ww * hh + y * ww + x, counted from the state the table left;
+ *   convolution -- rt_algo.cc:733-775 multiplies FFTs; the definition is the direct sum acc = 0.f; for i, for j: acc = acc + k[i][j] *
+ *     noise[clamp(y + i - c)][clamp(x + j - c)] in fp32, unfused.
+ * Every consumer of the generator reads bits 16..47 of its state, and bit k of an LCG's next state depends on bits <= k only, so the
+ * stream is a 48-bit LCG (a = 25214903917, c = 11) and any draw is reached by jump-ahead: one launch per region, no noise plane.
+ * `info` (or NULL): the regions that were derived, in the order they ran.
+ * ARTGPU_EUNSUPPORTED, image untouched: scale < 1 (sz would exceed 7); a working area with 3 * ww * hh >= 2^32; iso outside 100 .. 6400 or
+ * strength outside 0 .. 100 (rtgui/grain.cc:47,51); for artgpu_add_noise strength or coarseness outside 0 .. 100 (rtgui/smoothing.cc:348,351).
+ * ARTGPU_EINVAL: bad pointers, a channel other than ARTGPU_SMOOTHING_LUMINANCE / CHROMINANCE / RGB, scale not finite.  NaN-free input is the
+ * contract.  Not built: show_mask, the pipette buffers, the NAVIGATOR pipeline (where the reference adds no noise). */
+#define ARTGPU_FILM_GRAIN_MAX_REGIONS 4
+#define ARTGPU_GRAIN_TABLE_SIZE 5233
+typedef struct artgpu_film_grain_params {   /* GrainParams, defaults procparams.cc:2731-2737 */
+    int32_t enabled;           /* 0 */
+    int32_t iso;               /* 400 */
+    int32_t strength;          /* 50 */
+    int32_t color;             /* 0 */
+} artgpu_film_grain_params;
+typedef struct artgpu_film_grain_region_info {     /* what filmGrain and add_noise derived for one region */
+    int32_t channel, strength, coarseness, seed, sz;
+    float sf;
+} artgpu_film_grain_region_info;
+typedef struct artgpu_film_grain_info {
+    int32_t nregions;          /* 0 when the tool is disabled */
+    artgpu_film_grain_region_info region[ARTGPU_FILM_GRAIN_MAX_REGIONS];
+} artgpu_film_grain_info;
+int artgpu_film_grain(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_film_grain_params *params, const double ws[9], double scale, int output_pipeline,
+                      artgpu_film_grain_info *info /* or NULL */);
+/* One NOISE region of guidedSmoothing: the working area from `mask` (the crop rule; NULL = all ones, the frame), add_noise on it, the blend.
+ * first != 0: this call normalises the image (x * (1.f / 65535.f)) ahead of the region; last != 0: it stores x * 65535.f behind it.
+ * artgpu_film_grain is a loop over this call with first / last set at either end; a region in between finds and leaves the image
+ * normalised.  A mask with no pixel above zero skips the region (only the normalise passes asked for run). */
+int artgpu_add_noise(artgpu_ctx *ctx, artgpu_rgb *img, int strength, int coarseness, int channel, const artgpu_plane *mask, const double ws[9],
+                     double scale, int first, int last);
+/* Host only, no context: what add_noise builds before it reads a pixel.  normd: the 5233 NormalDistribution draws of a generator seeded
+ * `seed`; *state: the generator's low 48 bits after them; kernel / *sz: the normalised cone of `radius` (49 floats of room; pass NULL to skip).
+ * ARTGPU_EINVAL: seed == 0 (the reference asserts), a radius that is not finite, <= 0 or gives sz > 7. */
+int artgpu_grain_table(int seed, float normd[ARTGPU_GRAIN_TABLE_SIZE], float *kernel /* 49 or NULL */, int *sz, float radius, uint64_t *state);
+/* Diagnostic: the table indices randint(5233) of draws first .. first + n - 1 counted from `state` (artgpu_grain_table's), computed on the
+ * device by the jump-ahead the region kernel uses.  `out`: n host words.  ARTGPU_EINVAL unless first >= 0, 1 <= n <= 2^24, first + n <= 2^32 and state < 2^48. */
+int artgpu_grain_indices(artgpu_ctx *ctx, uint64_t state, int64_t first, int64_t n, uint32_t *out);
+/* Film grain in the per-frame pipe, a setting of the context (copied; batch lanes inherit it).  NULL = off, the default.  While set (and
+ * enabled) the three pipe entries run artgpu_film_grain's code as the OUTPUT pipeline with params->ws and params->scale behind texture boost
+ * and ahead of the first film simulation position (improcfun.cc:606-616); the image is in RGB mode there.  What artgpu_film_grain does not
+ * support fails the frame before any stage has run.  With the setting off the pipe launches exactly what it launched without it. */
+int artgpu_set_pipeline_film_grain(artgpu_ctx *ctx, const artgpu_film_grain_params *params);
 
 /* ImProcFunctions::Lanczos (rtengine/ipresize.cc:53-223), the Resize tool's resampler: Lanczos-3 from `src` into `dst`, whose size is the
  * caller's (imw x imh of artgpu_resize_scale; as in the reference it is not derived from `scale`).  src and dst are different images,

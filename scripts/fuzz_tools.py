@@ -1,10 +1,11 @@
-"""Random sizes through the N4 tools (log encoding, Lab adjustments, hsl equaliser, dual demosaic, VNG4): GPU vs oracle, bit for bit.
+"""Random sizes through the N4 tools (log encoding, Lab adjustments, hsl equaliser, dual demosaic, VNG4) and film grain: GPU vs oracle / checker, bit for bit.
 Not a test (takes a while); run on an MI355X box: `python scripts/fuzz_tools.py` (env SEED, N)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import oracle_lib as O
+import fg_lib
 from art_amd import capi, synth
 
 rng = np.random.default_rng(int(os.environ.get("SEED", "1")))
@@ -55,6 +56,11 @@ for it in range(int(os.environ.get("N", "12"))):
     src = [p.copy() for p in got]
     ctx.hsl_equalizer(capi.host_rgb(got), H_CURVE, S_CURVE, L_CURVE, sm, O.REC2020_WS_D, 1.0, True)
     res.append((f"hsl(sm={sm})", same(got, O.hsl_equalizer(src, H_CURVE, S_CURVE, L_CURVE, sm, scale=1.0, to_rgb=True))))
+    # film grain (the checker steps the generator serially: a random size is a random set of tile edges and draw numbers)
+    fkw = dict(iso=int(rng.integers(100, 6401)), strength=int(rng.integers(0, 101)), color=bool(rng.integers(0, 2)))
+    got = [p.copy() for p in img]
+    ctx.film_grain(capi.host_rgb(got), capi.film_grain_params(**fkw), O.REC2020_WS_D)
+    res.append((f"grain({fkw['iso']},{fkw['strength']},{int(fkw['color'])})", same(got, fg_lib.film_grain(img, **fkw)[0])))
     # demosaicers
     if w >= 96 and h >= 96:
         filt = [synth.FILTERS_RGGB, 0x16161616, 0x61616161, 0x49494949][it % 4]
