@@ -66,25 +66,12 @@ int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride,
     const size_t np = (size_t)W * H;
     int rc;
     std::vector<CcRegion> regs = pl.regs;
-    // host planes are staged once each (one plane may serve as both masks, and several regions may share one)
-    std::vector<const artgpu_plane *> host;
-    for (int i = 0; i < n; ++i)
-        for (const artgpu_plane *m : {regions[i].lmask, regions[i].abmask})
-            if (m && !m->on_device && std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) == host.end()) host.push_back(m);
-    float *staged = nullptr;
-    if (!host.empty()) {
-        if ((rc = pool_get(ctx, P_CC_MASK, host.size() * np * 4, &staged))) return rc;
-        for (size_t k = 0; k < host.size(); ++k)
-            HIPCHK(ctx, hipMemcpy2DAsync(staged + k * np, (size_t)W * 4, host[k]->p, (size_t)host[k]->row_stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const auto bind = [&](const artgpu_plane *m, const float **p, size_t *s) {
-        *p = nullptr; *s = 0;
-        if (!m) return;
-        if (m->on_device) { *p = m->p; *s = (size_t)(m->row_stride_bytes / 4); return; }
-        const size_t k = std::find_if(host.begin(), host.end(), [m](const artgpu_plane *q) { return q->p == m->p; }) - host.begin();
-        *p = staged + k * np; *s = W;
-    };
-    for (int i = 0; i < n; ++i) { bind(regions[i].lmask, &regs[i].lmask, &regs[i].l_stride); bind(regions[i].abmask, &regs[i].abmask, &regs[i].ab_stride); }
+    // lmask0, abmask0, lmask1, ...: one plane may serve as both masks, and several regions may share one
+    std::vector<const artgpu_plane *> masks(2 * n);
+    std::vector<const float *> mp(2 * n); std::vector<size_t> ms(2 * n);
+    for (int i = 0; i < n; ++i) { masks[2 * i] = regions[i].lmask; masks[2 * i + 1] = regions[i].abmask; }
+    if ((rc = bind_planes(ctx, W, H, masks.data(), 2 * n, P_CC_MASK, mp.data(), ms.data()))) return rc;
+    for (int i = 0; i < n; ++i) { regs[i].lmask = mp[2 * i]; regs[i].l_stride = ms[2 * i]; regs[i].abmask = mp[2 * i + 1]; regs[i].ab_stride = ms[2 * i + 1]; }
     CcArgs a = {};
     for (int k = 0; k < 3; ++k) a.img[k] = planes[k];
     a.stride = stride; a.w = W; a.h = H;

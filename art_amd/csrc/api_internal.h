@@ -3,10 +3,9 @@
 // (api_batch.hip) or a sibling stage.  This header is the list of what a stage exposes; everything a stage uses only itself stays
 // static or in an anonymous namespace in its own file.  The shared functions live in artgpu::api.  None of them is in the library's
 // dynamic symbol table, and no namespace opening has to say so: every translation unit is compiled with hidden visibility, and
-// nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers and the seven tools from raw CA correction to
-// capture sharpening in artgpu_api.hip, the demosaicers in api_demosaic.hip, the shared filters in api_filters.hip, the pixel passes in
-// api_pixelops.hip, the wavelet decomposition in api_wavelet.hip, the denoiser in api_denoise.hip (it exposes nothing), colour correction in
-// api_colorcorrection.hip, the tone equalizer in api_toneequalizer.hip, film simulation in api_filmsim.hip, film grain in api_filmgrain.hip, resize in api_resize.hip); none is inline.
+// nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers in artgpu_api.hip; every stage in the
+// api_<stage>.hip named after its kernel file, the demosaicers in api_demosaic.hip, the shared filters in api_filters.hip, the pixel passes
+// in api_pixelops.hip; api_denoise.hip exposes nothing); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -243,6 +242,9 @@ static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 int pool_get(artgpu_ctx *ctx, int slot, size_t bytes, float **out);
 int plane_to_pool(artgpu_ctx *ctx, const artgpu_plane *pl, int slot, float **out);
 int pool_to_plane(artgpu_ctx *ctx, const float *src, artgpu_plane *pl);
+// read-only planes (masks, area planes) as (pointer, row stride in floats): device planes in place, each distinct host plane staged once into `slot`
+int bind_plane(artgpu_ctx *ctx, const artgpu_plane *pl, int slot, const float **p, size_t *stride);
+int bind_planes(artgpu_ctx *ctx, int W, int H, const artgpu_plane *const *planes, int n, int slot, const float **p, size_t *stride);
 
 #ifndef ARTGPU_MAX_TILE_WG
 #define ARTGPU_MAX_TILE_WG 8192

@@ -106,6 +106,20 @@ def test_same_call_twice_same_bits(gpu_ctx):
     assert all(np.array_equal(cc_lib.bits(p), cc_lib.bits(q)) for p, q in zip(a, b))
 
 
+def test_one_host_mask_read_through_several_entries(gpu_ctx):
+    """one host plane is both masks of the first region and the lmask of the second: staged once, read through three entries; the same bits
+    as with three separate device planes"""
+    w, h = 4, 3
+    img = cc_lib.scene(w, h, seed=13)
+    m = cc_lib.mask("onelane", w, h)
+    first, second = dict(mode=cc_lib.RGB, **cc_lib.VARIANTS["pivot"]), dict(mode=cc_lib.YUV, **cc_lib.VARIANTS["sop"])
+    a, ia = _device_tool(gpu_ctx, img, [dict(first, lmask=m, abmask=m), dict(second, lmask=m, abmask=None)], True)
+    b, ib = _device_tool(gpu_ctx, img, [dict(first, lmask=m.copy(), abmask=m.copy()), dict(second, lmask=m.copy(), abmask=None)], True, device_masks=True)
+    assert [bytes(x) for x in ia] == [bytes(x) for x in ib]
+    assert all(np.array_equal(_bits(p), _bits(q)) for p, q in zip(a, b))
+    assert any(not np.array_equal(_bits(p), _bits(q)) for p, q in zip(a, img)), "the regions changed nothing"
+
+
 UNSUPPORTED = {
     "lut-mode": [dict(mode=cc_lib.JZAZBZ), dict(mode=cc_lib.LUT)],
     "power-zero": [dict(mode=cc_lib.RGB, power=(1.0, 0.0, 1.0))],

@@ -99,6 +99,23 @@ def test_same_call_twice_same_bits_and_the_scratch_returns(gpu_ctx):
     assert gpu_ctx.scratch_bytes() == base
 
 
+def test_one_host_mask_shared_by_two_regions(gpu_ctx):
+    """two regions share one host mask and a third has its own: two planes are staged, the shared one is read through two entries; the same
+    bits and the same info per region as with three separate device masks"""
+    w, h = 67, 41
+    img = sm_lib.scene(w, h, seed=12)
+    shared, own = sm_lib.mask("between", w, h), sm_lib.mask("corners2", w, h)
+    fields = [dict(mode=sm_lib.GUIDED, channel=sm_lib.L, radius=2), dict(mode=sm_lib.GUIDED, channel=sm_lib.CH, radius=1, epsilon=2),
+              dict(mode=sm_lib.GUIDED, channel=sm_lib.LC, radius=3)]
+    a, ia = _device_tool(gpu_ctx, img, [dict(f, mask=m) for f, m in zip(fields, (shared, shared, own))])
+    b, ib = _device_tool(gpu_ctx, img, [dict(f, mask=m) for f, m in zip(fields, (shared.copy(), shared.copy(), own.copy()))], device_masks=True)
+    assert len(ia) == len(ib) == 3
+    for i, (x, y) in enumerate(zip(ia, ib)):
+        assert sm_lib.info_fields(x) == sm_lib.info_fields(y), f"region {i}"
+    assert all(np.array_equal(_bits(p), _bits(q)) for p, q in zip(a, b))
+    assert any(not np.array_equal(_bits(p), _bits(q)) for p, q in zip(a, img)), "the regions changed nothing"
+
+
 @pytest.mark.parametrize("name", list(sm_lib.UNSUPPORTED))
 def test_unsupported_cases_leave_the_image_alone(gpu_ctx, name):
     w, h, regs = sm_lib.UNSUPPORTED[name]
