@@ -94,7 +94,7 @@ int artgpu_batch_run(artgpu_ctx *ctx, int nframes, const artgpu_plane *raws, con
     if (L <= 1) {
         for (int f = 0; f < nframes; ++f) {
             int rc = batch_settle_scratch(ctx, px_of(f), f + 1 < nframes ? px_of(f + 1) : -1);
-            if (!rc) rc = artgpu_pipeline_run(ctx, &raws[f], params, &outs[f]);
+            if (!rc) rc = pipeline_run_impl(ctx, &raws[f], params, &outs[f], true);
             if (rc) return rc;
         }
         return ARTGPU_OK;
@@ -106,7 +106,7 @@ int artgpu_batch_run(artgpu_ctx *ctx, int nframes, const artgpu_plane *raws, con
     return batch_on_lanes(ctx, L, [&](artgpu_ctx *c, int k) -> int {
         for (int f = k; f < nframes; f += L) {
             int rc2 = batch_settle_scratch(c, px_of(f), f + L < nframes ? px_of(f + L) : -1);
-            if (!rc2) rc2 = artgpu_pipeline_run(c, &raws[f], params, &outs[f]);
+            if (!rc2) rc2 = pipeline_run_impl(c, &raws[f], params, &outs[f], true);
             if (rc2) return rc2;
         }
         if (k > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, ARTGPU_EHIP, "batch_run: lane %d: stream", k);
@@ -203,7 +203,6 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
 
     // ---- upload (io_up) -> copyOriginalPixels + scaleColors (stream)
     ScaleArgs a = {};
-    a.w = W; a.h = H; a.src_u16 = in->is_u16 ? 1 : 0;
     if (in->on_device) { a.src = in->data; a.src_stride = (size_t)(in->row_stride_bytes / esz); }
     else {
         float *st;
@@ -216,16 +215,7 @@ int io_frame(artgpu_ctx *c, int i, const artgpu_sensor_frame *in, const artgpu_p
         a.src = st; a.src_stride = W;
     }
     a.dst = cfa; a.dst_stride = W;
-    a.bayer = p->sensor == 0 ? 1 : 0;
-    for (int r = 0; r < 6; ++r)
-        for (int col = 0; col < 6; ++col) {
-            int v;
-            if (p->sensor != 0) v = p->xtrans[r * 6 + col];
-            else v = (p->filters >> ((((r << 1) & 14) + (col & 1)) << 1)) & 3;
-            if (v < 0 || v > 2) return fail(c, ARTGPU_EUNSUPPORTED, "batch_run_io: three-colour CFAs only");
-            a.cfa[r * 6 + col] = v;
-        }
-    for (int k = 0; k < 4; ++k) { a.cblacksom[k] = in->cblacksom[k]; a.scale_mul[k] = in->scale_mul[k]; }
+    if ((rc = scale_args_fill(c, W, H, in->is_u16, p->filters, p->sensor != 0 ? p->xtrans : nullptr, in->cblacksom, in->scale_mul, "batch_run_io", &a))) return rc;
     a.chmax_bits = flags;
     HIPCHK(c, hipMemsetAsync(flags, 0, 8 * sizeof(int), c->stream));
     HIPCHK(c, launch_scale_colors(a, c->stream));

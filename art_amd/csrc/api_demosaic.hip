@@ -123,25 +123,21 @@ static int dual_blend_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, uint
     return ARTGPU_OK;
 }
 
-static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *raw, uint32_t filters,
-                               double initial_gain, int border, artgpu_rgb *out, DualReq *dual)
+// the events of artgpu_get_timings, recorded beside the launches (ev[0] .. ev[2]): waited for and read when the stage has been queued
+int demosaic_read_timings(artgpu_ctx *ctx, bool has_border)
 {
-    StageScope scope_(ctx, "RawImageSource::demosaic (Bayer)");
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!plane_ok(raw) || !out) return fail(ctx, ARTGPU_EINVAL, "demosaic_bayer: bad raw plane or null output");
-    if (method != ARTGPU_BAYER_AMAZE && method != ARTGPU_BAYER_RCD && method != ARTGPU_BAYER_VNG4) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: method %d is not on the device path", method);
-    if (!(initial_gain > 0.0)) return fail(ctx, ARTGPU_EINVAL, "demosaic_bayer: initial_gain must be > 0");
-    // RGB Bayer only: the reference falls back to igv_interpolate for 4-colour CFAs (rcd_demosaic.cc:57-66)
-    for (unsigned r = 0; r < 2; ++r)
-        for (unsigned c = 0; c < 2; ++c)
-            if (((filters >> ((((r << 1) & 14) + (c & 1)) << 1)) & 3) == 3) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: 4-colour CFA");
-    const int W = raw->w, H = raw->h;
-    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: image %dx%d smaller than 64x64", W, H);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&ctx->last.demosaic_ms, ctx->ev[0], ctx->ev[1]));
+    if (!has_border) { ctx->last.border_ms = 0.f; ctx->last.total_ms = ctx->last.demosaic_ms; return ARTGPU_OK; }
+    HIPCHK(ctx, hipEventElapsedTime(&ctx->last.border_ms, ctx->ev[1], ctx->ev[2]));
+    HIPCHK(ctx, hipEventElapsedTime(&ctx->last.total_ms, ctx->ev[0], ctx->ev[2]));
+    return ARTGPU_OK;
+}
 
-    DevImage d;
-    int rc = bind_images(ctx, raw, out, &d);
-    if (rc) return rc;
+// RawImageSource::demosaic for a Bayer sensor on a bound image, after demosaic_bayer_check; dual: the dual demosaic's second pass and blend behind it
+static int demosaic_bayer_run(artgpu_ctx *ctx, const DevImage &d, int W, int H, int method, uint32_t filters, double initial_gain, int border, DualReq *dual)
+{
+    int rc;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
 
     int bord = 0;
@@ -322,15 +318,21 @@ static int demosaic_bayer_impl(artgpu_ctx *ctx, int method, const artgpu_plane *
     if (rc) return rc;
     if (dual && (rc = dual_blend_dev(ctx, d, W, H, filters, dual))) return rc;
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    rc = unbind_images(ctx, out, &d);
-    if (rc) return rc;
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev[2]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.demosaic_ms, ctx->ev[0], ctx->ev[1]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.border_ms, ctx->ev[1], ctx->ev[2]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.total_ms, ctx->ev[0], ctx->ev[2]));
-    }
-    return ARTGPU_OK;
+    return ctx->timing ? demosaic_read_timings(ctx, true) : ARTGPU_OK;
+}
+
+// artgpu_demosaic_bayer and artgpu_dual_demosaic_bayer
+static int demosaic_bayer_entry(artgpu_ctx *ctx, int method, const artgpu_plane *raw, uint32_t filters, double initial_gain, int border, artgpu_rgb *out, DualReq *dual)
+{
+    StageScope scope_(ctx, "RawImageSource::demosaic (Bayer)");
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!plane_ok(raw) || !out) return fail(ctx, ARTGPU_EINVAL, "demosaic_bayer: bad raw plane or null output");
+    int rc;
+    if ((rc = demosaic_bayer_check(ctx, method, filters, initial_gain, raw->w, raw->h))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevImage d;
+    if ((rc = bind_images(ctx, raw, out, &d)) || (rc = demosaic_bayer_run(ctx, d, raw->w, raw->h, method, filters, initial_gain, border, dual))) return rc;
+    return unbind_images(ctx, out, &d);
 }
 
 } // namespace
@@ -340,7 +342,7 @@ extern "C" {
 int artgpu_demosaic_bayer(artgpu_ctx *ctx, int method, const artgpu_plane *raw, uint32_t filters,
                           double initial_gain, int border, artgpu_rgb *out)
 {
-    return demosaic_bayer_impl(ctx, method, raw, filters, initial_gain, border, out, nullptr);
+    return demosaic_bayer_entry(ctx, method, raw, filters, initial_gain, border, out, nullptr);
 }
 int artgpu_dual_demosaic_bayer(artgpu_ctx *ctx, int method, int second, const artgpu_plane *raw, uint32_t filters, double initial_gain, int border,
                                double *contrast, int auto_contrast, artgpu_rgb *out)
@@ -352,7 +354,7 @@ int artgpu_dual_demosaic_bayer(artgpu_ctx *ctx, int method, int second, const ar
     if (raw && (raw->w < 96 || raw->h < 96)) return fail(ctx, ARTGPU_EUNSUPPORTED, "dual_demosaic_bayer: image smaller than 96x96");
     DualReq req = {contrast, auto_contrast, second};
     // contrast == 0 without the automatic threshold: only the first demosaicer runs (dual_demosaic_RT.cc:43-71)
-    return demosaic_bayer_impl(ctx, method, raw, filters, initial_gain, border, out, (*contrast == 0.0 && !auto_contrast) ? nullptr : &req);
+    return demosaic_bayer_entry(ctx, method, raw, filters, initial_gain, border, out, (*contrast == 0.0 && !auto_contrast) ? nullptr : &req);
 }
 
 int artgpu_border_interpolate2(artgpu_ctx *ctx, const artgpu_plane *raw, uint32_t filters, int lborders, artgpu_rgb *out)
@@ -385,8 +387,39 @@ int artgpu_demosaic_xtrans(artgpu_ctx *ctx, int passes, int use_cielab, const ar
     StageScope scope_(ctx, "RawImageSource::xtrans_interpolate");
     if (!ctx) return ARTGPU_EINVAL;
     if (!plane_ok(raw) || !out || !xtrans || !rgb_cam) return fail(ctx, ARTGPU_EINVAL, "demosaic_xtrans: bad raw plane or null argument");
+    int rc;
+    // (the row bind_images gives the CFA plane: a device plane's own, a staged host plane's width)
+    if ((rc = demosaic_xtrans_check(ctx, passes, xtrans, raw->w, raw->h, raw->on_device ? (size_t)(raw->row_stride_bytes / 4) : (size_t)raw->w))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevImage d;
+    if ((rc = bind_images(ctx, raw, out, &d)) || (rc = demosaic_xtrans_dev(ctx, d, raw->w, raw->h, passes, use_cielab, xtrans, rgb_cam))) return rc;
+    return unbind_images(ctx, out, &d);
+}
+
+} // extern "C"
+
+namespace artgpu { namespace api {
+
+int demosaic_bayer_check(artgpu_ctx *ctx, int method, uint32_t filters, double initial_gain, int W, int H)
+{
+    if (method != ARTGPU_BAYER_AMAZE && method != ARTGPU_BAYER_RCD && method != ARTGPU_BAYER_VNG4) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: method %d is not on the device path", method);
+    if (!(initial_gain > 0.0)) return fail(ctx, ARTGPU_EINVAL, "demosaic_bayer: initial_gain must be > 0");
+    // RGB Bayer only: the reference falls back to igv_interpolate for 4-colour CFAs (rcd_demosaic.cc:57-66)
+    for (unsigned r = 0; r < 2; ++r)
+        for (unsigned c = 0; c < 2; ++c)
+            if (((filters >> ((((r << 1) & 14) + (c & 1)) << 1)) & 3) == 3) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: 4-colour CFA");
+    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_bayer: image %dx%d smaller than 64x64", W, H);
+    return ARTGPU_OK;
+}
+
+int demosaic_bayer_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, int method, uint32_t filters, double initial_gain, int border)
+{
+    return demosaic_bayer_run(ctx, d, W, H, method, filters, initial_gain, border, nullptr);
+}
+
+int demosaic_xtrans_check(artgpu_ctx *ctx, int passes, const int32_t xtrans[36], int W, int H, size_t raw_stride)
+{
     if (passes < 1 || passes > 4) return fail(ctx, ARTGPU_EINVAL, "demosaic_xtrans: passes must be 1..4");
-    const int W = raw->w, H = raw->h;
     if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: image %dx%d smaller than 64x64", W, H);
     int ngreen = 0;
     for (int i = 0; i < 36; ++i) {
@@ -394,13 +427,15 @@ int artgpu_demosaic_xtrans(artgpu_ctx *ctx, int passes, int use_cielab, const ar
         ngreen += xtrans[i] == 1;
     }
     if (ngreen != 20) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: not an X-Trans colour map (%d green of 36)", ngreen);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevImage d;
-    int rc = bind_images(ctx, raw, out, &d);
-    if (rc) return rc;
     // the reference keeps the hexagon offsets in `short` (xtrans_demosaic.cc:233): same range limit here
-    if (2 * (long long)d.raw_stride + 2 > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: row stride %zu exceeds the reference's short offsets", d.raw_stride);
+    if (2 * (long long)raw_stride + 2 > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "demosaic_xtrans: row stride %zu exceeds the reference's short offsets", raw_stride);
+    return ARTGPU_OK;
+}
 
+// RawImageSource::xtrans_interpolate on a bound image, after demosaic_xtrans_check
+int demosaic_xtrans_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, int passes, int use_cielab, const int32_t xtrans[36], const float rgb_cam[12])
+{
+    int rc;
     XtransArgs a = {};
     a.raw = d.raw; a.raw_stride = d.raw_stride;
     a.red = d.r; a.green = d.g; a.blue = d.b; a.out_stride = d.out_stride;
@@ -475,14 +510,7 @@ int artgpu_demosaic_xtrans(artgpu_ctx *ctx, int passes, int use_cielab, const ar
     if (ctx->timing) HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     HIPCHK(ctx, launch_xtrans(a, grid, ctx->stream));
     if (ctx->timing) { HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream)); HIPCHK(ctx, hipEventRecord(ctx->ev[2], ctx->stream)); }
-    rc = unbind_images(ctx, out, &d);
-    if (rc) return rc;
-    if (ctx->timing) {
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev[2]));
-        HIPCHK(ctx, hipEventElapsedTime(&ctx->last.demosaic_ms, ctx->ev[0], ctx->ev[1]));
-        ctx->last.border_ms = 0.f; ctx->last.total_ms = ctx->last.demosaic_ms;
-    }
-    return ARTGPU_OK;
+    return ctx->timing ? demosaic_read_timings(ctx, false) : ARTGPU_OK;
 }
 
-} // extern "C"
+} } // namespace artgpu::api

@@ -511,12 +511,18 @@ int DnRun::merged_pass()
 }
 
 // the checks of RGB_denoise's parameters that the public entry point and the tool share
-int rgb_denoise_args_ok(artgpu_ctx *ctx, const artgpu_denoise_params *p, const float *iws, double scale)
+int rgb_denoise_args_ok(artgpu_ctx *ctx, const artgpu_denoise_params *p, bool has_iws, double scale)
 {
     if (p->color_space != 0 && p->color_space != 1) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: color_space must be 0 (RGB) or 1 (LAB)");
-    if (p->color_space == 1 && !iws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: LAB mode needs the inverse working-space matrix");
+    if (p->color_space == 1 && !has_iws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: LAB mode needs the inverse working-space matrix");
     if (p->chrominance_method != 0 && p->chrominance_method != 1) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: chrominance_method must be 0 (MANUAL) or 1 (AUTOMATIC)");
     if (!(scale >= 1.0)) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: scale must be >= 1");
+    return ARTGPU_OK;
+}
+
+int rgb_denoise_size_ok(artgpu_ctx *ctx, int w, int h)
+{
+    if (w > 32767 || h > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: the reference holds the size in short (FTblockDN.cc:1779)");
     return ARTGPU_OK;
 }
 
@@ -526,14 +532,14 @@ int rgb_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_param
                     double expcomp, double scale, const artgpu_plane *ccalc, uint32_t flags, float *nresi, float *highresi, const DnFusion &fu)
 {
     const int w = d.w, h = d.h;
-    if (w > 32767 || h > 32767) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: the reference holds the size in short (FTblockDN.cc:1779)");
+    int rc = rgb_denoise_size_ok(ctx, w, h);
+    if (rc) return rc;
     if (p->luminance == 0 && p->chrominance == 0 && !ccalc) return ARTGPU_OK; // L1655-1668: nothing to do
     const DnPlan pl = dn_plan(w, h, p, scale, expcomp, flags, nresi || highresi, ccalc != nullptr,
                               ctx->shared.opt_dn_streams, ctx->shared.opt_dn_fused, ctx->shared.opt_dn_detail_plain, ctx->shared.opt_dn_wait_ms, ctx->shared.opt_dn_debug_stall, ctx->shared.opt_dn_mad_fold, ctx->shared.opt_dn_mad_fold_grid);
     if (pl.too_small) return fail(ctx, ARTGPU_EUNSUPPORTED, "rgb_denoise: %dx%d too small for %d wavelet levels on the device path", w, h, pl.levwav);
     DnBuffers b;
-    int rc = dn_buffers(ctx, pl, ccalc, &b);
-    if (rc) return rc;
+    if ((rc = dn_buffers(ctx, pl, ccalc, &b))) return rc;
     if (pl.fork && !ctx->dn_stream[0]) {
         HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->dn_stream[0], hipStreamNonBlocking));
         for (int k = 0; k < 2; ++k) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->dn_ev[k], hipEventDisableTiming));
@@ -658,10 +664,10 @@ bool noise_curve_on(const float *curve)
     return sum > 5.f;
 }
 
-// ImProcFunctions::denoise on device planes; `fu0`: what artgpu_improc_denoise_fused has decided to fuse of the stages around the tool (the
-// tool's own expcomp passes and `ccalc_nonneg` are decided here)
-int improc_denoise_dev(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_tool_params *p, const double ws[9], const double *iws,
-                              double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags, const DnFusion &fu0)
+// ImProcFunctions::denoise on the device image, after denoise_tool_check; `fu0`: what improc_denoise_dev has decided to fuse of the stages around
+// the tool (the tool's own expcomp passes and `ccalc_nonneg` are decided here)
+int denoise_tool_dev(artgpu_ctx *ctx, const DevRGB &d, const artgpu_denoise_tool_params *p, const double ws[9], const double *iws,
+                     double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags, const DnFusion &fu0)
 {
     float wsf[9];
     for (int k = 0; k < 9; ++k) wsf[k] = (float)ws[k];
@@ -686,19 +692,20 @@ int improc_denoise_dev(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_to
     p = &adj;
     artgpu_plane ccalc = {}, *ccalc_p = nullptr;
     if (noise_curve_on(noise_c_curve)) {
-        float *pl[3] = {img->r.p, img->g.p, img->b.p}, *map;
-        if (img->g.row_stride_bytes != img->r.row_stride_bytes || img->b.row_stride_bytes != img->r.row_stride_bytes)
-            return fail(ctx, ARTGPU_EINVAL, "improc_denoise: planes must share one row stride");
-        if ((rc = chroma_map_dev(ctx, pl, (size_t)(img->r.row_stride_bytes / 4), img->r.w, img->r.h, calclum_mat, ws, noise_c_curve, fu0.gi, &map))) return rc;
-        ccalc.p = map; ccalc.w = (img->r.w + 1) / 2; ccalc.h = (img->r.h + 1) / 2; ccalc.row_stride_bytes = (int64_t)ccalc.w * 4; ccalc.on_device = 1;
+        float *map;
+        if ((rc = chroma_map_dev(ctx, d.p, d.stride, d.w, d.h, calclum_mat, ws, noise_c_curve, fu0.gi, &map))) return rc;
+        ccalc = mk_dev_plane(map, (d.w + 1) / 2, (d.h + 1) / 2);
         ccalc_p = &ccalc;
     }
     // expcomp(+ecomp) / expcomp(-ecomp) (ipdenoise.cc:1161-1163,1181-1184) are fused into RGB_denoise's first and last pixel
     // passes when RGB_denoise will actually run them (same operations on the same values, two fewer passes over the image).
-    // (Whether it runs is asked of the ADJUSTED strengths here and of the caller's in artgpu_improc_denoise_fused: both are kept, see there.)
+    // (Whether it runs is asked of the ADJUSTED strengths here and of the caller's in improc_denoise_dev: both are kept, see there.)
     const bool dn_runs = !(p->dn.luminance == 0 && p->dn.chrominance == 0 && !ccalc_p);
     const bool fuse_pre = ecomp > 0 && dn_runs, fuse_post = fuse_pre && !p->smoothing_enabled;
-    if (ecomp > 0 && !fuse_pre) { if ((rc = artgpu_exposure(ctx, img, (float)std::pow(2.0, ecomp), 0.f))) return rc; }
+    if (ecomp > 0 && !fuse_pre) {
+        StageScope scope_(ctx, "ImProcFunctions::expcomp");
+        if ((rc = exposure_dev(ctx, d, (float)std::pow(2.0, ecomp), 0.f))) return rc;
+    }
     DnFusion fu = fu0;
     fu.pre_scale = fuse_pre ? (float)std::pow(2.0, ecomp) : 0.f;
     fu.post_scale = fuse_post ? (float)std::pow(2.0, -ecomp) : 0.f;
@@ -707,10 +714,6 @@ int improc_denoise_dev(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_to
     if (iws) for (int k = 0; k < 9; ++k) iwsf[k] = (float)iws[k];
     {
         StageScope scope_(ctx, "denoise::RGB_denoise");
-        if ((rc = rgb_denoise_args_ok(ctx, &p->dn, iws ? iwsf : nullptr, scale))) return rc;
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        DevRGB d;
-        if ((rc = bind_rgb(ctx, img, 4, true, &d, "rgb_denoise"))) return rc;       // (device planes: nothing is staged)
         if ((rc = rgb_denoise_dev(ctx, d, &p->dn, wsf, iws ? iwsf : nullptr, 0.0, scale, ccalc_p, flags, nullptr, nullptr, fu))) return rc;
     }
     // the exposure steps behind the tool's last stage -- its own expcomp(-ecomp) (L1181-1184) where yuv2rgb could not take it, and the STAGE_1
@@ -720,16 +723,23 @@ int improc_denoise_dev(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_to
     if (ecomp > 0 && !fuse_post) { chain_scale[chain_n] = (float)std::pow(2.0, -ecomp); chain_black[chain_n] = 0.f; ++chain_n; }
     if (fu.tail_on) { chain_scale[chain_n] = fu.tail_scale; chain_black[chain_n] = fu.tail_black; ++chain_n; }
     bool chained = false;
+    PixArgs a = {};
+    for (int k = 0; k < 3; ++k) a.dst[k] = d.p[k];
+    a.dst_stride = d.stride; a.w = d.w; a.h = d.h;
     if (p->smoothing_enabled) {
-        if ((rc = artgpu_denoise_guided_smoothing(ctx, img, ws, p->guided_chroma_radius, scale))) return rc;
+        {
+            StageScope scope_(ctx, "denoise::denoiseGuidedSmoothing");
+            if (p->guided_chroma_radius != 0 && (rc = denoise_guided_smoothing_dev(ctx, d, ws, p->guided_chroma_radius, scale))) return rc;   // ipsmoothing.cc:877-879
+        }
         if (p->nl_strength) {
-            PixArgs a = {};
-            float *pl[3] = {img->r.p, img->g.p, img->b.p};
-            for (int k = 0; k < 3; ++k) { a.dst[k] = pl[k]; a.mul[k] = wsf[3 + k]; }
-            a.dst_stride = (size_t)(img->r.row_stride_bytes / 4); a.w = img->r.w; a.h = img->r.h;
+            for (int k = 0; k < 3; ++k) a.mul[k] = wsf[3 + k];
             a.do_clip = 0;
             HIPCHK(ctx, launch_yuv_mode(a, ctx->stream));
-            if ((rc = artgpu_nlmeans(ctx, &img->g, 65535.f, p->nl_strength, p->nl_detail, (float)scale))) return rc;
+            {
+                StageScope scope_(ctx, "denoise::NLMeans");
+                artgpu_plane y = {d.p[1], d.w, d.h, (int64_t)d.stride * 4, 1};
+                if ((rc = nlm_dev(ctx, &y, 65535.f, p->nl_strength, p->nl_detail, (float)scale))) return rc;
+            }
             a.do_clip = 1;
             a.chain_n = chain_n;
             for (int k = 0; k < chain_n; ++k) { a.chain_scale[k] = chain_scale[k]; a.chain_black[k] = chain_black[k]; }
@@ -738,10 +748,6 @@ int improc_denoise_dev(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_to
         }
     }
     if (chain_n && !chained) {
-        PixArgs a = {};
-        float *pl[3] = {img->r.p, img->g.p, img->b.p};
-        for (int k = 0; k < 3; ++k) a.dst[k] = pl[k];
-        a.dst_stride = (size_t)(img->r.row_stride_bytes / 4); a.w = img->r.w; a.h = img->r.h;
         a.exp_scale = chain_scale[0]; a.black = chain_black[0];
         a.chain_n = chain_n - 1;
         if (chain_n > 1) { a.chain_scale[0] = chain_scale[1]; a.chain_black[0] = chain_black[1]; }
@@ -761,7 +767,7 @@ int artgpu_rgb_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_denoise_pa
     StageScope scope_(ctx, "denoise::RGB_denoise");
     if (!ctx) return ARTGPU_EINVAL;
     if (!img || !p || !ws) return fail(ctx, ARTGPU_EINVAL, "rgb_denoise: null argument");
-    int rc = rgb_denoise_args_ok(ctx, p, iws, scale);
+    int rc = rgb_denoise_args_ok(ctx, p, iws != nullptr, scale);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
@@ -798,13 +804,31 @@ int artgpu_denoise_compute_params(artgpu_ctx *ctx, const artgpu_rgb *planes, int
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB src;
-    int rc = bind_rgb(ctx, planes, 1, true, &src, "denoise_compute_params(planes)");
-    if (rc) return rc;
+    int rc;
+    if ((rc = bind_rgb(ctx, planes, 1, true, &src, "denoise_compute_params(planes)")) || (rc = dn_compute_params_check(ctx, src.w, src.h, border))) return rc;
+    return dn_compute_params_dev(ctx, src, border, mul, do_clip, cam_to_work, ws, chrominance_auto_factor, store, dn);
+}
+
+} // extern "C"
+
+namespace artgpu { namespace api {
+
+int dn_compute_params_check(artgpu_ctx *ctx, int W, int H, int border)
+{
     if (border < 0) return fail(ctx, ARTGPU_EINVAL, "denoise_compute_params: border %d", border);
-    const int widIm = src.w - 2 * border, heiIm = src.h - 2 * border;       // getFullSize
-    const int crW = widIm / 2, crH = heiIm / 2;                              // Tile_calc returns one tile: tileWskip = widIm (L836,875-876)
+    const int widIm = W - 2 * border, heiIm = H - 2 * border;       // getFullSize
     if (widIm < 100 || heiIm < 100)
         return fail(ctx, ARTGPU_EUNSUPPORTED, "denoise_compute_params: %dx%d is too small for the nine-crop layout (crops start 50 px in)", widIm, heiIm);
+    return ARTGPU_OK;
+}
+
+// denoiseComputeParams with an empty store and AUTOMATIC chroma (ipdenoise.cc:810-1010), after dn_compute_params_check
+int dn_compute_params_dev(artgpu_ctx *ctx, const DevRGB &src, int border, const float mul[3], int do_clip, const double cam_to_work[9], const double ws[9],
+                          double chrominance_auto_factor, artgpu_denoise_info_store *store, artgpu_denoise_params *dn)
+{
+    int rc;
+    const int widIm = src.w - 2 * border, heiIm = src.h - 2 * border;       // getFullSize
+    const int crW = widIm / 2, crH = heiIm / 2;                              // Tile_calc returns one tile: tileWskip = widIm (L836,875-876)
     const int coordW[3] = {50, widIm / 2 - crW / 2, widIm - crW - 50}, coordH[3] = {50, heiIm / 2 - crH / 2, heiIm - crH - 50};
     const int wid = (crW + 1) / 2, hei = (crH + 1) / 2, levwav = 5, nsub = 3 * levwav;   // levwav = max(2, 5 - ceil(log(1)))
     const size_t n = (size_t)crW * crH, n2 = (size_t)wid * hei;
@@ -887,6 +911,59 @@ int artgpu_denoise_compute_params(artgpu_ctx *ctx, const artgpu_rgb *planes, int
     return ARTGPU_OK;
 }
 
+int denoise_tool_check(artgpu_ctx *ctx, int w, int h, const artgpu_denoise_tool_params *p, const double *iws, double scale)
+{
+    int rc;
+    if ((rc = rgb_denoise_args_ok(ctx, &p->dn, iws != nullptr, scale))) return rc;
+    if ((rc = rgb_denoise_size_ok(ctx, w, h))) return rc;
+    if (!p->smoothing_enabled) return ARTGPU_OK;
+    if (p->guided_chroma_radius != 0 && (rc = denoise_guided_smoothing_check(ctx, w, h, p->guided_chroma_radius, scale))) return rc;
+    return p->nl_strength ? nlm_check(ctx, w, h) : ARTGPU_OK;
+}
+
+int improc_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const DevRGB *dem, const artgpu_denoise_fusion *fu, bool fuse_ok, const artgpu_denoise_tool_params *p,
+                       const double ws[9], const double *iws, double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags)
+{
+    // what of the neighbouring stages can really live inside the tool's pixel passes: the wavelet denoise has to run (its first pass reads the
+    // image, its last one writes it), on device planes; the exposure only when nothing stands between RGB_denoise and it.
+    // `dn_runs0` asks the caller's strengths, denoise_tool_dev's `dn_runs` the ones adjust_params has scaled.  adjust_params maps 0 to 0 and
+    // any other strength to another one of the same sign, so the two agree for every strength and scale a caller can mean; they part only
+    // where the arithmetic underflows (a denormal strength, an infinite scale).  Both are kept as they were.
+    const bool dn_runs0 = !(p->dn.luminance == 0 && p->dn.chrominance == 0 && !noise_curve_on(noise_c_curve));
+    const bool fuse_gi = dem && dn_runs0 && fuse_ok;
+    const bool fuse_exp = fu && fu->exposure_enabled && dn_runs0 && fuse_ok && !p->smoothing_enabled;
+    // with guided smoothing / NL-means behind the wavelet denoise the tool's last pixel pass is setMode(RGB) or its own expcomp(-ecomp):
+    // the exposure rides on that one
+    const bool tail_exp = fu && fu->exposure_enabled && dn_runs0 && fuse_ok && p->smoothing_enabled && (p->nl_strength || ecomp > 0);
+    int rc;
+    DnFusion f = {};
+    if (fuse_gi) {
+        GetImageFuse &g = f.gi;
+        g.on = 1;
+        for (int k = 0; k < 3; ++k) { g.src[k] = dem->p[k]; g.mul[k] = fu->mul[k]; }
+        g.stride = dem->stride;
+        g.sx1 = fu->sx1; g.sy1 = fu->sy1;
+        g.do_clip = fu->do_clip ? 1 : 0; g.has_mat = fu->cam_to_work ? 1 : 0;
+        for (int k = 0; k < 9; ++k) g.mat[k] = fu->cam_to_work ? fu->cam_to_work[k] : 0.0;
+    } else if (dem) {                                          // the separate pass it stands for
+        StageScope scope_(ctx, "RawImageSource::getImage");
+        if ((rc = get_image_dev(ctx, *dem, d, fu->sx1, fu->sy1, 1, fu->mul, fu->do_clip, fu->cam_to_work))) return rc;
+    }
+    if (fuse_exp) { f.exp_on = 1; f.exp_scale = fu->exp_scale; f.exp_black = fu->black; }
+    if (tail_exp) { f.tail_on = 1; f.tail_scale = fu->exp_scale; f.tail_black = fu->black; }
+    if ((rc = denoise_tool_dev(ctx, d, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags, f))) return rc;
+    // the exposure that could not be fused follows as its own pass
+    if (fu && fu->exposure_enabled && !fuse_exp && !tail_exp) {
+        StageScope scope_(ctx, "ImProcFunctions::expcomp");
+        return exposure_dev(ctx, d, fu->exp_scale, fu->black);
+    }
+    return ARTGPU_OK;
+}
+
+} } // namespace artgpu::api
+
+extern "C" {
+
 int artgpu_denoise_chroma_map(artgpu_ctx *ctx, const artgpu_rgb *img, const double *calclum_mat, const double ws[9],
                               const float noise_c_curve[501], artgpu_plane *ccalc)
 {
@@ -918,47 +995,20 @@ int artgpu_improc_denoise_fused(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_d
     StageScope scope_(ctx, "ImProcFunctions::denoise");
     if (!ctx) return ARTGPU_EINVAL;
     if (!img || !p || !ws) return fail(ctx, ARTGPU_EINVAL, "improc_denoise: null argument");
-    // what of the neighbouring stages can really live inside the tool's pixel passes: the wavelet denoise has to run (its first pass reads the
-    // image, its last one writes it), on device planes; the exposure only when nothing stands between RGB_denoise and it.
-    // `dn_runs0` asks the caller's strengths, improc_denoise_dev's `dn_runs` the ones adjust_params has scaled.  adjust_params maps 0 to 0 and
-    // any other strength to another one of the same sign, so the two agree for every strength and scale a caller can mean; they part only
-    // where the arithmetic underflows (a denormal strength, an infinite scale).  Both are kept as they were.
-    const bool dn_runs0 = !(p->dn.luminance == 0 && p->dn.chrominance == 0 && !noise_curve_on(noise_c_curve));
-    const bool dev_planes = img->r.on_device && (!fu || !fu->demosaiced || (fu->demosaiced->r.on_device && fu->demosaiced->g.on_device && fu->demosaiced->b.on_device));
-    const bool fuse_gi = fu && fu->demosaiced && dn_runs0 && dev_planes;
-    const bool fuse_exp = fu && fu->exposure_enabled && dn_runs0 && dev_planes && !p->smoothing_enabled;
-    // with guided smoothing / NL-means behind the wavelet denoise the tool's last pixel pass is setMode(RGB) or its own expcomp(-ecomp):
-    // the exposure rides on that one
-    const bool tail_exp = fu && fu->exposure_enabled && dn_runs0 && dev_planes && p->smoothing_enabled && (p->nl_strength || ecomp > 0);
+    const artgpu_rgb *dm = fu ? fu->demosaiced : nullptr;
+    if (dm && (!plane_ok(&dm->r) || !plane_ok(&dm->g) || !plane_ok(&dm->b) || dm->g.row_stride_bytes != dm->r.row_stride_bytes || dm->b.row_stride_bytes != dm->r.row_stride_bytes ||
+               fu->sx1 < 0 || fu->sy1 < 0 || fu->sx1 + img->r.w > dm->r.w || fu->sy1 + img->r.h > dm->r.h))
+        return fail(ctx, ARTGPU_EINVAL, "improc_denoise_fused: crop %dx%d+%d+%d outside the demosaiced planes", img->r.w, img->r.h, fu->sx1, fu->sy1);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // host planes: stage once (the image itself unless getImage is about to write it), run the whole tool on the staged copy, copy back; device
+    // planes are used in place
+    const bool fuse_ok = img->r.on_device && (!dm || (dm->r.on_device && dm->g.on_device && dm->b.on_device));
+    DevRGB d, dem;
     int rc;
-    DnFusion f = {};
-    if (fu && fu->demosaiced) {
-        const artgpu_rgb *dm = fu->demosaiced;
-        if (!plane_ok(&dm->r) || !plane_ok(&dm->g) || !plane_ok(&dm->b) || dm->g.row_stride_bytes != dm->r.row_stride_bytes || dm->b.row_stride_bytes != dm->r.row_stride_bytes ||
-            fu->sx1 < 0 || fu->sy1 < 0 || fu->sx1 + img->r.w > dm->r.w || fu->sy1 + img->r.h > dm->r.h)
-            return fail(ctx, ARTGPU_EINVAL, "improc_denoise_fused: crop %dx%d+%d+%d outside the demosaiced planes", img->r.w, img->r.h, fu->sx1, fu->sy1);
-        if (fuse_gi) {
-            GetImageFuse &g = f.gi;
-            g.on = 1;
-            g.src[0] = dm->r.p; g.src[1] = dm->g.p; g.src[2] = dm->b.p;
-            g.stride = (size_t)(dm->r.row_stride_bytes / 4);
-            g.sx1 = fu->sx1; g.sy1 = fu->sy1;
-            for (int k = 0; k < 3; ++k) g.mul[k] = fu->mul[k];
-            g.do_clip = fu->do_clip ? 1 : 0; g.has_mat = fu->cam_to_work ? 1 : 0;
-            for (int k = 0; k < 9; ++k) g.mat[k] = fu->cam_to_work ? fu->cam_to_work[k] : 0.0;
-        } else if ((rc = artgpu_get_image(ctx, dm, fu->sx1, fu->sy1, fu->mul, fu->do_clip, fu->cam_to_work, img))) {     // the separate call it stands for
-            return rc;
-        }
-    }
-    if (fuse_exp) { f.exp_on = 1; f.exp_scale = fu->exp_scale; f.exp_black = fu->black; }
-    if (tail_exp) { f.tail_on = 1; f.tail_scale = fu->exp_scale; f.tail_black = fu->black; }
-    // host planes: stage once, run the whole tool on the staged copy, copy back (device planes are used in place)
-    DevRGB d;
-    if ((rc = bind_rgb(ctx, img, 4, true, &d, "improc_denoise"))) return rc;
-    artgpu_rgb dv = mk_dev_rgb(d.p, d.w, d.h, d.stride);
-    if ((rc = improc_denoise_dev(ctx, &dv, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags, f))) return rc;
-    // the exposure that could not be fused follows as its own call
-    if (fu && fu->exposure_enabled && !fuse_exp && !tail_exp && (rc = artgpu_exposure(ctx, &dv, fu->exp_scale, fu->black))) return rc;
+    if ((dm && (rc = bind_rgb(ctx, dm, 1, true, &dem, "get_image(planes)"))) || (rc = bind_rgb(ctx, img, 4, !dm, &d, "improc_denoise")) ||
+        (rc = denoise_tool_check(ctx, d.w, d.h, p, iws, scale)) ||
+        (rc = improc_denoise_dev(ctx, d, dm ? &dem : nullptr, fu, fuse_ok, p, ws, iws, ecomp, scale, calclum_mat, noise_c_curve, flags)))
+        return rc;
     return unbind_rgb(ctx, img, &d);
 }
 

@@ -167,8 +167,16 @@ int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float 
     return gaussian_dev(ctx, mask, scratch, W, H, blur);
 }
 
+int nlm_check(artgpu_ctx *ctx, int W, int H)
+{
+    if (W < 32 || H < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image smaller than 32x32");
+    // (the tile kernel addresses a plane through 32-bit byte offsets)
+    if ((unsigned long long)(W + 14) * (unsigned long long)(H + 14) >= (1ull << 30)) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image of %dx%d exceeds 2^30 pixels", W, H);
+    return ARTGPU_OK;
+}
+
 // denoise::NLMeans (nlmeans.cc:44-320) on a contiguous device plane (rows of W floats), in place; enqueued on ctx->stream.  The caller has checked
-// strength != 0, W, H >= 32, (W + 14) * (H + 14) < 2^30 and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
+// strength != 0, nlm_check and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
 int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, int strength, int detail_thresh, float scale)
 {
     NlmArgs a = {};
@@ -194,6 +202,60 @@ int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, i
     return ARTGPU_OK;
 }
 
+// ... on any plane, after nlm_check
+int nlm_dev(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int strength, int detail_thresh, float scale)
+{
+    const int W = img->w, H = img->h;
+    float *work;
+    // a contiguous device plane is worked on where it lies (the kernels read the padded copy `pad` and the mask, and write the plane): two plane
+    // copies less per call, 0.16 ms of a 45 MP frame; anything else goes through a contiguous working copy
+    const bool in_place = img->on_device && img->row_stride_bytes == (int64_t)W * 4;
+    int rc = ARTGPU_OK;
+    if (in_place) work = img->p;
+    else if ((rc = plane_to_pool(ctx, img, P_SF, &work))) return rc;
+    if ((rc = nlm_plane_dev(ctx, work, W, H, normcoeff, strength, detail_thresh, scale))) return rc;
+    return in_place ? ARTGPU_OK : pool_to_plane(ctx, work, img);
+}
+
+// the radius the guided chroma smoothing works with at `scale`: rounded, never negative
+static int dgs_radius(int guided_chroma_radius, double scale)
+{
+    const int r = (int)std::round(guided_chroma_radius / scale);
+    return r > 0 ? r : 0;
+}
+
+int denoise_guided_smoothing_check(artgpu_ctx *ctx, int W, int H, int guided_chroma_radius, double scale)
+{
+    const int r = dgs_radius(guided_chroma_radius, scale);
+    const GfGrid grid = gf_grid(W, H, r);
+    if (r == 0 || grid.w < 8 || grid.h < 8) return fail(ctx, ARTGPU_EUNSUPPORTED, "denoise_guided_smoothing: radius/scale combination not on the device path");
+    return ARTGPU_OK;
+}
+
+int denoise_guided_smoothing_dev(artgpu_ctx *ctx, const DevRGB &d, const double ws[9], int guided_chroma_radius, double scale)
+{
+    const int W = d.w, H = d.h;
+    int rc;
+    GuidedArgs g = {};
+    for (int k = 0; k < 3; ++k) { g.rgb[k] = d.p[k]; g.ws1[k] = ws[3 + k]; }
+    g.stride = d.stride; g.W = W; g.H = H; g.epsilon = 0.001f;
+    const GfGrid grid = gf_grid(W, H, dgs_radius(guided_chroma_radius, scale));
+    g.w = grid.w; g.h = grid.h;
+    const size_t n = (size_t)W * H, nl = (size_t)g.w * g.h;
+    float *big, *low, *tmp;
+    if ((rc = pool_get(ctx, P_SF, 7 * n * 4, &big)) || (rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
+    for (int k = 0; k < 3; ++k) { g.in[k] = big + k * n; g.chan[k] = big + (3 + k) * n; }
+    g.guide = big + 6 * n;
+    for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
+    HIPCHK(ctx, launch_gf_prepare(g, ctx->stream));
+    HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
+    if ((rc = box_blur_planes(ctx, low, tmp, 8, nl, g.w, g.h, grid.rad))) return rc;              // meanI, corrI, meanp[3], corrIp[3]
+    HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
+    if ((rc = box_blur_planes(ctx, low + 2 * nl, tmp, 6, nl, g.w, g.h, grid.rad))) return rc;     // mean a[3], mean b[3]
+    HIPCHK(ctx, launch_gf_finish(g, ctx->stream));
+    return ARTGPU_OK;
+}
+
 } } // namespace artgpu::api
 
 extern "C" {
@@ -209,29 +271,10 @@ int artgpu_denoise_guided_smoothing(artgpu_ctx *ctx, artgpu_rgb *img, const doub
     if (guided_chroma_radius == 0) return ARTGPU_OK;   // ipsmoothing.cc:877-879
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
-    int rc = bind_rgb(ctx, img, 4, true, &d, "denoise_guided_smoothing");
-    if (rc) return rc;
-    const int W = d.w, H = d.h;
-    int r = (int)std::round(guided_chroma_radius / scale);
-    r = r > 0 ? r : 0;
-    GuidedArgs g = {};
-    for (int k = 0; k < 3; ++k) { g.rgb[k] = d.p[k]; g.ws1[k] = ws[3 + k]; }
-    g.stride = d.stride; g.W = W; g.H = H; g.epsilon = 0.001f;
-    const GfGrid grid = gf_grid(W, H, r);
-    g.w = grid.w; g.h = grid.h;
-    if (r == 0 || g.w < 8 || g.h < 8) return fail(ctx, ARTGPU_EUNSUPPORTED, "denoise_guided_smoothing: radius/scale combination not on the device path");
-    const size_t n = (size_t)W * H, nl = (size_t)g.w * g.h;
-    float *big, *low, *tmp;
-    if ((rc = pool_get(ctx, P_SF, 7 * n * 4, &big)) || (rc = pool_get(ctx, P_TMP, 8 * nl * 4, &low)) || (rc = pool_get(ctx, P_LIN, 8 * nl * 4, &tmp))) return rc;
-    for (int k = 0; k < 3; ++k) { g.in[k] = big + k * n; g.chan[k] = big + (3 + k) * n; }
-    g.guide = big + 6 * n;
-    for (int k = 0; k < 8; ++k) g.low[k] = low + k * nl;
-    HIPCHK(ctx, launch_gf_prepare(g, ctx->stream));
-    HIPCHK(ctx, launch_gf_subsample(g, ctx->stream));
-    if ((rc = box_blur_planes(ctx, low, tmp, 8, nl, g.w, g.h, grid.rad))) return rc;              // meanI, corrI, meanp[3], corrIp[3]
-    HIPCHK(ctx, launch_gf_ab(g, ctx->stream));
-    if ((rc = box_blur_planes(ctx, low + 2 * nl, tmp, 6, nl, g.w, g.h, grid.rad))) return rc;     // mean a[3], mean b[3]
-    HIPCHK(ctx, launch_gf_finish(g, ctx->stream));
+    int rc;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "denoise_guided_smoothing")) || (rc = denoise_guided_smoothing_check(ctx, d.w, d.h, guided_chroma_radius, scale)) ||
+        (rc = denoise_guided_smoothing_dev(ctx, d, ws, guided_chroma_radius, scale)))
+        return rc;
     return unbind_rgb(ctx, img, &d);
 }
 
@@ -294,20 +337,10 @@ int artgpu_nlmeans(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int stre
     if (!ctx) return ARTGPU_EINVAL;
     if (!plane_ok(img) || !(scale >= 1.f)) return fail(ctx, ARTGPU_EINVAL, "nlmeans: bad arguments");
     if (!strength) return ARTGPU_OK;                       // nlmeans.cc:52-54
-    if (img->w < 32 || img->h < 32) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image smaller than 32x32");
-    // (the tile kernel addresses a plane through 32-bit byte offsets)
-    if ((unsigned long long)(img->w + 14) * (unsigned long long)(img->h + 14) >= (1ull << 30)) return fail(ctx, ARTGPU_EUNSUPPORTED, "nlmeans: image of %dx%d exceeds 2^30 pixels", img->w, img->h);
+    int rc = nlm_check(ctx, img->w, img->h);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int W = img->w, H = img->h;
-    float *work;
-    // a contiguous device plane is worked on where it lies (the kernels read the padded copy `pad` and the mask, and write the plane): two plane
-    // copies less per call, 0.16 ms of a 45 MP frame; anything else goes through a contiguous working copy
-    const bool in_place = img->on_device && img->row_stride_bytes == (int64_t)W * 4;
-    int rc = ARTGPU_OK;
-    if (in_place) work = img->p;
-    else if ((rc = plane_to_pool(ctx, img, P_SF, &work))) return rc;
-    if ((rc = nlm_plane_dev(ctx, work, W, H, normcoeff, strength, detail_thresh, scale))) return rc;
-    return in_place ? ARTGPU_OK : pool_to_plane(ctx, work, img);
+    return nlm_dev(ctx, img, normcoeff, strength, detail_thresh, scale);
 }
 
 } // extern "C"

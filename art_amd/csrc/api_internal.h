@@ -5,7 +5,7 @@
 // dynamic symbol table, and no namespace opening has to say so: every translation unit is compiled with hidden visibility, and
 // nothing is exported unless include/artgpu.h declares it.  Each is defined once (the helpers in artgpu_api.hip; every stage in the
 // api_<stage>.hip named after its kernel file, the demosaicers in api_demosaic.hip, the shared filters in api_filters.hip, the pixel passes
-// in api_pixelops.hip; api_denoise.hip exposes nothing); none is inline.
+// in api_pixelops.hip); none is inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -207,7 +207,7 @@ struct DevImage {
     float *r, *g, *b; size_t out_stride;
     bool staged;
 };
-int bind_images(artgpu_ctx *ctx, const artgpu_plane *raw, artgpu_rgb *out, DevImage *d);
+int bind_images(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_rgb *out, DevImage *d);
 int unbind_images(artgpu_ctx *ctx, artgpu_rgb *out, const DevImage *d);
 
 // Generic RGB image binding: device planes are used in place, host planes are staged through
@@ -385,9 +385,41 @@ int const_table_dev(artgpu_ctx *ctx, int slot, size_t nfloats, void (*fill)(floa
 // Color::cachef / cachefy / denoiseGammaTab / denoiseIGammaTab, built on the host like the reference's (color.cc:202-292), in P_LABTABS
 int lab_tabs_dev(artgpu_ctx *ctx, float **tabs_out);
 
-// api_pixelops.hip
+// api_pixelops.hip: each *_dev is one launch on ctx->stream; the *_check beside it is every reason not to run, and launches nothing
+// RawImageSource::getImage + the matrix branch of convertColorSpace: `dst` from the window of `src` at (sx1, sy1), every skip-th pixel
+int get_image_dev(artgpu_ctx *ctx, const DevRGB &src, const DevRGB &dst, int sx1, int sy1, int skip, const float mul[3], int do_clip, const double *mat);
+int exposure_dev(artgpu_ctx *ctx, const DevRGB &d, float exp_scale, float black);
+int tone_curve_check(artgpu_ctx *ctx, int mode, float whitept);
+int tone_curve_dev(artgpu_ctx *ctx, const DevRGB &d, const float *lut65536, float whitept, int filmlike_clip);
+int tone_neutral_check(artgpu_ctx *ctx, const float *lut65536, float whitecoeff);
+int tone_neutral_dev(artgpu_ctx *ctx, const DevRGB &d, const float *lut65536, float whitecoeff, const artgpu_neutral_state *st);
 // Imagefloat::setMode(LAB) / (RGB) on device planes
 int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab);
+// scaleColors' ScaleArgs but for the buffers: the size, the 6x6 colour map (xtrans, or the Bayer word `filters` when it is null; a fourth
+// colour is refused under `who`), black levels and multipliers
+int scale_args_fill(artgpu_ctx *ctx, int w, int h, int src_is_u16, uint32_t filters, const int32_t *xtrans, const float cblacksom[4], const float scale_mul[4],
+                    const char *who, ScaleArgs *a);
+
+// api_demosaic.hip: the checks are what the entry points refuse about method, gain, colour map and size (raw_stride: the CFA plane's row in
+// floats as bind_images will produce it); the *_dev run on a bound image and keep the timing events beside the launches they time
+int demosaic_bayer_check(artgpu_ctx *ctx, int method, uint32_t filters, double initial_gain, int W, int H);
+int demosaic_bayer_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, int method, uint32_t filters, double initial_gain, int border);
+int demosaic_xtrans_check(artgpu_ctx *ctx, int passes, const int32_t xtrans[36], int W, int H, size_t raw_stride);
+int demosaic_xtrans_dev(artgpu_ctx *ctx, const DevImage &d, int W, int H, int passes, int use_cielab, const int32_t xtrans[36], const float rgb_cam[12]);
+
+// api_denoise.hip
+// denoiseComputeParams' nine-crop layout on W x H planes behind `border` (the 100 px rule); the estimate itself, which ends in the host wait its result needs
+int dn_compute_params_check(artgpu_ctx *ctx, int W, int H, int border);
+int dn_compute_params_dev(artgpu_ctx *ctx, const DevRGB &src, int border, const float mul[3], int do_clip, const double cam_to_work[9], const double ws[9],
+                          double chrominance_auto_factor, artgpu_denoise_info_store *store, artgpu_denoise_params *dn);
+// every reason ImProcFunctions::denoise has not to run on a w x h image: RGB_denoise's parameters and size, and with smoothing_enabled the
+// limits of the guided chroma smoothing and of NL-means behind it
+int denoise_tool_check(artgpu_ctx *ctx, int w, int h, const artgpu_denoise_tool_params *p, const double *iws, double scale);
+// the tool on the device image `d`, after denoise_tool_check.  fu: what artgpu_improc_denoise_fused may fuse of the stages around it (null: nothing;
+// its `demosaiced` is not read: `dem` is those planes, bound, or null); fuse_ok: the caller's planes were on the device (a staged copy keeps the
+// separate passes it always had)
+int improc_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const DevRGB *dem, const artgpu_denoise_fusion *fu, bool fuse_ok, const artgpu_denoise_tool_params *p,
+                       const double ws[9], const double *iws, double ecomp, double scale, const double *calclum_mat, const float *noise_c_curve, uint32_t flags);
 
 // api_wavelet.hip
 int wavelet_skip(int level);
@@ -408,8 +440,15 @@ int gaussian_dev(artgpu_ctx *ctx, float *img, float *tmp, int W, int H, double s
 int detail_mask_dev(artgpu_ctx *ctx, const float *src, size_t src_stride, float *mask, int W, int H,
                     float scaling, float threshold, float ceiling, float factor, float blur, float *scratch /* >= W*H + 2*(W/4)*(H/4) */);
 // denoise::NLMeans (nlmeans.cc:44-320) on a contiguous device plane (rows of W floats), in place; enqueued on ctx->stream.  The caller has checked
-// strength != 0, W, H >= 32, (W + 14) * (H + 14) < 2^30 and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
+// strength != 0, nlm_check and scale >= 1.  Scratch: P_TMP, P_LIN, P_BLOCKS
+int nlm_check(artgpu_ctx *ctx, int W, int H);                 // W, H >= 32, (W + 14) * (H + 14) < 2^30
 int nlm_plane_dev(artgpu_ctx *ctx, float *work, int W, int H, float normcoeff, int strength, int detail_thresh, float scale);
+// ... on any plane (host, or device rows with padding: through a contiguous working copy in P_SF)
+int nlm_dev(artgpu_ctx *ctx, artgpu_plane *img, float normcoeff, int strength, int detail_thresh, float scale);
+// denoise::denoiseGuidedSmoothing (ipsmoothing.cc:875) for a radius that is not 0 and scale >= 1: the radius / scale combinations the device path has
+// not, and the filter on the device image.  Scratch: P_SF, P_TMP, P_LIN
+int denoise_guided_smoothing_check(artgpu_ctx *ctx, int W, int H, int guided_chroma_radius, double scale);
+int denoise_guided_smoothing_dev(artgpu_ctx *ctx, const DevRGB &d, const double ws[9], int guided_chroma_radius, double scale);
 
 // api_colorcorrection.hip
 // the PQ tables of Color::init (P_PQ: forward, inverse, then the NEUTRAL curve's four hue anchors, which belong to the tables' lifetime)

@@ -66,13 +66,19 @@ bool pipeline_ca(const artgpu_pipeline_params *p)
 {
     return p->ca_enabled && (p->ca.autocorrect || fabs(p->ca.red) > 0.001 || fabs(p->ca.blue) > 0.001) && p->sensor == 0;
 }
+// what the CA correction of a frame refuses (cfa: the pattern as ca_correct_dev takes it)
+static int pipeline_ca_check(artgpu_ctx *ctx, int W, int H, const artgpu_pipeline_params *p, unsigned *cfa)
+{
+    if (!ca_cfa(p->filters, cfa)) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on RGB Bayer patterns only (filters 0x%08x)", p->filters);
+    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on a frame smaller than 64x64");
+    return ARTGPU_OK;
+}
 // CA correction of the CFA plane `raw` (device, rows of `stride` floats) in place, ahead of the demosaic
 int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, const artgpu_pipeline_params *p)
 {
     unsigned cfa;
-    if (!ca_cfa(p->filters, &cfa)) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on RGB Bayer patterns only (filters 0x%08x)", p->filters);
-    if (W < 64 || H < 64) return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline: CA correction on a frame smaller than 64x64");
-    return ca_correct_dev(ctx, raw, stride, W, H, cfa, &p->ca, nullptr);
+    const int rc = pipeline_ca_check(ctx, W, H, p, &cfa);
+    return rc ? rc : ca_correct_dev(ctx, raw, stride, W, H, cfa, &p->ca, nullptr);
 }
 
 } } // namespace artgpu::api
@@ -107,9 +113,9 @@ struct PipePlan {
     std::vector<TbPlan> tb;
 };
 // What the stages hand on: the CFA plane the demosaic reads (the caller's, or its CA-corrected copy in the pool), the demosaiced W x H planes in the
-// pool, the w x h image the later stages work on (the caller's planes if they are on the device, else a staged copy) as launchers / entry points take it
-// (with the Resize tool: planes of the pool, and `small` is the caller's imw x imh image the resampler writes)
-struct PipeFrame { artgpu_plane raw; artgpu_rgb dem; DevRGB d; artgpu_rgb img; DevRGB small; };
+// pool, the w x h image the later stages work on (the caller's planes if they are on the device, else a staged copy; with the Resize tool: planes of
+// the pool, and `small` is the caller's imw x imh image the resampler writes)
+struct PipeFrame { artgpu_plane raw; DevRGB dem; DevRGB d; DevRGB small; };
 
 // the MkPlan of n regions whose masks the pipe generates on its own image (mode: ARTGPU_MASKS_MODE_LAB or _RGB; full size, no crop)
 static int pipe_plan_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, int mode, const artgpu_mask_params *masks, int n, bool want_ab, const char *who, MkPlan *mk)
@@ -137,7 +143,12 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
 //   8. dehaze_check, te_check, fs_check, fg_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
-static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, PipePlan *pl)
+//   then the oldest stages in the order they run:   11. the CA correction's pattern and size (do_ca), demosaic_bayer_check / demosaic_xtrans_check
+//   12. dn_compute_params_check (AUTOMATIC chroma)   13. denoise_tool_check   14. tone_curve_check / tone_neutral_check
+// What is left to the stages is a refusal that depends on a number computed on the device: the automatic sharpening radius (pipe_stage2).  RGB_denoise's
+// "too small for n wavelet levels" is not one: dn_plan caps the levels by the smaller side (maxlev2), and for every cap the side already holds them
+// (levels 8 / 7 / 6 / 5 / 4 / 3 need a side of 255 / 127 / 63 / 31 / 15 / 7), so it fires for w or h under 8 alone, which check 1 has refused.
+static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, const artgpu_rgb *out, bool do_ca, PipePlan *pl)
 {
     if (!ctx) return ARTGPU_EINVAL;
     if (!plane_ok(raw_in) || !p || !out) return fail(ctx, ARTGPU_EINVAL, "pipeline_run: null/bad argument");
@@ -224,7 +235,18 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     }
     pl->sh_radius_pending = pl->sh_auto && !pl->sharpen.early;
     if (pl->tb_on && (rc = tb_check(ctx, w, h, pl->tb_regions, ntb, p->ws, scale, 1, "pipeline_run(texture boost)", &pl->tb))) return rc;
-    return ARTGPU_OK;
+    unsigned cfa;
+    if (do_ca && pipeline_ca(p) && (rc = pipeline_ca_check(ctx, pl->W, pl->H, p, &cfa))) return rc;
+    // (X-Trans: no CA correction, so the demosaic reads the caller's plane: a device plane's own rows, a staged host plane's dense ones)
+    if (p->sensor == 0) rc = demosaic_bayer_check(ctx, p->bayer_method, p->filters, p->initial_gain, pl->W, pl->H);
+    else rc = demosaic_xtrans_check(ctx, p->xtrans_passes, p->xtrans, pl->W, pl->H, raw_in->on_device ? (size_t)(raw_in->row_stride_bytes / 4) : (size_t)pl->W);
+    if (rc) return rc;
+    if (p->denoise_enabled) {
+        if (p->denoise.dn.chrominance_method == 1 && (rc = dn_compute_params_check(ctx, pl->W, pl->H, b))) return rc;
+        if ((rc = denoise_tool_check(ctx, w, h, &p->denoise, p->iws, scale))) return rc;
+    }
+    if (p->tone_enabled && p->tone_mode == ARTGPU_TONE_NEUTRAL) return tone_neutral_check(ctx, p->tone_lut, p->white_point);
+    return p->tone_enabled ? tone_curve_check(ctx, p->tone_mode, p->white_point) : ARTGPU_OK;
 }
 
 // The raw side: RawImageSource::CA_correct_RT between scaleColors and the demosaic, on a device copy (the caller's raw is never written), and
@@ -265,9 +287,17 @@ static int pipe_demosaic(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const
     int rc;
     for (int k = 0; k < 3; ++k)
         if ((rc = pool_get(ctx, P_PIPE_R + k, (size_t)pl.W * pl.H * 4, &dp[k]))) return rc;
-    fr->dem = mk_dev_rgb(dp, pl.W, pl.H, pl.W);
-    if (p->sensor == 0) rc = artgpu_demosaic_bayer(ctx, p->bayer_method, &fr->raw, p->filters, p->initial_gain, pl.b, &fr->dem);
-    else rc = artgpu_demosaic_xtrans(ctx, p->xtrans_passes, p->xtrans_passes > 1 ? 1 : 0, &fr->raw, p->xtrans, p->rgb_cam, &fr->dem);
+    fr->dem = DevRGB{{dp[0], dp[1], dp[2]}, (size_t)pl.W, pl.W, pl.H, false};
+    const artgpu_rgb dem = mk_dev_rgb(dp, pl.W, pl.H, pl.W);
+    DevImage di;                   // (a host CFA plane is staged here)
+    if ((rc = bind_images(ctx, &fr->raw, &dem, &di))) return rc;
+    if (p->sensor == 0) {
+        StageScope scope_(ctx, "RawImageSource::demosaic (Bayer)");
+        rc = demosaic_bayer_dev(ctx, di, pl.W, pl.H, p->bayer_method, p->filters, p->initial_gain, pl.b);
+    } else {
+        StageScope scope_(ctx, "RawImageSource::xtrans_interpolate");
+        rc = demosaic_xtrans_dev(ctx, di, pl.W, pl.H, p->xtrans_passes, p->xtrans_passes > 1 ? 1 : 0, p->xtrans, p->rgb_cam);
+    }
     if (rc) return rc;
     if (pl.rs_on) {
         // the full-size working image cannot be the caller's planes: they have the size the resampler writes
@@ -276,7 +306,6 @@ static int pipe_demosaic(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const
             if ((rc = pool_get(ctx, P_RS_IMG0 + k, (size_t)pl.w * pl.h * 4, &fr->d.p[k]))) return rc;
         fr->d.stride = pl.w; fr->d.w = pl.w; fr->d.h = pl.h; fr->d.staged = false;
     } else if ((rc = bind_rgb(ctx, out, 4, false, &fr->d, "pipeline_run(out)"))) return rc;
-    fr->img = mk_dev_rgb(fr->d.p, fr->d.w, fr->d.h, fr->d.stride);
     return ARTGPU_OK;
 }
 
@@ -292,28 +321,35 @@ static int pipe_input(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const Pi
         // ipf.denoiseComputeParams(imgsrc, currWB, dnstore, params.denoise) before getImage (simpleprocess.cc:254-256); a fresh store per frame
         static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         artgpu_denoise_info_store store = {};
-        if ((rc = artgpu_denoise_compute_params(ctx, &fr->dem, pl.b, p->mul, p->do_clip, cam_to_work ? cam_to_work : ident, p->ws,
-                                                p->chrominance_auto_factor != 0.0 ? p->chrominance_auto_factor : 1.0, &store, &dnp.dn)))
+        if ((rc = dn_compute_params_dev(ctx, fr->dem, pl.b, p->mul, p->do_clip, cam_to_work ? cam_to_work : ident, p->ws,
+                                        p->chrominance_auto_factor != 0.0 ? p->chrominance_auto_factor : 1.0, &store, &dnp.dn)))
             return rc;
     }
     if (p->denoise_enabled) {
         // getImage + convertColorSpace in front of the tool and the STAGE_1 exposure behind it live in the tool's own pixel passes where
-        // its parameters allow (artgpu_improc_denoise_fused: otherwise they run as the separate calls)
+        // its parameters allow (improc_denoise_dev: otherwise they run as the separate passes)
         static const double curve_points[9] = {1 /*FCT_MinMaxCPoints*/, 0.05, 0.50, 0.35, 0.35, 0.35, 0.05, 0.35, 0.35};   // ipdenoise.cc:1139-1149
         float curve[501];
         (void)noise_curve_lut(curve_points, 9, curve);
         const double ecomp = p->exposure_enabled ? p->expcomp : 0.0;       // ipdenoise.cc:1155
         artgpu_denoise_fusion fu = {};
-        fu.demosaiced = &fr->dem; fu.sx1 = pl.b; fu.sy1 = pl.b;
+        fu.sx1 = pl.b; fu.sy1 = pl.b;                       // (the demosaiced planes travel as fr->dem)
         for (int k = 0; k < 3; ++k) fu.mul[k] = p->mul[k];
         fu.do_clip = p->do_clip; fu.cam_to_work = cam_to_work;
         fu.exposure_enabled = p->exposure_enabled && !p->dehaze_enabled ? 1 : 0;      // (dehaze sits between the tool and the exposure)
         fu.exp_scale = (float)std::pow(2.0, p->expcomp); fu.black = (float)(p->black * 2000.0);
-        if ((rc = artgpu_improc_denoise_fused(ctx, &fr->img, &fu, &dnp, p->ws, p->iws, ecomp, pl.scale, cam_to_work, curve, 0u))) return rc;
-    } else if ((rc = artgpu_get_image(ctx, &fr->dem, pl.b, pl.b, p->mul, p->do_clip, cam_to_work, &fr->img))) return rc;
+        StageScope scope_(ctx, "ImProcFunctions::denoise");
+        if ((rc = improc_denoise_dev(ctx, d, &fr->dem, &fu, true, &dnp, p->ws, p->iws, ecomp, pl.scale, cam_to_work, curve, 0u))) return rc;
+    } else {
+        StageScope scope_(ctx, "RawImageSource::getImage");
+        if ((rc = get_image_dev(ctx, fr->dem, d, pl.b, pl.b, 1, p->mul, p->do_clip, cam_to_work))) return rc;
+    }
     // ImProcFunctions::dehaze, STAGE_0 of ImProcFunctions::process (improcfun.cc:577), ahead of the exposure (STAGE_1)
     if (p->dehaze_enabled && (rc = dehaze_dev(ctx, d.p, d.stride, d.w, d.h, &p->dehaze, p->ws, pl.dehaze, nullptr))) return rc;
-    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled) && (rc = artgpu_exposure(ctx, &fr->img, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0)))) return rc;
+    if (p->exposure_enabled && (!p->denoise_enabled || p->dehaze_enabled)) {
+        StageScope scope_(ctx, "ImProcFunctions::expcomp");
+        if ((rc = exposure_dev(ctx, d, (float)std::pow(2.0, p->expcomp), (float)(p->black * 2000.0)))) return rc;
+    }
     // ImProcFunctions::toneEqualizer, the last step of STAGE_1 (improcfun.cc:588), behind the exposure wherever that ran
     if (pl.te_on) return tone_equalizer_dev(ctx, d.p, d.stride, d.w, d.h, &ctx->shared.pipe_te, p->ws, pl.te, "pipeline_run(tone equalizer)");
     return ARTGPU_OK;
@@ -378,18 +414,22 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
     if (p->tone_enabled && p->tone_mode == ARTGPU_TONE_NEUTRAL) {
         artgpu_neutral_state st;
         for (int k = 0; k < 9; ++k) { st.ws[k] = p->ws[k]; st.iws[k] = p->iws[k]; st.to_out[k] = p->to_out[k]; st.to_work[k] = p->to_work[k]; }
-        if ((rc = artgpu_tone_curve_neutral(ctx, &fr->img, p->tone_lut, p->white_point, &st))) return rc;
-    } else if (p->tone_enabled && (rc = artgpu_tone_curve(ctx, &fr->img, p->tone_mode, p->tone_lut, p->white_point, 1))) return rc;
+        StageScope scope_(ctx, "ImProcFunctions::toneCurve (NEUTRAL)");
+        if ((rc = tone_neutral_dev(ctx, d, p->tone_lut, p->white_point, &st))) return rc;
+    } else if (p->tone_enabled) {
+        StageScope scope_(ctx, "ImProcFunctions::toneCurve");
+        if ((rc = tone_curve_dev(ctx, d, p->tone_lut, p->white_point, 1))) return rc;
+    }
     // ... or right behind it (filmSimulation.after_tone_curve, L618-620)
     if (pl.fs_on && s.pipe_fs_after && (rc = film_simulation_dev(ctx, d.p, d.stride, d.w, d.h, s.pipe_fs, &s.pipe_fs_par))) return rc;
     // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
     // L plane (Imagefloat::g), back to RGB
     if (pl.lc_on) {
-        if ((rc = artgpu_rgb_to_lab(ctx, &fr->img, p->ws)) || (pl.lc_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_lc, pl.lc_mk, nlc, false, &gen)))) return rc;
+        if ((rc = lab_switch_dev(ctx, d, p->ws, true)) || (pl.lc_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_lc, pl.lc_mk, nlc, false, &gen)))) return rc;
         for (int i = 0; i < nlc && pl.lc_gen; ++i) pl.lc_regs[i].mask = &gen[i];
         if ((rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, pl.lc_regions, nlc, nullptr))) return rc;
         // (with the Resize tool the image stays in LAB mode, as in the reference: iplocalcontrast.cc:441 does not switch back)
-        if (!pl.rs_on && (rc = artgpu_lab_to_rgb(ctx, &fr->img, p->iws))) return rc;
+        if (!pl.rs_on && (rc = lab_switch_dev(ctx, d, p->iws, false))) return rc;
     }
     if (!pl.rs_on) return unbind_rgb(ctx, out, &d);
     // ImProcFunctions::resize (simpleprocess.cc:402-414): Lanczos' setMode(LAB) is a no-op behind localContrast; the switch to RGB happens on the
@@ -402,14 +442,19 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
 
 namespace artgpu { namespace api {
 
-// One frame: the plan, then the stages (do_ca: artgpu_pipeline_run; io_frame has corrected its staged CFA plane itself)
+// One frame: the plan, then the stages (do_ca: artgpu_pipeline_run; io_frame has corrected its staged CFA plane itself).  The stages call *_dev
+// functions only, so a stage that reports to the progress listener / roctx does it through a StageScope opened here or in improc_denoise_dev, under
+// the name its entry point reports.  Which report: the frame itself, the demosaic, ImProcFunctions::denoise (inside it denoise::RGB_denoise,
+// denoiseGuidedSmoothing, NLMeans, and getImage or expcomp where the tool could not fuse them), getImage without the tool, the exposure on its own,
+// the two tone curves.  Silent inside a frame: CA correction, denoiseComputeParams, the Lab switches and every tool that has a *_check in the plan's
+// items 1 - 10 (whether those should report is a question of behaviour, not of structure).
 int pipeline_run_impl(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artgpu_pipeline_params *p, artgpu_rgb *out, bool do_ca)
 {
     StageScope scope_(ctx, "ImageProcessor (stage_init .. stage_finish)");
     PipePlan pl{};
     PipeFrame fr;
     int rc;
-    if ((rc = pipeline_plan(ctx, raw_in, p, out, &pl)) || (rc = pipe_raw_side(ctx, p, pl, raw_in, do_ca, &fr)) || (rc = pipe_demosaic(ctx, p, pl, out, &fr)) ||
+    if ((rc = pipeline_plan(ctx, raw_in, p, out, do_ca, &pl)) || (rc = pipe_raw_side(ctx, p, pl, raw_in, do_ca, &fr)) || (rc = pipe_demosaic(ctx, p, pl, out, &fr)) ||
         (rc = pipe_input(ctx, p, pl, &fr)) || (rc = pipe_stage2(ctx, p, pl, &fr)))
         return rc;
     return pipe_stage3(ctx, p, pl, out, &fr);

@@ -39,9 +39,101 @@ int lab_mode_switch(artgpu_ctx *ctx, artgpu_rgb *img, const double m[9], bool to
     return unbind_rgb(ctx, img, &d);
 }
 
+// artgpu_get_image and artgpu_get_image_skip
+int get_image_entry(artgpu_ctx *ctx, const artgpu_rgb *planes, int sx1, int sy1, int skip, const float mul[3], int do_clip, const double *mat, artgpu_rgb *image)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!planes || !image || !mul) return fail(ctx, ARTGPU_EINVAL, "get_image: null argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevRGB src, dst;
+    int rc;
+    if ((rc = bind_rgb(ctx, planes, 1, true, &src, "get_image(planes)")) || (rc = bind_rgb(ctx, image, 4, false, &dst, "get_image(image)")) ||
+        (rc = get_image_dev(ctx, src, dst, sx1, sy1, skip, mul, do_clip, mat)))
+        return rc;
+    return unbind_rgb(ctx, image, &dst);
+}
+
 } // namespace
 
 namespace artgpu { namespace api {
+
+int get_image_dev(artgpu_ctx *ctx, const DevRGB &src, const DevRGB &dst, int sx1, int sy1, int skip, const float mul[3], int do_clip, const double *mat)
+{
+    if (skip < 1 || skip > src.w || skip > src.h) return fail(ctx, ARTGPU_EINVAL, "get_image: skip %d", skip);
+    // transformRect (rawimagesource.cc:745-747): the caller's image is ceil(crop / skip); the last window may be pulled back inside
+    if (sx1 < 0 || sy1 < 0 || sx1 + (dst.w - 1) * skip >= src.w || sy1 + (dst.h - 1) * skip >= src.h)
+        return fail(ctx, ARTGPU_EINVAL, "get_image: crop %dx%d+%d+%d (skip %d) outside the %dx%d planes", dst.w, dst.h, sx1, sy1, skip, src.w, src.h);
+    PixArgs a = {};
+    for (int k = 0; k < 3; ++k) { a.src[k] = src.p[k]; a.dst[k] = dst.p[k]; a.mul[k] = mul[k]; }
+    a.src_stride = src.stride; a.dst_stride = dst.stride;
+    a.sx1 = sx1; a.sy1 = sy1; a.w = dst.w; a.h = dst.h;
+    a.skip = skip; a.src_w = src.w; a.src_h = src.h;
+    a.has_mul = 1; a.do_clip = do_clip ? 1 : 0;
+    a.has_mat = mat ? 1 : 0;
+    if (mat) for (int k = 0; k < 9; ++k) a.mat[k] = mat[k];
+    HIPCHK(ctx, launch_get_image_convert(a, ctx->stream));
+    return ARTGPU_OK;
+}
+
+int exposure_dev(artgpu_ctx *ctx, const DevRGB &d, float exp_scale, float black)
+{
+    PixArgs a = {};
+    for (int k = 0; k < 3; ++k) a.dst[k] = d.p[k];
+    a.dst_stride = d.stride; a.w = d.w; a.h = d.h;
+    a.exp_scale = exp_scale; a.black = black;
+    HIPCHK(ctx, launch_exposure(a, ctx->stream));
+    return ARTGPU_OK;
+}
+
+int tone_curve_check(artgpu_ctx *ctx, int mode, float whitept)
+{
+    if (mode != ARTGPU_TONE_STD) return fail(ctx, ARTGPU_EUNSUPPORTED, "tone_curve: curve mode %d is not on the device path", mode);
+    if (!(whitept > 0.f)) return fail(ctx, ARTGPU_EINVAL, "tone_curve: whitept %g", (double)whitept);
+    if (whitept > 1.f && ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "tone_curve: whitept %g needs the curve beyond the LUT (artgpu_set_curve_tail)", (double)whitept);
+    return ARTGPU_OK;
+}
+
+int tone_curve_dev(artgpu_ctx *ctx, const DevRGB &d, const float *lut65536, float whitept, int filmlike_clip)
+{
+    int rc;
+    PixArgs a = {};
+    for (int k = 0; k < 3; ++k) a.dst[k] = d.p[k];
+    a.dst_stride = d.stride; a.w = d.w; a.h = d.h;
+    a.do_clip = filmlike_clip ? 1 : 0; a.whitept = whitept;
+    a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
+    if (lut65536) {
+        if ((rc = upload_curve(ctx, lut65536))) return rc;
+        a.lut = ctx->lut;
+    }
+    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
+    HIPCHK(ctx, launch_tone_std(a, ctx->stream));
+    return ARTGPU_OK;
+}
+
+int tone_neutral_check(artgpu_ctx *ctx, const float *lut65536, float whitecoeff)
+{
+    if (!lut65536 || !(whitecoeff > 0.f)) return fail(ctx, ARTGPU_EINVAL, "tone_curve_neutral: null/invalid argument");
+    return ARTGPU_OK;
+}
+
+int tone_neutral_dev(artgpu_ctx *ctx, const DevRGB &d, const float *lut65536, float whitecoeff, const artgpu_neutral_state *st)
+{
+    int rc;
+    float *pq;
+    if ((rc = pq_tables_dev(ctx, &pq))) return rc;
+    if ((rc = upload_curve(ctx, lut65536))) return rc;
+    NeutralArgs a = {};
+    for (int k = 0; k < 3; ++k) a.img[k] = d.p[k];
+    a.stride = d.stride; a.w = d.w; a.h = d.h;
+    a.lut = ctx->lut; a.pq = pq; a.pq_inv = pq + 65536; a.hues = pq + 2 * 65536;
+    for (int k = 0; k < 9; ++k) { a.ws[k] = (float)st->ws[k]; a.iws[k] = (float)st->iws[k]; a.to_out[k] = st->to_out[k]; a.to_work[k] = st->to_work[k]; }
+    a.whitecoeff = whitecoeff;
+    a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
+    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
+    HIPCHK(ctx, launch_tone_neutral(a, ctx->stream));
+    return ARTGPU_OK;
+}
 
 int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab)
 {
@@ -57,6 +149,23 @@ int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_
     return ARTGPU_OK;
 }
 
+int scale_args_fill(artgpu_ctx *ctx, int w, int h, int src_is_u16, uint32_t filters, const int32_t *xtrans, const float cblacksom[4], const float scale_mul[4],
+                    const char *who, ScaleArgs *a)
+{
+    a->w = w; a->h = h; a->src_u16 = src_is_u16 ? 1 : 0;
+    a->bayer = xtrans ? 0 : 1;
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+            int v;
+            if (xtrans) v = xtrans[r * 6 + c];
+            else v = (filters >> ((((r << 1) & 14) + (c & 1)) << 1)) & 3;      // RawImage::FC, period 2 tiles the 6x6 map
+            if (v < 0 || v > 2) return fail(ctx, ARTGPU_EUNSUPPORTED, "%s: three-colour CFAs only", who);
+            a->cfa[r * 6 + c] = v;
+        }
+    for (int k = 0; k < 4; ++k) { a->cblacksom[k] = cblacksom[k]; a->scale_mul[k] = scale_mul[k]; }
+    return ARTGPU_OK;
+}
+
 } } // namespace artgpu::api
 
 extern "C" {
@@ -65,34 +174,13 @@ int artgpu_get_image(artgpu_ctx *ctx, const artgpu_rgb *planes, int sx1, int sy1
                      int do_clip, const double *mat, artgpu_rgb *image)
 {
     StageScope scope_(ctx, "RawImageSource::getImage");
-    return artgpu_get_image_skip(ctx, planes, sx1, sy1, 1, mul, do_clip, mat, image);
+    return get_image_entry(ctx, planes, sx1, sy1, 1, mul, do_clip, mat, image);
 }
 
 int artgpu_get_image_skip(artgpu_ctx *ctx, const artgpu_rgb *planes, int sx1, int sy1, int skip, const float mul[3],
                           int do_clip, const double *mat, artgpu_rgb *image)
 {
-    if (!ctx) return ARTGPU_EINVAL;
-    if (!planes || !image || !mul) return fail(ctx, ARTGPU_EINVAL, "get_image: null argument");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevRGB src, dst;
-    int rc = bind_rgb(ctx, planes, 1, true, &src, "get_image(planes)");
-    if (rc) return rc;
-    rc = bind_rgb(ctx, image, 4, false, &dst, "get_image(image)");
-    if (rc) return rc;
-    if (skip < 1 || skip > src.w || skip > src.h) return fail(ctx, ARTGPU_EINVAL, "get_image: skip %d", skip);
-    // transformRect (rawimagesource.cc:745-747): the caller's image is ceil(crop / skip); the last window may be pulled back inside
-    if (sx1 < 0 || sy1 < 0 || sx1 + (dst.w - 1) * skip >= src.w || sy1 + (dst.h - 1) * skip >= src.h)
-        return fail(ctx, ARTGPU_EINVAL, "get_image: crop %dx%d+%d+%d (skip %d) outside the %dx%d planes", dst.w, dst.h, sx1, sy1, skip, src.w, src.h);
-    PixArgs a = {};
-    for (int k = 0; k < 3; ++k) { a.src[k] = src.p[k]; a.dst[k] = dst.p[k]; a.mul[k] = mul[k]; }
-    a.src_stride = src.stride; a.dst_stride = dst.stride;
-    a.sx1 = sx1; a.sy1 = sy1; a.w = dst.w; a.h = dst.h;
-    a.skip = skip; a.src_w = src.w; a.src_h = src.h;
-    a.has_mul = 1; a.do_clip = do_clip ? 1 : 0;
-    a.has_mat = mat ? 1 : 0;
-    if (mat) for (int k = 0; k < 9; ++k) a.mat[k] = mat[k];
-    HIPCHK(ctx, launch_get_image_convert(a, ctx->stream));
-    return unbind_rgb(ctx, image, &dst);
+    return get_image_entry(ctx, planes, sx1, sy1, skip, mul, do_clip, mat, image);
 }
 
 int artgpu_convert_color_space(artgpu_ctx *ctx, artgpu_rgb *image, const double mat[9])
@@ -119,13 +207,8 @@ int artgpu_exposure(artgpu_ctx *ctx, artgpu_rgb *image, float exp_scale, float b
     if (!image) return fail(ctx, ARTGPU_EINVAL, "exposure: null image");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
-    int rc = bind_rgb(ctx, image, 4, true, &d, "exposure");
-    if (rc) return rc;
-    PixArgs a = {};
-    for (int k = 0; k < 3; ++k) a.dst[k] = d.p[k];
-    a.dst_stride = d.stride; a.w = d.w; a.h = d.h;
-    a.exp_scale = exp_scale; a.black = black;
-    HIPCHK(ctx, launch_exposure(a, ctx->stream));
+    int rc;
+    if ((rc = bind_rgb(ctx, image, 4, true, &d, "exposure")) || (rc = exposure_dev(ctx, d, exp_scale, black))) return rc;
     return unbind_rgb(ctx, image, &d);
 }
 
@@ -134,25 +217,11 @@ int artgpu_tone_curve(artgpu_ctx *ctx, artgpu_rgb *image, int mode, const float 
     StageScope scope_(ctx, "ImProcFunctions::toneCurve");
     if (!ctx) return ARTGPU_EINVAL;
     if (!image) return fail(ctx, ARTGPU_EINVAL, "tone_curve: null image");
-    if (mode != ARTGPU_TONE_STD) return fail(ctx, ARTGPU_EUNSUPPORTED, "tone_curve: curve mode %d is not on the device path", mode);
-    if (!(whitept > 0.f)) return fail(ctx, ARTGPU_EINVAL, "tone_curve: whitept %g", (double)whitept);
-    if (whitept > 1.f && ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST)
-        return fail(ctx, ARTGPU_EUNSUPPORTED, "tone_curve: whitept %g needs the curve beyond the LUT (artgpu_set_curve_tail)", (double)whitept);
+    int rc;
+    if ((rc = tone_curve_check(ctx, mode, whitept))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
-    int rc = bind_rgb(ctx, image, 4, true, &d, "tone_curve");
-    if (rc) return rc;
-    PixArgs a = {};
-    for (int k = 0; k < 3; ++k) a.dst[k] = d.p[k];
-    a.dst_stride = d.stride; a.w = d.w; a.h = d.h;
-    a.do_clip = filmlike_clip ? 1 : 0; a.whitept = whitept;
-    a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
-    if (lut65536) {
-        if ((rc = upload_curve(ctx, lut65536))) return rc;
-        a.lut = ctx->lut;
-    }
-    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
-    HIPCHK(ctx, launch_tone_std(a, ctx->stream));
+    if ((rc = bind_rgb(ctx, image, 4, true, &d, "tone_curve")) || (rc = tone_curve_dev(ctx, d, lut65536, whitept, filmlike_clip))) return rc;
     return unbind_rgb(ctx, image, &d);
 }
 
@@ -318,22 +387,11 @@ int artgpu_tone_curve_neutral(artgpu_ctx *ctx, artgpu_rgb *image, const float *l
 {
     StageScope scope_(ctx, "ImProcFunctions::toneCurve (NEUTRAL)");
     if (!ctx) return ARTGPU_EINVAL;
-    if (!image || !lut65536 || !st || !(whitecoeff > 0.f)) return fail(ctx, ARTGPU_EINVAL, "tone_curve_neutral: null/invalid argument");
+    int rc;
+    if ((rc = tone_neutral_check(ctx, image && st ? lut65536 : nullptr, whitecoeff))) return rc;      // (one message for every argument)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
-    int rc = bind_rgb(ctx, image, 4, true, &d, "tone_curve_neutral");
-    if (rc) return rc;
-    float *pq;
-    if ((rc = pq_tables_dev(ctx, &pq))) return rc;
-    if ((rc = upload_curve(ctx, lut65536))) return rc;
-    NeutralArgs a = {};
-    for (int k = 0; k < 3; ++k) a.img[k] = d.p[k];
-    a.stride = d.stride; a.w = d.w; a.h = d.h;
-    a.lut = ctx->lut; a.pq = pq; a.pq_inv = pq + 65536; a.hues = pq + 2 * 65536;
-    for (int k = 0; k < 9; ++k) { a.ws[k] = (float)st->ws[k]; a.iws[k] = (float)st->iws[k]; a.to_out[k] = st->to_out[k]; a.to_work[k] = st->to_work[k]; }
-    a.whitecoeff = whitecoeff;
-    a.tail_kind = ctx->shared.curve_tail_kind == ARTGPU_CURVE_TAIL_HOST ? 0 : ctx->shared.curve_tail_kind; a.tail_y = ctx->shared.curve_tail_y; a.tail_pc = ctx->shared.curve_tail_pc;
-    a.no_lds_lut = !ctx->shared.opt_lut_lds; a.cu_reserve = cu_reserve_of(ctx);
-    HIPCHK(ctx, launch_tone_neutral(a, ctx->stream));
+    if ((rc = bind_rgb(ctx, image, 4, true, &d, "tone_curve_neutral")) || (rc = tone_neutral_dev(ctx, d, lut65536, whitecoeff, st))) return rc;
     return unbind_rgb(ctx, image, &d);
 }
 
@@ -493,7 +551,6 @@ int artgpu_scale_colors(artgpu_ctx *ctx, const void *src, int32_t w, int32_t h, 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
     ScaleArgs a = {};
-    a.w = w; a.h = h; a.src_u16 = src_is_u16 ? 1 : 0;
     // source: device pointer as is, host buffer staged (2 or 4 bytes per pixel over PCIe)
     if (src_on_device) { a.src = src; a.src_stride = (size_t)(src_row_stride_bytes / esz); }
     else {
@@ -506,16 +563,7 @@ int artgpu_scale_colors(artgpu_ctx *ctx, const void *src, int32_t w, int32_t h, 
     if (dst->on_device) { out = dst->p; a.dst_stride = (size_t)(dst->row_stride_bytes / 4); }
     else { if ((rc = pool_get(ctx, P_PIPE_G, (size_t)w * h * 4, &out))) return rc; a.dst_stride = w; }
     a.dst = out;
-    a.bayer = xtrans ? 0 : 1;
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-            int v;
-            if (xtrans) v = xtrans[r * 6 + c];
-            else v = (filters >> ((((r << 1) & 14) + (c & 1)) << 1)) & 3;      // RawImage::FC, period 2 tiles the 6x6 map
-            if (v < 0 || v > 2) return fail(ctx, ARTGPU_EUNSUPPORTED, "scale_colors: three-colour CFAs only");
-            a.cfa[r * 6 + c] = v;
-        }
-    for (int k = 0; k < 4; ++k) { a.cblacksom[k] = cblacksom[k]; a.scale_mul[k] = scale_mul[k]; }
+    if ((rc = scale_args_fill(ctx, w, h, src_is_u16, filters, xtrans, cblacksom, scale_mul, "scale_colors", &a))) return rc;
     float *mx;
     if ((rc = pool_get(ctx, P_MAD, 3 * 32 * 4, &mx))) return rc;
     a.chmax_bits = reinterpret_cast<int *>(mx);

@@ -62,6 +62,16 @@ int reconstruct_dev(artgpu_ctx *ctx, DevDecomp &d, float *dst, hipStream_t st)
 
 } } // namespace artgpu::api
 
+// a decomposition handle's end: behind whatever the context's stream still does with its buffers
+static void wavelet_release(artgpu_ctx *ctx, artgpu_wavelet *wv)
+{
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+    if (wv->bands) (void)hipFree(wv->bands);
+    if (wv->lowpass[0]) (void)hipFree(wv->lowpass[0]);
+    if (wv->lowpass[1]) (void)hipFree(wv->lowpass[1]);
+    delete wv;
+}
+
 extern "C" {
 
 int artgpu_wavelet_decompose(artgpu_ctx *ctx, const artgpu_plane *src, int maxlvl, artgpu_wavelet **out)
@@ -89,7 +99,7 @@ int artgpu_wavelet_decompose(artgpu_ctx *ctx, const artgpu_plane *src, int maxlv
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&wv->lowpass[0]), wv->n * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&wv->lowpass[1]), wv->n * sizeof(float));
     if (e != hipSuccess) {
-        artgpu_wavelet_free(ctx, wv);
+        wavelet_release(ctx, wv);
         return fail(ctx, ARTGPU_ENOMEM, "wavelet_decompose: hipMalloc failed: %s", hipGetErrorString(e));
     }
     WaveArgs a = {};
@@ -107,14 +117,14 @@ int artgpu_wavelet_decompose(artgpu_ctx *ctx, const artgpu_plane *src, int maxlv
             wv->cur ^= 1;
         }
         if (le != hipSuccess) {
-            artgpu_wavelet_free(ctx, wv);
+            wavelet_release(ctx, wv);
             return fail(ctx, ARTGPU_EHIP, "wavelet_decompose: launch failed: %s", hipGetErrorString(le));
         }
     }
     if (!src->on_device) {
         const hipError_t se = hipStreamSynchronize(ctx->stream);
         if (se != hipSuccess) {
-            artgpu_wavelet_free(ctx, wv);
+            wavelet_release(ctx, wv);
             return fail(ctx, ARTGPU_EHIP, "wavelet_decompose: %s", hipGetErrorString(se));
         }
     }
@@ -190,11 +200,7 @@ int artgpu_wavelet_reconstruct(artgpu_ctx *ctx, artgpu_wavelet *wv, artgpu_plane
 int artgpu_wavelet_free(artgpu_ctx *ctx, artgpu_wavelet *wv)
 {
     if (!wv) return ARTGPU_EINVAL;
-    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
-    if (wv->bands) (void)hipFree(wv->bands);
-    if (wv->lowpass[0]) (void)hipFree(wv->lowpass[0]);
-    if (wv->lowpass[1]) (void)hipFree(wv->lowpass[1]);
-    delete wv;
+    wavelet_release(ctx, wv);
     return ARTGPU_OK;
 }
 

@@ -96,7 +96,7 @@ bool plane_ok(const artgpu_plane *p)
 }
 
 // Resolve device pointers for (raw, out); host planes are staged through ctx buffers.
-int bind_images(artgpu_ctx *ctx, const artgpu_plane *raw, artgpu_rgb *out, DevImage *d)
+int bind_images(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_rgb *out, DevImage *d)
 {
     const int W = raw->w, H = raw->h;
     const artgpu_plane *op[3] = {&out->r, &out->g, &out->b};

@@ -1030,10 +1030,12 @@ int artgpu_film_simulation_tables(float *gamma2curve /* 65536, host */, float *i
  * between the stages either way).  Disabled stages are skipped exactly like their `enabled == false` early-outs. */
 typedef struct {
     int32_t sensor;                 /* 0 = Bayer, 1 = X-Trans */
-    int32_t bayer_method;           /* ARTGPU_BAYER_* */
+    int32_t bayer_method;           /* ARTGPU_BAYER_*; what artgpu_demosaic_bayer does not support (a method off the device path, initial_gain <= 0, a
+                                     * four-colour CFA, a frame under 64x64) fails the frame before any stage has run */
     uint32_t filters;
     double initial_gain;
-    int32_t xtrans_passes;          /* 1 (ONE_PASS) or 3 (THREE_PASS, CIELab) */
+    int32_t xtrans_passes;          /* 1 (ONE_PASS) or 3 (THREE_PASS, CIELab); what artgpu_demosaic_xtrans does not support (passes, the colour map, a
+                                     * frame under 64x64, a row beyond the reference's short offsets) fails the frame before any stage has run */
     int32_t xtrans[36];
     float rgb_cam[12];
     int32_t border;                 /* raw.bayersensor.border / raw.xtranssensor.border */
@@ -1043,11 +1045,15 @@ typedef struct {
     double cam_to_work[9];          /* matrix branch of convertColorSpace */
     double ws[9], iws[9];           /* working space <-> XYZ (TMatrix) */
     int32_t denoise_enabled;
-    artgpu_denoise_tool_params denoise;
+    artgpu_denoise_tool_params denoise;   /* what artgpu_improc_denoise does not support (color_space, chrominance_method, scale < 1, a side above 32767, and
+                                     * with smoothing_enabled the limits of artgpu_denoise_guided_smoothing and artgpu_nlmeans) fails the frame before
+                                     * any stage has run; so does AUTOMATIC chroma on an image under 100x100 (artgpu_denoise_compute_params) */
     int32_t exposure_enabled;
     double expcomp, black;
     int32_t tone_enabled;
-    int32_t tone_mode;              /* ARTGPU_TONE_STD / ARTGPU_TONE_NEUTRAL */
+    int32_t tone_mode;              /* ARTGPU_TONE_STD / ARTGPU_TONE_NEUTRAL; what artgpu_tone_curve / artgpu_tone_curve_neutral do not support (another mode,
+                                     * white_point <= 0, white_point > 1 with the default curve tail, NEUTRAL without tone_lut) fails the frame before
+                                     * any stage has run */
     const float *tone_lut;          /* 65536 entries (host) */
     float white_point;
     float to_out[9], to_work[9];    /* NEUTRAL only */

@@ -7,7 +7,9 @@ the full message.  Two builds of the library that print the same file run the sa
 
 The matrix: every tool alone, all of them in one frame, the combinations of colour correction / smoothing / texture boost with and without
 pipe-generated masks (the legal ones and the refused ones), X-Trans with and without the automatic sharpening radius, a region count that
-is not the frame's, denoise x dehaze -- each at 392 x 296 and at 395 x 301 (a width that is no multiple of 4 behind the border)."""
+is not the frame's, denoise x dehaze, the NEUTRAL curve, the denoise tool with guided smoothing and NL-means behind the wavelets, AUTOMATIC
+chroma, and what the demosaicers, denoiseComputeParams, the denoise tool and the tone curves refuse -- each at 392 x 296 and at 395 x 301
+(a width that is no multiple of 4 behind the border; the two refusals that are about the frame's size bring their own)."""
 import argparse
 import ctypes as C
 import hashlib
@@ -58,7 +60,8 @@ def params(xtrans=False):
 
 def cases():
     """(name, what is on): keys dehaze, sharpen ('fixed' / 'auto'), cc, sm, tb, lc ('planes' = the regions' own, all ones / 'gen' = the pipe
-    generates the masks / 'caller' = device planes of the caller), denoise, ca, xtrans, mismatch"""
+    generates the masks / 'caller' = device planes of the caller), denoise (True / 'smoothing' / 'auto'), ca, xtrans, mismatch, neutral,
+    set (fields of the parameters, '__' for a member), size (the raw frame's instead of the run's)"""
     yield "plain", {}
     for tool in ("dehaze", "denoise", "ca", "xtrans"):
         yield tool, {tool: True}
@@ -78,10 +81,25 @@ def cases():
     yield "mismatch-lc", dict(lc="gen", tb="planes", mismatch=True)
     for dn, dh in itertools.product((False, True), (False, True)):
         yield f"denoise:{int(dn)}-dehaze:{int(dh)}", dict(denoise=dn, dehaze=dh)
+    yield "neutral", dict(neutral=True)
+    yield "neutral-denoise", dict(neutral=True, denoise=True)
+    yield "denoise-smoothing", dict(denoise="smoothing")
+    yield "denoise-smoothing-dehaze", dict(denoise="smoothing", dehaze=True)
+    yield "denoise-auto-chroma", dict(denoise="auto")
+    yield "refuse-tone-mode", dict(set=dict(tone_mode=2))
+    yield "refuse-white-point", dict(denoise=True, set=dict(white_point=1.5))
+    yield "refuse-neutral-null-lut", dict(neutral=True, set=dict(tone_lut=None))
+    yield "refuse-color-space", dict(denoise=True, set=dict(denoise__dn__color_space=2))
+    yield "refuse-smoothing-radius", dict(denoise="smoothing", set=dict(denoise__guided_chroma_radius=1, scale=4.0))
+    yield "refuse-bayer-method", dict(set=dict(bayer_method=99))
+    yield "refuse-initial-gain", dict(set=dict(initial_gain=0.0))
+    yield "refuse-raw-60x72", dict(size=(60, 72))
+    yield "refuse-auto-chroma-96x96", dict(denoise="auto", size=(104, 104))
 
 
 def run_case(ctx, W, H, on):
     xtrans = bool(on.get("xtrans"))
+    W, H = on.get("size", (W, H))
     p = params(xtrans)
     b = p.border
     w, h = W - 2 * b, H - 2 * b
@@ -93,6 +111,17 @@ def run_case(ctx, W, H, on):
     caller = capi.device_plane(ramp)
     if on.get("denoise"):
         p.denoise_enabled = 1
+    if on.get("denoise") == "smoothing":
+        p.denoise.smoothing_enabled = 1; p.denoise.nl_strength = 50
+    if on.get("denoise") == "auto":
+        p.denoise.dn.chrominance_method = 1; p.denoise.dn.chrominance = 0.0; p.chrominance_auto_factor = 1.5
+    if on.get("neutral"):
+        p.tone_mode = 1
+    for key, value in on.get("set", {}).items():
+        obj, names = p, key.split("__")
+        for name in names[:-1]:
+            obj = getattr(obj, name)
+        setattr(obj, names[-1], value)
     if on.get("ca"):
         p.ca_enabled = 1; p.ca = capi.CaParams(1, 2, 0.0, 0.0, 1)
     if on.get("dehaze"):

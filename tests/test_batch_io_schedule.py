@@ -56,40 +56,40 @@ def simulate(nframes, seed, drop=None, pinned_in=True, pinned_out=True, kinds=No
     for i, (kin, kout) in enumerate(kinds):
         assert kin in IN_KINDS and kout in OUT_KINDS
         s = i & 1
-        up = "C" if kin == "pageable" else "U"                          # :188 s_up (a pageable copy stays on the context's stream)
-        down = "D" if kout.startswith("pinned") else "C"                # :189 s_down
-        direct = kout == "pinned-direct"                                # :191 host_dev
+        up = "C" if kin == "pageable" else "U"                          # :192 s_up (a pageable copy stays on the context's stream)
+        down = "D" if kout.startswith("pinned") else "C"                # :193 s_down
+        direct = kout == "pinned-direct"                                # :195 host_dev
         on_device = kout == "device"
         if i >= 2 and drop != "down" and not (drop == "down_before_device" and on_device):
-            wait("C", f"down{s}")                                       # :198 working image / staging-out slot of turn i - 2 downloaded
+            wait("C", f"down{s}")                                       # :202 working image / staging-out slot of turn i - 2 downloaded
         if kin != "device":
             if i >= 2 and drop != "scaled":
-                wait(up, f"scaled{s}")                                  # :207 the kernel that read this slot two turns ago
-            op(up, "h2d", i, writes=[f"in{s}"])                         # :209 hipMemcpy2DAsync into the staging slot
-            record(up, f"up{s}")                                        # :210
+                wait(up, f"scaled{s}")                                  # :210 the kernel that read this slot two turns ago
+            op(up, "h2d", i, writes=[f"in{s}"])                         # :212 hipMemcpy2DAsync into the staging slot
+            record(up, f"up{s}")                                        # :213
             if drop != "up":
-                wait("C", f"up{s}")                                     # :211
-            op("C", "scale_colors", i, reads=[f"in{s}"])                # :227 launch_scale_colors (into the CFA plane)
-            record("C", f"scaled{s}")                                   # :228
+                wait("C", f"up{s}")                                     # :214
+            op("C", "scale_colors", i, reads=[f"in{s}"])                # :221 launch_scale_colors (into the CFA plane)
+            record("C", f"scaled{s}")                                   # :222
         else:
-            op("C", "scale_colors", i)                                  # :227 reads the caller's device buffer
-        op("C", "pipeline", i, writes=[f"img{s}"])                      # :233-252 CA, pipeline_run_impl, rgb2out in place
+            op("C", "scale_colors", i)                                  # :221 reads the caller's device buffer
+        op("C", "pipeline", i, writes=[f"img{s}"])                      # :227-246 CA, pipeline_run_impl, rgb2out in place
         if direct:
-            record("C", f"comp{s}")                                     # :258
+            record("C", f"comp{s}")                                     # :252
             if drop != "comp":
-                wait("D", f"comp{s}")                                   # :259
-            op("D", "scanlines_host", i, reads=[f"img{s}"])             # :261 launch_scanlines_host into the caller's pinned buffer
-            record("D", f"down{s}")                                     # :262
+                wait("D", f"comp{s}")                                   # :253
+            op("D", "scanlines_host", i, reads=[f"img{s}"])             # :255 launch_scanlines_host into the caller's pinned buffer
+            record("D", f"down{s}")                                     # :256
             continue
         if on_device:
-            op("C", "scanlines", i, reads=[f"img{s}"])                  # :271 launch_scanlines into the caller's device buffer
-            continue                                                    # (:273 nothing recorded, nothing downloaded)
-        op("C", "scanlines", i, reads=[f"img{s}"], writes=[f"out{s}"])  # :271 launch_scanlines into the staging slot
-        record("C", f"comp{s}")                                         # :274
+            op("C", "scanlines", i, reads=[f"img{s}"])                  # :265 launch_scanlines into the caller's device buffer
+            continue                                                    # (:267 nothing recorded, nothing downloaded)
+        op("C", "scanlines", i, reads=[f"img{s}"], writes=[f"out{s}"])  # :265 launch_scanlines into the staging slot
+        record("C", f"comp{s}")                                         # :268
         if drop != "comp":
-            wait(down, f"comp{s}")                                      # :275
-        op(down, "d2h", i, reads=[f"out{s}"])                           # :276 hipMemcpy2DAsync to the caller's buffer
-        record(down, f"down{s}")                                        # :277
+            wait(down, f"comp{s}")                                      # :269
+        op(down, "d2h", i, reads=[f"out{s}"])                           # :270 hipMemcpy2DAsync to the caller's buffer
+        record(down, f"down{s}")                                        # :271
 
     return ops
 

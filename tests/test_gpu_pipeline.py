@@ -396,3 +396,130 @@ def test_batch_lanes_inherit_the_pipe_settings_and_an_option():
         assert all((o[1] != r[1]).any() for o, r in zip(cleared, one))
     finally:
         ctx.close()
+
+
+def _progress_frame(kind):
+    """(raw, params, image width, image height) of the three frames test_pipeline_progress_sequence walks"""
+    lut = _lut()
+    if kind == "xtrans-denoise-dehaze":        # the dehaze sits between the tool and the exposure: the exposure runs on its own
+        W, H, b = 142, 128, 7
+        raw = synth.xtrans_frame(W, H, seed=4, noise=1500)
+        p = _params(lut, 0, xtrans=True)
+        dh, keep = capi.dehaze_params(depth=50)
+        p.dehaze_enabled = 1; p.dehaze = dh
+        return raw, p, W - 2 * b, H - 2 * b, (lut, keep)
+    W, H, b = 138, 122, 4                       # the image is 130 x 114: a width that is no multiple of 4
+    raw = synth.bayer_frame(W, H, synth.FILTERS_RGGB, seed=4, noise=1500)
+    p = _params(lut, 1 if kind == "bayer-neutral" else 0)
+    p.bayer_method = capi.BAYER_RCD
+    if kind == "bayer-neutral":
+        p.denoise_enabled = 0
+    else:
+        p.denoise = capi.DenoiseToolParams(capi.DenoiseParams(40.0, 50.0, 0, 15.0, 0.0, 0.0, 1.7, 0, 0, 0), 1, 3, 50, 80)
+    return raw, p, W - 2 * b, H - 2 * b, (lut,)
+
+
+def _scope(name):
+    return [(name, 0.0), (name, 1.0)]
+
+
+_FRAME = "ImageProcessor (stage_init .. stage_finish)"
+# recorded with the driver that reached these stages through their public entry points
+PROGRESS_EVENTS = {
+    "bayer-denoise-smoothing-std": [(_FRAME, 0.0)] + _scope("RawImageSource::demosaic (Bayer)") + [("ImProcFunctions::denoise", 0.0)] + _scope("denoise::RGB_denoise")
+                                   + _scope("denoise::denoiseGuidedSmoothing") + _scope("denoise::NLMeans") + [("ImProcFunctions::denoise", 1.0)]
+                                   + _scope("ImProcFunctions::toneCurve") + [(_FRAME, 1.0)],
+    "bayer-neutral": [(_FRAME, 0.0)] + _scope("RawImageSource::demosaic (Bayer)") + _scope("RawImageSource::getImage") + _scope("ImProcFunctions::expcomp")
+                     + _scope("ImProcFunctions::toneCurve (NEUTRAL)") + [(_FRAME, 1.0)],
+    "xtrans-denoise-dehaze": [(_FRAME, 0.0)] + _scope("RawImageSource::xtrans_interpolate") + [("ImProcFunctions::denoise", 0.0)] + _scope("denoise::RGB_denoise")
+                             + [("ImProcFunctions::denoise", 1.0)] + _scope("ImProcFunctions::expcomp") + _scope("ImProcFunctions::toneCurve") + [(_FRAME, 1.0)],
+}
+
+
+@pytest.mark.parametrize("kind", sorted(PROGRESS_EVENTS))
+def test_pipeline_progress_sequence(kind):
+    """The full (name, fraction) list one artgpu_pipeline_run reports to the progress listener.  The raw stages, the denoise tool with what
+    it runs inside, getImage, the exposure and the tone curves report; the tools that came later are silent inside a frame."""
+    raw, p, w, h, keep = _progress_frame(kind)
+    events = []
+    ctx = capi.Context(0)
+    try:
+        d_raw = torch.from_numpy(raw).cuda()
+        d_out = [torch.zeros((h, w), dtype=torch.float32, device="cuda") for _ in range(3)]
+        ctx.set_progress_callback(lambda stage, frac: events.append((stage, frac)))
+        ctx.pipeline_run(capi.device_plane(d_raw), p, capi.RGB(*[capi.device_plane(t) for t in d_out]))
+        ctx.synchronize()
+    finally:
+        ctx.set_progress_callback(None)
+        ctx.close()
+    print(kind, events)
+    assert events == PROGRESS_EVENTS[kind]
+    assert all(bool(torch.isfinite(t).all()) and float(t.max()) > 0 for t in d_out)
+    del keep
+
+
+def _neutral_null_lut(ctx, img):
+    st = capi.NeutralState()
+    st.ws[:] = [float(v) for v in O.REC2020_WS_D.reshape(9)]
+    st.iws[:] = [float(v) for v in O.REC2020_IWS_D.reshape(9)]
+    ctx._chk(capi.LIB.artgpu_tone_curve_neutral(ctx._h, C.byref(img), None, 1.0, C.byref(st)))
+
+
+def _set(p, **kw):
+    for k, v in kw.items():
+        obj, names = p, k.split("__")
+        for n in names[:-1]:
+            obj = getattr(obj, n)
+        setattr(obj, names[-1], v)
+
+
+# name -> (raw size, what the frame's parameters get, the stand-alone call that refuses the same arguments: (ctx, raw plane, demosaiced
+# planes of the raw's size, image of the frame's size, lut) -> raises)
+REFUSALS = {
+    "tone-mode-2": ((72, 68), dict(tone_mode=2), lambda c, raw, dem, img, lut: c.tone_curve(img, lut, 1.0, True, mode=2)),
+    "white-point-default-tail": ((72, 68), dict(white_point=1.5), lambda c, raw, dem, img, lut: c.tone_curve(img, lut, 1.5, True)),
+    "neutral-null-lut": ((72, 68), dict(tone_mode=1, tone_lut=None), lambda c, raw, dem, img, lut: _neutral_null_lut(c, img)),
+    "denoise-color-space-2": ((72, 68), dict(denoise__dn__color_space=2),
+                              lambda c, raw, dem, img, lut: c.rgb_denoise(img, capi.DenoiseParams(40.0, 50.0, 0, 15.0, 0.0, 0.0, 1.7, 0, 2, 0), O.REC2020_WS_D)),
+    "smoothing-radius-over-scale": ((72, 68), dict(denoise__smoothing_enabled=1, denoise__guided_chroma_radius=1, scale=4.0),
+                                    lambda c, raw, dem, img, lut: c.denoise_guided_smoothing(img, O.REC2020_WS_D, 1, 4.0)),
+    "bayer-method-99": ((72, 68), dict(bayer_method=99), lambda c, raw, dem, img, lut: c.demosaic_bayer(99, raw, synth.FILTERS_RGGB, 1.0, 4, dem)),
+    "initial-gain-0": ((72, 68), dict(initial_gain=0.0), lambda c, raw, dem, img, lut: c.demosaic_bayer(capi.BAYER_AMAZE, raw, synth.FILTERS_RGGB, 0.0, 4, dem)),
+    "raw-60x72": ((60, 72), {}, lambda c, raw, dem, img, lut: c.demosaic_bayer(capi.BAYER_AMAZE, raw, synth.FILTERS_RGGB, 1.0, 4, dem)),
+    "automatic-chroma-96x96": ((104, 104), dict(denoise__dn__chrominance_method=1),
+                               lambda c, raw, dem, img, lut: c.denoise_compute_params(dem, 4, MUL, True, MAT, O.REC2020_WS_D, capi.DenoiseParams(40.0, 50.0, 0, 0.0, 0.0, 0.0, 1.7, 0, 0, 1))),
+}
+
+
+@pytest.mark.parametrize("case", sorted(REFUSALS))
+def test_refused_frame_leaves_output_alone(case):
+    """What the demosaicers, denoiseComputeParams, the denoise tool and the tone curves do not support fails the frame before any stage has
+    run: the output planes, on the host or on the device, keep every bit, and the message is the stand-alone entry point's."""
+    (W, H), changes, standalone = REFUSALS[case]
+    b, sentinel = 4, np.float32(-7.25)
+    w, h = W - 2 * b, H - 2 * b
+    lut = _lut()
+    p = _params(lut, 0)
+    _set(p, **changes)
+    raw = synth.bayer_frame(W, H, synth.FILTERS_RGGB, seed=8, noise=1500)
+    ctx = capi.Context(0)
+    try:
+        d_raw = torch.from_numpy(raw).cuda()
+        d_dem = [torch.zeros((H, W), dtype=torch.float32, device="cuda") for _ in range(3)]
+        d_img = [torch.full((h, w), 1000.0, dtype=torch.float32, device="cuda") for _ in range(3)]
+        with pytest.raises(capi.ArtGpuError) as alone:
+            standalone(ctx, capi.device_plane(d_raw), capi.RGB(*[capi.device_plane(t) for t in d_dem]), capi.RGB(*[capi.device_plane(t) for t in d_img]), lut)
+        host = [np.full((h, w), sentinel, np.float32) for _ in range(3)]
+        dev = [torch.full((h, w), float(sentinel), dtype=torch.float32, device="cuda") for _ in range(3)]
+        torch.cuda.synchronize()
+        for where, out in (("host", capi.host_rgb(host)), ("device", capi.RGB(*[capi.device_plane(t) for t in dev]))):
+            with pytest.raises(capi.ArtGpuError) as frame:
+                ctx.pipeline_run(capi.device_plane(d_raw), p, out)
+            ctx.synchronize()
+            print(case, where, frame.value)
+            assert str(frame.value) == str(alone.value), where
+        for a, t in zip(host, dev):
+            assert (a.view(np.uint32) == sentinel.view(np.uint32)).all(), "host output written"
+            assert (t.cpu().numpy().view(np.uint32) == sentinel.view(np.uint32)).all(), "device output written"
+    finally:
+        ctx.close()
