@@ -311,6 +311,103 @@ def resize_scale(params, fw: int, fh: int):
     return imw.value, imh.value, np.float32(sc.value)
 
 
+class CreativeGradientsParams(C.Structure):
+    """artgpu_creative_gradients_params: GradientParams, PCVignetteParams, CropParams and ImProcFunctions' offset / full size / scale"""
+    _fields_ = [("gradient_enabled", C.c_int32), ("gradient_degree", C.c_double), ("gradient_feather", C.c_int32), ("gradient_strength", C.c_double),
+                ("gradient_center_x", C.c_int32), ("gradient_center_y", C.c_int32),
+                ("pcvignette_enabled", C.c_int32), ("pcvignette_strength", C.c_double), ("pcvignette_feather", C.c_int32), ("pcvignette_roundness", C.c_int32),
+                ("pcvignette_center_x", C.c_int32), ("pcvignette_center_y", C.c_int32),
+                ("crop_enabled", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_w", C.c_int32), ("crop_h", C.c_int32),
+                ("offset_x", C.c_int32), ("offset_y", C.c_int32), ("full_width", C.c_int32), ("full_height", C.c_int32), ("scale", C.c_double)]
+
+
+class CreativeGradientDerived(C.Structure):
+    """artgpu_creative_gradient_derived: grad_params and pcv_params as the kernel takes them"""
+    _fields_ = ([(n, C.c_int32) for n in ("apply_gradient", "apply_pcvignette", "cx", "cy", "angle_is_zero", "transpose", "bright_top", "h")] +
+                [(n, C.c_float) for n in ("ta", "yc", "xc", "ys", "ys_inv", "scale", "botmul", "topmul", "top_edge_0",
+                                          "oe_a", "oe_b", "oe1_a", "oe1_b", "oe2_a", "oe2_b", "ie_mul", "ie1_mul", "ie2_mul", "sepmix", "feather")] +
+                [(n, C.c_int32) for n in ("x1", "x2", "y1", "y2", "ex", "ey", "ew", "eh", "sep", "is_super_ellipse_mode", "is_portrait")] +
+                [("pcv_scale", C.c_float), ("fadeout_mul", C.c_float)])
+
+
+def creative_gradients_params(gradient=None, pcvignette=None, crop=None, offset=(0, 0), full=(-1, -1), scale=1.0) -> CreativeGradientsParams:
+    """gradient: (degree, feather, strength, center_x, center_y) or None; pcvignette: (strength, feather, roundness, center_x, center_y) or None;
+    crop: (x, y, w, h) or None"""
+    g = gradient if gradient is not None else (0.0, 25, 0.6, 0, 0)
+    v = pcvignette if pcvignette is not None else (0.6, 50, 50, 0, 0)
+    c = crop if crop is not None else (0, 0, 0, 0)
+    return CreativeGradientsParams(int(gradient is not None), float(g[0]), int(g[1]), float(g[2]), int(g[3]), int(g[4]),
+                                   int(pcvignette is not None), float(v[0]), int(v[1]), int(v[2]), int(v[3]), int(v[4]),
+                                   int(crop is not None), int(c[0]), int(c[1]), int(c[2]), int(c[3]),
+                                   int(offset[0]), int(offset[1]), int(full[0]), int(full[1]), float(scale))
+
+
+def creative_gradient_params(params: CreativeGradientsParams, w: int, h: int) -> CreativeGradientDerived:
+    """calcGradientParams / calcPCVignetteParams on the host (no context) for a w x h image"""
+    out = CreativeGradientDerived()
+    rc = LIB.artgpu_creative_gradient_params(C.byref(params), int(w), int(h), C.byref(out))
+    if rc:
+        raise ArtGpuError(f"artgpu_creative_gradient_params: error {rc}")
+    return out
+
+
+class SoftLightParams(C.Structure):
+    """artgpu_soft_light_params: SoftLightParams (enabled 0, strength 30)"""
+    _fields_ = [("enabled", C.c_int32), ("strength", C.c_int32)]
+
+
+def soft_light_params(strength=30, enabled=True) -> SoftLightParams:
+    return SoftLightParams(int(bool(enabled)), int(strength))
+
+
+def soft_light_lut(strength: int) -> np.ndarray:
+    """ImProcFunctions::softLight's 65536-entry table, built on the host (no context)"""
+    lut = np.empty(65536, np.float32)
+    rc = LIB.artgpu_soft_light_lut(int(strength), lut.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise ArtGpuError(f"artgpu_soft_light_lut: error {rc}")
+    return lut
+
+
+BW_SETTINGS = ("NormalContrast", "Panchromatic", "HyperPanchromatic", "LowSensitivity", "HighSensitivity", "Orthochromatic", "HighContrast", "Luminance",
+               "Landscape", "Portrait", "InfraRed", "RGB-Rel", "RGB-Abs", "ROYGCBPM-Rel", "ROYGCBPM-Abs")
+BW_FILTERS = ("None", "Red", "Orange", "Yellow", "YellowGreen", "Green", "Cyan", "Blue", "Purple")
+
+
+class BlackAndWhiteParams(C.Structure):
+    """artgpu_black_and_white_params: BlackWhiteParams (setting / filter: indices into BW_SETTINGS / BW_FILTERS)"""
+    _fields_ = [("enabled", C.c_int32), ("setting", C.c_int32), ("filter", C.c_int32), ("mixer_red", C.c_int32), ("mixer_green", C.c_int32),
+                ("mixer_blue", C.c_int32), ("gamma_red", C.c_int32), ("gamma_green", C.c_int32), ("gamma_blue", C.c_int32), ("cast_bottom", C.c_int32),
+                ("cast_top", C.c_int32), ("ulut", C.POINTER(C.c_float)), ("vlut", C.POINTER(C.c_float))]
+
+
+class BwMixer(C.Structure):
+    """artgpu_bw_mixer: what computeBWMixerConstants returns"""
+    _fields_ = [("bwr", C.c_float), ("bwg", C.c_float), ("bwb", C.c_float), ("kcorec", C.c_float), ("filcor", C.c_float),
+                ("rrm", C.c_double), ("ggm", C.c_double), ("bbm", C.c_double)]
+
+
+def black_and_white_params(setting="RGB-Rel", filter="None", mixer=(33, 33, 33), gamma=(0, 0, 0), cast=(0, 0), ulut=None, vlut=None, enabled=True):
+    """-> (BlackAndWhiteParams, keepalive); ulut / vlut: float32 arrays of 65536 entries (the colour cast's tables) or None"""
+    keep = [None if t is None else np.ascontiguousarray(t, np.float32) for t in (ulut, vlut)]
+    assert all(t is None or t.shape == (65536,) for t in keep)
+    ptr = [None if t is None else t.ctypes.data_as(C.POINTER(C.c_float)) for t in keep]
+    st = setting if isinstance(setting, int) else BW_SETTINGS.index(setting)
+    fl = filter if isinstance(filter, int) else BW_FILTERS.index(filter)
+    return BlackAndWhiteParams(int(bool(enabled)), int(st), int(fl), *[int(v) for v in mixer], *[int(v) for v in gamma], int(cast[0]), int(cast[1]), ptr[0], ptr[1]), keep
+
+
+def bw_mixer_constants(setting, filter, mixer=(33, 33, 33)) -> BwMixer:
+    """computeBWMixerConstants on the host (no context)"""
+    st = setting if isinstance(setting, int) else BW_SETTINGS.index(setting)
+    fl = filter if isinstance(filter, int) else BW_FILTERS.index(filter)
+    out = BwMixer()
+    rc = LIB.artgpu_bw_mixer_constants(int(st), int(fl), int(mixer[0]), int(mixer[1]), int(mixer[2]), C.byref(out))
+    if rc:
+        raise ArtGpuError(f"artgpu_bw_mixer_constants: error {rc}")
+    return out
+
+
 class Clut:
     """artgpu_clut: a HaldCLUT on a context's device.  `table`: uint16 array of level^3 entries, red fastest, 3 or 4 values each."""
 
@@ -646,6 +743,15 @@ def _load():
     lib.artgpu_grain_table.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_uint64)]
     lib.artgpu_grain_indices.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]
     lib.artgpu_set_pipeline_film_grain.argtypes = [C.c_void_p, C.POINTER(FilmGrainParams)]
+    lib.artgpu_creative_gradients.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(CreativeGradientsParams)]
+    lib.artgpu_creative_gradient_params.argtypes = [C.POINTER(CreativeGradientsParams), C.c_int, C.c_int, C.POINTER(CreativeGradientDerived)]
+    lib.artgpu_set_pipeline_creative_gradients.argtypes = [C.c_void_p, C.POINTER(CreativeGradientsParams)]
+    lib.artgpu_soft_light.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(SoftLightParams)]
+    lib.artgpu_soft_light_lut.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    lib.artgpu_set_pipeline_soft_light.argtypes = [C.c_void_p, C.POINTER(SoftLightParams)]
+    lib.artgpu_black_and_white.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(BlackAndWhiteParams), C.POINTER(C.c_double)]
+    lib.artgpu_bw_mixer_constants.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BwMixer)]
+    lib.artgpu_set_pipeline_black_and_white.argtypes = [C.c_void_p, C.POINTER(BlackAndWhiteParams)]
     lib.artgpu_resize_lanczos.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(RGB), C.c_float, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.artgpu_resize_scale.argtypes = [C.POINTER(ResizeParams), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
     lib.artgpu_set_pipeline_resize.argtypes = [C.c_void_p, C.POINTER(ResizeParams)]
@@ -719,6 +825,8 @@ PRIM_XDIVF2 = 20
 PRIM_XLOG_D = 21
 PRIM_XEXP_D = 22
 PRIM_FLOAT_TO_HALF = 23     # out: float32-sized words, the half in the low 16 bits (eval_primitive returns them as uint32)
+PRIM_XSINF_S = 24           # sleef.h's scalar xsinf
+PRIM_XCOSF_S = 25           # sleef.h's scalar xcosf, which under SSE2 is lane 0 of the vector form
 
 EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_option", "artgpu_get_option", "artgpu_set_curve_tail", "artgpu_set_curve_tail_parametric", "artgpu_create", "artgpu_destroy", "artgpu_last_error", "artgpu_version", "artgpu_set_stream",
            "artgpu_synchronize", "artgpu_enable_timing", "artgpu_get_timings", "artgpu_scratch_bytes", "artgpu_trim_scratch",
@@ -734,7 +842,10 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer",
            "artgpu_clut_create", "artgpu_clut_destroy", "artgpu_film_simulation", "artgpu_film_simulation_tables", "artgpu_set_pipeline_film_simulation",
            "artgpu_resize_lanczos", "artgpu_resize_scale", "artgpu_set_pipeline_resize",
-           "artgpu_film_grain", "artgpu_add_noise", "artgpu_grain_table", "artgpu_grain_indices", "artgpu_set_pipeline_film_grain"]
+           "artgpu_film_grain", "artgpu_add_noise", "artgpu_grain_table", "artgpu_grain_indices", "artgpu_set_pipeline_film_grain",
+           "artgpu_creative_gradients", "artgpu_creative_gradient_params", "artgpu_set_pipeline_creative_gradients",
+           "artgpu_soft_light", "artgpu_soft_light_lut", "artgpu_set_pipeline_soft_light",
+           "artgpu_black_and_white", "artgpu_bw_mixer_constants", "artgpu_set_pipeline_black_and_white"]
 
 
 def host_plane(a: np.ndarray) -> Plane:
@@ -1085,6 +1196,37 @@ class Context:
     def set_pipeline_resize(self, params: ResizeParams = None):
         """the Resize tool behind STAGE_3 of the per-frame pipe (None: off): outputs are then imw x imh of resize_scale on the bordered frame"""
         self._chk(LIB.artgpu_set_pipeline_resize(self._h, C.byref(params) if params is not None else None))
+
+    def creative_gradients(self, image: RGB, params: CreativeGradientsParams):
+        """ImProcFunctions::creativeGradients in place on an RGB image (params from creative_gradients_params())"""
+        self._chk(LIB.artgpu_creative_gradients(self._h, C.byref(image), C.byref(params) if params is not None else None))
+
+    creative_gradient_params = staticmethod(creative_gradient_params)
+
+    def set_pipeline_creative_gradients(self, params: CreativeGradientsParams = None):
+        """the graduated / vignette filters in pipeline_run / batch_run / batch_run_io: the first step of STAGE_3 (None: off).  The library copies it."""
+        self._chk(LIB.artgpu_set_pipeline_creative_gradients(self._h, C.byref(params) if params is not None else None))
+
+    def soft_light(self, image: RGB, params: SoftLightParams):
+        """ImProcFunctions::softLight in place on an RGB image (params from soft_light_params())"""
+        self._chk(LIB.artgpu_soft_light(self._h, C.byref(image), C.byref(params) if params is not None else None))
+
+    soft_light_lut = staticmethod(soft_light_lut)
+
+    def set_pipeline_soft_light(self, params: SoftLightParams = None):
+        """soft light in pipeline_run / batch_run / batch_run_io: behind the tone curve, ahead of local contrast (None: off).  The library copies it."""
+        self._chk(LIB.artgpu_set_pipeline_soft_light(self._h, C.byref(params) if params is not None else None))
+
+    def black_and_white(self, image: RGB, params: BlackAndWhiteParams, ws=None):
+        """ImProcFunctions::blackAndWhite in place on an RGB image (params from black_and_white_params()); ws: the colour cast only"""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel()) if ws is not None else None
+        self._chk(LIB.artgpu_black_and_white(self._h, C.byref(image), C.byref(params) if params is not None else None, wsd))
+
+    bw_mixer_constants = staticmethod(bw_mixer_constants)
+
+    def set_pipeline_black_and_white(self, params: BlackAndWhiteParams = None):
+        """black-and-white in pipeline_run / batch_run / batch_run_io: behind local contrast (None: off).  The library copies parameters and tables."""
+        self._chk(LIB.artgpu_set_pipeline_black_and_white(self._h, C.byref(params) if params is not None else None))
 
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""

@@ -31,6 +31,8 @@
 #include "resize.h"
 #include "masks.h"
 #include "sharpen.h"
+#include "blackwhite.h"
+#include "creativegradients.h"
 
 struct artgpu_ctx {
     int device = 0;
@@ -99,6 +101,12 @@ struct artgpu_ctx {
         artgpu_film_grain_params pipe_fg = {};
         int pipe_rs_on = 0;            // artgpu_set_pipeline_resize: a copy by value
         artgpu_resize_params pipe_rs = {};
+        int pipe_cg_on = 0;            // artgpu_set_pipeline_creative_gradients: a copy by value
+        artgpu_creative_gradients_params pipe_cg = {};
+        int pipe_sl_on = 0;            // artgpu_set_pipeline_soft_light: a copy by value
+        artgpu_soft_light_params pipe_sl = {};
+        int pipe_bw_on = 0;            // artgpu_set_pipeline_black_and_white: a copy by value; its ulut / vlut point into the parent's pipe_bw_tabs
+        artgpu_black_and_white_params pipe_bw = {};
     } shared;
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
@@ -108,6 +116,7 @@ struct artgpu_ctx {
     template <typename Region> struct PipeRegions { std::vector<Region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; };
     PipeRegions<artgpu_color_correction_region> pipe_cc_own;
     PipeRegions<artgpu_smoothing_region> pipe_sm_own;
+    std::vector<float> pipe_bw_tabs;       // artgpu_set_pipeline_black_and_white: the cast's two tables (batch lanes point at their parent's)
     artgpu_clut *pipe_fs_own = nullptr;    // artgpu_set_pipeline_film_simulation: the reference this context holds (batch lanes hold none)
     std::string err;
     int *fs_diag = nullptr;        // pinned host words the fused shrink pass writes before it traps (which strip waited for which): see fail()
@@ -168,6 +177,16 @@ struct artgpu_ctx {
     int rs_support = 0, rs_tile_w = 0;
     std::vector<int> rs_host;
     const float *rs_dev = nullptr;
+    // soft light's table (api_softlight.hip): the strength the host copy was built for, the copy, and where in P_SL_LUT (a slot nothing else
+    // writes) it was uploaded to: rebuilt when the strength changes, uploaded again when the slot moved
+    int sl_lut_strength = -1;
+    std::vector<float> sl_lut_host;
+    const float *sl_lut_dev = nullptr;
+    // black-and-white's tables (api_blackwhite.hip) in P_BW_TAB (a slot nothing else writes): [gamma r | g | b | ulut | vlut], 65536 floats each.
+    // The host copy of each, what the gamma tables were built for, and where they were uploaded to
+    std::vector<float> bw_tab_host[5];
+    float bw_gam_key[3] = {};
+    const float *bw_tab_dev = nullptr;
     // timing
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -236,6 +255,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_TE_PLANES, P_TE_LUT,                                                                                           // artgpu_tone_equalizer
        P_RS_TAB, P_RS_IMG0, P_RS_IMG1, P_RS_IMG2,                                                                       // artgpu_resize_lanczos: the tables; the pipe's full-size working image
        P_FG_WORK, P_FG_TAB, P_FG_IDX,                                                                                   // artgpu_film_grain: the planes a region writes, its tables; artgpu_grain_indices
+       P_SL_LUT, P_BW_TAB,                                                                                              // artgpu_soft_light's table; artgpu_black_and_white's gamma and cast tables
        P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
@@ -480,6 +500,23 @@ struct FgPlan { artgpu_film_grain_info info; double scale; };
 int fg_check(artgpu_ctx *ctx, int W, int H, const artgpu_film_grain_params *p, const double *ws, double scale, int output_pipeline, const char *who, FgPlan *pl);
 // the tool on device planes (rows of `stride` floats) in RGB mode, after fg_check; enqueued on ctx->stream
 int film_grain_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const double ws[9], const FgPlan &pl);
+
+// ---------------------------------------------------------------------------------------------
+// creative gradients, soft light, black-and-white
+// ---------------------------------------------------------------------------------------------
+// every reason not to run, and the derived parameters of the filters that do (apply_gradient / apply_pcvignette; both 0: nothing runs)
+int cg_check(artgpu_ctx *ctx, int W, int H, const artgpu_creative_gradients_params *p, const char *who, CgDerived *d);
+// the tool on device planes in RGB mode, after cg_check; one launch on ctx->stream
+int creative_gradients_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const CgDerived &d);
+// every reason not to run, and what the call derives on the host; nothing is uploaded or launched.  on == 0: the tool returns at once
+struct SlPlan { int on, strength; };
+int sl_check(artgpu_ctx *ctx, const artgpu_soft_light_params *p, const char *who, SlPlan *pl);
+// the tool on a device image in RGB mode, after sl_check; one launch on ctx->stream
+int soft_light_dev(artgpu_ctx *ctx, const DevRGB &d, const SlPlan &pl);
+struct BwPlan { int on, hasgamma; BwMixer mix; float gam[3]; const float *ulut, *vlut; };
+int bw_check(artgpu_ctx *ctx, const artgpu_black_and_white_params *p, const double *ws, const char *who, BwPlan *pl);
+// the tool on device planes in RGB mode, after bw_check; one launch on ctx->stream.  to_rgb: with a cast, leave in RGB mode (else YUV)
+int black_and_white_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, int H, const double *ws, const BwPlan &pl, int to_rgb);
 
 // ---------------------------------------------------------------------------------------------
 // resize

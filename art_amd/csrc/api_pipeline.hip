@@ -104,6 +104,9 @@ struct PipePlan {
     artgpu_tone_equalizer_info te;
     bool fs_on;                                                    // film simulation (artgpu_set_pipeline_film_simulation)
     FgPlan fg;                                                     // film grain (artgpu_set_pipeline_film_grain): the derived regions, none when off
+    CgDerived cg;                                                  // the graduated / vignette filters (artgpu_set_pipeline_creative_gradients): both apply_* 0 when off
+    SlPlan sl;                                                     // soft light (artgpu_set_pipeline_soft_light), black-and-white (artgpu_set_pipeline_black_and_white):
+    BwPlan bw;                                                     // `on` is 0 when off
     bool rs_on;                                                    // the Resize tool (artgpu_set_pipeline_resize) changes this frame's size: to imw x imh
     int imw, imh;
     float rs_scale;
@@ -139,10 +142,11 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 
 // Checks and derives everything; launches nothing and takes no pool slot, so a refused frame leaves the output planes alone.  The checks, in the
 // order they report (a frame that is wrong in two ways names the first):
-//   1. ctx, raw / p / out, the border, the Resize tool's result, the output's size (then hipSetDevice, the one HIP call here; then rs_check)   2. artgpu_set_pipeline_masks' counts against the frame's
+//   1. ctx, raw / p / out, the border, the Resize tool's result, the output's size (then hipSetDevice, the one HIP call here; then rs_check; then cg_check,
+//   whose result the mode walk needs)   2. artgpu_set_pipeline_masks' counts against the frame's
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
-//   8. dehaze_check, te_check, fs_check, fg_check   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
+//   8. dehaze_check, te_check, fs_check, fg_check, sl_check, bw_check (and a colour cast in front of the Resize tool)   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
 //   then the oldest stages in the order they run:   11. the CA correction's pattern and size (do_ca), demosaic_bayer_check / demosaic_xtrans_check
 //   12. dn_compute_params_check (AUTOMATIC chroma)   13. denoise_tool_check   14. tone_curve_check / tone_neutral_check
 // What is left to the stages is a refusal that depends on a number computed on the device: the automatic sharpening radius (pipe_stage2).  RGB_denoise's
@@ -181,6 +185,13 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     PipeMode mode = pl->cc_on ? PIPE_YUV : PIPE_RGB;           // (sharpening: RGB in, RGB out)
     const bool sm_masks_from_yuv = pl->sm_gen && mode == PIPE_YUV;
     if (pl->sm_on) mode = PIPE_RGB;
+    // creativeGradients, the first step of STAGE_3, starts with setMode(RGB): behind colour correction that is the switch colour correction ends with
+    if (s.pipe_cg_on) {
+        artgpu_creative_gradients_params cgp = s.pipe_cg;
+        cgp.offset_x = cgp.offset_y = 0; cgp.full_width = w; cgp.full_height = h; cgp.scale = 1.0;
+        if ((rc = cg_check(ctx, w, h, &cgp, "pipeline_run(creative gradients)", &pl->cg))) return rc;
+        if (pl->cg.apply_gradient || pl->cg.apply_pcvignette) mode = PIPE_RGB;
+    }
     const bool tb_masks_from_yuv = pl->tb_gen && mode == PIPE_YUV;
     pl->tb_in_yuv = pl->tb_on && mode == PIPE_YUV;
     pl->cc_to_rgb = !pl->tb_in_yuv;
@@ -224,6 +235,10 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     pl->fs_on = s.pipe_fs != nullptr;
     if (pl->fs_on && (rc = fs_check(ctx, s.pipe_fs, &s.pipe_fs_par, "pipeline_run(film simulation)"))) return rc;
     if (s.pipe_fg_on && (rc = fg_check(ctx, w, h, &s.pipe_fg, p->ws, scale, 1, "pipeline_run(film grain)", &pl->fg))) return rc;      // (the batch pipe is the OUTPUT pipeline)
+    if (s.pipe_sl_on && (rc = sl_check(ctx, &s.pipe_sl, "pipeline_run(soft light)", &pl->sl))) return rc;
+    if (s.pipe_bw_on && (rc = bw_check(ctx, &s.pipe_bw, p->ws, "pipeline_run(black and white)", &pl->bw))) return rc;
+    if (pl->bw.on && pl->bw.ulut && pl->rs_on)
+        return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run(black and white): the colour cast leaves the image in YUV mode, which the Resize tool's switch to LAB does not start from");
     // sharpening (STAGE_2): method, scale and, with the automatic radius, the sensor are checked before any stage runs
     pl->shpar = p->sharpening;
     pl->sh_on = p->sharpening_enabled != 0;
@@ -394,8 +409,8 @@ static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const P
     return ARTGPU_OK;
 }
 
-// STAGE_3 of ImProcFunctions::process and what follows: textureBoost, filmGrain, filmSimulation on either side of the tone curve, localContrast, [the Resize
-// tool]; then the image goes back to the caller's planes
+// STAGE_3 of ImProcFunctions::process and what follows: creativeGradients, textureBoost, filmGrain, filmSimulation on either side of the tone curve, softLight, localContrast,
+// blackAndWhite, [the Resize tool]; then the image goes back to the caller's planes
 static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePlan &pl, artgpu_rgb *out, PipeFrame *fr)
 {
     const DevRGB &d = fr->d;
@@ -403,7 +418,9 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
     const artgpu_ctx::Shared &s = ctx->shared;
     std::vector<artgpu_plane> gen;
     int rc;
-    // ImProcFunctions::textureBoost, the first arithmetic step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
+    // ImProcFunctions::creativeGradients, the first step of STAGE_3 (improcfun.cc:605)
+    if ((rc = creative_gradients_dev(ctx, d.p, d.stride, d.w, d.h, pl.cg))) return rc;
+    // ImProcFunctions::textureBoost, the next step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
     if (pl.tb_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_tb, pl.tb_mk, ntb, false, &gen))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     for (int i = 0; i < ntb && pl.tb_gen; ++i) pl.tb_regs[i].mask = &gen[i];
     if (pl.tb_on && (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, pl.tb_regions, ntb, p->ws, pl.tb, 1, nullptr, pl.tb_in_yuv))) return rc;
@@ -422,19 +439,24 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
     }
     // ... or right behind it (filmSimulation.after_tone_curve, L618-620)
     if (pl.fs_on && s.pipe_fs_after && (rc = film_simulation_dev(ctx, d.p, d.stride, d.w, d.h, s.pipe_fs, &s.pipe_fs_par))) return rc;
+    // ImProcFunctions::softLight (improcfun.cc:623): setMode(RGB) is a no-op here
+    if (pl.sl.on && (rc = soft_light_dev(ctx, d, pl.sl))) return rc;
     // ImProcFunctions::localContrast (improcfun.cc:625): setMode(LAB), [generateMasks on the LAB image, iplocalcontrast.cc:454,] the regions on the
     // L plane (Imagefloat::g), back to RGB
     if (pl.lc_on) {
         if ((rc = lab_switch_dev(ctx, d, p->ws, true)) || (pl.lc_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_lc, pl.lc_mk, nlc, false, &gen)))) return rc;
         for (int i = 0; i < nlc && pl.lc_gen; ++i) pl.lc_regs[i].mask = &gen[i];
         if ((rc = local_contrast_dev(ctx, d.p[1], d.stride, d.w, d.h, pl.lc_regions, nlc, nullptr))) return rc;
-        // (with the Resize tool the image stays in LAB mode, as in the reference: iplocalcontrast.cc:441 does not switch back)
-        if (!pl.rs_on && (rc = lab_switch_dev(ctx, d, p->iws, false))) return rc;
+        // (with the Resize tool the image stays in LAB mode, as in the reference: iplocalcontrast.cc:441 does not switch back; blackAndWhite's
+        // setMode(RGB) is that switch when the tool is on)
+        if ((!pl.rs_on || pl.bw.on) && (rc = lab_switch_dev(ctx, d, p->iws, false))) return rc;
     }
+    // ImProcFunctions::blackAndWhite (improcfun.cc:627).  With a colour cast the reference leaves YUV; the next setMode(RGB) (rgb2out's) happens here
+    if (pl.bw.on && (rc = black_and_white_dev(ctx, d.p, d.stride, d.w, d.h, p->ws, pl.bw, 1))) return rc;
     if (!pl.rs_on) return unbind_rgb(ctx, out, &d);
     // ImProcFunctions::resize (simpleprocess.cc:402-414): Lanczos' setMode(LAB) is a no-op behind localContrast; the switch to RGB happens on the
-    // small image (iprgb2out.cc:455)
-    if ((rc = resize_dev(ctx, d, fr->small, pl.rs_scale, pl.lc_on ? nullptr : p->ws, p->iws))) return rc;
+    // small image (iprgb2out.cc:455); behind blackAndWhite the image is in RGB mode, whatever ran before
+    if ((rc = resize_dev(ctx, d, fr->small, pl.rs_scale, pl.lc_on && !pl.bw.on ? nullptr : p->ws, p->iws))) return rc;
     return unbind_rgb(ctx, out, &fr->small);
 }
 

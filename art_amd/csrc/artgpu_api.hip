@@ -569,6 +569,8 @@ int artgpu_trim_scratch(artgpu_ctx *ctx)
     ctx->ncurve_host.clear();
     for (int k = 0; k < 3; ++k) ctx->rgbcurve_host[k].clear();
     ctx->te_lut_dev = nullptr;
+    ctx->sl_lut_dev = nullptr;
+    ctx->bw_tab_dev = nullptr;
     ctx->rs_dev = nullptr;
     int rc = ARTGPU_OK;
     for (artgpu_ctx *l : ctx->lanes) { const int r = artgpu_trim_scratch(l); if (r && !rc) rc = r; }

@@ -188,6 +188,43 @@ __device__ __forceinline__ void xsincosf_v(float d, float &sn, float &cs)
     sn = x; cs = y;
 }
 
+// xsinf(float) (rtengine/sleef.h:993-1016), the scalar form; xrintf is cvtss2si, round to nearest even
+__device__ __forceinline__ float xsinf_s(float d)
+{
+    const int q = __float2int_rn(d * (float)0.31830988618379067154);
+    const float qf = (float)q;
+    d = sl_mla(qf, -0.78515625f * 4, d);
+    d = sl_mla(qf, -0.00024127960205078125f * 4, d);
+    d = sl_mla(qf, -6.3329935073852539062e-07f * 4, d);
+    d = sl_mla(qf, -4.9604681473525147339e-10f * 4, d);
+    const float s = d * d;
+    if ((q & 1) != 0) d = -d;
+    float u = 2.6083159809786593541503e-06f;
+    u = sl_mla(u, s, -0.0001981069071916863322258f);
+    u = sl_mla(u, s, 0.00833307858556509017944336f);
+    u = sl_mla(u, s, -0.166666597127914428710938f);
+    return sl_mla(s, u * d, d);
+}
+// xcosf(float) under SSE2 = lane 0 of the vector form (sleef.h:1018-1021 -> sleefsseavx.h:1024-1049): the 0.5f is subtracted from the rounded
+// product before the rounding to an integer, q = 2 * rint + 1, and the sign follows bit 1 of q
+__device__ __forceinline__ float xcosf_s(float d)
+{
+    int q = __float2int_rn(d * (float)0.31830988618379067154 - 0.5f);
+    q = q + q + 1;
+    const float qf = (float)q;
+    d = sl_mla(qf, -0.78515625f * 2, d);
+    d = sl_mla(qf, -0.00024127960205078125f * 2, d);
+    d = sl_mla(qf, -6.3329935073852539062e-07f * 2, d);
+    d = sl_mla(qf, -4.9604681473525147339e-10f * 2, d);
+    const float s = d * d;
+    if ((q & 2) != 2) d = -d;
+    float u = 2.6083159809786593541503e-06f;
+    u = sl_mla(u, s, -0.0001981069071916863322258f);
+    u = sl_mla(u, s, 0.00833307858556509017944336f);
+    u = sl_mla(u, s, -0.166666597127914428710938f);
+    return sl_mla(s, u * d, d);
+}
+
 // pow_F, xlin2log, xlog2lin (rtengine/sleef.h:1296-1313): scalar exp / log forms
 __device__ __forceinline__ float pow_F(float a, float b) { return xexpf_s(b * xlogf_s(a)); }
 __device__ __forceinline__ float xlin2log(float x, float base) { return xlogf_s(x * (base - 1.f) + 1.f) / xlogf_s(base); }

@@ -8,6 +8,8 @@
 #include "kernels.h"
 #include "toneequalizer.h"
 #include "filmgrain.h"
+#include "blackwhite.h"
+#include "creativegradients.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -486,6 +488,222 @@ void build_grain_jump(FgJump *j)
         j->A[b] = (j->A[b - 1] * j->A[b - 1]) & FG_MASK48;
         j->C[b] = (j->A[b - 1] * j->C[b - 1] + j->C[b - 1]) & FG_MASK48;
     }
+}
+
+// ---------------------------------------------------------------- soft light's table, black-and-white's mixer constants and gamma tables
+namespace {
+// LUTf::operator[](float) (LUT.h:436-459) on the host; clip: LUT_CLIP_BELOW | LUT_CLIP_ABOVE set (the constructor's default) or neither (flags 0)
+float hs_lutf(const float *data, int size, float index, bool clip)
+{
+    const int maxs = size - 2;
+    int idx = (int)index;
+    if (index < 0.f || !(index == index)) {
+        if (clip) return data[0];
+        idx = 0;
+    } else if (index > (float)maxs) {
+        if (clip) return data[size - 1];
+        idx = maxs;
+    }
+    const float diff = index - (float)idx;
+    const float p1 = data[idx];
+    const float p2 = data[idx + 1] - p1;
+    return p1 + p2 * diff;
+}
+} // namespace
+
+// ImProcFunctions::softLight's LUTf f (ipsoftlight.cc:31-41, 55-60): f[i] = sl(blend, i).  Color::gamma_srgb / igamma_srgb are float-indexed
+// lookups in gammatab_srgb / igammatab_srgb, tables with flags 0 (color.cc:183-185): index 65535 goes through the extrapolating branch
+void build_soft_light_lut(int strength, float *lut)
+{
+    std::vector<float> gam(65536), igam(65536);
+    build_gamma2curve(gam.data());
+    build_igammatab_srgb(igam.data());
+    const float blend = strength / 100.f;
+    for (int i = 0; i < 65536; ++i) {
+        float x = i;
+        float v = hs_lutf(gam.data(), 65536, x, false) / 65535.f;
+        const float v2 = v * v;
+        const float v22 = v2 * 2.f;
+        v = v2 + v22 - v22 * v;                                                   // Pegtop's formula
+        const float b = hs_lutf(igam.data(), 65536, v * 65535.f, false);
+        lut[i] = blend * b + (1.f - blend) * x;                                   // intp (rt_math.h:110-118)
+    }
+}
+
+// computeBWMixerConstants (ipbw.cc:50-211) with algo "" as blackAndWhite calls it, statement by statement.  L192-194 are part of the
+// definition: each of the three uses the mixer values the line before it has already overwritten.  kcorec comes in as 1.f (L258)
+void bw_mixer_constants(int setting, int filter, float mixerRed, float mixerGreen, float mixerBlue, BwMixer *o)
+{
+    static const float presets[BW_NPRESETS][3] = {{43.f, 33.f, 30.f}, {33.3f, 33.3f, 33.3f}, {41.f, 25.f, 34.f}, {27.f, 27.f, 46.f}, {30.f, 28.f, 42.f}, {0.f, 42.f, 58.f},
+                                                  {40.f, 34.f, 60.f}, {30.f, 59.f, 11.f}, {66.f, 24.f, 10.f}, {54.f, 44.f, 12.f}, {-40.f, 200.f, -17.f}};
+    static const float filters[BW_NFILTERS][4] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 0.05f, 0.f, 1.08f}, {1.f, 0.6f, 0.f, 1.35f}, {1.f, 1.f, 0.05f, 1.23f}, {0.6f, 1.f, 0.3f, 1.32f},
+                                                  {0.2f, 1.f, 0.3f, 1.41f}, {0.05f, 1.f, 1.f, 1.23f}, {0.f, 0.05f, 1.f, 1.20f}, {1.f, 0.05f, 1.f, 1.23f}};
+    float kcorec = 1.f;
+    float somm;
+    float som = mixerRed + mixerGreen + mixerBlue;
+    if (som >= 0.f && som < 1.f) som = 1.f;
+    if (som < 0.f && som > -1.f) som = -1.f;
+    if (setting >= 0 && setting < BW_NPRESETS) {
+        mixerRed = presets[setting][0];
+        mixerGreen = presets[setting][1];
+        mixerBlue = presets[setting][2];
+    }
+    if (setting == BW_RGB_ABS || setting == BW_ROYGCBPM_ABS) kcorec = som / 100.f;
+    o->rrm = mixerRed;
+    o->ggm = mixerGreen;
+    o->bbm = mixerBlue;
+    somm = mixerRed + mixerGreen + mixerBlue;
+    if (somm >= 0.f && somm < 1.f) somm = 1.f;
+    if (somm < 0.f && somm > -1.f) somm = -1.f;
+    mixerRed = mixerRed / somm;
+    mixerGreen = mixerGreen / somm;
+    mixerBlue = mixerBlue / somm;
+    float filred = 1.f, filgreen = 1.f, filblue = 1.f, filcor = 1.f;
+    if (filter >= 0 && filter < BW_NFILTERS) {
+        filred = filters[filter][0];
+        filgreen = filters[filter][1];
+        filblue = filters[filter][2];
+        filcor = filters[filter][3];
+    }
+    mixerRed = mixerRed * filred;
+    mixerGreen = mixerGreen * filgreen;
+    mixerBlue = mixerBlue * filblue;
+    if (mixerRed + mixerGreen + mixerBlue == 0) mixerRed += 1.f;
+    mixerRed = filcor * mixerRed / (mixerRed + mixerGreen + mixerBlue);
+    mixerGreen = filcor * mixerGreen / (mixerRed + mixerGreen + mixerBlue);
+    mixerBlue = filcor * mixerBlue / (mixerRed + mixerGreen + mixerBlue);
+    if (filter != 0) {
+        som = mixerRed + mixerGreen + mixerBlue;
+        if (som >= 0.f && som < 1.f) som = 1.f;
+        if (som < 0.f && som > -1.f) som = -1.f;
+        if (setting == BW_RGB_ABS) kcorec = kcorec * som;
+    }
+    o->bwr = mixerRed; o->bwg = mixerGreen; o->bwb = mixerBlue; o->kcorec = kcorec; o->filcor = filcor;
+}
+
+// blackAndWhite's gamma exponent of one channel (ipbw.cc:225-251) and its table (L268-272)
+float bw_gamma_of(int gam)
+{
+    const float bwgam = float(gam);
+    const float gamval = bwgam < 0 ? 100.f : 125.f;
+    return 1.f - bwgam / gamval;
+}
+void build_bw_gamma_table(float gamma, float *lut)
+{
+    for (int i = 0; i < 65536; ++i) lut[i] = hs_pow_F(float(i) / 65535.f, gamma) * 65535.f;
+}
+
+// ---------------------------------------------------------------- the graduated filter's and the vignette filter's derived parameters
+// calcGradientParams (iptransform.cc:677-758), statement by statement.  Unqualified sqrt / fabs / cos / tan / fmod / pow are the overloads the
+// reference's translation unit sees (rtengine.h pulls in <math.h> through lcms2.h, so the global names carry the float overloads): sqrt of the
+// float sum is the float one, everything on gradient_angle is double
+void cg_gradient_params(int oW, int oH, const CgInput &gradient, CgDerived *gp)
+{
+    constexpr double RT_PI = 3.14159265358979323846;
+    int w = oW;
+    int h = oH;
+    double gradient_stops = gradient.strength;
+    double gradient_span = gradient.feather / 100.0;
+    double gradient_center_x = gradient.center_x / 200.0 + 0.5;
+    double gradient_center_y = gradient.center_y / 200.0 + 0.5;
+    double gradient_angle = gradient.degree / 180.0 * RT_PI;
+    gradient_angle = std::fmod(gradient_angle, 2 * RT_PI);
+    if (gradient_angle < 0.0) gradient_angle += 2.0 * RT_PI;
+    bool bright_top = false, transpose = false, angle_is_zero = false;
+    gp->h = h;
+    double cosgrad = std::cos(gradient_angle);
+    if (std::fabs(cosgrad) < 0.707) {
+        transpose = true;
+        gradient_angle += 0.5 * RT_PI;
+        double gxc = gradient_center_x;
+        gradient_center_x = 1.0 - gradient_center_y;
+        gradient_center_y = gxc;
+    }
+    gradient_angle = std::fmod(gradient_angle, 2 * RT_PI);
+    if (gradient_angle > 0.5 * RT_PI && gradient_angle < RT_PI) {
+        gradient_angle += RT_PI;
+        bright_top = true;
+    } else if (gradient_angle >= RT_PI && gradient_angle < 1.5 * RT_PI) {
+        gradient_angle -= RT_PI;
+        bright_top = true;
+    }
+    if (std::fabs(gradient_angle) < 0.001 || std::fabs(gradient_angle - 2 * RT_PI) < 0.001) {
+        gradient_angle = 0;
+        angle_is_zero = true;
+    }
+    if (transpose) bright_top = !bright_top;
+    if (transpose) { int tmp = w; w = h; h = tmp; }
+    gp->scale = 1.0 / std::pow(2.0, gradient_stops);           // pow(int, double) promotes the 2
+    if (bright_top) { gp->topmul = 1.0; gp->botmul = gp->scale; }
+    else { gp->topmul = gp->scale; gp->botmul = 1.0; }
+    gp->ta = std::tan(gradient_angle);
+    gp->xc = w * gradient_center_x;
+    gp->yc = h * gradient_center_y;
+    gp->ys = std::sqrt((float)h * h + (float)w * w) * (gradient_span / std::cos(gradient_angle));     // float sqrt, double product
+    gp->ys_inv = 1.0 / gp->ys;
+    gp->top_edge_0 = gp->yc - gp->ys / 2.0;
+    if (gp->ys < 1.0 / h) {
+        gp->ys_inv = 0;
+        gp->ys = 0;
+    }
+    gp->bright_top = bright_top; gp->transpose = transpose; gp->angle_is_zero = angle_is_zero;
+}
+
+// calcPCVignetteParams (L828-895): powf is the host libm's, as in the reference; the int fields truncate their float expressions
+void cg_pcvignette_params(int fW, int fH, int oW, int oH, const CgInput &pcvignette, CgDerived *pcv)
+{
+    double roundness = pcvignette.pcv_roundness / 100.0;
+    pcv->feather = pcvignette.pcv_feather / 100.0;
+    if (pcvignette.crop_enabled) {
+        float sW = float(oW) / fW;
+        float sH = float(oH) / fH;
+        pcv->ew = pcvignette.crop_w * sW;
+        pcv->eh = pcvignette.crop_h * sH;
+        pcv->x1 = pcvignette.crop_x * sW;
+        pcv->y1 = pcvignette.crop_y * sH;
+    } else {
+        pcv->ew = oW;
+        pcv->eh = oH;
+        pcv->x1 = 0;
+        pcv->y1 = 0;
+    }
+    float dW = pcvignette.pcv_center_x / 200.f * pcv->ew;
+    float dH = pcvignette.pcv_center_y / 200.f * pcv->eh;
+    pcv->ex = pcv->x1 + dW;
+    pcv->ey = pcv->y1 + dH;
+    pcv->x2 = pcv->x1 + pcv->ew + std::abs(dW);
+    pcv->y2 = pcv->y1 + pcv->eh + std::abs(dH);
+    pcv->fadeout_mul = 1.0 / (0.05 * sqrtf(oW * oW + oH * oH));
+    float short_side = (pcv->ew < pcv->eh) ? pcv->ew : pcv->eh;
+    float long_side = (pcv->ew > pcv->eh) ? pcv->ew : pcv->eh;
+    pcv->sep = 2;
+    pcv->sepmix = 0;
+    pcv->oe_a = std::sqrt(2.0) * long_side * 0.5;
+    pcv->oe_b = pcv->oe_a * short_side / long_side;
+    pcv->ie_mul = (1.0 / std::sqrt(2.0)) * (1.0 - pcv->feather);
+    pcv->is_super_ellipse_mode = 0;
+    pcv->is_portrait = (pcv->ew < pcv->eh);
+    if (roundness < 0.5) {
+        pcv->is_super_ellipse_mode = 1;
+        float sepf = 2 + 4 * powf(1.0 - 2 * roundness, 1.3);
+        pcv->sep = ((int)sepf) & ~0x1;
+        pcv->sepmix = (sepf - pcv->sep) * 0.5;
+        pcv->oe1_a = powf(2.0, 1.0 / pcv->sep) * long_side * 0.5;
+        pcv->oe1_b = pcv->oe1_a * short_side / long_side;
+        pcv->ie1_mul = (1.0 / powf(2.0, 1.0 / pcv->sep)) * (1.0 - pcv->feather);
+        pcv->oe2_a = powf(2.0, 1.0 / (pcv->sep + 2)) * long_side * 0.5;
+        pcv->oe2_b = pcv->oe2_a * short_side / long_side;
+        pcv->ie2_mul = (1.0 / powf(2.0, 1.0 / (pcv->sep + 2))) * (1.0 - pcv->feather);
+    }
+    if (roundness > 0.5) {
+        float rad = sqrtf(pcv->ew * pcv->ew + pcv->eh * pcv->eh) / 2.0;
+        float diff_a = rad - pcv->oe_a;
+        float diff_b = rad - pcv->oe_b;
+        pcv->oe_a = pcv->oe_a + diff_a * 2 * (roundness - 0.5);
+        pcv->oe_b = pcv->oe_b + diff_b * 2 * (roundness - 0.5);
+    }
+    pcv->pcv_scale = powf(2, -pcvignette.pcv_strength);
+    if (pcvignette.pcv_strength >= 6.0) pcv->pcv_scale = 0.0;
 }
 
 } // namespace artgpu

@@ -104,7 +104,8 @@ hipError_t launch_amaze_stream(const AmazeStreamArgs &s, int grid, hipStream_t s
 // ---- device math primitives on caller arrays (selftest.hip; the ids are the ARTGPU_PRIM_* values of include/artgpu.h) ----
 enum { PRIM_XEXPF_S = 0, PRIM_XEXPF_V, PRIM_XEXPF_VN, PRIM_XEXPF_V_LDEXP, PRIM_XLOGF_S, PRIM_XLOGF_V, PRIM_XLOGF_VN, PRIM_POW_F, PRIM_XLIN2LOG,
        PRIM_XLOG2LIN, PRIM_XCBRTF, PRIM_XATAN2F, PRIM_XSINCOSF, PRIM_LUTF_SCALAR, PRIM_LUTF_VECTOR, PRIM_MEDIAN3, PRIM_VMINF, PRIM_VMAXF,
-       PRIM_VINTPF, PRIM_XDIV2F, PRIM_XDIVF2, PRIM_XLOG_D, PRIM_XEXP_D, PRIM_FLOAT_TO_HALF, PRIM_COUNT };
+       PRIM_VINTPF, PRIM_XDIV2F, PRIM_XDIVF2, PRIM_XLOG_D, PRIM_XEXP_D, PRIM_FLOAT_TO_HALF, PRIM_XSINF_S, PRIM_XCOSF_S,
+       PRIM_COUNT };
 struct PrimArgs {
     int prim;
     long long n;
@@ -188,6 +189,7 @@ struct PixArgs {
     int tail_kind;         // curves::setLutVal above 65535 (artgpu_set_curve_tail): 0 LUT clip, 1 constant, 2 identity, 4 parametric
     double tail_y;
     ParamCurve tail_pc;    // kind 4 (artgpu_set_curve_tail_parametric)
+    int keep_above;        // tone: 1 = soft light's rule (the kernels' KEEP instantiation, no tail): a value that is not <= 65535, NaN included, is stored as it came
     int no_lds_lut;        // artgpu_set_option "lut_lds" 0: the plain one-lane-per-pixel kernels (table lookups served by L2) on every frame size
     int cu_reserve;        // CUs a kernel running BESIDE this frame's holds (artgpu_batch_run_io's download): the persistent one-workgroup-per-CU shape, which shares
                            // no CU with anything, launches that many workgroups fewer -- a workgroup without a CU would start when that kernel ends, 5 ms later
@@ -450,6 +452,7 @@ void build_cachefy(float *lut65536);
 void build_denoise_gamma_tabs(float *gtab65536, float *igtab65536);
 void build_gamma2curve(float *lut65536);        // Color::gamma2curve's values (dehaze's strength table, film simulation)
 void build_igammatab_srgb(float *lut65536);     // Color::igammatab_srgb (film simulation)
+void build_soft_light_lut(int strength, float *lut65536);   // ImProcFunctions::softLight's LUTf f
 
 struct ShrinkArgs {
     float *coef;            // bands of the decomposition being shrunk: [nsub][n]

@@ -110,8 +110,12 @@ __global__ void __launch_bounds__(256) exposure_kernel(PixArgs a)
     }
 }
 
-template <bool PC>
-__global__ void __launch_bounds__(256) tone_std_kernel(PixArgs a)
+// KEEP (PixArgs::keep_above): ImProcFunctions::softLight's `apply` (ipsoftlight.cc:62-70) on the same table shape -- a value that fails
+// x <= 65535.f (above the table, or NaN) stays as it is; everything else is the LUTf lookup with both clip flags, which is what the tone
+// curve's is.  The two pixel loops are written once, as bodies; soft light's kernels (sl_apply_kernel, sl_apply_lds_kernel) are their KEEP
+// instantiations and the tone curve's kernels the others, the code they were
+template <bool PC, bool KEEP>
+__device__ __forceinline__ void tone_std_body(const PixArgs &a)
 {
     const float Lmax = 65535.f * a.whitept;
     FOR_IMAGE_XY(y, x, a.w, a.h) {
@@ -119,22 +123,25 @@ __global__ void __launch_bounds__(256) tone_std_kernel(PixArgs a)
         float r = a.dst[0][di], g = a.dst[1][di], b = a.dst[2][di];
         if (a.do_clip) filmlike_clip_px(r, g, b, Lmax);
         if (a.lut) {
-            r = (a.tail_kind && r > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, r) : lutf(a.lut, 65536, std_max(r, 0.f));
-            g = (a.tail_kind && g > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, g) : lutf(a.lut, 65536, std_max(g, 0.f));
-            b = (a.tail_kind && b > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, b) : lutf(a.lut, 65536, std_max(b, 0.f));
+            r = (KEEP && !(r <= 65535.f)) ? r : (a.tail_kind && r > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, r) : lutf(a.lut, 65536, std_max(r, 0.f));
+            g = (KEEP && !(g <= 65535.f)) ? g : (a.tail_kind && g > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, g) : lutf(a.lut, 65536, std_max(g, 0.f));
+            b = (KEEP && !(b <= 65535.f)) ? b : (a.tail_kind && b > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, b) : lutf(a.lut, 65536, std_max(b, 0.f));
         }
         a.dst[0][di] = r; a.dst[1][di] = g; a.dst[2][di] = b;
     }
 }
 
+template <bool PC>
+__global__ void __launch_bounds__(256) tone_std_kernel(PixArgs a) { tone_std_body<PC, false>(a); }
+__global__ void __launch_bounds__(256) sl_apply_kernel(PixArgs a) { tone_std_body<false, true>(a); }
+
 // The same with the lower LUT_LDS_N entries of the curve resident in LDS (lutf_lookup_lds, devsleef.h; 159 KB of the CU's 160 KB): the 65536-entry LUT
 // (256 KB) does not fit L1, so every lookup of the kernel above is an L2 line gather (6 per pixel, ~1.5 TB/s effective); linear
 // scene data sit mostly in the lower part of the range, and those lookups become LDS reads.  Entries above come from L2 as before.
 // One persistent workgroup of 1024 threads per CU, rows strided over the workgroups.
-template <bool PC>
-__global__ void __launch_bounds__(1024) tone_std_lds_kernel(PixArgs a)
+template <bool PC, bool KEEP>
+__device__ __forceinline__ void tone_std_lds_body(const PixArgs &a, float *tone_lds)
 {
-    extern __shared__ float tone_lds[];
     lut_lds_fill(tone_lds, a.lut, 1024);
     const float Lmax = 65535.f * a.whitept;
     for (int yb = blockIdx.x; yb < a.h; yb += LDSK_ROWS * gridDim.x)
@@ -153,12 +160,24 @@ __global__ void __launch_bounds__(1024) tone_std_lds_kernel(PixArgs a)
                 const size_t di = (size_t)y * a.dst_stride + x;
                 float rr = r[k], gg = g[k], bb = b[k];
                 if (a.do_clip) filmlike_clip_px(rr, gg, bb, Lmax);
-                rr = (a.tail_kind && rr > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, rr) : lutf_lookup_lds<true>(tone_lds, a.lut, 65536, std_max(rr, 0.f));
-                gg = (a.tail_kind && gg > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, gg) : lutf_lookup_lds<true>(tone_lds, a.lut, 65536, std_max(gg, 0.f));
-                bb = (a.tail_kind && bb > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, bb) : lutf_lookup_lds<true>(tone_lds, a.lut, 65536, std_max(bb, 0.f));
+                rr = (KEEP && !(rr <= 65535.f)) ? rr : (a.tail_kind && rr > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, rr) : lutf_lookup_lds<true>(tone_lds, a.lut, 65536, std_max(rr, 0.f));
+                gg = (KEEP && !(gg <= 65535.f)) ? gg : (a.tail_kind && gg > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, gg) : lutf_lookup_lds<true>(tone_lds, a.lut, 65536, std_max(gg, 0.f));
+                bb = (KEEP && !(bb <= 65535.f)) ? bb : (a.tail_kind && bb > 65535.f) ? curve_tail<PC>(a.tail_kind, a.tail_y, a.tail_pc, bb) : lutf_lookup_lds<true>(tone_lds, a.lut, 65536, std_max(bb, 0.f));
                 a.dst[0][di] = rr; a.dst[1][di] = gg; a.dst[2][di] = bb;
             }
         }
+}
+
+template <bool PC>
+__global__ void __launch_bounds__(1024) tone_std_lds_kernel(PixArgs a)
+{
+    extern __shared__ float tone_lds[];
+    tone_std_lds_body<PC, false>(a, tone_lds);
+}
+__global__ void __launch_bounds__(1024) sl_apply_lds_kernel(PixArgs a)
+{
+    extern __shared__ float tone_lds[];
+    tone_std_lds_body<false, true>(a, tone_lds);
 }
 
 // Imagefloat::setMode RGB -> YUV (imagefloat.cc:700-725: Y -> g plane, u = Y-b -> b plane, v = r-Y -> r plane) and
@@ -462,16 +481,19 @@ hipError_t launch_tone_std(const PixArgs &a, hipStream_t s)
     if (a.lut && (long long)a.w * a.h >= (1 << 22) && (reinterpret_cast<uintptr_t>(a.lut) & 15) == 0 && !a.no_lds_lut && device_block_fits(LUT_LDS_N * (int)sizeof(float), 1024)) {
         const size_t lds = (size_t)LUT_LDS_N * sizeof(float);
         const bool pc = a.tail_kind == 4;
-        hipError_t e = hipFuncSetAttribute(pc ? reinterpret_cast<const void *>(tone_std_lds_kernel<true>) : reinterpret_cast<const void *>(tone_std_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(a.keep_above ? reinterpret_cast<const void *>(sl_apply_lds_kernel) :
+                                           pc ? reinterpret_cast<const void *>(tone_std_lds_kernel<true>) : reinterpret_cast<const void *>(tone_std_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (a.cu_reserve > 0) cus = cus - a.cu_reserve > 1 ? cus - a.cu_reserve : 1;
-        if (pc) hipLaunchKernelGGL(tone_std_lds_kernel<true>, dim3(cus < a.h ? cus : a.h), dim3(1024), lds, s, a);
+        if (a.keep_above) hipLaunchKernelGGL(sl_apply_lds_kernel, dim3(cus < a.h ? cus : a.h), dim3(1024), lds, s, a);
+        else if (pc) hipLaunchKernelGGL(tone_std_lds_kernel<true>, dim3(cus < a.h ? cus : a.h), dim3(1024), lds, s, a);
         else hipLaunchKernelGGL(tone_std_lds_kernel<false>, dim3(cus < a.h ? cus : a.h), dim3(1024), lds, s, a);
         return hipGetLastError();
     }
-    if (a.tail_kind == 4) hipLaunchKernelGGL(tone_std_kernel<true>, image_grid(a.w, a.h), dim3(256), 0, s, a);
+    if (a.keep_above) hipLaunchKernelGGL(sl_apply_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a);
+    else if (a.tail_kind == 4) hipLaunchKernelGGL(tone_std_kernel<true>, image_grid(a.w, a.h), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(tone_std_kernel<false>, image_grid(a.w, a.h), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -43,6 +43,8 @@ __global__ void __launch_bounds__(256) prim_eval_kernel(PrimArgs p)
     case PRIM_XLOG_D: ((double *)p.out0)[i] = pc_xlog(((const double *)p.a)[i]); break;
     case PRIM_XEXP_D: ((double *)p.out0)[i] = pc_xexp(((const double *)p.a)[i]); break;
     case PRIM_FLOAT_TO_HALF: ((unsigned *)p.out0)[i] = float_to_half_dng(a[i]); break;     // (32-bit words: the half in the low 16 bits)
+    case PRIM_XSINF_S: o0[i] = xsinf_s(a[i]); break;
+    case PRIM_XCOSF_S: o0[i] = xcosf_s(a[i]); break;
     default: break;
     }
 }

@@ -38,8 +38,14 @@
 //                                                      color != 0 adds the chrominance region)
 //              [--resize-scale S | --resize-fit WxH]   (the Resize tool behind STAGE_3, simpleprocess.cc:402-414: ImProcFunctions::resizeScale with
 //                                                      dataspec 0 (scale S) or 3 (fit the W x H box; never upscales), then ImProcFunctions::resize)
+//              [--gradient DEG,FEATHER,STRENGTH,CX,CY] [--vignette STRENGTH,FEATHER,ROUNDNESS,CX,CY]   (ImProcFunctions::creativeGradients, the first step
+//                                                      of STAGE_3: the graduated filter's GradientParams and the vignette filter's PCVignetteParams)
+//              [--soft-light N]                        (ImProcFunctions::softLight behind the tone curve: strength 0 .. 100)
+//              [--bw SETTING[,FILTER[,R,G,B[,GR,GG,GB]]]]   (ImProcFunctions::blackAndWhite, the last step of STAGE_3: SETTING and FILTER by the
+//                                                      reference's names (NormalContrast .. InfraRed, RGB-Rel, RGB-Abs, ROYGCBPM-Rel, ROYGCBPM-Abs; None, Red ..
+//                                                      Purple), the mixer's and the gamma's red, green and blue)
 //   artgpu-cli --batch a.u16,b.u16,... --width W --height H [--lanes N] [--black B] [--method ..] [--denoise L,C] [--expcomp E] [--ca ..] [--dehaze ..] [--sharpen ..]
-//              [--tone-equalizer ..] [--film-simulation ..] [--film-grain ..] [--resize-scale ..] [--resize-fit ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
+//              [--tone-equalizer ..] [--film-simulation ..] [--film-grain ..] [--gradient ..] [--vignette ..] [--soft-light ..] [--bw ..] [--resize-scale ..] [--resize-fit ..] [--texture-boost ..] [--texture-boost-mask ..] [--color-correction ..] [--color-correction-mask ..] [--smoothing ..] [--smoothing-mask ..] [--out prefix]
 //              the batch queue's loop (simpleprocess.cc:586-612): uint16 sensor frames through scaleColors + the same stages, 16-bit
 //              scanlines as the writers take them (getScanline: clip and truncate), written as prefix.K.ppm; artgpu_batch_run_io
 #include <cctype>
@@ -120,6 +126,10 @@ int main(int argc, char **argv)
     bool rs_enable = false;                                        // ResizeParams
     int rs_dataspec = 0, rs_width = 900, rs_height = 900;
     double rs_scale = 1.0;
+    bool gr_enable = false, pv_enable = false, sl_enable = false, bw_enable = false;      // GradientParams, PCVignetteParams, SoftLightParams, BlackWhiteParams
+    double gr_degree = 0.0, gr_strength = 0.6, pv_strength = 0.6;
+    int gr_feather = 25, gr_cx = 0, gr_cy = 0, pv_feather = 50, pv_roundness = 50, pv_cx = 0, pv_cy = 0, sl_strength = 30;
+    int bw_setting = ARTGPU_BW_RGB_REL, bw_filter = ARTGPU_BW_FILTER_NONE, bw_mix[3] = {33, 33, 33}, bw_gam[3] = {0, 0, 0};
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -276,6 +286,30 @@ int main(int argc, char **argv)
             if (std::sscanf(next(), "%d,%d,%d", &fg_iso, &fg_strength, &fg_color) < 2) { std::fprintf(stderr, "--film-grain iso,strength[,color]\n"); return 2; }
             fg_enable = true;
         }
+        else if (a == "--gradient") {
+            if (std::sscanf(next(), "%lf,%d,%lf,%d,%d", &gr_degree, &gr_feather, &gr_strength, &gr_cx, &gr_cy) != 5) { std::fprintf(stderr, "--gradient DEG,FEATHER,STRENGTH,CX,CY\n"); return 2; }
+            gr_enable = true;
+        }
+        else if (a == "--vignette") {
+            if (std::sscanf(next(), "%lf,%d,%d,%d,%d", &pv_strength, &pv_feather, &pv_roundness, &pv_cx, &pv_cy) != 5) { std::fprintf(stderr, "--vignette STRENGTH,FEATHER,ROUNDNESS,CX,CY\n"); return 2; }
+            pv_enable = true;
+        }
+        else if (a == "--soft-light") { sl_strength = std::atoi(next()); sl_enable = true; }
+        else if (a == "--bw") {
+            static const char *const settings[] = {"NormalContrast", "Panchromatic", "HyperPanchromatic", "LowSensitivity", "HighSensitivity", "Orthochromatic", "HighContrast",
+                                                   "Luminance", "Landscape", "Portrait", "InfraRed", "RGB-Rel", "RGB-Abs", "ROYGCBPM-Rel", "ROYGCBPM-Abs"};
+            static const char *const filters_[] = {"None", "Red", "Orange", "Yellow", "YellowGreen", "Green", "Cyan", "Blue", "Purple"};
+            std::vector<std::string> f;
+            const std::string v = next();
+            for (size_t pos = 0;;) { const size_t e = v.find(',', pos); f.push_back(v.substr(pos, e == std::string::npos ? std::string::npos : e - pos)); if (e == std::string::npos) break; pos = e + 1; }
+            bw_setting = bw_filter = -1;
+            for (int k = 0; k < ARTGPU_BW_SETTING_COUNT; ++k) if (f[0] == settings[k]) bw_setting = k;
+            if (f.size() < 2) bw_filter = ARTGPU_BW_FILTER_NONE;
+            else for (int k = 0; k < ARTGPU_BW_FILTER_COUNT; ++k) if (f[1] == filters_[k]) bw_filter = k;
+            if (bw_setting < 0 || bw_filter < 0 || (f.size() != 1 && f.size() != 2 && f.size() != 5 && f.size() != 8)) { std::fprintf(stderr, "--bw SETTING[,FILTER[,R,G,B[,GR,GG,GB]]]\n"); return 2; }
+            for (size_t k = 2; k < f.size(); ++k) (k < 5 ? bw_mix[k - 2] : bw_gam[k - 5]) = std::atoi(f[k].c_str());
+            bw_enable = true;
+        }
         else if (a == "--resize-scale") { rs_scale = std::atof(next()); rs_dataspec = 0; rs_enable = true; }
         else if (a == "--resize-fit") {
             if (std::sscanf(next(), "%dx%d", &rs_width, &rs_height) != 2 || rs_width < 1 || rs_height < 1) { std::fprintf(stderr, "--resize-fit WxH\n"); return 2; }
@@ -334,6 +368,14 @@ int main(int argc, char **argv)
         params.grain.enabled = fg_enable; params.grain.iso = fg_iso; params.grain.strength = fg_strength; params.grain.color = fg_color != 0;
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
+        params.gradient.enabled = gr_enable; params.gradient.degree = gr_degree; params.gradient.feather = gr_feather; params.gradient.strength = gr_strength;
+        params.gradient.centerX = gr_cx; params.gradient.centerY = gr_cy;
+        params.pcvignette.enabled = pv_enable; params.pcvignette.strength = pv_strength; params.pcvignette.feather = pv_feather; params.pcvignette.roundness = pv_roundness;
+        params.pcvignette.centerX = pv_cx; params.pcvignette.centerY = pv_cy;
+        params.softlight.enabled = sl_enable; params.softlight.strength = sl_strength;
+        params.blackwhite.enabled = bw_enable; params.blackwhite.setting = bw_setting; params.blackwhite.filter = bw_filter;
+        params.blackwhite.mixerRed = bw_mix[0]; params.blackwhite.mixerGreen = bw_mix[1]; params.blackwhite.mixerBlue = bw_mix[2];
+        params.blackwhite.gammaRed = bw_gam[0]; params.blackwhite.gammaGreen = bw_gam[1]; params.blackwhite.gammaBlue = bw_gam[2];
         params.resize.enabled = rs_enable; params.resize.dataspec = rs_dataspec; params.resize.scale = rs_scale; params.resize.width = rs_width; params.resize.height = rs_height;
             BatchQueue q(ctx, 16);
             std::vector<std::string> names;
@@ -418,6 +460,14 @@ int main(int argc, char **argv)
         params.grain.enabled = fg_enable; params.grain.iso = fg_iso; params.grain.strength = fg_strength; params.grain.color = fg_color != 0;
         params.smoothing.enabled = sm_enable; params.smoothing.regions = {sm_region};
         if (smm_enable) params.smoothing.masks = {ProcParams::SmoothingMask{true, nullptr, &sm_mask}};
+        params.gradient.enabled = gr_enable; params.gradient.degree = gr_degree; params.gradient.feather = gr_feather; params.gradient.strength = gr_strength;
+        params.gradient.centerX = gr_cx; params.gradient.centerY = gr_cy;
+        params.pcvignette.enabled = pv_enable; params.pcvignette.strength = pv_strength; params.pcvignette.feather = pv_feather; params.pcvignette.roundness = pv_roundness;
+        params.pcvignette.centerX = pv_cx; params.pcvignette.centerY = pv_cy;
+        params.softlight.enabled = sl_enable; params.softlight.strength = sl_strength;
+        params.blackwhite.enabled = bw_enable; params.blackwhite.setting = bw_setting; params.blackwhite.filter = bw_filter;
+        params.blackwhite.mixerRed = bw_mix[0]; params.blackwhite.mixerGreen = bw_mix[1]; params.blackwhite.mixerBlue = bw_mix[2];
+        params.blackwhite.gammaRed = bw_gam[0]; params.blackwhite.gammaGreen = bw_gam[1]; params.blackwhite.gammaBlue = bw_gam[2];
         params.resize.enabled = rs_enable; params.resize.dataspec = rs_dataspec; params.resize.scale = rs_scale; params.resize.width = rs_width; params.resize.height = rs_height;
         params.localContrast.enabled = lc_enable;
         if (lc_enable) {

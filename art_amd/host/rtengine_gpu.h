@@ -250,6 +250,38 @@ struct ProcParams {
     // GrainParams (procparams.cc:2731-2737)
     struct { bool enabled = false; int iso = 400; int strength = 50; bool color = false; } grain;
     artgpu_film_grain_params grainParams() const { return artgpu_film_grain_params{grain.enabled ? 1 : 0, grain.iso, grain.strength, grain.color ? 1 : 0}; }
+    // GradientParams, PCVignetteParams (procparams.cc:2355-2389), CropParams' box, SoftLightParams (L2675-2679), BlackWhiteParams (L2470-2482)
+    struct { bool enabled = false; double degree = 0.0; int feather = 25; double strength = 0.60; int centerX = 0, centerY = 0; } gradient;
+    struct { bool enabled = false; double strength = 0.60; int feather = 50, roundness = 50, centerX = 0, centerY = 0; } pcvignette;
+    struct { bool enabled = false; int x = -1, y = -1, w = 15000, h = 15000; } crop;
+    struct { bool enabled = false; int strength = 30; } softlight;
+    struct {
+        bool enabled = false;
+        int filter = ARTGPU_BW_FILTER_NONE, setting = ARTGPU_BW_RGB_REL;
+        int mixerRed = 33, mixerGreen = 33, mixerBlue = 33, gammaRed = 0, gammaGreen = 0, gammaBlue = 0;
+        int colorCastBottom = 0, colorCastTop = 0;
+        std::vector<float> ulut, vlut;             // the colour cast's tables (ipbw.cc:325-341), filled by the application: 65536 entries each
+    } blackwhite;
+    // offset, full size (-1: the image's own) and scale are ImProcFunctions' (improcfun.h:216-230), which the caller passes
+    artgpu_creative_gradients_params creativeGradientsParams(int offset_x, int offset_y, int full_width, int full_height, double scale_) const
+    {
+        artgpu_creative_gradients_params q = {};
+        q.gradient_enabled = gradient.enabled ? 1 : 0; q.gradient_degree = gradient.degree; q.gradient_feather = gradient.feather;
+        q.gradient_strength = gradient.strength; q.gradient_center_x = gradient.centerX; q.gradient_center_y = gradient.centerY;
+        q.pcvignette_enabled = pcvignette.enabled ? 1 : 0; q.pcvignette_strength = pcvignette.strength; q.pcvignette_feather = pcvignette.feather;
+        q.pcvignette_roundness = pcvignette.roundness; q.pcvignette_center_x = pcvignette.centerX; q.pcvignette_center_y = pcvignette.centerY;
+        q.crop_enabled = crop.enabled ? 1 : 0; q.crop_x = crop.x; q.crop_y = crop.y; q.crop_w = crop.w; q.crop_h = crop.h;
+        q.offset_x = offset_x; q.offset_y = offset_y; q.full_width = full_width; q.full_height = full_height; q.scale = scale_;
+        return q;
+    }
+    artgpu_soft_light_params softLightParams() const { return artgpu_soft_light_params{softlight.enabled ? 1 : 0, softlight.strength}; }
+    artgpu_black_and_white_params blackAndWhiteParams() const
+    {
+        const auto &b = blackwhite;
+        const bool cast = b.colorCastBottom > 0 && b.ulut.size() == 65536 && b.vlut.size() == 65536;
+        return artgpu_black_and_white_params{b.enabled ? 1 : 0, b.setting, b.filter, b.mixerRed, b.mixerGreen, b.mixerBlue, b.gammaRed, b.gammaGreen, b.gammaBlue,
+                                             b.colorCastBottom, b.colorCastTop, cast ? b.ulut.data() : nullptr, cast ? b.vlut.data() : nullptr};
+    }
     // SmoothingParams (procparams.cc:2753-2775, procparams.h:1289-1347): regions with the reference's defaults (mode GUIDED, channel RGB);
     // masks[i].enabled and either the blend plane the application's generateMasks made of masks[i] (`blend`; nullptr = all ones) or the Mask itself
     struct SmoothingRegion {
@@ -417,7 +449,7 @@ public:
     ImProcFunctions(Context &c, const ProcParams *p, double scale = 1.0) : ctx(c), params(p), scale(scale) {}
 
     // ImProcFunctions::process (improcfun.cc:567-641): same step order; steps that are disabled / identity in the
-    // default ProcParams and not on the device path (DRC, impulse denoise, defringe, ... blackAndWhite) are
+    // default ProcParams and not on the device path (DRC, impulse denoise, defringe, the DCP look) are
     // skipped here exactly as their `enabled == false` early-outs skip them.  STAGE_2 holds capture sharpening, its first step.
     bool process(Pipeline pipeline, Stage stage, Imagefloat *img)
     {
@@ -426,12 +458,14 @@ public:
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); toneEqualizer(img); break;   // improcfun.cc:581-588
         case Stage::STAGE_2: sharpening(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595, 601, 602
-        case Stage::STAGE_3:                                                                  // improcfun.cc:606-625 (the steps this library has)
+        case Stage::STAGE_3:                                                                  // improcfun.cc:605-627 (the steps this library has)
+            creativeGradients(img);                                                           // L605
             textureBoost(img); filmGrain(img); logEncoding(img); saturationVibrance(img);       // L606-611
             if (!params->filmSimulation.after_tone_curve) filmSimulation(img);                // L614-616
             toneCurve(img);
             if (params->filmSimulation.after_tone_curve) filmSimulation(img);                 // L618-620
-            rgbCurves(img); labAdjustments(img); localContrast(img);
+            rgbCurves(img); labAdjustments(img); softLight(img); localContrast(img);          // L621-625
+            blackAndWhite(img);                                                               // L627
             break;
         }
         return false;
@@ -550,6 +584,29 @@ public:
         const artgpu_film_grain_params gp = params->grainParams();
         artgpu_rgb i = img->view();
         ctx.check(artgpu_film_grain(ctx.get(), &i, &gp, params->workingSpace, scale, cur_pipeline == Pipeline::OUTPUT ? 1 : 0, nullptr));
+    }
+    // ImProcFunctions::creativeGradients (iptransform.cc:1390-1408) with the viewport members below (full_width 0 = the image's own size, the
+    // reference's -1)
+    void creativeGradients(Imagefloat *img)
+    {
+        const bool own = full_width <= 0 || full_height <= 0;
+        const artgpu_creative_gradients_params cp = params->creativeGradientsParams(offset_x, offset_y, own ? -1 : full_width, own ? -1 : full_height, scale);
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_creative_gradients(ctx.get(), &i, &cp));
+    }
+    // ImProcFunctions::softLight (ipsoftlight.cc:46-82)
+    void softLight(Imagefloat *img)
+    {
+        const artgpu_soft_light_params sp = params->softLightParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_soft_light(ctx.get(), &i, &sp));
+    }
+    // ImProcFunctions::blackAndWhite (ipbw.cc:214-365).  The mirror's images are in RGB mode between calls, so a colour cast comes back as RGB
+    void blackAndWhite(Imagefloat *img)
+    {
+        const artgpu_black_and_white_params bp = params->blackAndWhiteParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_black_and_white(ctx.get(), &i, &bp, params->workingSpace));
     }
     // ImProcFunctions::resizeScale (ipresize.cc:226-297) without a crop
     static float resizeScale(const ProcParams *params, int fw, int fh, int &imw, int &imh)
@@ -846,6 +903,13 @@ public:
         // ImProcFunctions::filmGrain behind texture boost
         const artgpu_film_grain_params fg = p.grainParams();
         ctx.check(artgpu_set_pipeline_film_grain(ctx.get(), p.grain.enabled ? &fg : nullptr));
+        // ImProcFunctions::creativeGradients ahead of texture boost, softLight behind the tone curve, blackAndWhite behind local contrast
+        const artgpu_creative_gradients_params cgp = p.creativeGradientsParams(0, 0, -1, -1, 1.0);
+        ctx.check(artgpu_set_pipeline_creative_gradients(ctx.get(), p.gradient.enabled || p.pcvignette.enabled ? &cgp : nullptr));
+        const artgpu_soft_light_params slp = p.softLightParams();
+        ctx.check(artgpu_set_pipeline_soft_light(ctx.get(), p.softlight.enabled ? &slp : nullptr));
+        const artgpu_black_and_white_params bwp = p.blackAndWhiteParams();
+        ctx.check(artgpu_set_pipeline_black_and_white(ctx.get(), p.blackwhite.enabled ? &bwp : nullptr));
         // ImProcFunctions::resize behind STAGE_3 (the jobs' scanline buffers have the size addJob derived from the same parameters)
         const artgpu_resize_params rs = p.resizeParams();
         ctx.check(artgpu_set_pipeline_resize(ctx.get(), p.resize.enabled ? &rs : nullptr));
@@ -868,6 +932,9 @@ public:
         (void)artgpu_set_pipeline_film_simulation(ctx.get(), nullptr, nullptr, 0);
         (void)artgpu_set_pipeline_film_grain(ctx.get(), nullptr);
         (void)artgpu_set_pipeline_resize(ctx.get(), nullptr);
+        (void)artgpu_set_pipeline_creative_gradients(ctx.get(), nullptr);
+        (void)artgpu_set_pipeline_soft_light(ctx.get(), nullptr);
+        (void)artgpu_set_pipeline_black_and_white(ctx.get(), nullptr);
         for (size_t k = 0; k < jobs.size(); ++k) { jobs[k].status = out[k].status; for (int c = 0; c < 4; ++c) jobs[k].chmax[c] = out[k].chmax[c]; }
         ctx.check(rc);
     }

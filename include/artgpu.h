@@ -488,12 +488,14 @@ int artgpu_ordered_sum_f32(artgpu_ctx *ctx, const float *x, int64_t n, int on_de
  * operand order, vintpf), median.h (median3), LUT.h:349-377 / 436-459 (LUTf::operator[] for vfloat / float).  The product path never calls it.
  * XSINCOSF writes sin to out0 and cos to out1; XLIN2LOG / XLOG2LIN take the base in `param`; the LUTF_* forms look a[i] up in
  * table[table_size]; XLOG_D / XEXP_D read and write double arrays; FLOAT_TO_HALF (DNG_FloatToHalf, halffloat.h:9-46: the half-float scanlines)
- * writes 32-bit words with the half in the low 16 bits.  Returns ARTGPU_EINVAL for a missing operand. */
+ * writes 32-bit words with the half in the low 16 bits; XSINF_S / XCOSF_S are sleef.h:993-1046's scalar xsinf and xcosf, the latter being lane 0 of
+ * sleefsseavx.h:1024-1049's vector form under SSE2 (tests/test_gpu_creative_primitives.py).  Returns ARTGPU_EINVAL for a missing operand. */
 enum {
     ARTGPU_PRIM_XEXPF_S = 0, ARTGPU_PRIM_XEXPF_V, ARTGPU_PRIM_XEXPF_VN, ARTGPU_PRIM_XEXPF_V_LDEXP, ARTGPU_PRIM_XLOGF_S, ARTGPU_PRIM_XLOGF_V,
     ARTGPU_PRIM_XLOGF_VN, ARTGPU_PRIM_POW_F, ARTGPU_PRIM_XLIN2LOG, ARTGPU_PRIM_XLOG2LIN, ARTGPU_PRIM_XCBRTF, ARTGPU_PRIM_XATAN2F,
     ARTGPU_PRIM_XSINCOSF, ARTGPU_PRIM_LUTF_SCALAR, ARTGPU_PRIM_LUTF_VECTOR, ARTGPU_PRIM_MEDIAN3, ARTGPU_PRIM_VMINF, ARTGPU_PRIM_VMAXF,
     ARTGPU_PRIM_VINTPF, ARTGPU_PRIM_XDIV2F, ARTGPU_PRIM_XDIVF2, ARTGPU_PRIM_XLOG_D, ARTGPU_PRIM_XEXP_D, ARTGPU_PRIM_FLOAT_TO_HALF,
+    ARTGPU_PRIM_XSINF_S, ARTGPU_PRIM_XCOSF_S,
     ARTGPU_PRIM_COUNT
 };
 int artgpu_eval_primitive(artgpu_ctx *ctx, int prim, const void *a, const void *b, const void *c, void *out0, void *out1, int64_t n,
@@ -1248,6 +1250,129 @@ int artgpu_resize_scale(const artgpu_resize_params *params, int fw, int fh, int 
  * bits as with the setting off.  An unsupported scale, a result smaller than one pixel or an `out` of another size fail the frame before any
  * stage has run.  With the setting off the pipe allocates and launches exactly what it did without it. */
 int artgpu_set_pipeline_resize(artgpu_ctx *ctx, const artgpu_resize_params *params);
+
+/* ImProcFunctions::creativeGradients (rtengine/iptransform.cc:1390-1408): the graduated filter and the vignette filter, i.e.
+ * transformLuminanceOnly(img, img, ..., creative = true) (L987-1048), in place on an image in RGB mode.  One kernel, one pixel per lane,
+ * 12 bytes in and 12 bytes out per pixel, no scratch plane.
+ *   what runs: needsGradient / needsPCVignetting (L1354-1362): enabled and fabs(strength) > 1e-15.  With neither, ARTGPU_OK without a launch;
+ *   geometry: the pixel (x, y) of the image is (offset_x + x, offset_y + y) of a picture of cw x ch = full_width x full_height (the image's
+ *     own size when full_width < 0, L1397-1403), and fw = int(cw * scale), fh = int(ch * scale) is what the crop's numbers refer to;
+ *   derived parameters: calcGradientParams (L677-758) and calcPCVignetteParams (L828-895) run once per call on the host, statement by
+ *     statement in the reference's double / float mixture, with the host's libm (fmod, cos, tan, pow, powf) as in the reference.
+ *     artgpu_creative_gradient_params (host only, no context) hands the result out; the kernel takes that struct by value;
+ *   per pixel: calcGradientFactor (L761-812) and calcPCVignetteFactor (L898-983) with normn / pow3 / pow4 (L36-89) and sleef's scalar xsinf /
+ *     xcosf / xcbrtf.  Each returns a float; `factor` is the double 1.0 times each of them, and a channel is float(double(pixel) * factor).
+ *     With one tool on that equals the float product (the double product of two floats is exact), with both on the channel product is
+ *     rounded twice; the kernel has one form for each.  Only normn's cases 2, 4, 6 and 8 can occur (sep = int(sepf) & ~1 with sepf in 2 .. 6).
+ * ARTGPU_EINVAL: bad pointers, values that are not finite, full_width >= 0 with full_height < 1, scale <= 0.  ARTGPU_EUNSUPPORTED, image
+ * untouched: a roundness outside 0 .. 100 (sep would leave 2 .. 6), a feather outside 0 .. 100, a negative offset, and a size, offset + size or
+ * crop beyond 32767 (the reference squares distances and sizes in int).  Not built: the lens-correction vignetting
+ * branch of transformLuminanceOnly (creative = false). */
+typedef struct artgpu_creative_gradients_params {
+    int32_t gradient_enabled;                  /* GradientParams, defaults procparams.cc: false, 0, 25, 0.60, 0, 0 */
+    double gradient_degree;
+    int32_t gradient_feather;
+    double gradient_strength;
+    int32_t gradient_center_x, gradient_center_y;
+    int32_t pcvignette_enabled;                /* PCVignetteParams: false, 0.60, 50, 50, 0, 0 */
+    double pcvignette_strength;
+    int32_t pcvignette_feather, pcvignette_roundness, pcvignette_center_x, pcvignette_center_y;
+    int32_t crop_enabled, crop_x, crop_y, crop_w, crop_h;      /* CropParams: only the vignette filter reads them */
+    int32_t offset_x, offset_y, full_width, full_height;       /* ImProcFunctions::offset_x .. full_height: 0, 0, -1, -1 */
+    double scale;                              /* ImProcFunctions::scale: 1 */
+} artgpu_creative_gradients_params;
+typedef struct artgpu_creative_gradient_derived {   /* grad_params and pcv_params (iptransform.cc:668-675, 815-825), bools as int32 */
+    int32_t apply_gradient, apply_pcvignette;
+    int32_t cx, cy;                            /* offset_x, offset_y */
+    int32_t angle_is_zero, transpose, bright_top, h;
+    float ta, yc, xc, ys, ys_inv, scale, botmul, topmul, top_edge_0;
+    float oe_a, oe_b, oe1_a, oe1_b, oe2_a, oe2_b, ie_mul, ie1_mul, ie2_mul, sepmix, feather;
+    int32_t x1, x2, y1, y2, ex, ey, ew, eh, sep, is_super_ellipse_mode, is_portrait;
+    float pcv_scale, fadeout_mul;
+} artgpu_creative_gradient_derived;
+int artgpu_creative_gradients(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_creative_gradients_params *params);
+/* w x h: the image's size (what full_width < 0 stands for).  Fields of a tool that does not run are zero. */
+int artgpu_creative_gradient_params(const artgpu_creative_gradients_params *params, int w, int h, artgpu_creative_gradient_derived *out);
+/* The two filters in the per-frame pipe, a setting of the context (copied; batch lanes inherit it).  NULL = off, the default.  While set the
+ * three pipe entries run artgpu_creative_gradients' code as the first step of STAGE_3, ahead of texture boost and its masks
+ * (improcfun.cc:605), with offset 0, the frame's size behind the border as the full size and scale 1, whatever the struct holds there.
+ * The step starts with setMode(RGB): behind colour correction (which leaves YUV) that is the switch colour correction ends with, and texture
+ * boost then finds RGB.  What the call refuses fails the frame before any stage has run.  With the setting off, or with neither filter
+ * running, the pipe launches exactly what it launched without it. */
+int artgpu_set_pipeline_creative_gradients(artgpu_ctx *ctx, const artgpu_creative_gradients_params *params);
+
+/* ImProcFunctions::softLight (rtengine/ipsoftlight.cc:31-82) in place on an image in RGB mode: one table, applied to the three channels.
+ *   table: artgpu_soft_light_lut builds it on the host (no context) as the reference does per call: for i in 0 .. 65535
+ *     v = Color::gamma_srgb(float(i)) / 65535.f; v2 = v * v; v22 = v2 * 2.f; v = v2 + v22 - v22 * v (Pegtop's formula);
+ *     lut[i] = intp(strength / 100.f, Color::igamma_srgb(v * 65535.f), float(i)) with rt_math.h's intp, a * b + (1 - a) * c.  The two colour
+ *     functions are float-indexed LUTf lookups in tables that do not clip (color.cc:183-185), restated on the host.  The context keeps the
+ *     table of the last strength on the device;
+ *   pixels: x <= 65535.f takes LUTf::operator[](float) with both clip flags (a value below 0 takes entry 0); a value above 65535 and a NaN,
+ *     which fails the comparison, stay as they are.  The kernel is the tone curve's (the same table shape) with that rule switched on,
+ *     and takes the same LUT-in-LDS shape on large frames.
+ * Not enabled or strength <= 0: ARTGPU_OK without a launch, as the reference returns.  ARTGPU_EUNSUPPORTED: strength above 100 (the GUI's
+ * range, rtgui/softlight.cc).  ARTGPU_EINVAL: bad pointers. */
+typedef struct artgpu_soft_light_params {   /* SoftLightParams, defaults procparams.cc:2675-2679 */
+    int32_t enabled;           /* 0 */
+    int32_t strength;          /* 30 */
+} artgpu_soft_light_params;
+int artgpu_soft_light(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_soft_light_params *params);
+int artgpu_soft_light_lut(int strength, float lut[65536]);
+/* Soft light in the per-frame pipe, a setting of the context (copied; batch lanes inherit it).  NULL = off, the default.  While set (and
+ * enabled with strength > 0) the three pipe entries run artgpu_soft_light's code behind the tone curve and the second film simulation
+ * position, ahead of local contrast (improcfun.cc:623); the image is in RGB mode there.  What artgpu_soft_light refuses fails the frame
+ * before any stage has run.  With the setting off the pipe launches exactly what it launched without it. */
+int artgpu_set_pipeline_soft_light(artgpu_ctx *ctx, const artgpu_soft_light_params *params);
+
+/* ImProcFunctions::blackAndWhite (rtengine/ipbw.cc:214-365) in place on an image in RGB mode.
+ *   mixer: computeBWMixerConstants (L50-211) runs on the host exactly as written, from float(mixer_red / _green / _blue), the setting and the
+ *     filter, with kcorec starting at 1.  L192-194 are part of the definition: each of the three statements reads the mixer values the
+ *     statement before it has already overwritten.  artgpu_bw_mixer_constants (host only, no context) hands the result out;
+ *   gamma: gamma = 1.f - float(g) / (g < 0 ? 100.f : 125.f) per channel; if any is not 1, three tables pow_F(float(i) / 65535.f, gamma) *
+ *     65535.f (sleef's scalar pow_F restated on the host) and a lookup per channel in front of the mix;
+ *   pixels: columns below W & ~3 are the reference's 4-wide body (LUTf::operator[](vfloat), LUT.h:349-377), the remaining columns its scalar
+ *     tail (operator[](float), L436-459); (bwr * r + bwg * g + bwb * b) * kcorec in float, left to right, written to all three channels;
+ *   colour cast (cast_bottom > 0): ulut / vlut, 65536 floats each, come from the caller as tone, RGB and Lab curves do, because filling
+ *     them takes DiagonalCurve's spline, which is host code of the application.  ART fills them like this (L319-341): s = pow_F(bottom /
+ *     100.f, 3.f), h = top / 180.f * pi; for i: x = Color::gamma_srgbclipped(i) / 65535.f, y = DiagonalCurve(curves::filmcurve_def)
+ *     .getVal(x) * 65535.f, c = FlatCurve{FCT_MinMaxCPoints, 0, 0, 0.35, 0, 0.5, 1, 0.35, 0.35, 1, 0, 0, 0.35}.getVal(x), hsl2yuv(h, s * c, u, v),
+ *     ulut[i] = y * u, vlut[i] = y * v.  Behind the mix, in registers: setMode(YUV) with row 1 of `ws` as floats, u += ulut[Y], v += vlut[Y]
+ *     with the same body / tail rule.  The reference leaves the image in YUV mode; the stand-alone call hands back RGB (Color::yuv2rgb), as
+ *     artgpu_texture_boost and artgpu_color_correction do.  cast_top is not read by the device path (it only shapes the caller's tables).
+ * Not enabled: ARTGPU_OK without a launch.  ARTGPU_EINVAL: bad pointers, a setting or filter outside the enums, a cast without ulut / vlut
+ * or without ws.  ARTGPU_EUNSUPPORTED: a gamma outside -100 .. 100 or a mixer value outside -100 .. 200 (the GUI's ranges). */
+enum {   /* BlackWhiteParams::setting */
+    ARTGPU_BW_NORMAL_CONTRAST = 0, ARTGPU_BW_PANCHROMATIC, ARTGPU_BW_HYPER_PANCHROMATIC, ARTGPU_BW_LOW_SENSITIVITY, ARTGPU_BW_HIGH_SENSITIVITY,
+    ARTGPU_BW_ORTHOCHROMATIC, ARTGPU_BW_HIGH_CONTRAST, ARTGPU_BW_LUMINANCE, ARTGPU_BW_LANDSCAPE, ARTGPU_BW_PORTRAIT, ARTGPU_BW_INFRARED,
+    ARTGPU_BW_RGB_REL, ARTGPU_BW_RGB_ABS, ARTGPU_BW_ROYGCBPM_REL, ARTGPU_BW_ROYGCBPM_ABS, ARTGPU_BW_SETTING_COUNT
+};
+enum {   /* BlackWhiteParams::filter */
+    ARTGPU_BW_FILTER_NONE = 0, ARTGPU_BW_FILTER_RED, ARTGPU_BW_FILTER_ORANGE, ARTGPU_BW_FILTER_YELLOW, ARTGPU_BW_FILTER_YELLOW_GREEN,
+    ARTGPU_BW_FILTER_GREEN, ARTGPU_BW_FILTER_CYAN, ARTGPU_BW_FILTER_BLUE, ARTGPU_BW_FILTER_PURPLE, ARTGPU_BW_FILTER_COUNT
+};
+typedef struct artgpu_black_and_white_params {   /* BlackWhiteParams, defaults procparams.cc:2470-2482 */
+    int32_t enabled;           /* 0 */
+    int32_t setting;           /* ARTGPU_BW_RGB_REL */
+    int32_t filter;            /* ARTGPU_BW_FILTER_NONE */
+    int32_t mixer_red, mixer_green, mixer_blue;   /* 33, 33, 33 */
+    int32_t gamma_red, gamma_green, gamma_blue;   /* 0, 0, 0 */
+    int32_t cast_bottom, cast_top;                /* colorCast.getBottom() / getTop(): 0, 0 */
+    const float *ulut, *vlut;  /* the cast's tables, 65536 floats each (host; the call keeps its own copy); NULL without a cast */
+} artgpu_black_and_white_params;
+typedef struct artgpu_bw_mixer {   /* computeBWMixerConstants' results */
+    float bwr, bwg, bwb, kcorec, filcor;
+    double rrm, ggm, bbm;
+} artgpu_bw_mixer;
+int artgpu_black_and_white(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_black_and_white_params *params, const double ws[9] /* the cast only */);
+int artgpu_bw_mixer_constants(int setting, int filter, int mixer_red, int mixer_green, int mixer_blue, artgpu_bw_mixer *out);
+/* Black-and-white in the per-frame pipe, a setting of the context (parameters and tables copied; batch lanes inherit it).  NULL = off, the
+ * default.  While set (and enabled) the three pipe entries run artgpu_black_and_white's code behind local contrast (improcfun.cc:627).  The
+ * tool needs RGB, so with it on the image goes back from LAB to RGB behind local contrast even when the Resize tool follows, and the
+ * resampler then takes its ARTGPU_RESIZE_RGB path; with a cast the image is in YUV mode behind the tool and is switched to RGB as the
+ * reference's next setMode(RGB) would (rgb2out's); a cast together with the Resize tool is ARTGPU_EUNSUPPORTED, because Lanczos' setMode(LAB)
+ * then starts from YUV (Imagefloat::yuv_to_lab), which the device path has not.  What artgpu_black_and_white refuses fails the frame before
+ * any stage has run.  With the setting off the pipe launches exactly what it launched without it. */
+int artgpu_set_pipeline_black_and_white(artgpu_ctx *ctx, const artgpu_black_and_white_params *params);
 
 /* This rank's share of a batch: frames are independent (batchProcessingThread handles them one after another,
  * simpleprocess.cc:586-612), so a multi-GPU batch is one context per GPU each running its own frames; the completion
