@@ -512,6 +512,46 @@ def sharpening_params(enabled=True, method=SHARPEN_RLD, amount=200, contrast=20.
                             float(corner_boost), int(corner_latitude), int(offset_x), int(offset_y), int(full_width), int(full_height), 0)
 
 
+class ImpulseDenoiseParams(C.Structure):
+    """artgpu_impulse_denoise_params: ImpulseDenoiseParams (defaults: off, 50)"""
+    _fields_ = [("enabled", C.c_int32), ("thresh", C.c_int32)]
+
+
+class ImpulseDenoiseInfo(C.Structure):
+    _fields_ = [("early_out", C.c_int32), ("thresh", C.c_float), ("sigma", C.c_float), ("impthr", C.c_float), ("impulse_pixels", C.c_int64)]
+
+
+def impulse_denoise_params(enabled=True, thresh=50):
+    return ImpulseDenoiseParams(1 if enabled else 0, int(thresh))
+
+
+DEFRINGE_MAX_HALFWIN = 11
+DEFRINGE_BLUR_COPY, DEFRINGE_BLUR_3X3, DEFRINGE_BLUR_YVV = 0, 1, 2
+# DefringeParams' default hue curve (procparams.cc:1839-1865)
+DEFRINGE_DEFAULT_HUECURVE = (1.0, 0.166666667, 0., 0.35, 0.35, 0.347, 0., 0.35, 0.35, 0.513667426, 0., 0.35, 0.35, 0.668944571, 0., 0.35, 0.35,
+                             0.8287775246, 0.97835991, 0.35, 0.35, 0.9908883827, 0., 0.35, 0.35)
+
+
+class DefringeParams(C.Structure):
+    """artgpu_defringe_params: DefringeParams (defaults: off, 2.0, 13, DEFRINGE_DEFAULT_HUECURVE)"""
+    _fields_ = [("enabled", C.c_int32), ("threshold", C.c_int32), ("radius", C.c_double), ("huecurve", C.POINTER(C.c_double)),
+                ("nhuecurve", C.c_int32), ("pad_", C.c_int32)]
+
+
+class DefringeInfo(C.Structure):
+    _fields_ = [("early_out", C.c_int32), ("halfwin", C.c_int32), ("blur", C.c_int32), ("curve", C.c_int32), ("radius", C.c_double),
+                ("chromave", C.c_double), ("threshfactor", C.c_float), ("pad_", C.c_int32), ("corrected_pixels", C.c_int64)]
+
+
+def defringe_params(enabled=True, radius=2.0, threshold=13, huecurve=DEFRINGE_DEFAULT_HUECURVE):
+    """huecurve: FlatCurve control points, or None / () for no curve.  The structure keeps the array alive."""
+    pts = [float(v) for v in (huecurve or ())]
+    arr = (C.c_double * len(pts))(*pts) if pts else None
+    p = DefringeParams(1 if enabled else 0, int(threshold), float(radius), C.cast(arr, C.POINTER(C.c_double)) if pts else None, len(pts), 0)
+    p._keep = arr
+    return p
+
+
 class PipelineParams(C.Structure):
     pass
 
@@ -716,6 +756,10 @@ def _load():
     lib.artgpu_rl_deconvolution.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(Plane), C.c_void_p, C.c_double, C.c_float, C.POINTER(SharpeningInfo)]
     lib.artgpu_gaussian_blur_ex.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(Plane), C.POINTER(Plane), C.c_double, C.c_int]
     lib.artgpu_deconv_auto_radius.argtypes = [C.c_void_p, C.POINTER(Plane), C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.artgpu_impulse_denoise.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(ImpulseDenoiseParams), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                           C.POINTER(ImpulseDenoiseInfo)]
+    lib.artgpu_defringe.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(DefringeParams), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int,
+                                    C.POINTER(DefringeInfo)]
     lib.artgpu_texture_boost_plane.argtypes = [C.c_void_p, C.POINTER(Plane), C.POINTER(TextureBoostRegion), C.c_double, C.c_int, C.POINTER(TextureBoostInfo)]
     lib.artgpu_texture_boost.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(TextureBoostRegion), C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int,
                                          C.POINTER(TextureBoostInfo)]
@@ -724,6 +768,7 @@ def _load():
     lib.artgpu_set_pipeline_masks.argtypes = [C.c_void_p, C.POINTER(MaskParams), C.c_int, C.POINTER(MaskParams), C.c_int]
     lib.artgpu_color_correction.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(ColorCorrectionRegion), C.c_int, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.c_int, C.POINTER(ColorCorrectionInfo)]
+    lib.artgpu_color_correction_yuv.argtypes = lib.artgpu_color_correction.argtypes
     lib.artgpu_set_pipeline_color_correction.argtypes = [C.c_void_p, C.POINTER(ColorCorrectionRegion), C.c_int, C.POINTER(MaskParams)]
     lib.artgpu_smoothing.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(SmoothingRegion), C.c_int, C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(SmoothingInfo)]
@@ -752,6 +797,7 @@ def _load():
     lib.artgpu_black_and_white.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(BlackAndWhiteParams), C.POINTER(C.c_double)]
     lib.artgpu_bw_mixer_constants.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BwMixer)]
     lib.artgpu_set_pipeline_black_and_white.argtypes = [C.c_void_p, C.POINTER(BlackAndWhiteParams)]
+    lib.artgpu_set_pipeline_impulse_defringe.argtypes = [C.c_void_p, C.POINTER(ImpulseDenoiseParams), C.POINTER(DefringeParams)]
     lib.artgpu_resize_lanczos.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(RGB), C.c_float, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.artgpu_resize_scale.argtypes = [C.POINTER(ResizeParams), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
     lib.artgpu_set_pipeline_resize.argtypes = [C.c_void_p, C.POINTER(ResizeParams)]
@@ -775,6 +821,7 @@ def _load():
     lib.artgpu_log_encoding.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(LogEncParams), C.POINTER(C.c_double), C.c_int, C.c_int]
     lib.artgpu_rgb_to_lab.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(C.c_double)]
     lib.artgpu_lab_to_rgb.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(C.c_double)]
+    lib.artgpu_lab_to_yuv.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(C.c_double)]
     lib.artgpu_lab_histogram.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(C.c_uint32)]
     lib.artgpu_lab_adjustments.argtypes = [C.c_void_p, C.POINTER(RGB), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]
     lib.artgpu_dual_demosaic_bayer.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Plane), C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(RGB)]
@@ -834,11 +881,11 @@ EXPORTS = ["artgpu_eval_primitive", "artgpu_set_progress_callback", "artgpu_set_
            "artgpu_convert_color_space", "artgpu_exposure", "artgpu_tone_curve",
            "artgpu_wavelet_decompose", "artgpu_wavelet_mad", "artgpu_wavelet_info", "artgpu_wavelet_get_band", "artgpu_wavelet_set_band",
            "artgpu_wavelet_reconstruct", "artgpu_wavelet_free", "artgpu_rgb_denoise", "artgpu_denoise_guided_smoothing",
-           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
+           "artgpu_gaussian_blur", "artgpu_detail_mask", "artgpu_nlmeans", "artgpu_improc_denoise", "artgpu_improc_denoise_fused", "artgpu_noise_curve_lut", "artgpu_denoise_chroma_map", "artgpu_tone_curve_neutral", "artgpu_demosaic_xtrans", "artgpu_pipeline_run", "artgpu_batch_run", "artgpu_batch_run_io", "artgpu_scale_colors", "artgpu_channel_mixer", "artgpu_rgb_curves", "artgpu_denoise_compute_params", "artgpu_ordered_sum_f32", "artgpu_get_image_skip", "artgpu_saturation_vibrance", "artgpu_set_batch_lanes", "artgpu_batch_complete", "artgpu_rgb2out_matrix", "artgpu_get_scanlines", "artgpu_guided_filter", "artgpu_hsl_equalizer", "artgpu_log_encoding", "artgpu_rgb_to_lab", "artgpu_lab_to_rgb", "artgpu_lab_to_yuv", "artgpu_lab_histogram", "artgpu_lab_adjustments", "artgpu_dual_demosaic_bayer", "artgpu_raw_ca_correct", "artgpu_local_contrast_curve_lut", "artgpu_local_contrast",
            "artgpu_dehaze", "artgpu_dehaze_strength_lut", "artgpu_dehaze_estimate_ambient", "artgpu_dehaze_dark_channel",
-           "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius",
+           "artgpu_sharpening", "artgpu_rl_deconvolution", "artgpu_gaussian_blur_ex", "artgpu_deconv_auto_radius", "artgpu_impulse_denoise", "artgpu_defringe", "artgpu_set_pipeline_impulse_defringe",
            "artgpu_texture_boost_plane", "artgpu_texture_boost", "artgpu_generate_masks", "artgpu_set_pipeline_masks",
-           "artgpu_color_correction", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing",
+           "artgpu_color_correction", "artgpu_color_correction_yuv", "artgpu_set_pipeline_color_correction", "artgpu_smoothing", "artgpu_set_pipeline_smoothing",
            "artgpu_tone_equalizer", "artgpu_tone_equalizer_lut", "artgpu_set_pipeline_tone_equalizer",
            "artgpu_clut_create", "artgpu_clut_destroy", "artgpu_film_simulation", "artgpu_film_simulation_tables", "artgpu_set_pipeline_film_simulation",
            "artgpu_resize_lanczos", "artgpu_resize_scale", "artgpu_set_pipeline_resize",
@@ -1086,15 +1133,15 @@ class Context:
                                                 tb if texture_boost_masks else None, len(texture_boost_masks or [])))
         del k1, k2
 
-    def color_correction(self, image: RGB, regions, ws, iws, to_rgb: bool = False, want_info: bool = False):
-        """ImProcFunctions::colorCorrection in place on an RGB image (left in YUV mode unless to_rgb).  regions: what
-        color_correction_regions() takes.  Returns the list of ColorCorrectionInfo (one per region) when want_info."""
+    def color_correction(self, image: RGB, regions, ws, iws, to_rgb: bool = False, want_info: bool = False, from_yuv: bool = False):
+        """ImProcFunctions::colorCorrection in place on an RGB image, or with from_yuv on one in YUV mode already (left in YUV mode unless to_rgb).
+        regions: what color_correction_regions() takes.  Returns the list of ColorCorrectionInfo (one per region) when want_info."""
         arr, keep = color_correction_regions(regions)
         n = len(regions)
         wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
         iwsd = (C.c_double * 9)(*np.asarray(iws, np.float64).ravel())
         info = (ColorCorrectionInfo * max(n, 1))() if want_info else None
-        self._chk(LIB.artgpu_color_correction(self._h, C.byref(image), arr, n, wsd, iwsd, 1 if to_rgb else 0, info))
+        self._chk((LIB.artgpu_color_correction_yuv if from_yuv else LIB.artgpu_color_correction)(self._h, C.byref(image), arr, n, wsd, iwsd, 1 if to_rgb else 0, info))
         del keep
         return list(info)[:n] if want_info else None
 
@@ -1228,6 +1275,12 @@ class Context:
         """black-and-white in pipeline_run / batch_run / batch_run_io: behind local contrast (None: off).  The library copies parameters and tables."""
         self._chk(LIB.artgpu_set_pipeline_black_and_white(self._h, C.byref(params) if params is not None else None))
 
+    def set_pipeline_impulse_defringe(self, impulse: "ImpulseDenoiseParams" = None, defringe: "DefringeParams" = None):
+        """impulse noise reduction / defringe in pipeline_run / batch_run / batch_run_io: behind the sharpening, ahead of colour correction (None: off).
+        The library copies the parameters and the hue curve."""
+        self._chk(LIB.artgpu_set_pipeline_impulse_defringe(self._h, C.byref(impulse) if impulse is not None else None,
+                                                           C.byref(defringe) if defringe is not None else None))
+
     def sharpening(self, image: RGB, params: "SharpeningParams", ws, scale: float = 1.0, want_info: bool = False):
         """ImProcFunctions::sharpening (method rld) in place (params from sharpening_params()); returns the SharpeningInfo when want_info."""
         wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
@@ -1240,6 +1293,26 @@ class Context:
         info = SharpeningInfo() if want_info else None
         self._chk(LIB.artgpu_rl_deconvolution(self._h, C.byref(luminance), C.byref(blend), C.c_void_p(int(impulse)), float(sigma), float(amount),
                                               C.byref(info) if want_info else None))
+        return info
+
+    def impulse_denoise(self, image: RGB, params: "ImpulseDenoiseParams", ws, iws=None, scale: float = 1.0, to_rgb: bool = True, want_info: bool = False):
+        """ImProcFunctions::impulsedenoise in place on an image in RGB mode (params from impulse_denoise_params()); to_rgb False leaves the image in
+        LAB mode as the reference does; returns the ImpulseDenoiseInfo when want_info."""
+        wsd = (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        iwsd = None if iws is None else (C.c_double * 9)(*np.asarray(iws, np.float64).ravel())
+        info = ImpulseDenoiseInfo() if want_info else None
+        self._chk(LIB.artgpu_impulse_denoise(self._h, C.byref(image), C.byref(params), wsd, iwsd, float(scale), 1 if to_rgb else 0,
+                                             C.byref(info) if want_info else None))
+        return info
+
+    def defringe(self, image: RGB, params: "DefringeParams", ws, iws=None, scale: float = 1.0, to_rgb: bool = True, want_info: bool = False, from_lab: bool = False):
+        """ImProcFunctions::defringe in place on an image in RGB mode, or in LAB mode with from_lab (params from defringe_params()); to_rgb False leaves
+        the image in LAB mode as the reference does; returns the DefringeInfo when want_info."""
+        wsd = None if ws is None else (C.c_double * 9)(*np.asarray(ws, np.float64).ravel())
+        iwsd = None if iws is None else (C.c_double * 9)(*np.asarray(iws, np.float64).ravel())
+        info = DefringeInfo() if want_info else None
+        self._chk(LIB.artgpu_defringe(self._h, C.byref(image), C.byref(params), wsd, iwsd, float(scale), 1 if from_lab else 0, 1 if to_rgb else 0,
+                                      C.byref(info) if want_info else None))
         return info
 
     def gaussian_blur_ex(self, src: Plane, dst: Plane, div, sigma: float, gausstype: int):
@@ -1337,6 +1410,10 @@ class Context:
 
     def lab_to_rgb(self, image: RGB, iws):
         self._chk(LIB.artgpu_lab_to_rgb(self._h, C.byref(image), (C.c_double * 9)(*[float(v) for v in np.asarray(iws, dtype=np.float64).reshape(9)])))
+
+    def lab_to_yuv(self, image: RGB, iws):
+        """Imagefloat::setMode(YUV) on an image in LAB mode (lab_to_yuv), in place"""
+        self._chk(LIB.artgpu_lab_to_yuv(self._h, C.byref(image), (C.c_double * 9)(*[float(v) for v in np.asarray(iws, dtype=np.float64).reshape(9)])))
 
     def lab_histogram(self, image: RGB):
         hist = np.zeros(65536, np.uint32)

@@ -129,10 +129,10 @@ int color_correction_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride,
 
 } } // namespace artgpu::api
 
-extern "C" {
+namespace {
 
-int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
-                            const double iws[9], int to_rgb, artgpu_color_correction_info *info)
+int color_correction_entry(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9], const double iws[9],
+                           int from_yuv, int to_rgb, artgpu_color_correction_info *info)
 {
     StageScope scope_(ctx, "ImProcFunctions::colorCorrection");
     if (!ctx) return ARTGPU_EINVAL;
@@ -143,8 +143,24 @@ int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevRGB d;
     if ((rc = bind_rgb(ctx, img, 4, true, &d, "color_correction"))) return rc;
-    if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regions, pl, 0, to_rgb, info))) return rc;
+    if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regions, pl, from_yuv, to_rgb, info))) return rc;
     return unbind_rgb(ctx, img, &d);
+}
+
+} // namespace
+
+extern "C" {
+
+int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
+                            const double iws[9], int to_rgb, artgpu_color_correction_info *info)
+{
+    return color_correction_entry(ctx, img, regions, nregions, ws, iws, 0, to_rgb, info);
+}
+
+int artgpu_color_correction_yuv(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
+                                const double iws[9], int to_rgb, artgpu_color_correction_info *info)
+{
+    return color_correction_entry(ctx, img, regions, nregions, ws, iws, 1, to_rgb, info);
 }
 
 } // extern "C"

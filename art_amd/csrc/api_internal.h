@@ -33,6 +33,8 @@
 #include "sharpen.h"
 #include "blackwhite.h"
 #include "creativegradients.h"
+#include "impulse.h"
+#include "defringe.h"
 
 struct artgpu_ctx {
     int device = 0;
@@ -107,6 +109,9 @@ struct artgpu_ctx {
         artgpu_soft_light_params pipe_sl = {};
         int pipe_bw_on = 0;            // artgpu_set_pipeline_black_and_white: a copy by value; its ulut / vlut point into the parent's pipe_bw_tabs
         artgpu_black_and_white_params pipe_bw = {};
+        int pipe_imp_on = 0, pipe_df_on = 0;   // artgpu_set_pipeline_impulse_defringe: copies by value; the hue curve points into the parent's pipe_df_curve
+        artgpu_impulse_denoise_params pipe_imp = {};
+        artgpu_defringe_params pipe_df = {};
     } shared;
     float *sh_host = nullptr;      // pinned: the auto radius' maximum ratio on its way to the host (pipeline: launched early, waited for where it is used)
     hipEvent_t sh_ev = nullptr;
@@ -116,6 +121,7 @@ struct artgpu_ctx {
     template <typename Region> struct PipeRegions { std::vector<Region> regs; std::vector<artgpu_plane> planes; PipeMasks masks; };
     PipeRegions<artgpu_color_correction_region> pipe_cc_own;
     PipeRegions<artgpu_smoothing_region> pipe_sm_own;
+    std::vector<double> pipe_df_curve;     // artgpu_set_pipeline_impulse_defringe: defringe's hue curve (batch lanes point at their parent's)
     std::vector<float> pipe_bw_tabs;       // artgpu_set_pipeline_black_and_white: the cast's two tables (batch lanes point at their parent's)
     artgpu_clut *pipe_fs_own = nullptr;    // artgpu_set_pipeline_film_simulation: the reference this context holds (batch lanes hold none)
     std::string err;
@@ -257,6 +263,7 @@ enum { P_L = 0, P_A, P_B, P_LBANDS, P_LLOW0, P_LLOW1, P_CBANDS, P_CLOW0, P_CLOW1
        P_FG_WORK, P_FG_TAB, P_FG_IDX,                                                                                   // artgpu_film_grain: the planes a region writes, its tables; artgpu_grain_indices
        P_SL_LUT, P_BW_TAB,                                                                                              // artgpu_soft_light's table; artgpu_black_and_white's gamma and cast tables
        P_MADPART,                                                                                                       // RGB_denoise: the counting analysis kernels' bins (launch_mad_fold)
+       P_DF_STATE,                                                                                                      // artgpu_defringe: state, hue curve, the sum's partials (its planes: P_SH_PLANES)
        P_NSLOTS };
 static_assert(P_NSLOTS <= artgpu_ctx::NPOOL, "grow artgpu_ctx::pool");
 int pool_get(artgpu_ctx *ctx, int slot, size_t bytes, float **out);
@@ -415,6 +422,8 @@ int tone_neutral_check(artgpu_ctx *ctx, const float *lut65536, float whitecoeff)
 int tone_neutral_dev(artgpu_ctx *ctx, const DevRGB &d, const float *lut65536, float whitecoeff, const artgpu_neutral_state *st);
 // Imagefloat::setMode(LAB) / (RGB) on device planes
 int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_lab);
+// Imagefloat::setMode(YUV) on device planes in LAB mode (lab_to_yuv)
+int lab_to_yuv_dev(artgpu_ctx *ctx, const DevRGB &d, const double iws[9]);
 // scaleColors' ScaleArgs but for the buffers: the size, the 6x6 colour map (xtrans, or the Bayer word `filters` when it is null; a fourth
 // colour is refused under `who`), black levels and multipliers
 int scale_args_fill(artgpu_ctx *ctx, int w, int h, int src_is_u16, uint32_t filters, const int32_t *xtrans, const float cblacksom[4], const float scale_mul[4],
@@ -547,6 +556,27 @@ int sharpen_dev(artgpu_ctx *ctx, float *const planes[3], size_t stride, int W, i
 int plane_into(artgpu_ctx *ctx, const artgpu_plane *pl, float *dst);
 int auto_radius_dev(artgpu_ctx *ctx, const float *raw, size_t stride, int W, int H, uint32_t filters, float lower, float upper, float **result);
 float auto_radius_of(float maxRatio);
+
+// ---------------------------------------------------------------------------------------------
+// impulse noise reduction, defringe
+// ---------------------------------------------------------------------------------------------
+// what impulsedenoise derives from its parameters (impulse_denoise.cc:182-187, rt_algo.cc:511-517); early: artgpu_impulse_denoise_info::early_out
+struct ImpPlan { int early; float thresh, sigma, impthr; };
+ImpPlan imp_plan(int W, int H, const artgpu_impulse_denoise_params *p, double scale);
+// the tool on a device image, enqueued on ctx->stream; already_lab: the tool ahead left the image in LAB mode (setMode(LAB) does nothing);
+// to_rgb: setMode(RGB) with iws on top.  The host waits only to fill `info`
+int impulse_denoise_dev(artgpu_ctx *ctx, const DevRGB &d, const ImpPlan &pl, const double ws[9], const double *iws, int already_lab, int to_rgb,
+                        artgpu_impulse_denoise_info *info);
+// what defringe derives before it touches anything (PF_correct_RT.cc:47-50, 130, 212-216; gauss.cc:1437-1461), and every reason not to run
+struct DfPlan {
+    int early, halfwin, blur, curve_n, thresh;     // curve_n: points of the polyline; 0: no curve; -1: FCT_Empty
+    double radius;
+    float c0, c1, c2, b0, b1;                      // DF_BLUR_3X3
+    std::vector<double> tab;                       // poly_x, poly_y, dyByDx
+};
+int df_plan(artgpu_ctx *ctx, int W, int H, const artgpu_defringe_params *p, double scale, const char *who, DfPlan *pl);
+int defringe_dev(artgpu_ctx *ctx, const DevRGB &d, const DfPlan &pl, const double ws[9], const double *iws, int already_lab, int to_rgb,
+                 artgpu_defringe_info *info);
 
 // ---------------------------------------------------------------------------------------------
 // api_pipeline.hip: what io_frame (api_batch.hip) takes from the frame driver

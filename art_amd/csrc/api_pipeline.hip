@@ -85,7 +85,7 @@ int pipeline_ca_dev(artgpu_ctx *ctx, float *raw, size_t stride, int W, int H, co
 
 namespace {
 
-enum PipeMode { PIPE_RGB, PIPE_YUV };
+enum PipeMode { PIPE_RGB, PIPE_YUV, PIPE_LAB };
 // Everything a frame decides before its first launch (pipeline_plan).  The stages only read it, but for the `mask` pointers of lc_regs / tb_regs,
 // which pipe_stage3 aims at the planes it generates.
 struct PipePlan {
@@ -93,6 +93,10 @@ struct PipePlan {
     double scale;
     bool lc_on, lc_gen, tb_on, tb_gen, cc_on, cc_gen, sm_on, sm_gen;   // the local tools: on, and the pipe generates their masks (artgpu_set_pipeline_*)
     bool cc_to_rgb, tb_in_yuv;     // the mode walk: colour correction ends with the switch back to RGB; texture boost finds the image in YUV mode
+    bool imp_on, df_on, id_lab;    // impulse noise reduction / defringe run (artgpu_set_pipeline_impulse_defringe, the gates passed); either leaves LAB mode
+    bool sm_from_lab, tb_from_lab, lab_to_rgb_end;   // ... which smoothing / texture boost find (masks on the LAB image, then their switch), or STAGE_2 ends with the switch to RGB
+    ImpPlan imp;
+    DfPlan df;
     std::vector<artgpu_local_contrast_region> lc_regs;             // copies of the regions whose masks the pipe generates ...
     std::vector<artgpu_texture_boost_region> tb_regs;
     const artgpu_local_contrast_region *lc_regions;                // ... or the caller's
@@ -143,7 +147,7 @@ static int pipe_gen_masks(artgpu_ctx *ctx, const artgpu_pipeline_params *p, cons
 // Checks and derives everything; launches nothing and takes no pool slot, so a refused frame leaves the output planes alone.  The checks, in the
 // order they report (a frame that is wrong in two ways names the first):
 //   1. ctx, raw / p / out, the border, the Resize tool's result, the output's size (then hipSetDevice, the one HIP call here; then rs_check; then cg_check,
-//   whose result the mode walk needs)   2. artgpu_set_pipeline_masks' counts against the frame's
+//   whose result the mode walk needs; before it df_plan: defringe's radius, window and curve)   2. artgpu_set_pipeline_masks' counts against the frame's
 //   3. local contrast masks: region list, mk_plan   4. texture boost masks: region list, mk_plan   5. colour correction: texture boost's masks from a YUV image,
 //   cc_check, mk_plan   6. smoothing: its masks from a YUV image, sm_check, sm_plan_region of the mask-less regions, mk_plan   7. local_contrast_check
 //   8. dehaze_check, te_check, fs_check, fg_check, sl_check, bw_check (and a colour cast in front of the Resize tool)   9. sharpening: X-Trans with the automatic radius, sharpen_check   10. tb_check
@@ -182,19 +186,34 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     //    0  1 |      RGB       |      RGB       |           -             |     0     |     ok     |    ok
     //    1  0 |       -        |      YUV       |         1 / 0           |     1     |     -      |  refused
     //    1  1 |      YUV       |      RGB       |         1 / 1           |     0     |  refused   |    ok
-    PipeMode mode = pl->cc_on ? PIPE_YUV : PIPE_RGB;           // (sharpening: RGB in, RGB out)
+    // Impulse noise reduction and defringe sit between the sharpening and colour correction; the first of them that runs does setMode(LAB), and the image
+    // stays LAB until the next tool's setMode (id: either runs).  The mask engine reads LAB, so whatever finds the LAB image generates its masks on it:
+    //   id cc sm | in front of cc | in front of sm | in front of tb | hand-over
+    //    1  1  . |      LAB       |   as above     |   as above     | cc's masks on LAB, lab_to_yuv, cc from_yuv; then the rows above
+    //    1  0  1 |       -        |      LAB       |      RGB       | sm's masks on LAB, lab_to_rgb (sm's setMode(RGB))
+    //    1  0  0 |       -        |       -        |      LAB       | tb's masks on LAB, lab_to_yuv, tb in_yuv; without tb (or with a gradient filter ahead of
+    //            |                |                |                | it: creativeGradients' setMode(RGB)) STAGE_2 ends with lab_to_rgb
+    if (s.pipe_imp_on) pl->imp = imp_plan(w, h, &s.pipe_imp, scale);
+    pl->imp_on = s.pipe_imp_on && !pl->imp.early;
+    if (s.pipe_df_on && (rc = df_plan(ctx, w, h, &s.pipe_df, scale, "pipeline_run(defringe)", &pl->df))) return rc;
+    pl->df_on = s.pipe_df_on && !pl->df.early;
+    pl->id_lab = pl->imp_on || pl->df_on;
+    PipeMode mode = pl->cc_on ? PIPE_YUV : (pl->id_lab ? PIPE_LAB : PIPE_RGB);           // (sharpening: RGB in, RGB out)
     const bool sm_masks_from_yuv = pl->sm_gen && mode == PIPE_YUV;
+    pl->sm_from_lab = pl->sm_on && mode == PIPE_LAB;
     if (pl->sm_on) mode = PIPE_RGB;
     // creativeGradients, the first step of STAGE_3, starts with setMode(RGB): behind colour correction that is the switch colour correction ends with
     if (s.pipe_cg_on) {
         artgpu_creative_gradients_params cgp = s.pipe_cg;
         cgp.offset_x = cgp.offset_y = 0; cgp.full_width = w; cgp.full_height = h; cgp.scale = 1.0;
         if ((rc = cg_check(ctx, w, h, &cgp, "pipeline_run(creative gradients)", &pl->cg))) return rc;
-        if (pl->cg.apply_gradient || pl->cg.apply_pcvignette) mode = PIPE_RGB;
+        if (pl->cg.apply_gradient || pl->cg.apply_pcvignette) { pl->lab_to_rgb_end = mode == PIPE_LAB; mode = PIPE_RGB; }
     }
     const bool tb_masks_from_yuv = pl->tb_gen && mode == PIPE_YUV;
-    pl->tb_in_yuv = pl->tb_on && mode == PIPE_YUV;
+    pl->tb_from_lab = pl->tb_on && mode == PIPE_LAB;
+    pl->tb_in_yuv = pl->tb_on && mode != PIPE_RGB;
     pl->cc_to_rgb = !pl->tb_in_yuv;
+    if (mode == PIPE_LAB && !pl->tb_on) pl->lab_to_rgb_end = true;     // film grain, the tone curve, the end of the pipe: setMode(RGB)
     // regions whose blend planes the pipe generates itself (artgpu_set_pipeline_masks): the regions' own `mask` pointers are
     // not read, the planes of artgpu_generate_masks take their place; what it does not support fails the frame here
     if ((pl->lc_gen && s.pipe_nlc != nlc) || (pl->tb_gen && s.pipe_ntb != ntb))
@@ -208,7 +227,7 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
     if (pl->tb_gen) {
         if (!p->texture_boost_regions) return fail(ctx, ARTGPU_EINVAL, "pipeline_run(texture boost): bad region list");
         own(pl->tb_regs, p->texture_boost_regions, ntb);
-        if ((rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_tb, ntb, false, "pipeline_run(texture boost masks)", &pl->tb_mk))) return rc;
+        if ((rc = pipe_plan_masks(ctx, p, *pl, pl->tb_from_lab ? ARTGPU_MASKS_MODE_LAB : ARTGPU_MASKS_MODE_RGB, s.pipe_tb, ntb, false, "pipeline_run(texture boost masks)", &pl->tb_mk))) return rc;
     }
     pl->lc_regions = pl->lc_gen ? pl->lc_regs.data() : p->local_contrast_regions;
     pl->tb_regions = pl->tb_gen ? pl->tb_regs.data() : p->texture_boost_regions;
@@ -216,7 +235,7 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
         if (tb_masks_from_yuv)
             return fail(ctx, ARTGPU_EUNSUPPORTED, "pipeline_run: colour correction leaves the image in YUV mode, which the mask engine cannot generate texture boost's masks from");
         if ((rc = cc_check(ctx, w, h, s.pipe_cc, s.pipe_ncc, p->ws, p->iws, !pl->cc_gen, "pipeline_run(colour correction)", &pl->cc))) return rc;
-        if (pl->cc_gen && (rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_cc_masks, s.pipe_ncc, true, "pipeline_run(colour correction masks)", &pl->cc_mk))) return rc;
+        if (pl->cc_gen && (rc = pipe_plan_masks(ctx, p, *pl, pl->id_lab ? ARTGPU_MASKS_MODE_LAB : ARTGPU_MASKS_MODE_RGB, s.pipe_cc_masks, s.pipe_ncc, true, "pipeline_run(colour correction masks)", &pl->cc_mk))) return rc;
     }
     if (pl->sm_on) {      // ImProcFunctions::guidedSmoothing (artgpu_set_pipeline_smoothing): what does not depend on a mask's box is checked here
         if (sm_masks_from_yuv)
@@ -226,7 +245,7 @@ static int pipeline_plan(artgpu_ctx *ctx, const artgpu_plane *raw_in, const artg
             SmRegionPlan sp;
             if (!s.pipe_sm[i].mask && (rc = sm_plan_region(ctx, w, h, s.pipe_sm[i], nullptr, scale, "pipeline_run(smoothing)", i, &sp))) return rc;
         }
-        if (pl->sm_gen && (rc = pipe_plan_masks(ctx, p, *pl, ARTGPU_MASKS_MODE_RGB, s.pipe_sm_masks, s.pipe_nsm, false, "pipeline_run(smoothing masks)", &pl->sm_mk))) return rc;
+        if (pl->sm_gen && (rc = pipe_plan_masks(ctx, p, *pl, pl->sm_from_lab ? ARTGPU_MASKS_MODE_LAB : ARTGPU_MASKS_MODE_RGB, s.pipe_sm_masks, s.pipe_nsm, false, "pipeline_run(smoothing masks)", &pl->sm_mk))) return rc;
     }
     if (pl->lc_on && (rc = local_contrast_check(ctx, w, h, pl->lc_regions, nlc, scale, "pipeline_run(local contrast)"))) return rc;
     if (p->dehaze_enabled && (rc = dehaze_check(ctx, w, h, &p->dehaze, p->ws, scale, "pipeline_run(dehaze)", &pl->dehaze))) return rc;
@@ -370,7 +389,7 @@ static int pipe_input(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const Pi
     return ARTGPU_OK;
 }
 
-// STAGE_2 of ImProcFunctions::process: sharpening, colorCorrection, guidedSmoothing
+// STAGE_2 of ImProcFunctions::process: sharpening, impulsedenoise, defringe, colorCorrection, guidedSmoothing
 static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const PipePlan &pl, PipeFrame *fr)
 {
     const DevRGB &d = fr->d;
@@ -388,14 +407,19 @@ static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const P
         }
         if ((rc = sharpen_dev(ctx, d.p, d.stride, d.w, d.h, &shpar, p->ws, shp, nullptr))) return rc;
     }
-    // ImProcFunctions::colorCorrection, STAGE_2 behind the sharpening (improcfun.cc:601): generateMasks(rgb, ., &Lmask, &abmask) on the RGB image
-    // (ipcolorcorrection.cc:236), then the tool.  It leaves the image in YUV mode for textureBoost, whose setMode(YUV) is then a no-op
+    // ImProcFunctions::impulsedenoise and ::defringe (improcfun.cc:597-599): the first that runs switches to LAB mode, which the image keeps
+    if (pl.imp_on && (rc = impulse_denoise_dev(ctx, d, pl.imp, p->ws, nullptr, 0, 0, nullptr))) return rc;
+    if (pl.df_on && (rc = defringe_dev(ctx, d, pl.df, p->ws, nullptr, pl.imp_on, 0, nullptr))) return rc;
+    // ImProcFunctions::colorCorrection, STAGE_2 behind them (improcfun.cc:601): generateMasks(rgb, ., &Lmask, &abmask) on the image as it is, RGB or LAB
+    // (ipcolorcorrection.cc:236), then the tool, whose setMode(YUV) on a LAB image is lab_to_yuv.  It leaves the image in YUV mode for textureBoost,
+    // whose setMode(YUV) is then a no-op
     if (pl.cc_on) {
         const int n = s.pipe_ncc;
         std::vector<artgpu_color_correction_region> regs(s.pipe_cc, s.pipe_cc + n);
         if (pl.cc_gen && (rc = pipe_gen_masks(ctx, p, d, P_CC_GEN, s.pipe_cc_masks, pl.cc_mk, n, true, &gen))) return rc;
         for (int i = 0; i < n && pl.cc_gen; ++i) { regs[i].lmask = &gen[i]; regs[i].abmask = &gen[n + i]; }
-        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), pl.cc, 0, pl.cc_to_rgb, nullptr))) return rc;
+        if (pl.id_lab && (rc = lab_to_yuv_dev(ctx, d, p->iws))) return rc;
+        if ((rc = color_correction_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), pl.cc, pl.id_lab, pl.cc_to_rgb, nullptr))) return rc;
     }
     // ImProcFunctions::guidedSmoothing, the last step of STAGE_2 (improcfun.cc:602): generateMasks on the image (ipsmoothing.cc:929), setMode(RGB)
     // (colour correction ahead of it ends with that switch), the tool
@@ -404,8 +428,10 @@ static int pipe_stage2(artgpu_ctx *ctx, const artgpu_pipeline_params *p, const P
         std::vector<artgpu_smoothing_region> regs(s.pipe_sm, s.pipe_sm + n);
         if (pl.sm_gen && (rc = pipe_gen_masks(ctx, p, d, P_SM_GEN, s.pipe_sm_masks, pl.sm_mk, n, false, &gen))) return rc;
         for (int i = 0; i < n && pl.sm_gen; ++i) regs[i].mask = &gen[i];
+        if (pl.sm_from_lab && (rc = lab_switch_dev(ctx, d, p->iws, false))) return rc;
         if ((rc = smoothing_dev(ctx, d.p, d.stride, d.w, d.h, regs.data(), n, p->ws, pl.scale, nullptr, "pipeline_run(smoothing)"))) return rc;
     }
+    if (pl.lab_to_rgb_end) return lab_switch_dev(ctx, d, p->iws, false);
     return ARTGPU_OK;
 }
 
@@ -423,6 +449,7 @@ static int pipe_stage3(artgpu_ctx *ctx, const artgpu_pipeline_params *p, PipePla
     // ImProcFunctions::textureBoost, the next step of STAGE_3 (improcfun.cc:606); the batch pipe is the OUTPUT pipeline: high_detail
     if (pl.tb_gen && (rc = pipe_gen_masks(ctx, p, d, P_MK_OUT, ctx->shared.pipe_tb, pl.tb_mk, ntb, false, &gen))) return rc;   // iptextureboost.cc:210, ahead of setMode(YUV)
     for (int i = 0; i < ntb && pl.tb_gen; ++i) pl.tb_regs[i].mask = &gen[i];
+    if (pl.tb_from_lab && (rc = lab_to_yuv_dev(ctx, d, p->iws))) return rc;          // textureBoost's setMode(YUV) on the LAB image impulsedenoise / defringe left
     if (pl.tb_on && (rc = texture_boost_dev(ctx, d.p, d.stride, d.w, d.h, pl.tb_regions, ntb, p->ws, pl.tb, 1, nullptr, pl.tb_in_yuv))) return rc;
     // ImProcFunctions::filmGrain, right behind texture boost (improcfun.cc:608): its guidedSmoothing starts with setMode(RGB), which texture boost ended with
     if (pl.fg.info.nregions > 0 && (rc = film_grain_dev(ctx, d.p, d.stride, d.w, d.h, p->ws, pl.fg))) return rc;
@@ -506,6 +533,20 @@ int artgpu_set_pipeline_color_correction(artgpu_ctx *ctx, const artgpu_color_cor
     if (n < 0 || (n > 0 && !regions) || (n == 0 && masks)) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_color_correction: bad arguments");
     own_pipe_regions(ctx->pipe_cc_own, regions, n, {&artgpu_color_correction_region::lmask, &artgpu_color_correction_region::abmask}, masks,
                      &ctx->shared.pipe_cc, &ctx->shared.pipe_cc_masks, &ctx->shared.pipe_ncc);
+    return ARTGPU_OK;
+}
+
+int artgpu_set_pipeline_impulse_defringe(artgpu_ctx *ctx, const artgpu_impulse_denoise_params *impulse, const artgpu_defringe_params *defringe)
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (defringe && (defringe->nhuecurve < 0 || (defringe->nhuecurve > 0 && !defringe->huecurve))) return fail(ctx, ARTGPU_EINVAL, "set_pipeline_impulse_defringe: bad hue curve");
+    artgpu_ctx::Shared &s = ctx->shared;
+    s.pipe_imp_on = impulse != nullptr;
+    s.pipe_imp = impulse ? *impulse : artgpu_impulse_denoise_params{};
+    s.pipe_df_on = defringe != nullptr;
+    s.pipe_df = defringe ? *defringe : artgpu_defringe_params{};
+    ctx->pipe_df_curve.assign(s.pipe_df.huecurve, s.pipe_df.huecurve + s.pipe_df.nhuecurve);
+    s.pipe_df.huecurve = ctx->pipe_df_curve.empty() ? nullptr : ctx->pipe_df_curve.data();
     return ARTGPU_OK;
 }
 

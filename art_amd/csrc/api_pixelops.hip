@@ -149,6 +149,16 @@ int lab_switch_dev(artgpu_ctx *ctx, const DevRGB &d, const double m[9], bool to_
     return ARTGPU_OK;
 }
 
+int lab_to_yuv_dev(artgpu_ctx *ctx, const DevRGB &d, const double iws[9])
+{
+    LabArgs a = {};
+    for (int k = 0; k < 3; ++k) a.img[k] = d.p[k];
+    a.stride = d.stride; a.w = d.w; a.h = d.h;
+    for (int k = 0; k < 9; ++k) a.iws[k] = (float)iws[k];
+    HIPCHK(ctx, launch_lab_to_yuv(a, ctx->stream));
+    return ARTGPU_OK;
+}
+
 int scale_args_fill(artgpu_ctx *ctx, int w, int h, int src_is_u16, uint32_t filters, const int32_t *xtrans, const float cblacksom[4], const float scale_mul[4],
                     const char *who, ScaleArgs *a)
 {
@@ -227,6 +237,17 @@ int artgpu_tone_curve(artgpu_ctx *ctx, artgpu_rgb *image, int mode, const float 
 
 int artgpu_rgb_to_lab(artgpu_ctx *ctx, artgpu_rgb *img, const double ws[9]) { return lab_mode_switch(ctx, img, ws, true, "rgb_to_lab"); }
 int artgpu_lab_to_rgb(artgpu_ctx *ctx, artgpu_rgb *img, const double iws[9]) { return lab_mode_switch(ctx, img, iws, false, "lab_to_rgb"); }
+
+int artgpu_lab_to_yuv(artgpu_ctx *ctx, artgpu_rgb *img, const double iws[9])
+{
+    if (!ctx) return ARTGPU_EINVAL;
+    if (!img || !iws) return fail(ctx, ARTGPU_EINVAL, "lab_to_yuv: null argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevRGB d;
+    int rc;
+    if ((rc = bind_rgb(ctx, img, 4, true, &d, "lab_to_yuv")) || (rc = lab_to_yuv_dev(ctx, d, iws))) return rc;
+    return unbind_rgb(ctx, img, &d);
+}
 
 int artgpu_lab_histogram(artgpu_ctx *ctx, const artgpu_rgb *img, uint32_t hist[65536])
 {

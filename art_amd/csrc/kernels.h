@@ -260,6 +260,7 @@ struct LabArgs {
 };
 hipError_t launch_rgb_to_lab(const LabArgs &a, hipStream_t s);
 hipError_t launch_lab_to_rgb(const LabArgs &a, hipStream_t s);
+hipError_t launch_lab_to_yuv(const LabArgs &a, hipStream_t s);       // Imagefloat::lab_to_yuv (imagefloat.cc:988-1022), iws only
 hipError_t launch_lab_hist(const LabArgs &a, hipStream_t s);
 hipError_t launch_lab_adjust(const LabArgs &a, hipStream_t s);
 // ---- dual demosaic blend (dualdemosaic.hip; dual_demosaic_RT.cc:73-152, rt_algo.cc:315-498) ----

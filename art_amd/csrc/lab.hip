@@ -99,6 +99,35 @@ __global__ void __launch_bounds__(256) lab_to_rgb_kernel(LabArgs a)
     }
 }
 
+// Imagefloat::lab_to_yuv (imagefloat.cc:988-1022), what setMode(YUV) does to an image in LAB mode: Lab2XYZ and xyz2rgb as in lab_to_rgb, but Y is the
+// XYZ one, not a row of the matrix: g = Y, b = Y - B, r = R - Y.  (In bits this is not lab_to_rgb followed by the RGB -> YUV switch.)
+__global__ void __launch_bounds__(256) lab_to_yuv_kernel(LabArgs a)
+{
+    const int W4 = a.w & ~3;
+    const float c1By116 = (float)(1.0 / 116.0), c16By116 = (float)(16.0 / 116.0);
+    FOR_IMAGE_XY(y, x, a.w, a.h) {
+        const size_t i = (size_t)y * a.stride + x;
+        const float LL = a.img[1][i] / 327.68f, aa = a.img[0][i] / 327.68f, bb = a.img[2][i] / 327.68f;
+        const float fy = (c1By116 * LL) + c16By116;
+        const float fx = (0.002f * aa) + fy;
+        const float fz = fy - (0.005f * bb);
+        const float xx = 65535.0f * f2xyz(fx) * D50x;
+        const float zz = 65535.0f * f2xyz(fz) * D50z;
+        float yy;
+        if (x < W4) {
+            const float res1 = fy * fy * fy, res2 = LL / (float)(24389.0 / 27.0);
+            yy = (LL > 8.f ? res1 : res2) * 65535.f;
+        } else {
+            yy = ((double)LL > 8.0) ? 65535.0f * fy * fy * fy : (float)((double)(65535.0f * LL) / (24389.0 / 27.0));
+        }
+        const float R = a.iws[0] * xx + a.iws[1] * yy + a.iws[2] * zz;
+        const float B = a.iws[6] * xx + a.iws[7] * yy + a.iws[8] * zz;
+        a.img[1][i] = yy;
+        a.img[2][i] = yy - B;
+        a.img[0][i] = R - yy;
+    }
+}
+
 // hist16[(int)L]++ (iplabadjustments.cc:300-327); LUTu::operator[](int) clamps the index, an out-of-range float -> int is x86's INT_MIN
 __global__ void __launch_bounds__(256) lab_hist_kernel(LabArgs a)
 {
@@ -145,6 +174,11 @@ hipError_t launch_rgb_to_lab(const LabArgs &a, hipStream_t s)
 hipError_t launch_lab_to_rgb(const LabArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(lab_to_rgb_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_lab_to_yuv(const LabArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(lab_to_yuv_kernel, image_grid(a.w, a.h), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_lab_hist(const LabArgs &a, hipStream_t s)

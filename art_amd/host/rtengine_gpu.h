@@ -122,6 +122,17 @@ struct ProcParams {
                                         sharpening.deconvradius, sharpening.deconvCornerBoost, sharpening.deconvCornerLatitude, offset_x, offset_y,
                                         full_width, full_height, 0};
     }
+    // ImpulseDenoiseParams (procparams.h:736-744) and DefringeParams (procparams.h:721-731; defaults procparams.cc:1835-1867)
+    struct { bool enabled = false; int thresh = 50; } impulseDenoise;
+    struct { bool enabled = false; double radius = 2.0; int threshold = 13;
+             std::vector<double> huecurve = {1 /*FCT_MinMaxCPoints*/, 0.166666667, 0., 0.35, 0.35, 0.347, 0., 0.35, 0.35, 0.513667426, 0, 0.35, 0.35, 0.668944571, 0., 0.35, 0.35,
+                                             0.8287775246, 0.97835991, 0.35, 0.35, 0.9908883827, 0., 0.35, 0.35}; } defringe;
+    artgpu_impulse_denoise_params impulseDenoiseParams() const { return artgpu_impulse_denoise_params{impulseDenoise.enabled ? 1 : 0, impulseDenoise.thresh}; }
+    artgpu_defringe_params defringeParams() const
+    {
+        return artgpu_defringe_params{defringe.enabled ? 1 : 0, defringe.threshold, defringe.radius, defringe.huecurve.empty() ? nullptr : defringe.huecurve.data(),
+                                      (int32_t)defringe.huecurve.size(), 0};
+    }
     // rtengine::procparams::Mask (procparams.cc:1014-1053, 1122-1137) as generateMasks' parametric path reads it.  `area` is
     // generate_area_mask's finished plane (rasterising the shapes is host code of the application).  deltaE, drawn, external and linked masks,
     // a mask curve other than the identity: flags only, artgpu_generate_masks answers them with ARTGPU_EUNSUPPORTED
@@ -457,7 +468,7 @@ public:
         switch (stage) {
         case Stage::STAGE_0: dehaze(img); break;                                              // improcfun.cc:577
         case Stage::STAGE_1: channelMixer(img); exposure(img); hslEqualizer(img); toneEqualizer(img); break;   // improcfun.cc:581-588
-        case Stage::STAGE_2: sharpening(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595, 601, 602
+        case Stage::STAGE_2: sharpening(img); impulsedenoise(img); defringe(img); colorCorrection(img); guidedSmoothing(img); break;   // improcfun.cc:595-602
         case Stage::STAGE_3:                                                                  // improcfun.cc:605-627 (the steps this library has)
             creativeGradients(img);                                                           // L605
             textureBoost(img); filmGrain(img); logEncoding(img); saturationVibrance(img);       // L606-611
@@ -642,6 +653,22 @@ public:
         artgpu_rgb i = img->view();
         ctx.check(artgpu_sharpening(ctx.get(), &i, &sp, params->workingSpace, scale, nullptr));
         return false;
+    }
+    // ImProcFunctions::impulsedenoise (impulse_denoise.cc:179-189) and ::defringe (PF_correct_RT.cc:210-218), the tools behind the sharpening in STAGE_2.  The
+    // reference leaves the image in LAB mode for the next tool's setMode; this mirror has no mode tracking and converts back at once (like labAdjustments)
+    void impulsedenoise(Imagefloat *img)
+    {
+        if (!params->impulseDenoise.enabled) return;
+        const artgpu_impulse_denoise_params ip = params->impulseDenoiseParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_impulse_denoise(ctx.get(), &i, &ip, params->workingSpace, params->workingSpaceInverse, scale, 1, nullptr));
+    }
+    void defringe(Imagefloat *img)
+    {
+        if (!params->defringe.enabled) return;
+        const artgpu_defringe_params dp = params->defringeParams();
+        artgpu_rgb i = img->view();
+        ctx.check(artgpu_defringe(ctx.get(), &i, &dp, params->workingSpace, params->workingSpaceInverse, scale, 0, 1, nullptr));
     }
     int offset_x = 0, offset_y = 0;    // with full_width / full_height (logEncoding): where the image lies in the full frame (improcfun.h setViewport)
     // ImProcFunctions::channelMixer (ipchmixer.cc:152-234), RGB_MATRIX mode: the nine percentages / 1000 (L185-199)
@@ -870,7 +897,11 @@ public:
         std::vector<artgpu_mask_params> tb_mp;
         if (ProcParams::regionMasks(p.textureBoost, tb_masks)) tb_mp = ProcParams::maskParams(tb_masks, tb_areas);
         ctx.check(artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, tb_mp.empty() ? nullptr : tb_mp.data(), (int)tb_mp.size()));
-        // ImProcFunctions::colorCorrection behind the sharpening: the regions (and their Masks, generated by the pipe) as a setting of the context
+        // ImProcFunctions::impulsedenoise and ::defringe behind the sharpening
+        const artgpu_impulse_denoise_params imp = p.impulseDenoiseParams();
+        const artgpu_defringe_params dfp = p.defringeParams();
+        ctx.check(artgpu_set_pipeline_impulse_defringe(ctx.get(), p.impulseDenoise.enabled ? &imp : nullptr, p.defringe.enabled ? &dfp : nullptr));
+        // ImProcFunctions::colorCorrection behind them: the regions (and their Masks, generated by the pipe) as a setting of the context
         std::vector<artgpu_plane> cc_blends, cc_areas;
         std::vector<artgpu_color_correction_region> cc_regions;
         std::vector<const ProcParams::Mask *> cc_masks;
@@ -926,6 +957,7 @@ public:
         ctx.check(artgpu_set_batch_lanes(ctx.get(), lanes));
         const int rc = artgpu_batch_run_io(ctx.get(), (int)jobs.size(), in.data(), &pp, out.data());
         (void)artgpu_set_pipeline_masks(ctx.get(), nullptr, 0, nullptr, 0);
+        (void)artgpu_set_pipeline_impulse_defringe(ctx.get(), nullptr, nullptr);
         (void)artgpu_set_pipeline_color_correction(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_smoothing(ctx.get(), nullptr, 0, nullptr);
         (void)artgpu_set_pipeline_tone_equalizer(ctx.get(), nullptr);

@@ -456,6 +456,10 @@ int artgpu_log_encoding(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_logenc_pa
  * form of each pixel's column (and, for XYZ2Lab, of its group of four). */
 int artgpu_rgb_to_lab(artgpu_ctx *ctx, artgpu_rgb *img, const double ws[9]);
 int artgpu_lab_to_rgb(artgpu_ctx *ctx, artgpu_rgb *img, const double iws[9]);
+/* Imagefloat::setMode(YUV) on an image in LAB mode = lab_to_yuv (imagefloat.cc:988-1022), in place: Lab2XYZ, xyz2rgb with iws, then g = Y,
+ * b = Y - B, r = R - Y with the Y of XYZ.  Columns below 4 * (W / 4) take the 4-wide body's Lab2XYZ, the others the scalar one, as in
+ * artgpu_lab_to_rgb.  In bits this is NOT artgpu_lab_to_rgb followed by the RGB -> YUV switch (there Y is a row of ws times the rounded RGB). */
+int artgpu_lab_to_yuv(artgpu_ctx *ctx, artgpu_rgb *img, const double iws[9]);
 int artgpu_lab_histogram(artgpu_ctx *ctx, const artgpu_rgb *img, uint32_t hist[65536]);
 int artgpu_lab_adjustments(artgpu_ctx *ctx, artgpu_rgb *img, const float *lcurve, const float *acurve, const float *bcurve, float chroma);
 
@@ -697,6 +701,93 @@ int artgpu_gaussian_blur_ex(artgpu_ctx *ctx, artgpu_plane *src, artgpu_plane *ds
 int artgpu_deconv_auto_radius(artgpu_ctx *ctx, const artgpu_plane *raw, uint32_t filters, float lower_limit, float clip_val,
                               float *radius, float *max_ratio /* may be NULL */);
 
+/* Impulse noise reduction: ImProcFunctions::impulsedenoise (rtengine/impulse_denoise.cc:179-189; the second tool of STAGE_2,
+ * improcfun.cc:589-603) with impulse_nr (L33-174), in place on an image in RGB mode (host or device, any row stride or start offset):
+ *   the gates of L182: enabled, W >= 8, H >= 8, scale >= 0.5 -- otherwise nothing happens and the call succeeds (info->early_out says which);
+ *   float t = thresh / scale (the quotient in double, narrowed); impulse_nr(img, t / 20.0) hands markImpulse the float of that double;
+ *   setMode(LAB) (artgpu_rgb_to_lab with `ws`): afterwards g = L, r = a, b = b;
+ *   markImpulse on the L plane (rt_algo.cc:497-596): the low-pass is gaussianBlur at max(2.f, thresh - 1.f), always the recursive gaussian;
+ *   impthr = max(1.f, 5.5f - thresh); a pixel is impish when |L - lpf| exceeds impthr / 24 times the sum over the rest of its 5 x 5 window
+ *   (the columns the reference's 4-wide loop covers test the sign bit as _mm_movemask_ps does);
+ *   for every impish pixel, over its 5 x 5 window clamped at the four edges, row-major, skipping impish neighbours:
+ *   dirwt = 1 / (SQR(L[i1][j1] - L[i][j]) + 1.f), norm += dirwt and three sums of dirwt * {L, a, b} (float, unfused, from 0); the three
+ *   quotients by norm are written `if (norm)`.  Only impish pixels are written and only other pixels are read, so the result does not
+ *   depend on the order of the pixels: the reference's bits.
+ * to_rgb != 0 applies setMode(RGB) (artgpu_lab_to_rgb with `iws`) on top; the reference leaves the image in LAB mode (to_rgb == 0, `iws` may
+ * then be NULL), as artgpu_texture_boost's to_rgb.  A non-NULL `info` costs the call's one host wait.
+ * ARTGPU_EINVAL, image untouched: a bad image, NULL params or ws, to_rgb without iws.
+ * Device scratch (context pool, shared with artgpu_sharpening): three full-size planes and a byte plane. */
+typedef struct artgpu_impulse_denoise_params {   /* ImpulseDenoiseParams (procparams.h:736-744; defaults: off, 50) */
+    int32_t enabled;
+    int32_t thresh;
+} artgpu_impulse_denoise_params;
+typedef struct artgpu_impulse_denoise_info {
+    int32_t early_out;                /* 0 none; 1 !enabled, 2 W or H < 8, 3 scale < 0.5 (or not a number) */
+    float thresh;                     /* what markImpulse received */
+    float sigma;                      /* max(2.f, thresh - 1.f) */
+    float impthr;                     /* max(1.f, 5.5f - thresh) */
+    int64_t impulse_pixels;           /* non-zero bytes of the impulse map */
+} artgpu_impulse_denoise_info;
+int artgpu_impulse_denoise(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_impulse_denoise_params *params, const double ws[9],
+                           const double *iws /* to_rgb only */, double scale, int to_rgb, artgpu_impulse_denoise_info *info /* may be NULL */);
+
+/* Defringe: ImProcFunctions::defringe (rtengine/PF_correct_RT.cc:210-218; the third tool of STAGE_2) with PF_correct_RT (L44-205), in place
+ * on an image in RGB mode (host or device, any row stride or start offset):
+ *   the gates of L212: enabled, W >= 8, H >= 8 -- otherwise nothing happens and the call succeeds (info->early_out says which);
+ *   radius = params.radius / scale in double, halfwin = ceil(2 * radius) + 1; setMode(LAB) (g = L, r = a, b = b);
+ *   tmpa = gaussianBlur(a), tmpb = gaussianBlur(b), src != dst, GAUSS_STANDARD (gauss.cc:1437-1523): a copy below 0.25, the non-separated
+ *   gauss3x3 (gauss.cc:129-174, coefficients in double on the host, L1448-1461) in [0.25, 0.6), the recursive gaussian from 0.6;
+ *   L73-114: chroma = chromaChfactor * (SQR(a - tmpa) + SQR(b - tmpb)); with a hue curve (huecurve non-empty and huecurve[0] above
+ *   FCT_Linear; the tool's default has one) chromaChfactor = SQR(1.f + chparam), chparam = float(curve.getVal(huelab_to_huehsv2(xatan2f(b,
+ *   a))) - 0.5f), doubled when negative; the curve is FlatCurve(huecurve) (periodic, 1000 polygon points), evaluated in double;
+ *   chromave = the double sum of the float chroma values / (H * W).  DEFINITION 1: the reference's sum is an OpenMP reduction whose last
+ *   bits depend on the schedule; here it is taken in a fixed order that depends on W * H alone (pixels in row-major index order form chunks of
+ *   4096; within a chunk 256 strided sub-sums of 16, folded pairwise at distances 32 .. 1 within each group of 64 and the four groups in
+ *   order; the chunks' sums combined the same way), without atomics: the same bits on every run;
+ *   nothing more happens unless chromave > 0.0 (L119); wt = float(1.f / (chroma + chromave)), threshfactor = float(1.f / (SQR(thresh / 33.f)
+ *   * chromave * 5.0f + chromave)), both in the reference's float / double mix, on the device;
+ *   every pixel with wt < threshfactor becomes a = atot / norm, b = btot / norm, the sums of wt * a, wt * b and wt over its (2 halfwin - 1)^2
+ *   window clamped to the image, row-major, float, unfused.  DEFINITION 2: EVERY WINDOW READS THE TOOL'S INPUT a AND b (the values behind
+ *   setMode(LAB)).  The reference overwrites a and b while other pixels' windows read them, under schedule(dynamic,16), so its own output
+ *   depends on thread timing; one thread gives a raster-order sweep in which each corrected pixel depends on the ones before it.  The SET of
+ *   corrected pixels is the reference's (wt is complete before the loop), and so is every corrected pixel whose window holds no other
+ *   corrected pixel.
+ * from_lab != 0: the image is in LAB mode already (artgpu_impulse_denoise with to_rgb == 0 ran ahead), setMode(LAB) does nothing and `ws` is
+ * not read.  to_rgb as in artgpu_impulse_denoise.  A non-NULL `info` costs the call's one host wait; without it the tool never waits for the device.
+ * ARTGPU_EUNSUPPORTED, image untouched, decided before any kernel runs:
+ *   - radius / scale not finite or >= 25;
+ *   - halfwin > ARTGPU_DEFRINGE_MAX_HALFWIN (radius / scale > 5: at the GUI's largest radius, 5, every scale below 1; at the default
+ *     radius 2, scales below 0.4), the limit of the averaging kernel's tile in LDS;
+ *   - W < 2 * halfwin - 2, where the reference's first column loop (L144-151) reads past the end of the row;
+ *   - more than 2^31 - 1 pixels; a hue curve whose polyline exceeds 64 KB.
+ * ARTGPU_EINVAL: a bad image, NULL params or ws, to_rgb without iws, scale <= 0, a negative radius, nhuecurve < 0 or without huecurve.
+ * Device scratch (context pool): four full-size planes (shared with artgpu_sharpening), 64 KB + 8 bytes per 4096 pixels. */
+#define ARTGPU_DEFRINGE_MAX_HALFWIN 11
+#define ARTGPU_DEFRINGE_BLUR_COPY 0
+#define ARTGPU_DEFRINGE_BLUR_3X3  1
+#define ARTGPU_DEFRINGE_BLUR_YVV  2
+typedef struct artgpu_defringe_params {   /* DefringeParams (procparams.h:721-731; defaults procparams.cc:1835-1867: off, 2.0, 13, six points) */
+    int32_t enabled;
+    int32_t threshold;
+    double radius;
+    const double *huecurve;           /* FlatCurve control points {type, x, y, left tangent, right tangent, ...}; read during the call only */
+    int32_t nhuecurve;                /* doubles in huecurve; 0: no curve */
+    int32_t pad_;
+} artgpu_defringe_params;
+typedef struct artgpu_defringe_info {
+    int32_t early_out;                /* 0 none; 1 !enabled, 2 W or H < 8 */
+    int32_t halfwin;
+    int32_t blur;                     /* ARTGPU_DEFRINGE_BLUR_* */
+    int32_t curve;                    /* 0: no hue curve; 1: evaluated; -1: a curve FlatCurve's constructor leaves empty (getVal = 0.5) */
+    double radius;                    /* params.radius / scale */
+    double chromave;
+    float threshfactor;               /* 0 unless chromave > 0 */
+    int32_t pad_;
+    int64_t corrected_pixels;         /* pixels with wt < threshfactor */
+} artgpu_defringe_info;
+int artgpu_defringe(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_defringe_params *params, const double *ws /* unless from_lab */,
+                    const double *iws /* to_rgb only */, double scale, int from_lab, int to_rgb, artgpu_defringe_info *info /* may be NULL */);
+
 /* Texture boost: ImProcFunctions::textureBoost (rtengine/iptextureboost.cc:183-248; the first arithmetic step of STAGE_3, improcfun.cc:606),
  * ART's detail tool.  artgpu_texture_boost_plane is one texture_boost call (L37-178) in place on a Y plane (host or device, any row stride),
  * without a mask blend:
@@ -865,6 +956,10 @@ typedef struct artgpu_color_correction_info {     /* one per region */
 } artgpu_color_correction_info;
 int artgpu_color_correction(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
                             const double iws[9], int to_rgb, artgpu_color_correction_info *info /* nregions entries or NULL */);
+/* ... on an image that is in YUV mode already (g = Y, b = u, r = v), where the tool's setMode(YUV) does nothing: behind artgpu_lab_to_yuv on the
+ * LAB image artgpu_impulse_denoise / artgpu_defringe leave with to_rgb == 0, which is how the reference reaches colorCorrection from them. */
+int artgpu_color_correction_yuv(artgpu_ctx *ctx, artgpu_rgb *img, const artgpu_color_correction_region *regions, int nregions, const double ws[9],
+                                const double iws[9], int to_rgb, artgpu_color_correction_info *info /* nregions entries or NULL */);
 
 /* ImProcFunctions::guidedSmoothing (rtengine/ipsmoothing.cc:902-1073), ART's "Smoothing" tool, modes GUIDED and NLMEANS: the last step of
  * STAGE_2, behind colorCorrection (improcfun.cc:602).  `img`: RGB mode, 0..65535, host or device, any row stride, in place.  The image is
@@ -1104,6 +1199,18 @@ int artgpu_pipeline_run(artgpu_ctx *ctx, const artgpu_plane *raw, const artgpu_p
  * from the frame's region count is ARTGPU_EINVAL, what artgpu_generate_masks does not support ARTGPU_EUNSUPPORTED, both before any stage runs. */
 int artgpu_set_pipeline_masks(artgpu_ctx *ctx, const artgpu_mask_params *local_contrast_masks, int nlc,
                               const artgpu_mask_params *texture_boost_masks, int ntb);
+/* Impulse noise reduction and defringe in the per-frame pipe, a setting of the context for the same reason.  Either pointer may be NULL = that
+ * tool off; both off is the default, and the pipe then launches exactly what it launched before.  The parameters (and the hue curve) are
+ * copied; batch lanes inherit them.  While set, the three pipe entries run artgpu_impulse_denoise's / artgpu_defringe's code with
+ * params->scale behind the sharpening and ahead of colour correction, in the reference's order (improcfun.cc:597-599).  The first of the
+ * two whose gates pass does setMode(LAB), and the image stays in LAB mode until the next tool's setMode, as in the reference:
+ *   colour correction next, or texture boost with no tool in between: pipe-generated masks are generated on the LAB image
+ *   (ARTGPU_MASKS_MODE_LAB), then artgpu_lab_to_yuv and the tool's existing YUV input;
+ *   smoothing next: its pipe-generated masks on the LAB image, then its setMode(RGB) = artgpu_lab_to_rgb;
+ *   otherwise (a gradient filter, film grain, the tone curve, the end of the pipe): artgpu_lab_to_rgb at the end of STAGE_2.
+ * What artgpu_defringe refuses fails the frame before any stage runs. */
+int artgpu_set_pipeline_impulse_defringe(artgpu_ctx *ctx, const artgpu_impulse_denoise_params *impulse /* or NULL */,
+                                         const artgpu_defringe_params *defringe /* or NULL */);
 /* Colour correction in the per-frame pipe, a setting of the context for the same reason.  regions: n entries (deep-copied; batch lanes share
  * the copy); NULL / 0 = off, the default.  masks: n entries or NULL, copied as artgpu_set_pipeline_masks copies them.  While set, the three
  * pipe entries run artgpu_color_correction's code after the sharpening and before texture boost (STAGE_2, improcfun.cc:601).  With `masks`
