@@ -64,7 +64,7 @@ int texture_boost_region_dev(artgpu_ctx *ctx, float *Y, size_t stride, int W, in
     float *planes, *low, *tmp, *stf;
     int rc;
     if ((rc = pool_get(ctx, P_TB_PLANES, (pl.isguided ? 2 : 3) * nw * 4, &planes)) || (rc = pool_get(ctx, P_TB_LOW, nlow * 4, &low)) ||
-        (rc = pool_get(ctx, P_TB_TMP, nlow * 4, &tmp)) || (rc = pool_get(ctx, P_TB_STATE, (sizeof(TbState) / 4 + TB_MAX_PARTIALS) * 4, &stf)))
+        (rc = pool_get(ctx, P_TB_TMP, nlow * 4, &tmp)) || (rc = pool_get(ctx, P_TB_STATE, (sizeof(TbState) / 4 + 3 * TB_MAX_PARTIALS) * 4, &stf)))      // state | minima | their 64-bit indices
         return rc;
     TbState *st = reinterpret_cast<TbState *>(stf);
     *state = st;
@@ -72,7 +72,8 @@ int texture_boost_region_dev(artgpu_ctx *ctx, float *Y, size_t stride, int W, in
     const float *mk = nullptr;
     size_t m_stride = 0;
     if (do_blend && (rc = bind_plane(ctx, mask, P_TB_MASK, &mk, &m_stride))) return rc;
-    TbPrepareArgs pa = {Y, stride, W, H, src, mid, pl.w, pl.h, stf + sizeof(TbState) / 4};
+    TbPrepareArgs pa = {Y, stride, W, H, src, mid, pl.w, pl.h, stf + sizeof(TbState) / 4,
+                        reinterpret_cast<unsigned long long *>(stf + sizeof(TbState) / 4 + TB_MAX_PARTIALS)};
     HIPCHK(ctx, launch_tb_prepare(pa, st, ctx->stream));
     for (int i = 0; i < iterations; ++i) {
         if (pl.isguided) {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "devmath.h"
 #include "devsleef.h"
+#define LIBMPOWF_OPAQUE        // see libmpowf.h
 #include "jzazbzdev.h"
 #include "colorcorrection.h"
 #include <cmath>

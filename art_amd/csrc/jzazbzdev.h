@@ -1,26 +1,27 @@
 // art_amd/csrc/jzazbzdev.h -- Color::rgb2jzazbz / jzazbz2rgb on the device (reference: rtengine/color.cc:48-86, 6706-6742 and color.h:1765-1778),
 // shared by the NEUTRAL tone curve (tonecurve.hip) and the colour correction (colorcorrection.hip), as labdev.h shares Color::rgb2lab.
 // The PQ tables are the host-built ones (build_pq_luts: Color::init's jzazbz_pq_ / jzazbz_pq_inv_); an argument outside [0, 1] takes
-// PQ / PQ_inv themselves, a per-pixel powf (the device's powf there: tolerance).  The two conversions take the table
+// PQ / PQ_inv themselves, a per-pixel powf with the bits of the host's libm (libmpowf.h; the tests keep their tolerance there).  The two conversions take the table
 // lookup as a callable, so that a kernel decides where its tables live and what else a lookup records.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "devmath.h"
 #include "devsleef.h"
+#include "libmpowf.h"
 
 namespace artgpu {
 
 __device__ __forceinline__ float dev_PQ(float X)
 {
     X = std_max(X, 1e-10f);
-    const float XX = powf(X * 1e-4f, 0.1593017578125f);
-    return powf((0.8359375f + 18.8515625f * XX) / (1 + 18.6875f * XX), 134.034375f);
+    const float XX = libm_powf(X * 1e-4f, 0.1593017578125f);
+    return libm_powf((0.8359375f + 18.8515625f * XX) / (1 + 18.6875f * XX), 134.034375f);
 }
 __device__ __forceinline__ float dev_PQ_inv(float X)
 {
     X = std_max(X, 1e-10f);
-    const float XX = powf(X, 7.460772656268214e-03f);
-    return 1e4f * powf((0.8359375f - XX) / (18.6875f * XX - 18.8515625f), 6.277394636015326f);
+    const float XX = libm_powf(X, 7.460772656268214e-03f);
+    return 1e4f * libm_powf((0.8359375f - XX) / (18.6875f * XX - 18.8515625f), 6.277394636015326f);
 }
 // LUTf::operator[](float), flags 0, index >= 0 here
 __device__ __forceinline__ float lut_noclip(const float *__restrict__ data, float index)

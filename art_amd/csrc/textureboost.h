@@ -15,7 +15,8 @@ struct TbState { float minval; float pad[15]; };
 struct TbPrepareArgs {
     const float *Y; size_t stride; int W, H;
     float *src, *mid; int w, h;            // w x h == W x H unless the rescale of L57-63 is taken
-    float *partial;                        // one minimum per workgroup
+    float *partial;                        // one minimum per workgroup ...
+    unsigned long long *partial_idx;       // ... and the raster index of the first pixel that holds it
 };
 struct TbConvArgs { const float *src; float *dst; int w, h; int K; float coef[TB_MAX_K * TB_MAX_K]; };
 // the statistics grid of a self-guided filter on `mid`: plane 0 = I1 -> meanI -> mean a, plane 1 = I1 * I1 -> corrI -> mean b (DhGuided)

@@ -22,45 +22,64 @@ namespace {
 constexpr float TB_INF = __builtin_huge_valf();     // RT_INFINITY
 constexpr float TB_LO = 1e-5f, TB_HI = 32.f;        // L75-76
 
+// rt_math.h:54-64 folded over the plane in raster order (L92, L99): min(a, b) = b < a ? b : a keeps a when the two compare equal, so where a
+// +0.0 and a -0.0 are both the plane's minimum the earlier pixel's is minval -- and minval is what L145 / L154 write into every pixel it wins.
+// (v, vi): a pixel's value and its raster index in the work plane.  A NaN never replaces m, as before.
+__device__ __forceinline__ void tb_min_first(float &m, unsigned long long &mi, float v, unsigned long long vi)
+{
+    if (v < m || (v == m && vi < mi)) { m = v; mi = vi; }
+}
+// the 256 (m, mi) of a workgroup folded into entry 0
+__device__ __forceinline__ void tb_min_fold(float *lds, unsigned long long *ldi, int t, float m, unsigned long long mi)
+{
+    lds[t] = m; ldi[t] = mi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            float a = lds[t]; unsigned long long ai = ldi[t];
+            tb_min_first(a, ai, lds[t + s], ldi[t + s]);
+            lds[t] = a; ldi[t] = ai;
+        }
+        __syncthreads();
+    }
+}
+
 // L85-101: v = src / 65535.f, mid = clamp(v), the workgroup's minimum of v.  With the rescale of L57-63, src is rescaleBilinear(Y) evaluated
 // here.  Columns below 4 * (w / 4) clamp the way the reference's vector body does (vmaxf(vminf(v, hi), lo)), the others the way LIM does: the
 // two part for a NaN only.
 __global__ void __launch_bounds__(256) tb_prepare_kernel(TbPrepareArgs a)
 {
     __shared__ float lds[256];
+    __shared__ unsigned long long ldi[256];
     const bool same = a.w == a.W && a.h == a.H;
     const float col_scale = (float)a.W / (float)a.w, row_scale = (float)a.H / (float)a.h;
     const int wvec = (a.w / 4) * 4;
     float m = TB_INF;
+    unsigned long long mi = ~0ull;
     FOR_IMAGE_XY(y, x, a.w, a.h) {
         const float s = same ? a.Y[(size_t)y * a.stride + x] : dh_bilinear(a.Y, a.stride, a.W, a.H, x * col_scale, y * row_scale);
         const float v = s / 65535.f;
         const size_t i = (size_t)y * a.w + x;
         a.src[i] = v;
         a.mid[i] = x < wvec ? sse_max(sse_min(v, TB_HI), TB_LO) : std_max(TB_LO, std_min(v, TB_HI));
-        m = std_min(m, v);
+        tb_min_first(m, mi, v, i);
     }
     const int t = threadIdx.x;
-    lds[t] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) lds[t] = std_min(lds[t], lds[t + s]);
-        __syncthreads();
+    tb_min_fold(lds, ldi, t, m, mi);
+    if (t == 0) {
+        a.partial[blockIdx.y * gridDim.x + blockIdx.x] = lds[0];
+        a.partial_idx[blockIdx.y * gridDim.x + blockIdx.x] = ldi[0];
     }
-    if (t == 0) a.partial[blockIdx.y * gridDim.x + blockIdx.x] = lds[0];
 }
-__global__ void __launch_bounds__(256) tb_min_final_kernel(const float *partial, int n, TbState *st)
+__global__ void __launch_bounds__(256) tb_min_final_kernel(const float *partial, const unsigned long long *partial_idx, int n, TbState *st)
 {
     __shared__ float lds[256];
+    __shared__ unsigned long long ldi[256];
     float m = TB_INF;
-    for (int k = threadIdx.x; k < n; k += 256) m = std_min(m, partial[k]);
+    unsigned long long mi = ~0ull;
+    for (int k = threadIdx.x; k < n; k += 256) tb_min_first(m, mi, partial[k], partial_idx[k]);
     const int t = threadIdx.x;
-    lds[t] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) lds[t] = std_min(lds[t], lds[t + s]);
-        __syncthreads();
-    }
+    tb_min_fold(lds, ldi, t, m, mi);
     if (t == 0) st->minval = lds[0];
 }
 
@@ -191,7 +210,7 @@ hipError_t launch_tb_prepare(const TbPrepareArgs &a, TbState *st, hipStream_t s)
     const int gx = (a.w + 255) / 256;
     const dim3 grid(gx > 64 ? 64 : gx, a.h > 1024 ? 1024 : a.h);          // grid.x * grid.y <= TB_MAX_PARTIALS
     hipLaunchKernelGGL(tb_prepare_kernel, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(tb_min_final_kernel, dim3(1), dim3(256), 0, s, a.partial, (int)(grid.x * grid.y), st);
+    hipLaunchKernelGGL(tb_min_final_kernel, dim3(1), dim3(256), 0, s, a.partial, a.partial_idx, (int)(grid.x * grid.y), st);
     return hipGetLastError();
 }
 hipError_t launch_tb_conv(const TbConvArgs &a, hipStream_t s)

@@ -66,6 +66,15 @@ def info_tuple(i):
             np.array(i.sigma[:n], np.float32), np.array(i.maxp[:n], np.float32))
 
 
+def info_fields(i):
+    """every field of an Info-shaped structure (all ten entries of the three arrays) as a tuple of ints and float32 bit patterns, each NaN as
+    one pattern: which NaN an operation returns is not shared between the two machines"""
+    def f(v):
+        v = np.float32(v)
+        return 0x7fc00000 if np.isnan(v) else int(v.view(np.uint32))
+    return (int(i.nlevels), f(i.ave), f(i.min0), f(i.max0)) + tuple(f(v) for name in ("mean", "sigma", "maxp") for v in getattr(i, name))
+
+
 def copy_info(src):
     """an Info with the fields of any structure of that layout (capi.LocalContrastInfo)"""
     dst = Info()

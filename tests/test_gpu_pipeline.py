@@ -283,13 +283,9 @@ def test_progress_callback_and_roctx_ranges(gpu_ctx):
     assert len(events) == n                                       # removed
 
 
-def test_pipeline_all_tools_equal_the_tools_one_by_one(gpu_ctx):
-    """Dehaze, sharpening with a fixed radius, colour correction and smoothing (GUIDED and NLMEANS) with caller planes, texture boost with
-    pipe-generated masks (legal behind colour correction because smoothing sits in between), the standard tone curve and local contrast with
-    pipe-generated masks in ONE frame, against the same tools called through their own entry points, in pipe order, on what a run with all of
-    them off returns.  No other test has more than three of them on at once, which is where the walk over the colour modes and the mask slot
-    that texture boost and local contrast share can go wrong.  Both sides are this build's kernels in the same order: float32 bit patterns,
-    no tolerance."""
+def all_tools_pipe_against_the_tools_one_by_one(gpu_ctx, raw):
+    """the body of test_pipeline_all_tools_equal_the_tools_one_by_one for a 392 x 296 RGGB frame `raw` (tests/test_gpu_tool_domains.py hands it
+    value-domain families)"""
     import lc_lib
     import mk_lib
     import sm_lib
@@ -297,10 +293,9 @@ def test_pipeline_all_tools_equal_the_tools_one_by_one(gpu_ctx):
     import test_gpu_colorcorrection as CC
     import test_gpu_masks as MK
     import test_gpu_smoothing as SM
-    W, H = 392, 296
+    H, W = raw.shape
     w, h = W - 8, H - 8
     WS, IWS = O.REC2020_WS_D, O.REC2020_IWS_D
-    raw = synth.bayer_frame(W, H, synth.FILTERS_RGGB, seed=71, noise=1500)
     lut = _lut()
     p = _params(lut, 0)
     p.denoise_enabled = 0; p.exposure_enabled = 0; p.tone_enabled = 0
@@ -353,6 +348,16 @@ def test_pipeline_all_tools_equal_the_tools_one_by_one(gpu_ctx):
         assert nbad == 0, (name, nbad)
     assert not np.array_equal(got[1], base[1])
     del keep, keep_dh, keep_tb, keep_lc, t_tb, t_lc
+
+
+def test_pipeline_all_tools_equal_the_tools_one_by_one(gpu_ctx):
+    """Dehaze, sharpening with a fixed radius, colour correction and smoothing (GUIDED and NLMEANS) with caller planes, texture boost with
+    pipe-generated masks (legal behind colour correction because smoothing sits in between), the standard tone curve and local contrast with
+    pipe-generated masks in ONE frame, against the same tools called through their own entry points, in pipe order, on what a run with all of
+    them off returns.  No other test has more than three of them on at once, which is where the walk over the colour modes and the mask slot
+    that texture boost and local contrast share can go wrong.  Both sides are this build's kernels in the same order: float32 bit patterns,
+    no tolerance."""
+    all_tools_pipe_against_the_tools_one_by_one(gpu_ctx, synth.bayer_frame(392, 296, synth.FILTERS_RGGB, seed=71, noise=1500))
 
 
 def test_batch_lanes_inherit_the_pipe_settings_and_an_option():
